@@ -1,9 +1,14 @@
 #!/usr/bin/env python3
 """Throughput benchmark of the GRL hot path on MI355X (contract in the task statement).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
         N > 1 and no torchrun environment: bench.py spawns the N ranks itself (one process per GPU, RCCL);
         under `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...` it uses the launcher's ranks.
+
+A plain run sets up, warms up, times the K steps and prints the headline line (metric, value, unit, ms_per_step, dtype, the
+workload's configuration); nothing else runs on the GPU.  `--full` adds the untimed passes listed below to the line.
+`--dump-outputs DIR` writes what the timed path returned in its last step (rank 0) as DIR/output.npy (float32), or, above 64 MB,
+DIR/output_sample.npy: the same 2^23 elements of the flattened output every run (seeded draw of indices, in ascending order).
 
 Workload (BASELINE.json configs[2], the configuration the metric is quoted on): GRL-Base x4 SR,
 released-checkpoint geometry (window 32, stripes 64x64, anchor /2), batches of 256x256 LQ tiles,
@@ -13,7 +18,7 @@ offsets move more often -- the regime a user of the reference's checkpoints sees
 constructor's scales instead).  One step = one forward of `--tiles` tiles per GPU with the tiles already resident in HBM.  Tiles are independent units: ranks shard them
 with no data-path collective (weak scaling); the only collectives are the timing barrier/max.
 
-The timed region contains no probes.  After it, separate untimed passes collect
+The timed region contains no probes.  With --full, separate untimed passes after it collect
   roofline       : the dominant kernel (cosine window / stripe attention, MFMA-bound): algorithmic FLOPs per launch /
                    its mean launch duration from HIP events on the launching stream, against the 2.5 PFLOP/s fp16/bf16 dense peak.
                    `frac` = the kernel alone on the GPU (overlap off, `exclusive_*`); `concurrent_frac` = its residency inside the timed
@@ -182,6 +187,23 @@ def timed_steps(model, x, steps, world):
     return dt, y
 
 
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SAMPLE = 1 << 23
+
+
+def dump_outputs(out_dir, y):
+    """The timed path's output as float32 .npy: whole when it fits DUMP_MAX_BYTES, else a fixed seeded sample of it."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    y = y.detach().float()
+    if y.numel() * 4 <= DUMP_MAX_BYTES:
+        np.save(os.path.join(out_dir, "output.npy"), y.cpu().numpy())
+        return
+    idx = torch.randint(y.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values
+    np.save(os.path.join(out_dir, "output_sample.npy"), y.reshape(-1)[idx.to(y.device)].cpu().numpy())
+
+
 def training_leg(args, dev, rank, world):
     """A few optimizer steps of BASELINE configs[4] (reference: engines/base.py:221-236, tools/trainer.py:135-142,
     config/optimizer/adamw.yaml, config/loss/l1.yaml) on synthetic pairs."""
@@ -337,6 +359,8 @@ def run(args, rank, world, local_rank):
             y = model(x)
     dt, y = timed_steps(model, x, args.steps, world)
     assert torch.isfinite(y).all()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, y)
     precision_mode = model.precision   # (of the timed leg: `auto` is resolved per weight set, the other leg may differ)
     cal = getattr(model, "calibration", None)
     calibration = None
@@ -346,32 +370,33 @@ def run(args, rank, world, local_rank):
                                "operands, costliest first, until max <= bar_max and rms <= bar_rms on the probe (tests: five weight draws of "
                                "this configuration + one at this tile size hold 1e-3 against the float64 reference in this mode)")
 
-    # ---- untimed passes (rank 0 measures; every rank runs the same launches so that the barriers match) ----
+    # ---- untimed passes of --full (rank 0 measures; every rank runs the same launches so that the barriers match) ----
     groups = model.stream_groups(args.tiles)   # tile groups advancing on separate HIP streams (one launch = one group)
-    with torch.no_grad():
-        ops.profile_begin()
-        dt_probe, _ = timed_steps(model, x, args.steps, world)
-        prof = ops.profile_end()
-        excl = {}
-        if groups > 1:
-            os.environ["GRL_SPLIT_STREAMS"] = "1"
-            model(x)
-            torch.cuda.synchronize()
+    excl = {}
+    if args.full:
+        with torch.no_grad():
             ops.profile_begin()
-            model(x)
-            p1 = ops.profile_end()
-            del os.environ["GRL_SPLIT_STREAMS"]
-            a1 = attention_launches(p1)
-            if a1:
-                ms1 = sum(a1) / len(a1)
-                fl1 = attention_flops_per_launch(cfg, args.tiles, (side, side))
-                excl = {"exclusive_mean_launch_ms": round(ms1, 4), "exclusive_tiles_per_launch": args.tiles,
-                        "exclusive_achieved": round(fl1 / (ms1 * 1e-3) / 1e12, 2),
-                        "exclusive_frac": round(fl1 / (ms1 * 1e-3) / 1e12 / PEAK_F16_TFLOPS, 4)}
+            dt_probe, _ = timed_steps(model, x, args.steps, world)
+            prof = ops.profile_end()
+            if groups > 1:
+                os.environ["GRL_SPLIT_STREAMS"] = "1"
+                model(x)
+                torch.cuda.synchronize()
+                ops.profile_begin()
+                model(x)
+                p1 = ops.profile_end()
+                del os.environ["GRL_SPLIT_STREAMS"]
+                a1 = attention_launches(p1)
+                if a1:
+                    ms1 = sum(a1) / len(a1)
+                    fl1 = attention_flops_per_launch(cfg, args.tiles, (side, side))
+                    excl = {"exclusive_mean_launch_ms": round(ms1, 4), "exclusive_tiles_per_launch": args.tiles,
+                            "exclusive_achieved": round(fl1 / (ms1 * 1e-3) / 1e12, 2),
+                            "exclusive_frac": round(fl1 / (ms1 * 1e-3) / 1e12 / PEAK_F16_TFLOPS, 4)}
 
     # the other logit-scale regime, same K steps
     other = None
-    if not args.no_other_scales:
+    if args.full and not args.no_other_scales:
         with torch.no_grad():
             if trained_regime:
                 for (_, p_), v in zip(scale_params, init_scales):
@@ -392,7 +417,7 @@ def run(args, rank, world, local_rank):
     # what the other precision modes cost on the timed leg's weights (same tiles, fewer steps): every contraction on split operands
     # (`high`: 5e-6 from the float64 reference) and, when the calibration moved blocks, plain fp16 operands everywhere
     precision_legs = None
-    if not args.no_precision_legs and args.config == 3 and world == 1:
+    if args.full and not args.no_precision_legs and args.config == 3 and world == 1:
         with torch.no_grad():                      # the timed leg's logit scales again (the leg above swapped them)
             gs = torch.Generator().manual_seed(7)
             for (_, p_), v in zip(scale_params, init_scales):
@@ -417,7 +442,7 @@ def run(args, rank, world, local_rank):
 
     # strong-scaling leg: one fixed tile list sharded over the ranks, stitched through the RCCL all-gather
     tiled = None
-    if world > 1 and not args.no_tiled:
+    if args.full and world > 1 and not args.no_tiled:
         n_t = 8 * world
         cols = 8
         rows = n_t // cols
@@ -430,7 +455,7 @@ def run(args, rank, world, local_rank):
                  "collective": f"all_gather_into_tensor of {n_t // world} x (3, {side * scale}, {side * scale}) fp32 tiles per rank (RCCL)"}
 
     training = None
-    if not args.no_train and args.config == 3:
+    if args.full and not args.no_train and args.config == 3:
         del model, x, y
         torch.cuda.empty_cache()
         try:      # a secondary leg: its failure is reported in the line, it does not take the headline measurement down with it
@@ -440,23 +465,6 @@ def run(args, rank, world, local_rank):
 
     if rank == 0:
         mp = world * args.tiles * side * side * args.steps / dt / 1e6
-        att = attention_launches(prof)
-        att_ms = sum(att) / max(len(att), 1)
-        fl = attention_flops_per_launch(cfg, args.tiles // groups, (side, side))
-        ach = fl / (att_ms * 1e-3) / 1e12 if att_ms > 0 else 0.0
-        traffic, traffic_source = None, None
-        tpath = os.path.join(ROOT, "profiles", "attention_traffic.json")
-        live = measure_attention_traffic(args.tiles // groups) if (args.config == 3 and world == 1 and not args.no_traffic) else None
-        if live and "bytes_per_launch" in live:
-            traffic = live["bytes_per_launch"]
-            traffic_source = (f"measured in this run: rocprofv3 --kernel-trace --pmc FETCH_SIZE / WRITE_SIZE (separate passes) over tools/bench_kernels.py, "
-                              f"{live['tiles_per_launch']} tiles per launch, mean of the three attention launches of a block; KiB units, FETCH_SIZE x2 (gfx950): "
-                              f"FETCH {live['FETCH_SIZE_KiB_mean']} KiB, WRITE {live['WRITE_SIZE_KiB_mean']} KiB")
-        elif args.config == 3 and os.path.isfile(tpath):
-            traffic = json.load(open(tpath)).get("hbm_bytes_per_tile")  # PMC pass (profiles/), per tile
-            traffic = traffic * (args.tiles // groups) if traffic else None
-            traffic_source = ("profiles/attention_traffic.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of an earlier profile run, not measured in "
-                              "this run" + (f": {live['error']}" if live and "error" in live else ": rocprofv3 not available or --no-traffic") + ")")
         conf = {
             "workload": label + (", random-init weights with checkpoint-like logit scales exp(min(ln 100 + 0.3 N(0,1), ln 100)): about half of the heads at "
                                  "the clamp, the regime of every released checkpoint" if trained_regime else ", random-init weights and logit scales (10)"),
@@ -469,42 +477,61 @@ def run(args, rank, world, local_rank):
         }
         if gflop_tile:
             conf.update(gflop_per_tile=gflop_tile, model_tflops=round(gflop_tile * 1e9 * world * args.tiles * args.steps / dt / 1e12, 2))
-        # Roofline of the dominant kernel.  `frac` is the kernel alone on the GPU (the `exclusive` pass: overlap off, one launch per
-        # attention call over all tiles) -- what the kernel is capable of; `concurrent_frac` is its per-launch residency inside the timed
-        # schedule, where a launch shares the GPU with the other tile group's kernels and therefore understates it; `whole_network_frac`
-        # prices the whole step's algorithmic FLOPs (5468.5 GFLOP per tile) against the same peak.
-        roofline = {
-            # the row-streaming kernel serves the 32-aligned geometry of config 3; the window-12 / -16 geometries of configs 2 and 4
-            # run the generic kernel (grl_attention_fwd's dispatch, csrc/attention.hip)
-            "kernel": "attn_rows_kernel (cosine window / anchored-stripe attention, csrc/attention_rows.hip)" if args.config == 3 else
-                      "attn_kernel (generic cosine window / anchored-stripe attention, csrc/attention.hip)",
-            "bound": "mfma",
-            # `achieved` / `frac`: the kernel's mean launch duration measured live in the step's own schedule (HIP events on the
-            # launching streams of a repeat of the timed region) -- with two tile groups on two streams a launch shares the GPU with
-            # the other group's kernels; `exclusive_*` below: the kernel alone on the GPU; `whole_network_frac`: the step's FLOPs
-            "whole_network_frac": round(gflop_tile * 1e9 * world * args.tiles * args.steps / dt / 1e12 / PEAK_F16_TFLOPS, 4) if gflop_tile else None,
-            "achieved": round(ach, 2),
-            "peak": PEAK_F16_TFLOPS,
-            "unit": "TFLOP/s",
-            "frac": round(ach / PEAK_F16_TFLOPS, 4),
-            "frac_is": "in the timed schedule (two tile groups on two HIP streams share the GPU)" if groups > 1 else "in the timed schedule (one stream)",
-            "concurrent_achieved": round(ach, 2),
-            "concurrent_frac": round(ach / PEAK_F16_TFLOPS, 4),
-            "logit_scale_regime": "checkpoint-like" if trained_regime else "random-init",
-            "traffic": traffic,
-            "traffic_source": traffic_source,
-            "algorithmic_bytes_per_launch": int(37.65e6 * (args.tiles // groups)) if args.config == 3 else None,
-            "launches_timed": len(att),
-            "mean_launch_ms": round(att_ms, 4),
-            "flops_per_launch": fl,
-            "probe_pass_ms_per_step": round(dt_probe / args.steps * 1e3, 3),
-            "time_share_of_step": round(sum(att) / (dt_probe * 1e3), 3) if att else None,
-            "time_share_note": "sum of the launches' own durations / step time; the tile groups run on concurrent streams, so launches overlap "
-                               "and the shares of all kernels add up to more than 1" if groups > 1 else None,
-            "concurrent_streams": groups,
-            "tiles_per_launch": args.tiles // groups,
-            **excl,
-        }
+        roofline = None
+        if args.full:
+            att = attention_launches(prof)
+            att_ms = sum(att) / max(len(att), 1)
+            fl = attention_flops_per_launch(cfg, args.tiles // groups, (side, side))
+            ach = fl / (att_ms * 1e-3) / 1e12 if att_ms > 0 else 0.0
+            traffic, traffic_source = None, None
+            tpath = os.path.join(ROOT, "profiles", "attention_traffic.json")
+            live = measure_attention_traffic(args.tiles // groups) if (args.config == 3 and world == 1 and not args.no_traffic) else None
+            if live and "bytes_per_launch" in live:
+                traffic = live["bytes_per_launch"]
+                traffic_source = (f"measured in this run: rocprofv3 --kernel-trace --pmc FETCH_SIZE / WRITE_SIZE (separate passes) over tools/bench_kernels.py, "
+                                  f"{live['tiles_per_launch']} tiles per launch, mean of the three attention launches of a block; KiB units, FETCH_SIZE x2 (gfx950): "
+                                  f"FETCH {live['FETCH_SIZE_KiB_mean']} KiB, WRITE {live['WRITE_SIZE_KiB_mean']} KiB")
+            elif args.config == 3 and os.path.isfile(tpath):
+                traffic = json.load(open(tpath)).get("hbm_bytes_per_tile")  # PMC pass (profiles/), per tile
+                traffic = traffic * (args.tiles // groups) if traffic else None
+                traffic_source = ("profiles/attention_traffic.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of an earlier profile run, not measured in "
+                                  "this run" + (f": {live['error']}" if live and "error" in live else ": rocprofv3 not available or --no-traffic") + ")")
+            # Roofline of the dominant kernel.  `frac` is the kernel alone on the GPU (the `exclusive` pass: overlap off, one launch per
+            # attention call over all tiles) -- what the kernel is capable of; `concurrent_frac` is its per-launch residency inside the timed
+            # schedule, where a launch shares the GPU with the other tile group's kernels and therefore understates it; `whole_network_frac`
+            # prices the whole step's algorithmic FLOPs (5468.5 GFLOP per tile) against the same peak.
+            roofline = {
+                # the row-streaming kernel serves the 32-aligned geometry of config 3; the window-12 / -16 geometries of configs 2 and 4
+                # run the generic kernel (grl_attention_fwd's dispatch, csrc/attention.hip)
+                "kernel": "attn_rows_kernel (cosine window / anchored-stripe attention, csrc/attention_rows.hip)" if args.config == 3 else
+                          "attn_kernel (generic cosine window / anchored-stripe attention, csrc/attention.hip)",
+                "bound": "mfma",
+                # `achieved` / `frac`: the kernel's mean launch duration measured live in the step's own schedule (HIP events on the
+                # launching streams of a repeat of the timed region) -- with two tile groups on two streams a launch shares the GPU with
+                # the other group's kernels; `exclusive_*` below: the kernel alone on the GPU; `whole_network_frac`: the step's FLOPs
+                "whole_network_frac": round(gflop_tile * 1e9 * world * args.tiles * args.steps / dt / 1e12 / PEAK_F16_TFLOPS, 4) if gflop_tile else None,
+                "achieved": round(ach, 2),
+                "peak": PEAK_F16_TFLOPS,
+                "unit": "TFLOP/s",
+                "frac": round(ach / PEAK_F16_TFLOPS, 4),
+                "frac_is": "in the timed schedule (two tile groups on two HIP streams share the GPU)" if groups > 1 else "in the timed schedule (one stream)",
+                "concurrent_achieved": round(ach, 2),
+                "concurrent_frac": round(ach / PEAK_F16_TFLOPS, 4),
+                "logit_scale_regime": "checkpoint-like" if trained_regime else "random-init",
+                "traffic": traffic,
+                "traffic_source": traffic_source,
+                "algorithmic_bytes_per_launch": int(37.65e6 * (args.tiles // groups)) if args.config == 3 else None,
+                "launches_timed": len(att),
+                "mean_launch_ms": round(att_ms, 4),
+                "flops_per_launch": fl,
+                "probe_pass_ms_per_step": round(dt_probe / args.steps * 1e3, 3),
+                "time_share_of_step": round(sum(att) / (dt_probe * 1e3), 3) if att else None,
+                "time_share_note": "sum of the launches' own durations / step time; the tile groups run on concurrent streams, so launches overlap "
+                                   "and the shares of all kernels add up to more than 1" if groups > 1 else None,
+                "concurrent_streams": groups,
+                "tiles_per_launch": args.tiles // groups,
+                **excl,
+            }
         line = {
             "metric": "LQ megapixels/s, " + label.split(":")[1].split(",")[0].strip() + f", {side}x{side} LQ tiles",
             "value": round(mp, 4),
@@ -519,8 +546,9 @@ def run(args, rank, world, local_rank):
             "dtype": "f16 MFMA operands (attention, linear, conv), f32 accumulate + residual stream",
             "data": "synthetic",
             "config": conf,
-            "roofline": roofline,
         }
+        if roofline:
+            line["roofline"] = roofline
         if other:
             line["random_init_scales" if trained_regime else "trained_scales"] = other
         if precision_legs:
@@ -529,7 +557,7 @@ def run(args, rank, world, local_rank):
             line["tiled"] = tiled
         if training:
             line["training"] = training
-        if not args.no_cpu_baseline and world == 1:      # rank 0 at N = 1 only: the other ranks would sit in the barrier
+        if args.full and not args.no_cpu_baseline and world == 1:      # rank 0 at N = 1 only: the other ranks would sit in the barrier
             line["cpu_baseline"] = cpu_baseline(cfg, side if not args.cpu_baseline_side else args.cpu_baseline_side)
         print(json.dumps(line), flush=True)
     if world > 1:
@@ -562,7 +590,14 @@ def main():
     ap.add_argument("--no-train", action="store_true")
     ap.add_argument("--train-steps", type=int, default=3)
     ap.add_argument("--train-batch", type=int, default=8, help="64x64 LQ patches per GPU per training step")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the untimed passes (roofline, other logit scales, precision legs, tiled, training, "
+                         "CPU baseline); the --no-* options above select among them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the timed path's output of its last step (rank 0) as float32 .npy under DIR (a fixed seeded sample above 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is not None:                       # launched by torch.distributed.run

@@ -2,20 +2,30 @@
 
 1. Against the golden fixtures (outputs of the REAL reference network, tests/golden/*.npz): runs
    everywhere, including the GPU box.
-2. Against the live, unmodified reference when /root/reference is present (build container):
-   whole network, individual modules (WindowAttention, AnchorStripeAttention, CAB) and the
-   index / mask / table generators in models/common/ops.py, plus the reference's own
+2. Against what the unmodified reference computes, frozen by oracle/make_golden_pins.py (tests/golden/pins/, samples of the larger tensors):
+   whole network, individual modules (WindowAttention, AnchorStripeAttention, CAB), the training-step
+   gradients and the index / mask / table generators in models/common/ops.py, plus the reference's own
    self-check numbers (ops.py:472-551: table sizes 640/1197/121/225).
 """
+import json
+import os
+import zlib
+
+import numpy as np
 import pytest
 import torch
 
 from oracle import engine_oracle as E
 from oracle import grl_oracle as O
-from oracle import refshim
+from oracle import make_golden_pins as P
 from tests.util import golden_names, golden_state_dict, load_golden, product_shapes
 
-needs_ref = pytest.mark.skipif(not refshim.reference_available(), reason="reference tree not mounted")
+PINS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "pins")
+
+
+def _pins(name):
+    return np.load(os.path.join(PINS, name + ".npz"), allow_pickle=False)
+
 
 # the fixtures the oracle re-runs in seconds; the large ones (256x256 bench tiles, 384x384 deblur tiles: minutes of CPU)
 # carry their oracle-vs-reference agreement in their metadata (checked below) and are exercised by the GPU tests
@@ -41,72 +51,71 @@ def test_golden_set_complete():
         assert meta["oracle_vs_reference_maxabs"] < 5e-6
 
 
-@needs_ref
 def test_reference_selfcheck_numbers():
     """ops.py:472-551 prints these table sizes for windows (4,86)/(8,8) x df {1,2}."""
-    ops = refshim.import_reference_ops()
+    z = _pins("ops")
     want = {((4, 86), 1): 1197, ((4, 86), 2): 640, ((8, 8), 1): 225, ((8, 8), 2): 121}
+    assert list(want) == P.TABLE_CASES
     for (win, df), rows in want.items():
         t = O.coords_table(win, df)
         assert t.shape[1] * t.shape[2] == rows
-        tr = ops.get_relative_coords_table_all(list(win), [0, 0], df)
+        tr = torch.from_numpy(z["table_" + P.tag(win, df)])
         assert torch.equal(t, tr)
         for w2a in (True, False):
             i0 = O.rel_index(win, df, w2a)
-            assert torch.equal(i0, ops.get_relative_position_index_simple(list(win), df, w2a).long())
-            assert torch.equal(i0.float(), ops.get_relative_position_index_all(list(win), df, w2a).float())
+            assert torch.equal(i0, torch.from_numpy(z["index_simple_" + P.tag(win, df, int(w2a))]).long())
+            assert torch.equal(i0.float(), torch.from_numpy(z["index_all_" + P.tag(win, df, int(w2a))]).float())
             assert int(i0.min()) == 0 and int(i0.max()) == rows - 1
 
 
-@needs_ref
 @pytest.mark.parametrize("res,win,shift,df", [((32, 32), (8, 8), (4, 4), 1), ((16, 64), (8, 32), (4, 16), 4),
                                               ((64, 64), (64, 64), (32, 32), 2), ((24, 48), (12, 24), (6, 12), 4),
                                               ((32, 32), (8, 32), (4, 0), 4)])
 def test_masks_match_reference(res, win, shift, df):
-    ops = refshim.import_reference_ops()
+    z = _pins("ops")
+    t = P.tag(res, win, shift, df)
     if df == 1:
-        assert torch.equal(O.shift_mask(res, win, shift, mode="w"), ops.calculate_mask(list(res), list(win), list(shift)))
+        assert torch.equal(O.shift_mask(res, win, shift, mode="w"), P.unpack_mask(z["mask_" + t], z["mask_shape_" + t]))
     for mode, w2a in (("w2a", True), ("a2w", False)):
-        assert torch.equal(O.shift_mask(res, win, shift, df, mode), ops.calculate_mask_all(list(res), list(win), list(shift), df, w2a))
+        ref = P.unpack_mask(z[f"mask_all_{t}_{int(w2a)}"], z[f"mask_all_shape_{t}_{int(w2a)}"])
+        assert torch.equal(O.shift_mask(res, win, shift, df, mode), ref)
 
 
-@needs_ref
 @pytest.mark.parametrize("model,geom,up,size", [("tiny", "sr_ckpt_df4", 2, 64), ("base", "yaml", 4, 32)])
 def test_whole_network_and_modules_match_reference(model, geom, up, size):
+    """The reference's whole output, and three modules of layers[0].blocks[2] (window shift + stripe shift active) on the seeded,
+    perturbed constructor weights: the oracle rebuilds the modules' inputs (the recipe checked them against the reference's:
+    bitwise) and its module outputs are compared with a fixed sample of the reference's."""
     from grl_image_restoration_amd.presets import make_config
 
-    GRL = refshim.import_reference_grl()
+    z = _pins("net_" + P.tag(model, geom, up, size))
+    meta = json.loads(str(z["meta"]))
     cfg = make_config(model, geom, upscale=up, img_size=size)
-    torch.manual_seed(0)
-    ref = GRL(**cfg).eval()
-    sd = O.perturb_state_dict(ref.state_dict(), 0)
-    ref.load_state_dict(sd)
+    assert meta["cfg"] == json.loads(json.dumps(cfg))
+    assert meta["oracle_module_inputs_vs_reference_maxabs"] < 1e-6
+    sd = P.net_case_weights(cfg)
     lq, _ = O.synthetic_pair("sr", (size, size), up)
-    cap = {}
-    hooks = []
-    blk = ref.layers[0].blocks[2]  # window shift + stripe shift active
-    hooks.append(blk.attn.window_attn.register_forward_hook(lambda m, i, o: cap.__setitem__("win", (i, o))))
-    hooks.append(blk.attn.stripe_attn.register_forward_hook(lambda m, i, o: cap.__setitem__("stripe", (i, o))))
-    if cfg["local_connection"]:
-        hooks.append(blk.conv.register_forward_hook(lambda m, i, o: cap.__setitem__("cab", (i, o))))
-    with torch.no_grad():
-        y = ref(lq)
-        yo = O.grl_forward(lq, cfg, sd)
-    for h in hooks:
-        h.remove()
-    assert (y - yo).abs().max().item() < 5e-6
+    x_size = tuple(meta["x_size"])
+    yo, ins = P.block2_inputs(cfg, sd, lq, x_size)
+    assert (torch.from_numpy(z["output"]) - yo).abs().max().item() < 5e-6
+
+    def vs_ref(mine, name):
+        ref = z[name + "_sample"]
+        idx = P.sample_index(mine.numel(), meta["module_sample"], zlib.crc32(name.encode()))
+        assert ref.shape == idx.shape
+        return np.abs(mine.reshape(-1).numpy()[idx] - ref).max()
+
     sched = O.block_schedule(cfg, (size, size))[0][2]
     pre = "layers.0.blocks.2."
-    (qkv, x_size, *_), out = cap["win"]
-    mine = O.window_attention(qkv, x_size, sched["window"], sched["window_shift"], sched["nh_w"], sd, pre + "attn.window_attn.")
-    assert (mine - out).abs().max().item() < 2e-6
-    (qkv, anchor, x_size, *_), out = cap["stripe"]
-    mine = O.anchor_stripe_attention(qkv, anchor, x_size, sched["stripe"], sched["stripe_shift_size"], sched["stripe_shift"],
-                                     sched["df"], sched["nh_s"], sd, pre + "attn.stripe_attn.")
-    assert (mine - out).abs().max().item() < 2e-6
-    if cfg["local_connection"]:
-        (x, x_size), out = cap["cab"]
-        assert (O.cab(x, x_size, sd, pre + "conv.") - out).abs().max().item() < 2e-6
+    with torch.no_grad():
+        mine = O.window_attention(ins["win_qkv"], x_size, sched["window"], sched["window_shift"], sched["nh_w"], sd, pre + "attn.window_attn.")
+        assert vs_ref(mine, "win_out") < 2e-6
+        mine = O.anchor_stripe_attention(ins["stripe_qkv"], ins["stripe_anchor"], x_size, sched["stripe"], sched["stripe_shift_size"],
+                                         sched["stripe_shift"], sched["df"], sched["nh_s"], sd, pre + "attn.stripe_attn.")
+        assert vs_ref(mine, "stripe_out") < 2e-6
+        assert ("cab_out_sample" in z.files) == bool(cfg["local_connection"])
+        if cfg["local_connection"]:
+            assert vs_ref(O.cab(ins["cab_x"], x_size, sd, pre + "conv."), "cab_out") < 2e-6
 
 
 def test_engine_restatements():
@@ -164,14 +173,30 @@ def test_oracle_gradients_reproduce_golden():
         assert ((g - r).norm() / r.norm().clamp_min(1e-12)).item() < 2e-4, k
 
 
-@needs_ref
 def test_oracle_gradients_match_live_reference():
+    """The reference's training step (make_golden_grads.make_case): loss, input gradient, the set of parameter gradients and every
+    gradient of <= 4096 elements in full (tests/golden_grads/), the larger ones by their norm and a fixed sample (tests/golden/pins/)."""
     from oracle import make_golden_grads as G
 
-    cfg, sd, lq, gt = G.make_case()
-    loss, gin, grads = G.reference_step(cfg, sd, lq, gt)
+    meta, zg = _load_grad_fixture()
+    z = _pins("grads")
+    cfg = meta["cfg"]
+    sd = P.grads_case_weights(cfg)
+    lq, gt = torch.from_numpy(zg["input"]), torch.from_numpy(zg["target"])
+    loss, gin = meta["loss"], torch.from_numpy(zg["grad_input"])
+    names = json.loads(str(zg["grad_norm_names"]))
     lo, gio, go = G.oracle_step(cfg, sd, lq, gt)
-    assert abs(float(loss) - float(lo)) < 1e-6 and set(grads) == set(go)
+    assert abs(loss - float(lo)) < 1e-6 and set(names) == set(go)
     assert ((gin - gio).norm() / gin.norm()).item() < 1e-4
-    for k in grads:
-        assert ((grads[k] - go[k]).norm() / grads[k].norm().clamp_min(1e-20)).item() < 1e-4, k
+    sample = json.loads(str(z["meta"]))["grad_sample"]
+    for k, n in zip(names, zg["grad_norms"]):
+        g = go[k]
+        if g.numel() <= 4096:
+            r = torch.from_numpy(zg["grad::" + k])
+            assert ((r - g).norm() / r.norm().clamp_min(1e-20)).item() < 1e-4, k
+        else:
+            assert abs(g.norm().item() - n) <= 1e-4 * n, k
+            r = z["sample::" + k]
+            mine = g.reshape(-1).numpy()[P.sample_index(g.numel(), sample, zlib.crc32(k.encode()))]
+            assert mine.shape == r.shape
+            assert np.linalg.norm(r - mine) / max(np.linalg.norm(r), 1e-20) < 1e-4, k

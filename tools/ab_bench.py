@@ -14,7 +14,7 @@ try:
     for r in range(rounds):
         for v in variants:
             shutil.copy(v, lib)
-            out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "10", "--warmup", "3", "--no-train", "--no-cpu-baseline"] + extra,
+            out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "10", "--warmup", "3", "--full", "--no-train", "--no-cpu-baseline"] + extra,
                                  capture_output=True, text=True, timeout=900)
             try:
                 d = json.loads(out.stdout.strip().splitlines()[-1])

@@ -3,7 +3,7 @@
 #   kernel_stats.txt     rocprofv3 --kernel-trace --stats summary of the bench command (per-kernel calls / avg / share)
 #   pmc_hbm.txt          FETCH_SIZE / WRITE_SIZE per kernel (separate --pmc passes) over the per-kernel micro-benchmark
 #   pmc_sq.txt           SQ / GRBM counters (MFMA-busy, VALU, wait buckets) for attention, QKV, block tail, CAB convs
-#   bench_line.json      the default bench.py line;  bench_config2.json / bench_config4.json: BASELINE configs[1] / [3]
+#   bench_line.json      the bench.py --full line;  bench_config2.json / bench_config4.json: BASELINE configs[1] / [3]
 #   step_breakdown_configN.txt   tools/step_breakdown.py: share of a forward per C-ABI entry point, random-init and trained scales
 set -u
 ROOT=$(pwd)
@@ -39,7 +39,7 @@ for c in "8 3" "16 2" "4 4"; do
   set -- $c
   { python tools/step_breakdown.py $1 $2; python tools/step_breakdown.py $1 $2 --trained; } 2>&1 | grep -v amdgpu.ids > $OUT/step_breakdown_config$2.txt
 done
-python bench.py --config 2 --tiles 16 --no-cpu-baseline --no-traffic > $OUT/bench_config2.json 2> $OUT/bench_config2.err
-python bench.py --config 4 --tiles 4 --no-cpu-baseline --no-traffic > $OUT/bench_config4.json 2> $OUT/bench_config4.err
-python bench.py > $OUT/bench_line.json 2> $OUT/bench_stderr.txt
+python bench.py --full --config 2 --tiles 16 --no-cpu-baseline --no-traffic > $OUT/bench_config2.json 2> $OUT/bench_config2.err
+python bench.py --full --config 4 --tiles 4 --no-cpu-baseline --no-traffic > $OUT/bench_config4.json 2> $OUT/bench_config4.err
+python bench.py --full > $OUT/bench_line.json 2> $OUT/bench_stderr.txt
 tail -c 600 $OUT/bench_line.json
