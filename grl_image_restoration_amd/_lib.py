@@ -9,7 +9,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgrl_hip.so")
-ABI_VERSION = 22
+ABI_VERSION = 23
 DT_F32, DT_BF16, DT_F16 = 0, 1, 2
 
 EPI_PLAIN, EPI_GELU, EPI_GROUPNORM, EPI_LN_RES, EPI_GELU_GRAD = 0, 1, 2, 3, 4
@@ -53,6 +53,8 @@ EXPORTS = [
     "grl_head_planes_bwd",
     "grl_cpb_table_fwd",
     "grl_cpb_table_bwd",
+    "grl_image_metrics_workspace_bytes",
+    "grl_image_metrics",
     "grl_debug_dirty_lds",
     "grl_abi_version",
     "grl_build_info",
@@ -480,6 +482,29 @@ class GrlCpbArgs(_Strict):
     ]
 
 
+METRIC_PSNR, METRIC_PSNR_Y, METRIC_SSIM, METRIC_SSIM_Y, METRIC_PSNRB, METRIC_PSNRB_Y = 1, 2, 4, 8, 16, 32
+METRIC_COUNT = 6
+
+
+class GrlMetricArgs(_Strict):
+    _fields_ = [
+        ("restored", C.c_void_p),
+        ("restored_stride", C.c_int64 * 4),
+        ("shape", C.c_int32 * 4),
+        ("target", C.c_void_p),
+        ("target_stride", C.c_int64 * 4),
+        ("target_shape", C.c_int32 * 4),
+        ("border", C.c_int32),
+        ("metrics", C.c_int32),
+        ("taps", C.c_double * 11),
+        ("y_coef", C.c_float * 3),
+        ("reserved0", C.c_int32),
+        ("workspace", C.c_void_p),
+        ("workspace_bytes", C.c_int64),
+        ("out", C.c_void_p),
+    ]
+
+
 _lib = None
 
 
@@ -577,6 +602,10 @@ def lib():
     L.grl_cpb_table_fwd.restype = C.c_int
     L.grl_cpb_table_bwd.argtypes = [C.c_void_p, C.POINTER(GrlCpbArgs)]
     L.grl_cpb_table_bwd.restype = C.c_int
+    L.grl_image_metrics_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32]
+    L.grl_image_metrics_workspace_bytes.restype = C.c_int64
+    L.grl_image_metrics.argtypes = [C.c_void_p, C.POINTER(GrlMetricArgs)]
+    L.grl_image_metrics.restype = C.c_int
     L.grl_debug_dirty_lds.argtypes = [C.c_void_p]
     L.grl_debug_dirty_lds.restype = C.c_int
     _lib = L

@@ -8,10 +8,11 @@ Restates, for the MI355X module, the three pieces of the reference's evaluation 
   psnr_y            engines/base.py:256-268    tensor_round -> shave(scale) for SR -> PSNR on the matlab-style Y channel
                     utils/utils_image.py:8-11,30-33,43-79; utils/metrics/psnr.py:44-48
   evaluate_folder   the validation loop over an LQ / GT image folder pair (whole image, or the reference's tiled
-                    inference through ``tiling.forward_tiled``)
+                    inference through ``tiling.forward_tiled``); with ``metric_group`` one of the reference's metric groups
+                    (config/metric/*.yaml, ``metrics.image_metrics``) instead of PSNR-Y alone
 
     python -m grl_image_restoration_amd.evaluate --model base --geometry sr_ckpt_df2 --scale 4 \\
-        --ckpt sr_grl_base_c3x4.ckpt --lq Set5/LRbicx4 --gt Set5/GTmod12 [--tile 256 --overlap 32]
+        --ckpt sr_grl_base_c3x4.ckpt --lq Set5/LRbicx4 --gt Set5/GTmod12 [--tile 256 --overlap 32] [--metric restorer]
 """
 import argparse
 import os
@@ -86,11 +87,14 @@ def psnr_y(restored: torch.Tensor, target: torch.Tensor, scale: int = 1) -> torc
 _IMG_EXT = (".png", ".jpg", ".jpeg", ".bmp", ".tif", ".tiff")
 
 
-def _read_image(path: str) -> torch.Tensor:
+def _read_image(path: str, mode: str = "RGB") -> torch.Tensor:
+    """(1, C, H, W) fp32 in [0, 1]; ``mode`` "RGB" (C = 3) or "L" (C = 1, the grayscale checkpoints)."""
     import numpy as np
     from PIL import Image
 
-    a = np.asarray(Image.open(path).convert("RGB"), dtype=np.float32) / 255.0
+    a = np.asarray(Image.open(path).convert(mode), dtype=np.float32) / 255.0
+    if a.ndim == 2:
+        a = a[:, :, None]
     return torch.from_numpy(a).permute(2, 0, 1).unsqueeze(0).contiguous()
 
 
@@ -106,10 +110,12 @@ def image_pairs(lq_dir: str, gt_dir: str) -> List[Tuple[str, str]]:
 
 @torch.no_grad()
 def evaluate_pairs(model, pairs: Iterable[Tuple[torch.Tensor, torch.Tensor]], scale: int, tile: int = 0, overlap: int = 32,
-                   device: str = "cuda:0") -> List[float]:
-    """PSNR-Y of ``model`` on (lq, gt) tensors in [0, 1], (1,3,h,w) / (1,3,h*scale,w*scale).  ``tile > 0`` uses the
-    reference's tiled inference (engines/base.py:90-116) through ``tiling.forward_tiled``."""
+                   device: str = "cuda:0", metric_group: Optional[str] = None):
+    """PSNR-Y of ``model`` on (lq, gt) tensors in [0, 1], (1,3,h,w) / (1,3,h*scale,w*scale): a list, one value per pair.
+    ``tile > 0`` uses the reference's tiled inference (engines/base.py:90-116) through ``tiling.forward_tiled``.
+    With ``metric_group`` (a key of ``metrics.GROUPS``): {metric name: mean over the pairs} of that group instead."""
     from . import tiling
+    from .metrics import image_metrics
 
     out = []
     for lq, gt in pairs:
@@ -119,27 +125,47 @@ def evaluate_pairs(model, pairs: Iterable[Tuple[torch.Tensor, torch.Tensor]], sc
         else:
             sr = model(lq)
         gt = gt.to(sr.device)[..., : sr.shape[-2], : sr.shape[-1]]
-        out.append(float(psnr_y(sr[..., : gt.shape[-2], : gt.shape[-1]], gt, scale)))
-    return out
+        sr = sr[..., : gt.shape[-2], : gt.shape[-1]]
+        if metric_group is None:
+            out.append(float(psnr_y(sr, gt, scale)))
+        else:
+            out.append({k: float(v.mean()) for k, v in image_metrics(sr, gt, metric_group, scale).items()})
+    if metric_group is None:
+        return out
+    return {k: sum(o[k] for o in out) / len(out) for k in out[0]}
 
 
 def evaluate_folder(model, lq_dir: str, gt_dir: str, scale: int, tile: int = 0, overlap: int = 32, device: str = "cuda:0",
-                    verbose: bool = True) -> float:
+                    verbose: bool = True, metric_group: Optional[str] = None, channels: int = 3):
+    """Mean PSNR-Y over the image pairs of two folders; with ``metric_group``, {metric name: mean} of that group.  ``channels`` 1
+    reads the images as grayscale."""
     pairs = image_pairs(lq_dir, gt_dir)
+    mode = "L" if channels == 1 else "RGB"
     vals = []
     for lq_p, gt_p in pairs:
-        v = evaluate_pairs(model, [(_read_image(lq_p), _read_image(gt_p))], scale, tile, overlap, device)[0]
+        v = evaluate_pairs(model, [(_read_image(lq_p, mode), _read_image(gt_p, mode))], scale, tile, overlap, device, metric_group)
+        v = v[0] if metric_group is None else v
         vals.append(v)
         if verbose:
-            print(f"{os.path.basename(lq_p):32s} PSNR-Y {v:7.3f} dB")
-    mean = sum(vals) / len(vals)
+            print(f"{os.path.basename(lq_p):32s} {_columns(v)}")
+    if metric_group is None:
+        mean = sum(vals) / len(vals)
+    else:
+        mean = {k: sum(v[k] for v in vals) / len(vals) for k in vals[0]}
     if verbose:
-        print(f"{'mean over ' + str(len(vals)) + ' images':32s} PSNR-Y {mean:7.3f} dB")
+        print(f"{'mean over ' + str(len(vals)) + ' images':32s} {_columns(mean)}")
     return mean
 
 
-def main(argv: Optional[List[str]] = None) -> float:
+def _columns(v) -> str:
+    if not isinstance(v, dict):
+        return f"PSNR-Y {v:7.3f} dB"
+    return "  ".join(f"{k} {x:7.4f}" if "ssim" in k else f"{k} {x:7.3f}" for k, x in v.items())
+
+
+def main(argv: Optional[List[str]] = None):
     from . import GRL, make_config
+    from .metrics import GROUPS
 
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--model", default="base", choices=["tiny", "small", "base"])
@@ -151,12 +177,15 @@ def main(argv: Optional[List[str]] = None) -> float:
     ap.add_argument("--tile", type=int, default=0)
     ap.add_argument("--overlap", type=int, default=32)
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--metric", default=None, choices=sorted(GROUPS),
+                    help="report this metric group of the reference (config/metric/*.yaml) instead of PSNR-Y alone")
+    ap.add_argument("--channels", type=int, default=3, choices=[1, 3], help="1: grayscale model and images (dn_*_c1, jpeg_*_c1)")
     a = ap.parse_args(argv)
-    model = GRL(**make_config(a.model, a.geometry, upscale=a.scale)).eval()
+    model = GRL(**make_config(a.model, a.geometry, upscale=a.scale, in_channels=a.channels)).eval()
     if a.ckpt:
         load_checkpoint(model, a.ckpt)
     model = model.to(a.device)
-    return evaluate_folder(model, a.lq, a.gt, a.scale, a.tile, a.overlap, a.device)
+    return evaluate_folder(model, a.lq, a.gt, a.scale, a.tile, a.overlap, a.device, metric_group=a.metric, channels=a.channels)
 
 
 if __name__ == "__main__":

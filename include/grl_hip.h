@@ -23,7 +23,7 @@ extern "C" {
 
 #define GRL_ERR_BAD_ARG (-1)
 #define GRL_ERR_UNSUPPORTED (-2)
-#define GRL_ABI_VERSION 22
+#define GRL_ABI_VERSION 23
 
 /* element kinds of activation / weight buffers */
 enum { GRL_DT_F32 = 0, GRL_DT_BF16 = 1, GRL_DT_F16 = 2 };
@@ -679,6 +679,41 @@ typedef struct GrlCpbArgs {
 
 int grl_cpb_table_fwd(void* stream, const GrlCpbArgs* args);
 int grl_cpb_table_bwd(void* stream, const GrlCpbArgs* args);
+
+/* Image-quality metrics of the reference's validation (ABI 23; evaluation, not the network):
+ *   replaces  tensor_round / shave / rgb2ycbcr (Y)   engines/base.py:256-271, utils/utils_image.py:8-11,30-33,43-79
+ *             psnr                                   utils/metrics/psnr.py:44-48
+ *             ssim (Gaussian 11x11, sigma 1.5)       utils/metrics/ssim.py:17-85
+ *             psnrb (blocking effect factor)         utils/metrics/psnrb.py:22-115
+ * restored / target: fp32 (B, C, H, W) with arbitrary element strides (views: crops, shaves), C = 1 or 3.  Both are rounded to 8 bit
+ * (clamp to [0, 1], round(x 255) / 255) on load; the metrics see the H-2 border x W-2 border interior.  Two launches: a tile pass writes
+ * per-workgroup fp64 partial sums into `workspace`, a second pass adds them per image in a fixed order and writes
+ * out[b][GRL_METRIC_COUNT] (fp64; entries of metrics not asked for are NaN).  No atomics: bitwise reproducible.
+ * Errors (GRL_ERR_BAD_ARG): shapes differ, C not 1 / 3, a _Y metric with C = 1, 2 border >= H or W, unknown / no metric bits,
+ * workspace smaller than grl_image_metrics_workspace_bytes. */
+enum { GRL_METRIC_PSNR = 1, GRL_METRIC_PSNR_Y = 2, GRL_METRIC_SSIM = 4, GRL_METRIC_SSIM_Y = 8, GRL_METRIC_PSNRB = 16,
+       GRL_METRIC_PSNRB_Y = 32, GRL_METRIC_COUNT = 6 /* out column of bit (1 << i) is i */ };
+
+typedef struct GrlMetricArgs {
+    const float* restored;      /* the prediction ("preds"); PSNR-B's blocking term is measured on it alone  */
+    int64_t restored_stride[4]; /* element strides of dims b, c, h, w                                        */
+    int32_t shape[4];           /* B, C, H, W of restored                                                    */
+    const float* target;
+    int64_t target_stride[4];
+    int32_t target_shape[4];    /* must equal shape                                                          */
+    int32_t border;             /* shave (the SR scale; 0 otherwise)                                         */
+    int32_t metrics;            /* GRL_METRIC_* bits                                                         */
+    double taps[11];            /* 1-D Gaussian taps: ssim.py's window, normalised in float64, times the     */
+                                /* square root of the sum of its fp32 11x11 window (the caller computes them) */
+    float y_coef[3];            /* fp32 65.481/255, 128.553/255, 24.966/255: Y = round(fma chain of x*255 + 16) */
+    int32_t reserved0;
+    void* workspace;            /* grl_image_metrics_workspace_bytes(B, H, W, border) bytes, no initialisation */
+    int64_t workspace_bytes;
+    double* out;                /* [B][GRL_METRIC_COUNT] */
+} GrlMetricArgs;
+
+int64_t grl_image_metrics_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t border);
+int grl_image_metrics(void* stream, const GrlMetricArgs* args);
 
 /* Debug aid (ABI 21; no reference counterpart): fills the LDS of every CU with 0xFF bytes (fp32 / fp16 NaN) by a launch on
  * `stream`.  LDS keeps what the previous workgroup left in it; a kernel that reads LDS it has not written is otherwise right or
