@@ -9,7 +9,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgrl_hip.so")
-ABI_VERSION = 23
+ABI_VERSION = 24
 DT_F32, DT_BF16, DT_F16 = 0, 1, 2
 
 EPI_PLAIN, EPI_GELU, EPI_GROUPNORM, EPI_LN_RES, EPI_GELU_GRAD = 0, 1, 2, 3, 4
@@ -55,6 +55,7 @@ EXPORTS = [
     "grl_cpb_table_bwd",
     "grl_image_metrics_workspace_bytes",
     "grl_image_metrics",
+    "grl_demosaic_matlab",
     "grl_debug_dirty_lds",
     "grl_abi_version",
     "grl_build_info",
@@ -505,6 +506,18 @@ class GrlMetricArgs(_Strict):
     ]
 
 
+class GrlDemosaicArgs(_Strict):
+    _fields_ = [
+        ("plane", C.c_void_p * 4),
+        ("stride", C.c_int64 * 3),
+        ("N", C.c_int32),
+        ("h", C.c_int32),
+        ("w", C.c_int32),
+        ("reserved0", C.c_int32),
+        ("out", C.c_void_p),
+    ]
+
+
 _lib = None
 
 
@@ -606,6 +619,8 @@ def lib():
     L.grl_image_metrics_workspace_bytes.restype = C.c_int64
     L.grl_image_metrics.argtypes = [C.c_void_p, C.POINTER(GrlMetricArgs)]
     L.grl_image_metrics.restype = C.c_int
+    L.grl_demosaic_matlab.argtypes = [C.c_void_p, C.POINTER(GrlDemosaicArgs)]
+    L.grl_demosaic_matlab.restype = C.c_int
     L.grl_debug_dirty_lds.argtypes = [C.c_void_p]
     L.grl_debug_dirty_lds.restype = C.c_int
     _lib = L

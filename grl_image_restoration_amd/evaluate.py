@@ -10,9 +10,17 @@ Restates, for the MI355X module, the three pieces of the reference's evaluation 
   evaluate_folder   the validation loop over an LQ / GT image folder pair (whole image, or the reference's tiled
                     inference through ``tiling.forward_tiled``); with ``metric_group`` one of the reference's metric groups
                     (config/metric/*.yaml, ``metrics.image_metrics``) instead of PSNR-Y alone
+  task "dn" / "dm"  the tasks whose LQ the reference builds from the GT (``task_inputs``): the GT is cropped to multiples of 8
+                    (data/datasets/base_image.py:419-425); denoising adds the reference's seeded validation noise
+                    (restoration_dn.py:133-143), demosaicking mosaics the GT and demosaics it with ``dm_matlab`` on the device
+                    (restoration_dm.py:25-35, engines/base.py:126-128), the whole image before any tiling
 
     python -m grl_image_restoration_amd.evaluate --model base --geometry sr_ckpt_df2 --scale 4 \\
         --ckpt sr_grl_base_c3x4.ckpt --lq Set5/LRbicx4 --gt Set5/GTmod12 [--tile 256 --overlap 32] [--metric restorer]
+    python -m grl_image_restoration_amd.evaluate --task dm --model small --geometry dm --ckpt dm_grl_small.ckpt \\
+        --gt kodak24 --metric restorer
+    python -m grl_image_restoration_amd.evaluate --task dn --sigma 25 --model small --geometry dn_df4 \\
+        --ckpt dn_grl_small_c3s25.ckpt --gt kodak24 --noise-prefix Kodak24 --metric restorer
 """
 import argparse
 import os
@@ -135,19 +143,68 @@ def evaluate_pairs(model, pairs: Iterable[Tuple[torch.Tensor, torch.Tensor]], sc
     return {k: sum(o[k] for o in out) / len(out) for k in out[0]}
 
 
-def evaluate_folder(model, lq_dir: str, gt_dir: str, scale: int, tile: int = 0, overlap: int = 32, device: str = "cuda:0",
-                    verbose: bool = True, metric_group: Optional[str] = None, channels: int = 3):
-    """Mean PSNR-Y over the image pairs of two folders; with ``metric_group``, {metric name: mean} of that group.  ``channels`` 1
-    reads the images as grayscale."""
-    pairs = image_pairs(lq_dir, gt_dir)
+TASKS = ("sr", "dn", "dm")
+
+
+def gt_images(gt_dir: str) -> List[str]:
+    """The image files of a GT folder, sorted (the same listing as ``image_pairs``)."""
+    paths = sorted(os.path.join(gt_dir, f) for f in os.listdir(gt_dir) if f.lower().endswith(_IMG_EXT))
+    if not paths:
+        raise ValueError(f"{gt_dir}: no images")
+    return paths
+
+
+def task_inputs(gt_dir: str, task: str, channels: int = 3, sigma: Optional[float] = None, noise_prefix: Optional[str] = None,
+                device: str = "cuda:0"):
+    """(file name, LQ, GT) for every image of ``gt_dir`` under a task that synthesises its input ("dn" or "dm"), as the reference's
+    validation sets do: GT read as 8 bit and cropped to multiples of 8; "dn" adds ``tasks.dn_noise`` at ``sigma`` (keyed by
+    ``noise_prefix/<file name>``: the reference's test-set name, by default the folder's base name matched to it case-insensitively by
+    ``tasks.dn_test_set_name``, and the path that the set's test.json lists; on the CPU, in fp32, as the data set does), "dm"
+    runs ``tasks.demosaic_gt`` on ``device`` (RGB only)."""
+    from . import tasks
+
+    if task not in ("dn", "dm"):
+        raise ValueError(f"task {task!r} reads its LQ from a folder; synthesised tasks: dn, dm")
+    if task == "dn" and sigma is None:
+        raise ValueError("task dn needs a noise sigma")
+    if task == "dm" and channels != 3:
+        raise ValueError("task dm works on RGB images")
+    if noise_prefix is None:
+        noise_prefix = tasks.dn_test_set_name(os.path.basename(os.path.normpath(gt_dir)))
     mode = "L" if channels == 1 else "RGB"
+    for p in gt_images(gt_dir):
+        name = os.path.relpath(p, gt_dir)
+        gt = tasks.modcrop(_read_image(p, mode), 8).contiguous()
+        if task == "dn":
+            noise = tasks.dn_noise(gt.shape[1:], sigma, tasks.dn_noise_key(f"{noise_prefix}/{name}"))
+            lq = gt + noise.unsqueeze(0)
+        else:
+            lq = tasks.demosaic_gt(gt.to(device))
+        yield name, lq, gt
+
+
+def evaluate_folder(model, lq_dir: Optional[str], gt_dir: str, scale: int, tile: int = 0, overlap: int = 32, device: str = "cuda:0",
+                    verbose: bool = True, metric_group: Optional[str] = None, channels: int = 3, task: str = "sr",
+                    sigma: Optional[float] = None, noise_prefix: Optional[str] = None):
+    """Mean PSNR-Y over the image pairs of two folders; with ``metric_group``, {metric name: mean} of that group.  ``channels`` 1
+    reads the images as grayscale.  ``task`` "dn" / "dm" ignores ``lq_dir`` and builds the LQ from the GT (``task_inputs``;
+    ``scale`` must be 1)."""
+    if task not in TASKS:
+        raise ValueError(f"unknown task {task!r}: one of {TASKS}")
+    mode = "L" if channels == 1 else "RGB"
+    if task == "sr":
+        items = ((os.path.basename(lq_p), _read_image(lq_p, mode), _read_image(gt_p, mode)) for lq_p, gt_p in image_pairs(lq_dir, gt_dir))
+    else:
+        if scale != 1:
+            raise ValueError(f"task {task} restores at scale 1, got {scale}")
+        items = task_inputs(gt_dir, task, channels, sigma, noise_prefix, device)
     vals = []
-    for lq_p, gt_p in pairs:
-        v = evaluate_pairs(model, [(_read_image(lq_p, mode), _read_image(gt_p, mode))], scale, tile, overlap, device, metric_group)
+    for name, lq, gt in items:
+        v = evaluate_pairs(model, [(lq, gt)], scale, tile, overlap, device, metric_group)
         v = v[0] if metric_group is None else v
         vals.append(v)
         if verbose:
-            print(f"{os.path.basename(lq_p):32s} {_columns(v)}")
+            print(f"{name:32s} {_columns(v)}")
     if metric_group is None:
         mean = sum(vals) / len(vals)
     else:
@@ -170,9 +227,11 @@ def main(argv: Optional[List[str]] = None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--model", default="base", choices=["tiny", "small", "base"])
     ap.add_argument("--geometry", default="sr_ckpt_df2", help="a key of presets.GEOMETRIES")
-    ap.add_argument("--scale", type=int, default=4, help="1 for denoising / deblurring")
+    ap.add_argument("--task", default="sr", choices=TASKS,
+                    help="sr: LQ images from --lq (SR, deblurring, JPEG); dn / dm: the LQ is made from --gt (denoising, demosaicking)")
+    ap.add_argument("--scale", type=int, default=None, help="4 by default for --task sr; 1 for everything else")
     ap.add_argument("--ckpt", default=None, help="reference checkpoint (.ckpt / .pth); random init without it")
-    ap.add_argument("--lq", required=True)
+    ap.add_argument("--lq", default=None, help="LQ folder (--task sr only)")
     ap.add_argument("--gt", required=True)
     ap.add_argument("--tile", type=int, default=0)
     ap.add_argument("--overlap", type=int, default=32)
@@ -180,12 +239,28 @@ def main(argv: Optional[List[str]] = None):
     ap.add_argument("--metric", default=None, choices=sorted(GROUPS),
                     help="report this metric group of the reference (config/metric/*.yaml) instead of PSNR-Y alone")
     ap.add_argument("--channels", type=int, default=3, choices=[1, 3], help="1: grayscale model and images (dn_*_c1, jpeg_*_c1)")
+    ap.add_argument("--sigma", type=float, default=None, help="--task dn: noise level on the 0..255 scale (15, 25, 50)")
+    ap.add_argument("--noise-prefix", default=None,
+                    help="--task dn: the reference's test-set name (Set12, BSD68, CBSD68, Kodak24, McMaster, Urban100; case matters) "
+                         "that starts the noise seed key '<prefix>/<file name>'; a different prefix draws different noise.  Default: "
+                         "the --gt folder's name, matched case-insensitively to one of those")
     a = ap.parse_args(argv)
+    if a.task == "sr" and a.lq is None:
+        ap.error("--lq is required with --task sr")
+    if a.task != "sr" and a.lq is not None:
+        ap.error(f"--task {a.task} builds its LQ from --gt; --lq is not used")
+    if a.task == "dn" and a.sigma is None:
+        ap.error("--task dn needs --sigma")
+    if a.scale is None:
+        a.scale = 4 if a.task == "sr" else 1
+    if a.task != "sr" and a.scale != 1:
+        ap.error(f"--task {a.task} restores at --scale 1")
     model = GRL(**make_config(a.model, a.geometry, upscale=a.scale, in_channels=a.channels)).eval()
     if a.ckpt:
         load_checkpoint(model, a.ckpt)
     model = model.to(a.device)
-    return evaluate_folder(model, a.lq, a.gt, a.scale, a.tile, a.overlap, a.device, metric_group=a.metric, channels=a.channels)
+    return evaluate_folder(model, a.lq, a.gt, a.scale, a.tile, a.overlap, a.device, metric_group=a.metric, channels=a.channels,
+                           task=a.task, sigma=a.sigma, noise_prefix=a.noise_prefix)
 
 
 if __name__ == "__main__":

@@ -241,6 +241,9 @@ class GRL(nn.Module):
         #                                      fast 1.16e-3 -> + stage/after/last convs split 1.0e-3 -> + CAB conv1 split 8.2e-4
         #                                      (with the q/k projection split instead: 7.8e-4, but 4.0 instead of 5.6 MP/s)
         #          GRL-Small denoise           fast 1.14e-3 -> + stage/after/last convs split 7.2e-4
+        #          GRL-Small demosaic (8x8 windows, 32x32 stripes: the `dm` preset)
+        #                                      fast + those splits 1.07e-3 -> calibrated (_calibrated_plan, 6 of 16 blocks split) 5.4e-4,
+        #                                      +17 % time at 512x512; so narrow models with windows of 8 or less always calibrate
         #          GRL-Tiny                    high (fast + splits 6e-4 .. 8e-4, but 8e-3 at clamp scales)
         precision = os.environ.get("GRL_PRECISION", precision)
         if precision not in ("auto", "fast", "high"):
@@ -596,7 +599,12 @@ class GRL(nn.Module):
                     a = blk.attn
                     for t in (a.window_attn.attn_transform, a.stripe_attn.attn_transform1, a.stripe_attn.attn_transform2):
                         smax = max(smax, float(tables.clamped_scale(t.logit_scale).max()))
-            if smax > float(os.environ.get("GRL_NARROW_HIGH_SCALE", "25")):
+            if smax <= float(os.environ.get("GRL_NARROW_HIGH_SCALE", "25")) and self.window_size[0] <= 8:
+                # 8x8 windows (the demosaicking geometry): fp16 operands miss the 1e-3 bar even at random-init scales (GRL-Small
+                # 1.07e-3 against 7.1e-4 at the 16x16 denoising geometry), so the blocks are chosen by measurement here as well
+                if os.environ.get("GRL_CALIBRATE", "1") != "0":
+                    self._calibrate_narrow = True
+            elif smax > float(os.environ.get("GRL_NARROW_HIGH_SCALE", "25")):
                 # round 6: not `high` throughout any more -- the blocks are chosen by measurement (_calibrated_plan), everything split
                 # only if the probe asks for it; GRL_CALIBRATE=0 restores the blanket rule
                 if os.environ.get("GRL_CALIBRATE", "1") == "0":

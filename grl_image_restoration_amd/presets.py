@@ -1,7 +1,7 @@
 """Constructor presets for the GRL model family and the geometries the reference ships.
 
 Sources (reference tree): config/model/grl/grl_{tiny,small,base}.yaml, the experiment files
-config/experiment/{sr,dn,db_motion}/grl/*.yaml and the evaluation commands in
+config/experiment/{sr,dn,db_motion}/grl/*.yaml, config/experiment/dm/grl.yaml and the evaluation commands in
 scripts/grl/grl_test.md (which override window/stripe/anchor geometry per released checkpoint).
 See SURVEY.md appendix B for the file:line of every number below.
 """
@@ -60,6 +60,8 @@ GEOMETRIES = {
     "dn_df2": dict(window_size=32, stripe_size=[64, 128], stripe_groups=[None, None], anchor_window_down_factor=2),
     # motion deblurring Base (db_motion/grl_p480.yaml:33-44)
     "deblur": dict(window_size=12, stripe_size=[48, 96], stripe_groups=[None, None], anchor_window_down_factor=4),
+    # demosaicking Small (dm/grl.yaml:27-37, grl_test.md:11-15)
+    "dm": dict(window_size=8, stripe_size=[32, 32], stripe_groups=[None, None], anchor_window_down_factor=4),
 }
 
 _UPSAMPLER = {"tiny": "pixelshuffledirect", "small": "pixelshuffle", "base": "pixelshuffle"}

@@ -1,0 +1,174 @@
+"""Front ends of the tasks whose degraded (LQ) input the reference builds from the ground truth (GT) itself.
+
+  mosaic_bayer   utils/utils_mosaic.py:114-133      RGB -> packed RGGB mosaic (CFA4: planes R, G, G, B at half resolution),
+                 (mosaic_CFA_Bayer)                 what data/datasets/restoration_dm.py:25-35 feeds the demosaicking model
+  dm_matlab      utils/utils_mosaic.py:36-111       MATLAB's gradient-corrected linear demosaic of a CFA4 batch, applied by
+                                                    engines/base.py:126-128 before ``self.model(x)`` (training and evaluation)
+  demosaic_gt    both of the above                  the demosaicking LQ of a GT batch
+  modcrop        data/datasets/base_image.py:419-425   the validation GT crop to a multiple of ``modulo`` (8)
+  dn_noise_key   data/datasets/restoration_dn.py:133-143   the validation noise of the denoising task: numpy's MT19937 seeded
+  dn_noise                                          with the SHA-256 of the image name, drawn as N(0, sigma / 255)
+
+CUDA fp32 tensors go through ``grl_demosaic_matlab`` of libgrl_hip.so (csrc/demosaic.hip); there is no torch fallback for them.
+``demosaic_gt`` on CUDA is a single launch that reads the RGB image in place on the RGGB lattice, without forming the mosaic.  CPU
+tensors take the float64 torch restatement below, cast back to the input dtype.  On 8-bit inputs both paths are exact (the filter
+weights are dyadic) and therefore bitwise equal to each other and to the reference run in float64.  The noise is CPU numpy by
+design: only the reference's own generator stream reproduces its denoising PSNRs.
+"""
+import ctypes as C
+import hashlib
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+
+# ---- demosaicking --------------------------------------------------------------------------------------------------------------
+def mosaic_bayer(rgb: torch.Tensor) -> torch.Tensor:
+    """(N, 3, H, W) RGB -> (N, 4, H/2, W/2) packed RGGB mosaic: R at (even, even), G at (even, odd), G at (odd, even), B at
+    (odd, odd).  H and W must be even (the reference's slicing fails on odd sides as well)."""
+    _check_rgb(rgb)
+    return torch.stack(_lattice(rgb), 1)
+
+
+def _check_rgb(rgb: torch.Tensor):
+    if rgb.dim() != 4 or rgb.shape[1] != 3:
+        raise ValueError(f"need an (N, 3, H, W) RGB batch, got {tuple(rgb.shape)}")
+    if rgb.shape[-2] % 2 or rgb.shape[-1] % 2:
+        raise ValueError(f"the RGGB mosaic needs even sides, got {tuple(rgb.shape[-2:])}")
+
+
+def _lattice(rgb: torch.Tensor):
+    """The four RGGB planes of an RGB batch as strided views (no copy)."""
+    return rgb[:, 0, 0::2, 0::2], rgb[:, 1, 0::2, 1::2], rgb[:, 1, 1::2, 0::2], rgb[:, 2, 1::2, 1::2]
+
+
+def _check_packed(N: int, h: int, w: int):
+    if h < 2 or w < 2:
+        raise ValueError(f"dm_matlab needs a packed mosaic of at least 2 x 2 cells, got {h} x {w}")
+    if N < 1:
+        raise ValueError("empty batch")
+
+
+def dm_matlab(cfa4: torch.Tensor) -> torch.Tensor:
+    """(N, 4, h, w) packed RGGB mosaic -> (N, 3, 2h, 2w) RGB, as the reference's ``dm_matlab``: reflect padding by 2 of the
+    full-resolution mosaic, MATLAB's four gradient-corrected 5x5 filters, native samples kept."""
+    if cfa4.dim() != 4 or cfa4.shape[1] != 4:
+        raise ValueError(f"need an (N, 4, h, w) packed mosaic, got {tuple(cfa4.shape)}")
+    N, _, h, w = cfa4.shape
+    _check_packed(N, h, w)
+    if cfa4.is_cuda:
+        return hip_demosaic([cfa4[:, i] for i in range(4)])
+    return _torch_dm_matlab(cfa4)
+
+
+def demosaic_gt(rgb: torch.Tensor) -> torch.Tensor:
+    """``dm_matlab(mosaic_bayer(rgb))``: the demosaicking task's model input for a GT batch.  On CUDA one launch reads ``rgb`` on
+    the RGGB lattice in place."""
+    _check_rgb(rgb)
+    N, _, H, W = rgb.shape
+    _check_packed(N, H // 2, W // 2)
+    if rgb.is_cuda:
+        return hip_demosaic(list(_lattice(rgb)))
+    return dm_matlab(mosaic_bayer(rgb))
+
+
+def hip_demosaic(planes) -> torch.Tensor:
+    """One ``grl_demosaic_matlab`` launch on four (N, h, w) fp32 CUDA views with equal strides (R, G, G, B); the sizes are checked
+    by the library."""
+    from . import _lib
+
+    L = _lib.lib()
+    p0 = planes[0]
+    if any(p.dtype != torch.float32 for p in planes):
+        raise TypeError(f"grl_demosaic_matlab takes fp32 tensors, got {p0.dtype}")
+    if any(p.shape != p0.shape or p.stride() != p0.stride() or p.device != p0.device for p in planes):
+        raise ValueError("the four mosaic planes need one shape, one stride triple and one device")
+    N, h, w = p0.shape
+    out = torch.empty(N, 3, 2 * h, 2 * w, dtype=torch.float32, device=p0.device)
+    args = _lib.GrlDemosaicArgs(plane=(C.c_void_p * 4)(*[p.data_ptr() for p in planes]), stride=(C.c_int64 * 3)(*p0.stride()),
+                                N=N, h=h, w=w, out=out.data_ptr())
+    _lib.check(L.grl_demosaic_matlab(_lib.stream_ptr(), C.byref(args)), "grl_demosaic_matlab")
+    return out
+
+
+_KERNELS = None
+
+
+def matlab_kernels() -> torch.Tensor:
+    """(4, 1, 5, 5) float64: the four 5x5 filters of utils_mosaic.py:44-86 (all scaled by 1/8) as correlation kernels, indexed
+    [dy + 2][dx + 2]: 0 G at R / B sites, 1 R / B at G sites along the row, 2 its transpose (along the column), 3 R at B / B at
+    R sites."""
+    global _KERNELS
+    if _KERNELS is None:
+        k = torch.zeros(4, 5, 5, dtype=torch.float64)
+        cross1 = [(1, 2), (3, 2), (2, 1), (2, 3)]          # the four neighbours at distance 1
+        cross2 = [(0, 2), (4, 2), (2, 0), (2, 4)]          # ... and at distance 2
+        diag = [(1, 1), (1, 3), (3, 1), (3, 3)]
+        k[0, 2, 2] = 4
+        for i, j in cross1:
+            k[0, i, j] = 2
+        for i, j in cross2:
+            k[0, i, j] = -1
+        k[1, 2, 2] = 5
+        k[1, 2, 1] = k[1, 2, 3] = 4
+        k[1, 2, 0] = k[1, 2, 4] = -1
+        k[1, 0, 2] = k[1, 4, 2] = 0.5
+        for i, j in diag:
+            k[1, i, j] = -1
+        k[2] = k[1].t()
+        k[3, 2, 2] = 6
+        for i, j in diag:
+            k[3, i, j] = 2
+        for i, j in cross2:
+            k[3, i, j] = -1.5
+        _KERNELS = (k / 8).unsqueeze(1)
+    return _KERNELS
+
+
+def _torch_dm_matlab(cfa4: torch.Tensor) -> torch.Tensor:
+    N, _, h, w = cfa4.shape
+    x = cfa4.double()
+    mosaic = torch.empty(N, 1, 2 * h, 2 * w, dtype=torch.float64, device=x.device)
+    for i, (r, c) in enumerate(((0, 0), (0, 1), (1, 0), (1, 1))):
+        mosaic[:, 0, r::2, c::2] = x[:, i]
+    conv = F.conv2d(F.pad(mosaic, (2, 2, 2, 2), mode="reflect"), matlab_kernels().to(x.device))
+    rgb = mosaic.repeat(1, 3, 1, 1)
+    # (channel, cell row, cell column) <- filter; the remaining entry of each site is its native sample
+    fill = [(1, 0, 0, 0), (1, 1, 1, 0),                     # G at R and B sites
+            (0, 0, 1, 1), (0, 1, 0, 2), (0, 1, 1, 3),       # R at the G sites and at B
+            (2, 0, 1, 2), (2, 1, 0, 1), (2, 0, 0, 3)]       # B at the G sites and at R
+    for ch, r, c, k in fill:
+        rgb[:, ch, r::2, c::2] = conv[:, k, r::2, c::2]
+    return rgb.to(cfa4.dtype)
+
+
+# ---- validation crop and denoising noise ---------------------------------------------------------------------------------------
+def modcrop(img: torch.Tensor, modulo: int = 8) -> torch.Tensor:
+    """Top-left crop of the last two dimensions to multiples of ``modulo`` (a view)."""
+    H, W = img.shape[-2:]
+    return img[..., : H // modulo * modulo, : W // modulo * modulo]
+
+
+# the reference's test-set names (restoration_dn.py:69-84): they start the noise seed key, case included
+DN_TEST_SETS = ("Set12", "BSD68", "CBSD68", "Kodak24", "McMaster", "Urban100")
+
+
+def dn_test_set_name(folder: str) -> str:
+    """The reference's name of a denoising test set from a folder name, matched case-insensitively ("kodak24" -> "Kodak24"); other
+    names are returned as they are."""
+    return {n.lower(): n for n in DN_TEST_SETS}.get(folder.lower(), folder)
+
+
+def dn_noise_key(name: str) -> str:
+    """The string the reference seeds an image's validation noise with: its name up to the first underscore (the reference's names
+    are ``"<TestSet>/<path in test.json>"``)."""
+    return name.split("_")[0]
+
+
+def dn_noise(shape, sigma: float, key: str) -> torch.Tensor:
+    """The reference's validation noise for one (C, H, W) image, bit for bit: numpy's RandomState seeded with the SHA-256 digest of
+    ``key`` read as eight uint32 words, ``normal(0, sigma / 255, shape)`` in float64, cast to fp32 (CPU)."""
+    seed = np.frombuffer(hashlib.sha256(key.encode("utf-8")).digest(), dtype="uint32")
+    noise = np.random.RandomState(seed).normal(0, sigma / 255, tuple(shape))
+    return torch.from_numpy(noise).float()

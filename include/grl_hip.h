@@ -23,7 +23,7 @@ extern "C" {
 
 #define GRL_ERR_BAD_ARG (-1)
 #define GRL_ERR_UNSUPPORTED (-2)
-#define GRL_ABI_VERSION 23
+#define GRL_ABI_VERSION 24
 
 /* element kinds of activation / weight buffers */
 enum { GRL_DT_F32 = 0, GRL_DT_BF16 = 1, GRL_DT_F16 = 2 };
@@ -714,6 +714,25 @@ typedef struct GrlMetricArgs {
 
 int64_t grl_image_metrics_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t border);
 int grl_image_metrics(void* stream, const GrlMetricArgs* args);
+
+/* Demosaicking of an RGGB Bayer mosaic by MATLAB's gradient-corrected linear filters (ABI 24; the input front end of the
+ * demosaicking task, not the network):
+ *   replaces  dm_matlab   utils/utils_mosaic.py:36-111 (applied to every batch by engines/base.py:126-128)
+ * plane[0..3]: R (even rows, even columns), G (even, odd), G (odd, even), B (odd, odd) of the mosaic, each N x h x w fp32 with the
+ * element strides `stride` (batch, row, column) shared by all four: the packed (N, 4, h, w) CFA4 tensor of the reference, or an RGB
+ * image (N, 3, 2h, 2w) read in place on the RGGB lattice (strides 3*4hw, 4w, 2).  out: contiguous fp32 (N, 3, 2h, 2w), 8-byte aligned.
+ * The full-resolution mosaic is reflect-padded by 2 (as torch's "reflect") and every interpolated sample is its 5x5 stencil summed in
+ * fp64 and rounded once to fp32 (on 8-bit inputs: bitwise the reference run in float64, cast to fp32); native samples are copied.
+ * Errors (GRL_ERR_BAD_ARG): a null pointer, N <= 0, h < 2 or w < 2 (the reference's reflection fails there too). */
+typedef struct GrlDemosaicArgs {
+    const float* plane[4];      /* R, G at even rows, G at odd rows, B                        */
+    int64_t stride[3];          /* element strides of batch, packed row, packed column          */
+    int32_t N, h, w;            /* batch and packed size; the output is 2h x 2w                 */
+    int32_t reserved0;
+    float* out;
+} GrlDemosaicArgs;
+
+int grl_demosaic_matlab(void* stream, const GrlDemosaicArgs* args);
 
 /* Debug aid (ABI 21; no reference counterpart): fills the LDS of every CU with 0xFF bytes (fp32 / fp16 NaN) by a launch on
  * `stream`.  LDS keeps what the previous workgroup left in it; a kernel that reads LDS it has not written is otherwise right or
