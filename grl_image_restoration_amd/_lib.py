@@ -9,7 +9,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgrl_hip.so")
-ABI_VERSION = 24
+ABI_VERSION = 25
 DT_F32, DT_BF16, DT_F16 = 0, 1, 2
 
 EPI_PLAIN, EPI_GELU, EPI_GROUPNORM, EPI_LN_RES, EPI_GELU_GRAD = 0, 1, 2, 3, 4
@@ -56,6 +56,7 @@ EXPORTS = [
     "grl_image_metrics_workspace_bytes",
     "grl_image_metrics",
     "grl_demosaic_matlab",
+    "grl_imresize",
     "grl_debug_dirty_lds",
     "grl_abi_version",
     "grl_build_info",
@@ -518,6 +519,23 @@ class GrlDemosaicArgs(_Strict):
     ]
 
 
+class GrlResizeArgs(_Strict):
+    _fields_ = [
+        ("src", C.c_void_p),
+        ("stride", C.c_int64 * 4),
+        ("N", C.c_int32), ("C", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+        ("out_h", C.c_int32), ("out_w", C.c_int32),
+        ("taps_h", C.c_int32), ("taps_w", C.c_int32),
+        ("wh", C.c_void_p),
+        ("ih", C.c_void_p),
+        ("ww", C.c_void_p),
+        ("iw", C.c_void_p),
+        ("out", C.c_void_p),
+        ("quantize", C.c_int32),
+        ("reserved0", C.c_int32),
+    ]
+
+
 _lib = None
 
 
@@ -621,6 +639,8 @@ def lib():
     L.grl_image_metrics.restype = C.c_int
     L.grl_demosaic_matlab.argtypes = [C.c_void_p, C.POINTER(GrlDemosaicArgs)]
     L.grl_demosaic_matlab.restype = C.c_int
+    L.grl_imresize.argtypes = [C.c_void_p, C.POINTER(GrlResizeArgs)]
+    L.grl_imresize.restype = C.c_int
     L.grl_debug_dirty_lds.argtypes = [C.c_void_p]
     L.grl_debug_dirty_lds.restype = C.c_int
     _lib = L

@@ -14,6 +14,9 @@ Restates, for the MI355X module, the three pieces of the reference's evaluation 
                     (data/datasets/base_image.py:419-425); denoising adds the reference's seeded validation noise
                     (restoration_dn.py:133-143), demosaicking mosaics the GT and demosaics it with ``dm_matlab`` on the device
                     (restoration_dm.py:25-35, engines/base.py:126-128), the whole image before any tiling
+  task "sr_bicubic" classical SR scored from the GT folder alone: the GT is cropped to a multiple of the scale and the LQ is its
+                    MATLAB-bicubic downscale, 8-bit quantised (``tasks.sr_lq``; restoration_sr.py:130-141,
+                    utils/matlab_functions.py:91-188), made on the device
 
     python -m grl_image_restoration_amd.evaluate --model base --geometry sr_ckpt_df2 --scale 4 \\
         --ckpt sr_grl_base_c3x4.ckpt --lq Set5/LRbicx4 --gt Set5/GTmod12 [--tile 256 --overlap 32] [--metric restorer]
@@ -21,6 +24,8 @@ Restates, for the MI355X module, the three pieces of the reference's evaluation 
         --gt kodak24 --metric restorer
     python -m grl_image_restoration_amd.evaluate --task dn --sigma 25 --model small --geometry dn_df4 \\
         --ckpt dn_grl_small_c3s25.ckpt --gt kodak24 --noise-prefix Kodak24 --metric restorer
+    python -m grl_image_restoration_amd.evaluate --task sr_bicubic --scale 4 --model base --geometry sr_ckpt_df2 \\
+        --ckpt sr_grl_base_c3x4.ckpt --gt Set5/original --metric restorer
 """
 import argparse
 import os
@@ -143,7 +148,7 @@ def evaluate_pairs(model, pairs: Iterable[Tuple[torch.Tensor, torch.Tensor]], sc
     return {k: sum(o[k] for o in out) / len(out) for k in out[0]}
 
 
-TASKS = ("sr", "dn", "dm")
+TASKS = ("sr", "dn", "dm", "sr_bicubic")
 
 
 def gt_images(gt_dir: str) -> List[str]:
@@ -155,16 +160,19 @@ def gt_images(gt_dir: str) -> List[str]:
 
 
 def task_inputs(gt_dir: str, task: str, channels: int = 3, sigma: Optional[float] = None, noise_prefix: Optional[str] = None,
-                device: str = "cuda:0"):
-    """(file name, LQ, GT) for every image of ``gt_dir`` under a task that synthesises its input ("dn" or "dm"), as the reference's
+                device: str = "cuda:0", scale: int = 1):
+    """(file name, LQ, GT) for every image of ``gt_dir`` under a task that synthesises its input ("dn", "dm" or "sr_bicubic"), as the reference's
     validation sets do: GT read as 8 bit and cropped to multiples of 8; "dn" adds ``tasks.dn_noise`` at ``sigma`` (keyed by
     ``noise_prefix/<file name>``: the reference's test-set name, by default the folder's base name matched to it case-insensitively by
     ``tasks.dn_test_set_name``, and the path that the set's test.json lists; on the CPU, in fp32, as the data set does), "dm"
-    runs ``tasks.demosaic_gt`` on ``device`` (RGB only)."""
+    runs ``tasks.demosaic_gt`` on ``device`` (RGB only).  "sr_bicubic" crops the GT to a multiple of ``scale`` instead (the
+    reference's ``modcrop(img_gt, self.scale)``, restoration_sr.py:130) and makes the LQ with ``tasks.sr_lq`` on ``device``."""
     from . import tasks
 
-    if task not in ("dn", "dm"):
-        raise ValueError(f"task {task!r} reads its LQ from a folder; synthesised tasks: dn, dm")
+    if task not in ("dn", "dm", "sr_bicubic"):
+        raise ValueError(f"task {task!r} reads its LQ from a folder; synthesised tasks: dn, dm, sr_bicubic")
+    if task == "sr_bicubic" and int(scale) < 2:
+        raise ValueError(f"task sr_bicubic needs a scale above 1, got {scale}")
     if task == "dn" and sigma is None:
         raise ValueError("task dn needs a noise sigma")
     if task == "dm" and channels != 3:
@@ -174,6 +182,10 @@ def task_inputs(gt_dir: str, task: str, channels: int = 3, sigma: Optional[float
     mode = "L" if channels == 1 else "RGB"
     for p in gt_images(gt_dir):
         name = os.path.relpath(p, gt_dir)
+        if task == "sr_bicubic":
+            gt = tasks.modcrop(_read_image(p, mode), int(scale)).contiguous()
+            yield name, tasks.sr_lq(gt.to(device), int(scale))[0], gt
+            continue
         gt = tasks.modcrop(_read_image(p, mode), 8).contiguous()
         if task == "dn":
             noise = tasks.dn_noise(gt.shape[1:], sigma, tasks.dn_noise_key(f"{noise_prefix}/{name}"))
@@ -188,12 +200,14 @@ def evaluate_folder(model, lq_dir: Optional[str], gt_dir: str, scale: int, tile:
                     sigma: Optional[float] = None, noise_prefix: Optional[str] = None):
     """Mean PSNR-Y over the image pairs of two folders; with ``metric_group``, {metric name: mean} of that group.  ``channels`` 1
     reads the images as grayscale.  ``task`` "dn" / "dm" ignores ``lq_dir`` and builds the LQ from the GT (``task_inputs``;
-    ``scale`` must be 1)."""
+    ``scale`` must be 1); so does "sr_bicubic", at a ``scale`` above 1."""
     if task not in TASKS:
         raise ValueError(f"unknown task {task!r}: one of {TASKS}")
     mode = "L" if channels == 1 else "RGB"
     if task == "sr":
         items = ((os.path.basename(lq_p), _read_image(lq_p, mode), _read_image(gt_p, mode)) for lq_p, gt_p in image_pairs(lq_dir, gt_dir))
+    elif task == "sr_bicubic":
+        items = task_inputs(gt_dir, task, channels, device=device, scale=scale)
     else:
         if scale != 1:
             raise ValueError(f"task {task} restores at scale 1, got {scale}")
@@ -228,8 +242,9 @@ def main(argv: Optional[List[str]] = None):
     ap.add_argument("--model", default="base", choices=["tiny", "small", "base"])
     ap.add_argument("--geometry", default="sr_ckpt_df2", help="a key of presets.GEOMETRIES")
     ap.add_argument("--task", default="sr", choices=TASKS,
-                    help="sr: LQ images from --lq (SR, deblurring, JPEG); dn / dm: the LQ is made from --gt (denoising, demosaicking)")
-    ap.add_argument("--scale", type=int, default=None, help="4 by default for --task sr; 1 for everything else")
+                    help="sr: LQ images from --lq (SR, deblurring, JPEG); dn / dm / sr_bicubic: the LQ is made from --gt (denoising, "
+                         "demosaicking, classical SR by MATLAB-bicubic downscaling at --scale)")
+    ap.add_argument("--scale", type=int, default=None, help="4 by default for --task sr / sr_bicubic; 1 for everything else")
     ap.add_argument("--ckpt", default=None, help="reference checkpoint (.ckpt / .pth); random init without it")
     ap.add_argument("--lq", default=None, help="LQ folder (--task sr only)")
     ap.add_argument("--gt", required=True)
@@ -252,9 +267,11 @@ def main(argv: Optional[List[str]] = None):
     if a.task == "dn" and a.sigma is None:
         ap.error("--task dn needs --sigma")
     if a.scale is None:
-        a.scale = 4 if a.task == "sr" else 1
-    if a.task != "sr" and a.scale != 1:
+        a.scale = 4 if a.task in ("sr", "sr_bicubic") else 1
+    if a.task in ("dn", "dm") and a.scale != 1:
         ap.error(f"--task {a.task} restores at --scale 1")
+    if a.task == "sr_bicubic" and a.scale < 2:
+        ap.error("--task sr_bicubic needs a --scale above 1")
     model = GRL(**make_config(a.model, a.geometry, upscale=a.scale, in_channels=a.channels)).eval()
     if a.ckpt:
         load_checkpoint(model, a.ckpt)

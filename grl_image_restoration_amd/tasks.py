@@ -8,15 +8,23 @@
   modcrop        data/datasets/base_image.py:419-425   the validation GT crop to a multiple of ``modulo`` (8)
   dn_noise_key   data/datasets/restoration_dn.py:133-143   the validation noise of the denoising task: numpy's MT19937 seeded
   dn_noise                                          with the SHA-256 of the image name, drawn as N(0, sigma / 255)
+  resize_tables  utils/matlab_functions.py:20-88    weights and (reflected, zero-based) input indices of MATLAB's bicubic resize along
+                 (calculate_weights_indices)        one axis, float64; the symmetric padding of lines 137-148 / 161-172 is in the indices
+  imresize       utils/matlab_functions.py:91-188   MATLAB's antialiased bicubic ``imresize`` of a batch, rows then columns
+  sr_lq          data/datasets/restoration_sr.py:130-141   the classical-SR LQ of a GT batch: modcrop to the scale, imresize by
+                                                    1 / scale, 8-bit quantisation (``tensor_round``: what an LQ image file holds)
 
 CUDA fp32 tensors go through ``grl_demosaic_matlab`` of libgrl_hip.so (csrc/demosaic.hip); there is no torch fallback for them.
 ``demosaic_gt`` on CUDA is a single launch that reads the RGB image in place on the RGGB lattice, without forming the mosaic.  CPU
 tensors take the float64 torch restatement below, cast back to the input dtype.  On 8-bit inputs both paths are exact (the filter
 weights are dyadic) and therefore bitwise equal to each other and to the reference run in float64.  The noise is CPU numpy by
-design: only the reference's own generator stream reproduces its denoising PSNRs.
+design: only the reference's own generator stream reproduces its denoising PSNRs.  ``imresize`` follows the same rule: CUDA fp32
+tensors go through ``grl_imresize`` (csrc/imresize.hip, one launch, fp64 sums, one rounding), CPU tensors through a float64 gather
+and sum by the same tables; the two agree to an fp32 rounding, not bitwise (cubic weights are not dyadic).
 """
 import ctypes as C
 import hashlib
+import math
 
 import numpy as np
 import torch
@@ -172,3 +180,141 @@ def dn_noise(shape, sigma: float, key: str) -> torch.Tensor:
     seed = np.frombuffer(hashlib.sha256(key.encode("utf-8")).digest(), dtype="uint32")
     noise = np.random.RandomState(seed).normal(0, sigma / 255, tuple(shape))
     return torch.from_numpy(noise).float()
+
+
+# ---- MATLAB bicubic imresize and the classical-SR LQ ---------------------------------------------------------------------------
+def _cubic(x: torch.Tensor) -> torch.Tensor:
+    """matlab_functions.py:10-17, same operation order."""
+    absx = torch.abs(x)
+    absx2 = absx**2
+    absx3 = absx**3
+    return (1.5 * absx3 - 2.5 * absx2 + 1) * ((absx <= 1).type_as(absx)) + (-0.5 * absx3 + 2.5 * absx2 - 4 * absx + 2) * (
+        ((absx > 1) * (absx <= 2)).type_as(absx))
+
+
+_TABLES = {}
+_DEVICE_TABLES = {}
+
+
+def resize_tables(in_len: int, out_len: int, scale: float, antialiasing: bool = True, axis: str = "axis"):
+    """(weights float64 (out_len, taps), indices int64 (out_len, taps)) of MATLAB's bicubic resize along one axis:
+    ``out[o] = sum_t weights[o, t] * in[indices[o, t]]``.  The reference's calculate_weights_indices in float64, operation for
+    operation; of its ``ceil(kernel_width) + 2`` tap columns the first and the last carry no weight (their distance to the centre
+    is at least half the kernel width) and are dropped as the reference drops them.  The indices are zero-based and already
+    reflected the way ``imresize`` pads symmetrically (-1 -> 0, -2 -> 1, n -> n-1, n+1 -> n-2).  An axis shorter than that padding
+    raises ValueError (the reference fails in a ``copy_`` there).  ``axis`` only names the axis in that message.  Cached."""
+    key = (int(in_len), int(out_len), float(scale), bool(antialiasing))
+    if key in _TABLES:
+        return _TABLES[key]
+    if in_len < 1 or out_len < 1 or not scale > 0:
+        raise ValueError(f"resize_tables: need positive lengths and scale, got {in_len}, {out_len}, {scale}")
+    f64 = torch.float64
+    kernel_width = 4.0
+    shrink = scale < 1 and antialiasing
+    if shrink:
+        kernel_width = kernel_width / scale
+    x = torch.linspace(1, out_len, out_len, dtype=f64)
+    u = x / scale + 0.5 * (1 - 1 / scale)
+    left = torch.floor(u - kernel_width / 2)
+    p = math.ceil(kernel_width) + 2
+    indices = left.view(out_len, 1).expand(out_len, p) + torch.linspace(0, p - 1, p, dtype=f64).view(1, p).expand(out_len, p)
+    distance = u.view(out_len, 1).expand(out_len, p) - indices
+    weights = scale * _cubic(distance * scale) if shrink else _cubic(distance)
+    weights = weights / torch.sum(weights, 1).view(out_len, 1).expand(out_len, p)
+    if float(weights[:, 0].abs().max()) > 1e-15 or float(weights[:, -1].abs().max()) > 1e-15:
+        raise AssertionError("resize_tables: an outer tap column carries weight")
+    weights = weights[:, 1 : p - 1].contiguous()
+    idx = indices[:, 1 : p - 1].long() - 1                         # zero-based, before the reflection
+    need = max(int(-idx.min()), int(idx.max()) - (in_len - 1), 0)
+    if need > in_len:
+        raise ValueError(f"imresize: {axis} has {in_len} pixels, but its symmetric padding at scale {scale:g} takes {need}: "
+                         f"the minimum length is {need}")
+    idx = torch.where(idx < 0, -idx - 1, idx)
+    idx = torch.where(idx >= in_len, 2 * in_len - 1 - idx, idx).contiguous()
+    _TABLES[key] = (weights, idx)
+    return _TABLES[key]
+
+
+def _device_tables(key, device):
+    k = key + (str(device),)
+    if k not in _DEVICE_TABLES:
+        w, i = resize_tables(*key)
+        _DEVICE_TABLES[k] = (w.to(device), i.to(torch.int32).to(device))
+    return _DEVICE_TABLES[k]
+
+
+def _round8(img: torch.Tensor) -> torch.Tensor:
+    """The reference's ``tensor_round`` (utils/utils_image.py:30-33), out of place."""
+    return (img.clamp(0.0, 1.0) * 255.0).round() / 255.0
+
+
+def imresize(img: torch.Tensor, scale: float, antialiasing: bool = True, quantize: bool = False) -> torch.Tensor:
+    """MATLAB's bicubic ``imresize`` of an (N, C, H, W) or (C, H, W) image by ``scale`` (both axes): output
+    ``ceil(H * scale) x ceil(W * scale)``, rows first, then columns, as the reference.  ``quantize`` applies ``tensor_round``
+    (8-bit levels) to the result.  CUDA tensors must be fp32 and take one ``grl_imresize`` launch, in place on any strided view;
+    CPU tensors are gathered and summed in float64 and cast back to their dtype."""
+    squeeze = img.dim() == 3
+    if squeeze:
+        img = img.unsqueeze(0)
+    if img.dim() != 4:
+        raise ValueError(f"need an (N, C, H, W) or (C, H, W) image, got {tuple(img.shape)}")
+    N, Cn, H, W = img.shape
+    if N < 1 or Cn < 1:
+        raise ValueError("empty batch")
+    out_h, out_w = math.ceil(H * scale), math.ceil(W * scale)
+    kh, kw = (H, out_h, float(scale), bool(antialiasing)), (W, out_w, float(scale), bool(antialiasing))
+    resize_tables(*kh, axis="the height")
+    resize_tables(*kw, axis="the width")
+    if img.is_cuda:
+        out = hip_resize(img, _device_tables(kh, img.device), _device_tables(kw, img.device), quantize)
+    else:
+        out = _torch_resize(img, resize_tables(*kh), resize_tables(*kw)).to(img.dtype)
+        if quantize:
+            out = _round8(out)
+    return out[0] if squeeze else out
+
+
+def _torch_resize(img: torch.Tensor, rows, cols) -> torch.Tensor:
+    """Float64 restatement: gather by the index table, multiply, sum; rows then columns.  Works on any device."""
+    (wh, ih), (ww, iw) = rows, cols
+    x = img.double()
+    N, Cn, H, W = x.shape
+    wh, ih, ww, iw = wh.to(x.device), ih.to(x.device).long(), ww.to(x.device), iw.to(x.device).long()
+    x = (x[:, :, ih.reshape(-1), :].view(N, Cn, ih.shape[0], ih.shape[1], W) * wh.view(1, 1, *wh.shape, 1)).sum(3)
+    return (x[..., iw.reshape(-1)].view(N, Cn, ih.shape[0], iw.shape[0], iw.shape[1]) * ww).sum(-1)
+
+
+def hip_resize(img: torch.Tensor, rows, cols, quantize: bool = False) -> torch.Tensor:
+    """One ``grl_imresize`` launch: ``img`` an (N, C, H, W) fp32 CUDA tensor or view, ``rows`` / ``cols`` (float64 weights, int32
+    indices) on the same device, (out_len, taps) each.  The sizes are checked by the library."""
+    from . import _lib
+
+    L = _lib.lib()
+    if img.dtype != torch.float32:
+        raise TypeError(f"grl_imresize takes fp32 tensors, got {img.dtype}")
+    (wh, ih), (ww, iw) = rows, cols
+    for w, i in (rows, cols):
+        if w.dtype != torch.float64 or i.dtype != torch.int32 or w.shape != i.shape or w.dim() != 2 or w.device != img.device:
+            raise ValueError("resize tables: float64 weights and int32 indices of one (out_len, taps) shape on the image's device")
+    wh, ih, ww, iw = wh.contiguous(), ih.contiguous(), ww.contiguous(), iw.contiguous()
+    N, Cn, H, W = img.shape
+    out = torch.empty(N, Cn, wh.shape[0], ww.shape[0], dtype=torch.float32, device=img.device)
+    args = _lib.GrlResizeArgs(src=img.data_ptr(), stride=(C.c_int64 * 4)(*img.stride()), N=N, C=Cn, H=H, W=W,
+                              out_h=wh.shape[0], out_w=ww.shape[0], taps_h=wh.shape[1], taps_w=ww.shape[1],
+                              wh=wh.data_ptr(), ih=ih.data_ptr(), ww=ww.data_ptr(), iw=iw.data_ptr(), out=out.data_ptr(),
+                              quantize=int(bool(quantize)))
+    _lib.check(L.grl_imresize(_lib.stream_ptr(), C.byref(args)), "grl_imresize")
+    return out
+
+
+def sr_lq(gt: torch.Tensor, scale: int, quantize: bool = True):
+    """The classical-SR LQ of a GT batch as the reference builds it: ``modcrop(gt, scale)``, then ``imresize`` by ``1 / scale``,
+    8-bit quantised by default.  Returns ``(lq, gt_cropped)``; ``gt_cropped`` is a view of ``gt``."""
+    scale = int(scale)
+    if scale < 1:
+        raise ValueError(f"sr_lq: scale must be a positive integer, got {scale}")
+    gtc = modcrop(gt, scale)
+    lq = imresize(gtc, 1 / scale, True, quantize)
+    if lq.shape[-2] * scale != gtc.shape[-2] or lq.shape[-1] * scale != gtc.shape[-1]:
+        raise RuntimeError(f"sr_lq: LQ {tuple(lq.shape[-2:])} x {scale} != GT {tuple(gtc.shape[-2:])}")
+    return lq, gtc

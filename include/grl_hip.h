@@ -23,7 +23,7 @@ extern "C" {
 
 #define GRL_ERR_BAD_ARG (-1)
 #define GRL_ERR_UNSUPPORTED (-2)
-#define GRL_ABI_VERSION 24
+#define GRL_ABI_VERSION 25
 
 /* element kinds of activation / weight buffers */
 enum { GRL_DT_F32 = 0, GRL_DT_BF16 = 1, GRL_DT_F16 = 2 };
@@ -733,6 +733,36 @@ typedef struct GrlDemosaicArgs {
 } GrlDemosaicArgs;
 
 int grl_demosaic_matlab(void* stream, const GrlDemosaicArgs* args);
+
+/* Separable resampling by per-axis tap tables: MATLAB's antialiased bicubic imresize (ABI 25; the LQ synthesis of classical SR):
+ *   replaces  imresize               utils/matlab_functions.py:91-188 (the double loop over output rows and columns)
+ *             its callers            data/datasets/restoration_sr.py:130-141, utils/utils_bsr/utils_sisr.py:210-219,
+ *                                    utils/metrics/niqe.py:470
+ * The caller computes the tables once per (input length, scale, antialiasing) in float64 -- calculate_weights_indices,
+ * matlab_functions.py:20-88, with the symmetric padding of lines 137-148 / 161-172 resolved into zero-based input indices -- and
+ * uploads them: for output row o, wh[o][0..taps_h) and ih[o][0..taps_h); for output column o, ww[o][..] and iw[o][..].  The
+ * kernel is scale-agnostic (down- and upsampling, any factor; indices outside the image are clamped).
+ * src: fp32, read in place through four ELEMENT strides (batch, channel, row, column): crops, channels-last tensors, views.
+ * out: contiguous fp32 (N, C, out_h, out_w).  Rows first, columns second; every weighted sum is accumulated in fp64, the row
+ * pass result is held in fp64, and an output is rounded once to fp32.  quantize != 0 fuses the reference's tensor_round
+ * (utils/utils_image.py:30-33: clamp to [0, 1], x 255, round half to even, / 255, in fp32) into the store.
+ * Errors (GRL_ERR_BAD_ARG): a null pointer, a non-positive size, taps < 1, misaligned tables, a grid beyond 2^31 - 1 workgroups. */
+typedef struct GrlResizeArgs {
+    const float* src;
+    int64_t stride[4];          /* element strides of batch, channel, row, column                 */
+    int32_t N, C, H, W;
+    int32_t out_h, out_w;
+    int32_t taps_h, taps_w;
+    const double* wh;           /* [out_h][taps_h] row weights                                    */
+    const int32_t* ih;          /* [out_h][taps_h] input rows, zero-based, reflection resolved    */
+    const double* ww;           /* [out_w][taps_w] column weights                                 */
+    const int32_t* iw;          /* [out_w][taps_w] input columns                                  */
+    float* out;
+    int32_t quantize;
+    int32_t reserved0;
+} GrlResizeArgs;
+
+int grl_imresize(void* stream, const GrlResizeArgs* args);
 
 /* Debug aid (ABI 21; no reference counterpart): fills the LDS of every CU with 0xFF bytes (fp32 / fp16 NaN) by a launch on
  * `stream`.  LDS keeps what the previous workgroup left in it; a kernel that reads LDS it has not written is otherwise right or

@@ -1,0 +1,144 @@
+"""tasks.resize_tables / imresize / sr_lq on the CPU against what the reference's MATLAB-style ``imresize`` produces
+(tests/golden/tasks/{imresize,sr_pipeline}.npz, written by tools/make_golden_resize.py: ``ref32`` the reference as it is, ``ref64``
+its own float64 tables summed in float64), the GrlResizeArgs C-ABI struct and the evaluate CLI's sr_bicubic options."""
+import ctypes
+import math
+import os
+import subprocess
+
+import pytest
+import torch
+
+from grl_image_restoration_amd import _lib, evaluate as EV, tasks as T
+from tests.test_tasks import ROOT, golden
+
+# one rounding of a value below 2 to fp32 is at most 2^-24 ~ 6e-8; the bar is one fp32 ulp at 1.0
+FP32_ULP = 1.2e-7
+
+
+def resize_cases():
+    return sorted(golden("imresize")[0]["cases"])
+
+
+def _tables(x, c):
+    H, W = x.shape[-2:]
+    return (T.resize_tables(H, math.ceil(H * c["scale"]), c["scale"], c["antialiasing"]),
+            T.resize_tables(W, math.ceil(W * c["scale"]), c["scale"], c["antialiasing"]))
+
+
+@pytest.mark.parametrize("name", resize_cases())
+def test_resize_tables_reproduce_ref64(name):
+    meta, z = golden("imresize")
+    c, x, ref64 = meta["cases"][name], z[f"{name}__in"], z[f"{name}__ref64"]
+    rows, cols = _tables(x, c)
+    for (w, i), n in ((rows, x.shape[-2]), (cols, x.shape[-1])):
+        assert w.dtype == torch.float64 and w.shape == i.shape and not i.dtype.is_floating_point
+        kernel_width = 4 / c["scale"] if c["scale"] < 1 and c["antialiasing"] else 4
+        assert w.shape[1] <= math.ceil(kernel_width) + 2
+        assert (w.sum(1) - 1).abs().max() <= 1e-15
+        assert int(i.min()) >= 0 and int(i.max()) < n
+    (wh, ih), (ww, iw) = rows, cols
+    y = x.double()
+    y = torch.stack([(y[:, :, ih[o], :] * wh[o].view(1, 1, -1, 1)).sum(2) for o in range(ih.shape[0])], 2)
+    y = torch.stack([(y[..., iw[o]] * ww[o]).sum(-1) for o in range(iw.shape[0])], -1)
+    assert y.shape == ref64.shape and (y - ref64).abs().max() <= 1e-14, (y - ref64).abs().max()
+
+
+def test_resize_tables_short_axes_raise():
+    T.resize_tables(9, 3, 1 / 4)                              # the smallest side the reference takes at 1/4 ...
+    with pytest.raises(ValueError, match="the height.*minimum length"):
+        T.resize_tables(5, 2, 1 / 4, axis="the height")       # ... and one where its symmetric copy fails
+    with pytest.raises(ValueError, match="the width"):
+        T.imresize(torch.rand(1, 3, 16, 5), 1 / 4)
+    with pytest.raises(ValueError, match="the height"):
+        T.imresize(torch.rand(3, 2, 16), 1 / 8)
+    with pytest.raises(ValueError):
+        T.imresize(torch.rand(16, 16), 1 / 2)
+
+
+@pytest.mark.parametrize("name", resize_cases())
+def test_cpu_imresize_matches_reference(name):
+    meta, z = golden("imresize")
+    c, x = meta["cases"][name], z[f"{name}__in"]
+    ref32, ref64 = z[f"{name}__ref32"], z[f"{name}__ref64"]
+    got = T.imresize(x, c["scale"], c["antialiasing"])
+    assert got.dtype == torch.float32 and got.shape == ref32.shape
+    d64, d32 = (got - ref64.float()).abs().max().item(), (got - ref32).abs().max().item()
+    print(f"{name}: |cpu - ref64| = {d64:.3e}, |cpu - ref32| = {d32:.3e} (ref32 vs ref64 {c['ref32_vs_ref64']:.3e})")
+    assert d64 <= FP32_ULP and d32 <= c["ref32_vs_ref64"] + FP32_ULP
+    got64 = T.imresize(x.double(), c["scale"], c["antialiasing"])
+    assert got64.dtype == torch.float64 and (got64 - ref64).abs().max() <= 1e-14
+    one = T.imresize(x[0], c["scale"], c["antialiasing"])      # (C, H, W)
+    assert one.shape == ref32.shape[1:] and torch.equal(one, got[0])
+
+
+def test_imresize_quantize_is_tensor_round():
+    _, z = golden("imresize")
+    x = z["u8_x3_10x11__in"] * 3 - 1                            # values outside [0, 1]: the clamp matters
+    plain = T.imresize(x, 3)
+    assert torch.equal(T.imresize(x, 3, quantize=True), EV.tensor_round(plain))
+    assert float(plain.min()) < 0 and float(plain.max()) > 1
+
+
+@pytest.mark.parametrize("scale", [2, 3, 4])
+def test_sr_lq_matches_the_reference_lq(scale):
+    """8-bit levels against the reference's LQ.  Exact ties occur (dyadic weights on k / 255 samples at 1/2 and 1/4) and the
+    reference's fp32 rounding decides them, so equality cannot be asked: a pixel may differ by one level, and only where 255 x the
+    reference's unrounded fp32 value is within 1e-3 of a half-integer; such pixels are at most 1 % of the image (the fixture's x2
+    LQ has 21 of 13455), so the allowance cannot hide a failure."""
+    meta, z = golden("sr_pipeline")
+    gt = z["gt"].float() / 255
+    lq, gtc = T.sr_lq(gt, scale)
+    H, W = gt.shape[-2] // scale * scale, gt.shape[-1] // scale * scale
+    assert torch.equal(gtc, gt[..., :H, :W]) and lq.shape == (1, 3, H // scale, W // scale) and lq.dtype == torch.float32
+    want, raw = z[f"lq_x{scale}"], z[f"lq_x{scale}_raw"].double()
+    a, b = (lq.double() * 255).round(), (want.double() * 255).round()
+    assert torch.equal(lq, a.float() / 255)                    # 8-bit levels, as tensor_round leaves them
+    near = ((raw * 255) % 1.0 - 0.5).abs() <= meta["near_tie"]
+    differ = a != b
+    print(f"x{scale}: {int(differ.sum())} pixels differ, {int(near.sum())} near ties of {raw.numel()}")
+    assert int(near.sum()) <= 0.01 * raw.numel()
+    assert (a - b).abs().max() <= 1 and not (differ & ~near).any()
+    unq, _ = T.sr_lq(gt, scale, quantize=False)
+    assert (unq - z[f"lq_x{scale}_raw"]).abs().max() <= 1e-6 + FP32_ULP
+
+
+def test_resize_struct_matches_header(tmp_path):
+    """sizeof / offsetof of every GrlResizeArgs field of include/grl_hip.h compiled with gcc against the ctypes mirror."""
+    st = _lib.GrlResizeArgs
+    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "grl_hip.h"', 'int main(void) {',
+             'printf("size %zu\\n", sizeof(GrlResizeArgs));']
+    lines += [f'printf("{f[0]} %zu\\n", offsetof(GrlResizeArgs, {f[0]}));' for f in st._fields_]
+    lines += ["return 0; }"]
+    src, exe = tmp_path / "layout.c", tmp_path / "layout"
+    src.write_text("\n".join(lines))
+    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
+    out = dict(l.split() for l in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
+    assert int(out["size"]) == ctypes.sizeof(st)
+    for f in st._fields_:
+        assert int(out[f[0]]) == getattr(st, f[0]).offset, f[0]
+    assert "grl_imresize" in _lib.EXPORTS and _lib.ABI_VERSION >= 25
+
+
+def test_evaluate_cli_sr_bicubic_arguments(tmp_path):
+    gt = tmp_path / "gt"
+    gt.mkdir()
+    assert "sr_bicubic" in EV.TASKS
+    with pytest.raises(SystemExit):
+        EV.main(["--task", "sr_bicubic", "--gt", str(gt), "--lq", str(gt)])
+    with pytest.raises(SystemExit):
+        EV.main(["--task", "sr_bicubic", "--gt", str(gt), "--scale", "1"])
+    with pytest.raises(ValueError):
+        list(EV.task_inputs(str(gt), "sr_bicubic", scale=1, device="cpu"))
+
+
+def test_task_inputs_sr_bicubic_on_cpu(tmp_path):
+    import numpy as np
+    from PIL import Image
+
+    d = tmp_path / "set"
+    d.mkdir()
+    Image.fromarray(np.random.RandomState(1).randint(0, 256, (31, 41, 3)).astype(np.uint8)).save(d / "a.png")
+    (name, lq, gt), = EV.task_inputs(str(d), "sr_bicubic", scale=3, device="cpu")
+    want = EV._read_image(str(d / "a.png"))[..., :30, :39]
+    assert name == "a.png" and torch.equal(gt, want) and torch.equal(lq, T.sr_lq(want, 3)[0]) and lq.shape == (1, 3, 10, 13)
