@@ -9,7 +9,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgrl_hip.so")
-ABI_VERSION = 25
+ABI_VERSION = 26
 DT_F32, DT_BF16, DT_F16 = 0, 1, 2
 
 EPI_PLAIN, EPI_GELU, EPI_GROUPNORM, EPI_LN_RES, EPI_GELU_GRAD = 0, 1, 2, 3, 4
@@ -57,6 +57,8 @@ EXPORTS = [
     "grl_image_metrics",
     "grl_demosaic_matlab",
     "grl_imresize",
+    "grl_image_niqe_workspace_bytes",
+    "grl_image_niqe_features",
     "grl_debug_dirty_lds",
     "grl_abi_version",
     "grl_build_info",
@@ -532,7 +534,27 @@ class GrlResizeArgs(_Strict):
         ("iw", C.c_void_p),
         ("out", C.c_void_p),
         ("quantize", C.c_int32),
+        ("out_f64", C.c_int32),
+    ]
+
+
+class GrlNiqeArgs(_Strict):
+    _fields_ = [
+        ("img", C.c_void_p),
+        ("stride", C.c_int64 * 4),
+        ("shape", C.c_int32 * 4),
+        ("window", C.c_double * 49),
+        ("grid", C.c_void_p),
+        ("ngrid", C.c_int32),
+        ("taps_h", C.c_int32), ("taps_w", C.c_int32),
         ("reserved0", C.c_int32),
+        ("wh", C.c_void_p),
+        ("ih", C.c_void_p),
+        ("ww", C.c_void_p),
+        ("iw", C.c_void_p),
+        ("workspace", C.c_void_p),
+        ("workspace_bytes", C.c_int64),
+        ("out", C.c_void_p),
     ]
 
 
@@ -641,6 +663,10 @@ def lib():
     L.grl_demosaic_matlab.restype = C.c_int
     L.grl_imresize.argtypes = [C.c_void_p, C.POINTER(GrlResizeArgs)]
     L.grl_imresize.restype = C.c_int
+    L.grl_image_niqe_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+    L.grl_image_niqe_workspace_bytes.restype = C.c_int64
+    L.grl_image_niqe_features.argtypes = [C.c_void_p, C.POINTER(GrlNiqeArgs)]
+    L.grl_image_niqe_features.restype = C.c_int
     L.grl_debug_dirty_lds.argtypes = [C.c_void_p]
     L.grl_debug_dirty_lds.restype = C.c_int
     _lib = L

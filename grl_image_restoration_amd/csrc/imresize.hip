@@ -9,7 +9,8 @@
 //
 // Arithmetic: every weighted sum is accumulated in fp64 (fp32 sample x fp64 weight).  The strip between the two passes is HELD IN
 // FP64, so a result is rounded once, to fp32, at the store; `quantize` then applies the reference's tensor_round to that fp32 value
-// in fp32 (clamp to [0, 1], x 255, round half to even, / 255 with a correctly rounded division), as torch does.
+// in fp32 (clamp to [0, 1], x 255, round half to even, / 255 with a correctly rounded division), as torch does.  `out_f64` stores the
+// fp64 sum itself, unrounded (NIQE's half-scale plane, csrc/niqe.hip).
 //
 // Shape: a workgroup of 256 threads owns TOY x TOX output pixels of one (image, channel) plane.
 //   1. the tile's slices of the four tables go to LDS (indices clamped to the image while loading; the column tables transposed, so
@@ -42,7 +43,7 @@ struct Params {
     int64_t sn, sc, sy, sx;
     int32_t C, H, W, out_h, out_w, taps_h, taps_w;
     int32_t toy, tox, nty, ntx, SH, SWP;    // SH = 0: no LDS map, every tile takes the direct path
-    int32_t vec4, quantize;
+    int32_t vec4, quantize, out_f64;
     const double *wh, *ww;
     const int32_t *ih, *iw;
     float* out;
@@ -65,7 +66,7 @@ __global__ __launch_bounds__(NT) void imresize_kernel(Params p) {
     const int oy0 = (t / p.ntx) * p.toy, ox0 = (t % p.ntx) * p.tox;
     const int ny = min(p.toy, p.out_h - oy0), nx = min(p.tox, p.out_w - ox0);
     const float* const src = p.in + n * p.sn + ch * p.sc;
-    float* const dst = p.out + (int64_t)plane * p.out_h * p.out_w;
+    float* const dst = p.out + (int64_t)plane * p.out_h * p.out_w * (p.out_f64 ? 2 : 1);    // fp64 planes are twice as long
     const int tid = threadIdx.x, th = p.taps_h, tw = p.taps_w;
 
     if (p.SH > 0) {
@@ -147,8 +148,10 @@ __global__ __launch_bounds__(NT) void imresize_kernel(Params p) {
                     const double* s = strip + oy * p.SWP - c0;
                     double acc = 0.0;
                     for (int k = 0; k < tw; ++k) acc += ww[k * p.tox + lx] * s[iw[k * p.tox + lx]];
+                    const int64_t o = (int64_t)(oy0 + oy) * p.out_w + ox0 + lx;
                     const float v = (float)acc;
-                    dst[(int64_t)(oy0 + oy) * p.out_w + ox0 + lx] = p.quantize ? round8(v) : v;
+                    if (p.out_f64) reinterpret_cast<double*>(dst)[o] = acc;
+                    else dst[o] = p.quantize ? round8(v) : v;
                 }
             }
             return;
@@ -170,8 +173,10 @@ __global__ __launch_bounds__(NT) void imresize_kernel(Params p) {
             for (int j = 0; j < th; ++j) v += gwh[j] * (double)col[(int64_t)clampi(gih[j], p.H - 1) * p.sy];
             acc += gww[k] * v;
         }
+        const int64_t o = (int64_t)(oy0 + oy) * p.out_w + ox0 + lx;
         const float v = (float)acc;
-        dst[(int64_t)(oy0 + oy) * p.out_w + ox0 + lx] = p.quantize ? round8(v) : v;
+        if (p.out_f64) reinterpret_cast<double*>(dst)[o] = acc;
+        else dst[o] = p.quantize ? round8(v) : v;
     }
 }
 
@@ -194,6 +199,7 @@ extern "C" int grl_imresize(void* stream, const GrlResizeArgs* a) {
     if ((uint64_t)a->wh % 8 || (uint64_t)a->ww % 8 || (uint64_t)a->ih % 4 || (uint64_t)a->iw % 4 || (uint64_t)a->out % 4 ||
         (uint64_t)a->src % 4)
         return GRL_ERR_BAD_ARG;
+    if (a->out_f64 && (a->quantize || (uint64_t)a->out % 8)) return GRL_ERR_BAD_ARG;
 
     static const int TILES[][2] = {{16, 64}, {8, 64}, {16, 32}, {8, 32}, {4, 32}, {4, 16}, {2, 16}, {1, 16}};
     Params p;
@@ -202,6 +208,7 @@ extern "C" int grl_imresize(void* stream, const GrlResizeArgs* a) {
     p.C = a->C; p.H = a->H; p.W = a->W; p.out_h = a->out_h; p.out_w = a->out_w; p.taps_h = a->taps_h; p.taps_w = a->taps_w;
     p.vec4 = p.sx == 1 && (uint64_t)a->src % 16 == 0 && p.sn % 4 == 0 && p.sc % 4 == 0 && p.sy % 4 == 0;
     p.quantize = a->quantize != 0;
+    p.out_f64 = a->out_f64 != 0;
     p.wh = a->wh; p.ww = a->ww; p.ih = a->ih; p.iw = a->iw;
     p.out = a->out;
     p.toy = 8; p.tox = 32; p.SH = 0; p.SWP = 0;

@@ -17,6 +17,9 @@ Restates, for the MI355X module, the three pieces of the reference's evaluation 
   task "sr_bicubic" classical SR scored from the GT folder alone: the GT is cropped to a multiple of the scale and the LQ is its
                     MATLAB-bicubic downscale, 8-bit quantised (``tasks.sr_lq``; restoration_sr.py:130-141,
                     utils/matlab_functions.py:91-188), made on the device
+  task "bsr"        blind / real-world SR (config/experiment/bsr/grl.yaml): LQ images only, no GT (``with_gt: False``); the metric is
+                    NIQE of the output (``metrics.niqe``, config/metric/restorer_niqe.yaml), against the pristine model the user
+                    names with ``--niqe-params`` or the environment variable GRL_NIQE_PARAMS
 
     python -m grl_image_restoration_amd.evaluate --model base --geometry sr_ckpt_df2 --scale 4 \\
         --ckpt sr_grl_base_c3x4.ckpt --lq Set5/LRbicx4 --gt Set5/GTmod12 [--tile 256 --overlap 32] [--metric restorer]
@@ -26,6 +29,8 @@ Restates, for the MI355X module, the three pieces of the reference's evaluation 
         --ckpt dn_grl_small_c3s25.ckpt --gt kodak24 --noise-prefix Kodak24 --metric restorer
     python -m grl_image_restoration_amd.evaluate --task sr_bicubic --scale 4 --model base --geometry sr_ckpt_df2 \\
         --ckpt sr_grl_base_c3x4.ckpt --gt Set5/original --metric restorer
+    python -m grl_image_restoration_amd.evaluate --task bsr --model base --geometry bsr --upsampler nearest+conv \\
+        --ckpt bsr_grl_base.ckpt --lq RealSRSet --niqe-params niqe_pris_params.npz
 """
 import argparse
 import os
@@ -123,10 +128,11 @@ def image_pairs(lq_dir: str, gt_dir: str) -> List[Tuple[str, str]]:
 
 @torch.no_grad()
 def evaluate_pairs(model, pairs: Iterable[Tuple[torch.Tensor, torch.Tensor]], scale: int, tile: int = 0, overlap: int = 32,
-                   device: str = "cuda:0", metric_group: Optional[str] = None):
+                   device: str = "cuda:0", metric_group: Optional[str] = None, niqe_params=None):
     """PSNR-Y of ``model`` on (lq, gt) tensors in [0, 1], (1,3,h,w) / (1,3,h*scale,w*scale): a list, one value per pair.
     ``tile > 0`` uses the reference's tiled inference (engines/base.py:90-116) through ``tiling.forward_tiled``.
-    With ``metric_group`` (a key of ``metrics.GROUPS``): {metric name: mean over the pairs} of that group instead."""
+    With ``metric_group`` (a key of ``metrics.ALL_GROUPS``): {metric name: mean over the pairs} of that group instead.  ``gt`` may be
+    None for the group "restorer_niqe", which scores the output alone against ``niqe_params``."""
     from . import tiling
     from .metrics import image_metrics
 
@@ -137,18 +143,22 @@ def evaluate_pairs(model, pairs: Iterable[Tuple[torch.Tensor, torch.Tensor]], sc
             sr = tiling.forward_tiled(model, lq, tile, overlap, scale)
         else:
             sr = model(lq)
-        gt = gt.to(sr.device)[..., : sr.shape[-2], : sr.shape[-1]]
-        sr = sr[..., : gt.shape[-2], : gt.shape[-1]]
+        if gt is None:
+            if metric_group != "restorer_niqe":
+                raise ValueError(f"metric group {metric_group!r} needs a ground truth; without one only restorer_niqe can be scored")
+        else:
+            gt = gt.to(sr.device)[..., : sr.shape[-2], : sr.shape[-1]]
+            sr = sr[..., : gt.shape[-2], : gt.shape[-1]]
         if metric_group is None:
             out.append(float(psnr_y(sr, gt, scale)))
         else:
-            out.append({k: float(v.mean()) for k, v in image_metrics(sr, gt, metric_group, scale).items()})
+            out.append({k: float(v.mean()) for k, v in image_metrics(sr, gt, metric_group, scale, niqe_params).items()})
     if metric_group is None:
         return out
     return {k: sum(o[k] for o in out) / len(out) for k in out[0]}
 
 
-TASKS = ("sr", "dn", "dm", "sr_bicubic")
+TASKS = ("sr", "dn", "dm", "sr_bicubic", "bsr")
 
 
 def gt_images(gt_dir: str) -> List[str]:
@@ -195,17 +205,23 @@ def task_inputs(gt_dir: str, task: str, channels: int = 3, sigma: Optional[float
         yield name, lq, gt
 
 
-def evaluate_folder(model, lq_dir: Optional[str], gt_dir: str, scale: int, tile: int = 0, overlap: int = 32, device: str = "cuda:0",
-                    verbose: bool = True, metric_group: Optional[str] = None, channels: int = 3, task: str = "sr",
-                    sigma: Optional[float] = None, noise_prefix: Optional[str] = None):
+def evaluate_folder(model, lq_dir: Optional[str], gt_dir: Optional[str], scale: int, tile: int = 0, overlap: int = 32,
+                    device: str = "cuda:0", verbose: bool = True, metric_group: Optional[str] = None, channels: int = 3,
+                    task: str = "sr", sigma: Optional[float] = None, noise_prefix: Optional[str] = None, niqe_params=None):
     """Mean PSNR-Y over the image pairs of two folders; with ``metric_group``, {metric name: mean} of that group.  ``channels`` 1
     reads the images as grayscale.  ``task`` "dn" / "dm" ignores ``lq_dir`` and builds the LQ from the GT (``task_inputs``;
-    ``scale`` must be 1); so does "sr_bicubic", at a ``scale`` above 1."""
+    ``scale`` must be 1); so does "sr_bicubic", at a ``scale`` above 1.  ``task`` "bsr" reads ``lq_dir`` alone (``gt_dir`` is not used)
+    and returns {"val_niqe": mean}; ``niqe_params`` is the pristine model of ``metrics.niqe`` (also for "restorer_niqe" elsewhere)."""
     if task not in TASKS:
         raise ValueError(f"unknown task {task!r}: one of {TASKS}")
     mode = "L" if channels == 1 else "RGB"
     if task == "sr":
         items = ((os.path.basename(lq_p), _read_image(lq_p, mode), _read_image(gt_p, mode)) for lq_p, gt_p in image_pairs(lq_dir, gt_dir))
+    elif task == "bsr":
+        if metric_group not in (None, "restorer_niqe"):
+            raise ValueError(f"task bsr has no ground truth: its metric group is restorer_niqe, not {metric_group!r}")
+        metric_group = "restorer_niqe"
+        items = ((os.path.relpath(p, lq_dir), _read_image(p, mode), None) for p in gt_images(lq_dir))
     elif task == "sr_bicubic":
         items = task_inputs(gt_dir, task, channels, device=device, scale=scale)
     else:
@@ -214,7 +230,7 @@ def evaluate_folder(model, lq_dir: Optional[str], gt_dir: str, scale: int, tile:
         items = task_inputs(gt_dir, task, channels, sigma, noise_prefix, device)
     vals = []
     for name, lq, gt in items:
-        v = evaluate_pairs(model, [(lq, gt)], scale, tile, overlap, device, metric_group)
+        v = evaluate_pairs(model, [(lq, gt)], scale, tile, overlap, device, metric_group, niqe_params)
         v = v[0] if metric_group is None else v
         vals.append(v)
         if verbose:
@@ -236,22 +252,28 @@ def _columns(v) -> str:
 
 def main(argv: Optional[List[str]] = None):
     from . import GRL, make_config
-    from .metrics import GROUPS
+    from .metrics import ALL_GROUPS
 
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--model", default="base", choices=["tiny", "small", "base"])
     ap.add_argument("--geometry", default="sr_ckpt_df2", help="a key of presets.GEOMETRIES")
     ap.add_argument("--task", default="sr", choices=TASKS,
                     help="sr: LQ images from --lq (SR, deblurring, JPEG); dn / dm / sr_bicubic: the LQ is made from --gt (denoising, "
-                         "demosaicking, classical SR by MATLAB-bicubic downscaling at --scale)")
-    ap.add_argument("--scale", type=int, default=None, help="4 by default for --task sr / sr_bicubic; 1 for everything else")
+                         "demosaicking, classical SR by MATLAB-bicubic downscaling at --scale); bsr: LQ images from --lq, no --gt, "
+                         "scored by NIQE")
+    ap.add_argument("--scale", type=int, default=None, help="4 by default for --task sr / sr_bicubic / bsr; 1 for everything else")
+    ap.add_argument("--upsampler", default=None, choices=["pixelshuffle", "pixelshuffledirect", "nearest+conv"],
+                    help="the reconstruction tail; default: the model size's classical-SR tail (bsr_grl_base.ckpt: nearest+conv)")
     ap.add_argument("--ckpt", default=None, help="reference checkpoint (.ckpt / .pth); random init without it")
-    ap.add_argument("--lq", default=None, help="LQ folder (--task sr only)")
-    ap.add_argument("--gt", required=True)
+    ap.add_argument("--lq", default=None, help="LQ folder (--task sr and bsr)")
+    ap.add_argument("--gt", default=None, help="GT folder (required, except with --task bsr)")
+    ap.add_argument("--niqe-params", default=None,
+                    help="restorer_niqe: the reference's utils/metrics/niqe_pris_params.npz (default: the environment variable "
+                         "GRL_NIQE_PARAMS)")
     ap.add_argument("--tile", type=int, default=0)
     ap.add_argument("--overlap", type=int, default=32)
     ap.add_argument("--device", default="cuda:0")
-    ap.add_argument("--metric", default=None, choices=sorted(GROUPS),
+    ap.add_argument("--metric", default=None, choices=sorted(ALL_GROUPS),
                     help="report this metric group of the reference (config/metric/*.yaml) instead of PSNR-Y alone")
     ap.add_argument("--channels", type=int, default=3, choices=[1, 3], help="1: grayscale model and images (dn_*_c1, jpeg_*_c1)")
     ap.add_argument("--sigma", type=float, default=None, help="--task dn: noise level on the 0..255 scale (15, 25, 50)")
@@ -260,24 +282,43 @@ def main(argv: Optional[List[str]] = None):
                          "that starts the noise seed key '<prefix>/<file name>'; a different prefix draws different noise.  Default: "
                          "the --gt folder's name, matched case-insensitively to one of those")
     a = ap.parse_args(argv)
+    if a.task != "bsr" and a.gt is None:
+        ap.error("the following arguments are required: --gt")
+    if a.task == "bsr":
+        if a.lq is None:
+            ap.error("--lq is required with --task bsr")
+        if a.gt is not None:
+            ap.error("--task bsr has no ground truth; --gt is not used")
+        if a.metric not in (None, "restorer_niqe"):
+            ap.error("--task bsr is scored by --metric restorer_niqe")
+        a.metric = "restorer_niqe"
     if a.task == "sr" and a.lq is None:
         ap.error("--lq is required with --task sr")
-    if a.task != "sr" and a.lq is not None:
+    if a.task not in ("sr", "bsr") and a.lq is not None:
         ap.error(f"--task {a.task} builds its LQ from --gt; --lq is not used")
     if a.task == "dn" and a.sigma is None:
         ap.error("--task dn needs --sigma")
     if a.scale is None:
-        a.scale = 4 if a.task in ("sr", "sr_bicubic") else 1
+        a.scale = 4 if a.task in ("sr", "sr_bicubic", "bsr") else 1
     if a.task in ("dn", "dm") and a.scale != 1:
         ap.error(f"--task {a.task} restores at --scale 1")
     if a.task == "sr_bicubic" and a.scale < 2:
         ap.error("--task sr_bicubic needs a --scale above 1")
-    model = GRL(**make_config(a.model, a.geometry, upscale=a.scale, in_channels=a.channels)).eval()
+    niqe_params = None
+    if a.metric == "restorer_niqe":
+        from .metrics import load_niqe_params
+
+        try:
+            niqe_params = load_niqe_params(a.niqe_params)
+        except ValueError as e:
+            ap.error(str(e))
+    overrides = {"upsampler": a.upsampler} if a.upsampler and a.scale > 1 else {}
+    model = GRL(**make_config(a.model, a.geometry, upscale=a.scale, in_channels=a.channels, **overrides)).eval()
     if a.ckpt:
         load_checkpoint(model, a.ckpt)
     model = model.to(a.device)
     return evaluate_folder(model, a.lq, a.gt, a.scale, a.tile, a.overlap, a.device, metric_group=a.metric, channels=a.channels,
-                           task=a.task, sigma=a.sigma, noise_prefix=a.noise_prefix)
+                           task=a.task, sigma=a.sigma, noise_prefix=a.noise_prefix, niqe_params=niqe_params)
 
 
 if __name__ == "__main__":

@@ -8,6 +8,7 @@ steps engines/base.py:256-271 takes first: ``tensor_round`` of both images and, 
   restorer_gray         val_psnr, val_ssim                                          grayscale denoising
   restorer_jpeg         restorer + val_psnrb, val_psnrb_y                           colour JPEG artifact removal
   restorer_jpeg_gray    val_psnr, val_ssim, val_psnrb                               grayscale JPEG artifact removal
+  restorer_niqe         val_niqe (no reference: ``target`` is ignored, no shave)    blind / real-world SR (``niqe`` below)
 
 CUDA tensors go through ``grl_image_metrics`` of libgrl_hip.so (csrc/metrics.hip: one tile pass, one per-image reduction); there
 is no torch fallback for them.  CPU tensors take the plain-torch restatement below (the same definitions, evaluated in float64 on
@@ -22,7 +23,8 @@ for SSIM, against its fp32 values for PSNR and PSNR-B.
 """
 import ctypes as C
 import math
-from typing import Dict, Tuple
+import os
+from typing import Dict, Optional, Tuple
 
 import torch
 import torch.nn.functional as F
@@ -35,6 +37,9 @@ GROUPS = {
     "restorer_jpeg": ("val_psnr", "val_psnr_y", "val_ssim", "val_ssim_y", "val_psnrb", "val_psnrb_y"),
     "restorer_jpeg_gray": ("val_psnr", "val_ssim", "val_psnrb"),
 }
+# groups that score the restored image alone (no ground truth): kept apart from GROUPS, whose every entry compares a pair
+NO_REFERENCE_GROUPS = {"restorer_niqe": ("val_niqe",)}
+ALL_GROUPS = {**GROUPS, **NO_REFERENCE_GROUPS}
 # GRL_METRIC_* bit of each metric; bit i is column i of grl_image_metrics' output
 BITS = {"val_psnr": 1, "val_psnr_y": 2, "val_ssim": 4, "val_ssim_y": 8, "val_psnrb": 16, "val_psnrb_y": 32}
 Y_COEF = (65.481, 128.553, 24.966)
@@ -72,11 +77,15 @@ def _check(restored: torch.Tensor, target: torch.Tensor, group: str, scale: int)
     return keys, border
 
 
-def image_metrics(restored: torch.Tensor, target: torch.Tensor, group: str = "restorer", scale: int = 1) -> Dict[str, torch.Tensor]:
+def image_metrics(restored: torch.Tensor, target: Optional[torch.Tensor], group: str = "restorer", scale: int = 1,
+                  niqe_params=None) -> Dict[str, torch.Tensor]:
     """Per-image metrics of ``group`` as the reference's validation step reports them: {name: float64 tensor of shape (B,)}.
     ``restored`` and ``target`` are (B, C, H, W) images in [0, 1] (values outside are clamped by the rounding), C = 3 or, for the
     *_gray groups, 1; ``scale > 1`` shaves ``scale`` pixels off every side first (SR).  PSNR is +inf for identical images;
-    PSNR-B is finite there and -inf for sides below 16 (the reference's counts are 0)."""
+    PSNR-B is finite there and -inf for sides below 16 (the reference's counts are 0).  Group "restorer_niqe" scores ``restored``
+    alone (``target`` may be None; no shave: the reference's border is 0) against the pristine model ``niqe_params`` (see ``niqe``)."""
+    if group in NO_REFERENCE_GROUPS:
+        return {"val_niqe": niqe(restored, niqe_params)}
     keys, border = _check(restored, target, group, scale)
     if restored.is_cuda:
         bits = 0
@@ -164,3 +173,230 @@ def _torch_metrics(restored, target, keys, border) -> Dict[str, torch.Tensor]:
         base, y = (k[:-2], "_y") if k.endswith("_y") else (k, "")
         out[k] = fn[base](*planes[y])
     return out
+
+
+# ---- NIQE (utils/metrics/niqe.py) ------------------------------------------------------------------------------------------------
+# The reference's only validation metric for blind SR (config/metric/restorer_niqe.yaml): no ground truth.  ``niqe`` scores the
+# 8-bit rounded image against a pristine multivariate Gaussian model, which is user data like a checkpoint: the reference's
+# utils/metrics/niqe_pris_params.npz, given as a path, as arrays, or through the environment variable GRL_NIQE_PARAMS.
+#
+# CUDA tensors take the features from ``grl_image_niqe_features`` (csrc/niqe.hip); there is no torch fallback for them.  CPU tensors
+# take ``niqe_features_torch``, the same definitions in float64 torch.  Both evaluate in float64 what the reference evaluates in
+# fp32; the 36 x 36 tail (nanmean, covariance, pinv, quadratic form; niqe.py:475-490) is float64 torch on the features' device.
+NIQE_ENV = "GRL_NIQE_PARAMS"
+NIQE_BLOCK = 96
+NIQE_FEATURES = 36
+_NIQE_SHIFTS = ((0, 1), (1, 0), (1, 1), (1, -1))
+_NIQE_WINDOW = None
+_NIQE_GRID = None
+_NIQE_DEVICE = {}
+
+
+def niqe_window() -> torch.Tensor:
+    """(7, 7) float64: MATLAB's fspecial('gaussian', 7, 7/6), the ``gaussian_window`` of the reference's parameter file."""
+    global _NIQE_WINDOW
+    if _NIQE_WINDOW is None:
+        sigma = 7.0 / 6.0
+        x = torch.arange(-3, 4, dtype=torch.float64)
+        h = torch.exp(-(x.view(7, 1) ** 2 + x.view(1, 7) ** 2) / (2 * sigma * sigma))
+        h[h < torch.finfo(torch.float64).eps * h.max()] = 0
+        _NIQE_WINDOW = h / h.sum()
+    return _NIQE_WINDOW
+
+
+def niqe_grid() -> torch.Tensor:
+    """(5, 9801) float64: estimate_aggd_param's search grid ``gam = arange(0.2, 10.001, 0.001)``, its ``r_gam`` (niqe.py:352-356), and
+    gamma(1 / gam), gamma(2 / gam), gamma(3 / gam) as niqe.py:368-369,395 evaluate them at the chosen alpha.  SciPy's gamma when it
+    is installed (what the reference calls), math.gamma otherwise."""
+    global _NIQE_GRID
+    if _NIQE_GRID is None:
+        import numpy as np
+
+        try:
+            from scipy.special import gamma
+        except ImportError:
+            gamma = np.vectorize(math.gamma, otypes=[np.float64])
+        gam = np.arange(0.2, 10.001, 0.001)
+        rec = np.reciprocal(gam)
+        r_gam = np.square(gamma(rec * 2)) / (gamma(rec) * gamma(rec * 3))
+        _NIQE_GRID = torch.from_numpy(np.stack([gam, r_gam, gamma(1 / gam), gamma(2 / gam), gamma(3 / gam)]).astype(np.float64))
+    return _NIQE_GRID
+
+
+def load_niqe_params(params=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(mu (36,), cov (36, 36)) float64 CPU tensors of the pristine model.  ``params``: a path to the reference's
+    niqe_pris_params.npz, a mapping with ``mu_pris_param`` and ``cov_pris_param``, a ``(mu, cov)`` pair, or None for the file that
+    the environment variable GRL_NIQE_PARAMS names."""
+    import numpy as np
+
+    if params is None:
+        params = os.environ.get(NIQE_ENV)
+        if not params:
+            raise ValueError(f"NIQE needs the pristine model (the reference's utils/metrics/niqe_pris_params.npz): pass its path as "
+                             f"--niqe-params / niqe_params, or set the environment variable {NIQE_ENV}")
+    if isinstance(params, (str, os.PathLike)):
+        if not os.path.isfile(params):
+            raise ValueError(f"NIQE parameter file {os.fspath(params)!r} not found (--niqe-params / niqe_params, or the environment "
+                             f"variable {NIQE_ENV})")
+        with np.load(params) as f:
+            params = {k: f[k] for k in ("mu_pris_param", "cov_pris_param")}
+    if hasattr(params, "keys"):
+        params = (params["mu_pris_param"], params["cov_pris_param"])
+    mu, cov = (torch.as_tensor(np.asarray(p.detach().cpu() if torch.is_tensor(p) else p), dtype=torch.float64) for p in params)
+    mu = mu.reshape(-1)
+    if mu.shape != (NIQE_FEATURES,) or cov.shape != (NIQE_FEATURES, NIQE_FEATURES):
+        raise ValueError(f"NIQE parameters: mu {tuple(mu.shape)} and cov {tuple(cov.shape)}, need (36,) and (36, 36)")
+    return mu, cov
+
+
+def _check_niqe(x: torch.Tensor):
+    if x.dim() != 4 or x.shape[1] not in (1, 3) or x.shape[0] < 1:
+        raise ValueError(f"NIQE needs a (B, C, H, W) batch with C = 1 or 3, got {tuple(x.shape)}")
+    if min(x.shape[-2:]) < NIQE_BLOCK:
+        raise ValueError(f"NIQE works on 96 x 96 blocks: a {tuple(x.shape[-2:])} image has none")
+
+
+def niqe(restored: torch.Tensor, params=None) -> torch.Tensor:
+    """NIQE of every image of a (B, C, H, W) batch in [0, 1] as the reference's validation reports it (NaturalImageQualityEvaluator,
+    niqe.py:549-583): (B,) float64, lower is better.  ``params``: the pristine model, see ``load_niqe_params``.  Raises ValueError
+    for an image whose blocks are all flat (the reference fails there with "SVD did not converge")."""
+    _check_niqe(restored)
+    mu, cov = load_niqe_params(params)
+    feat = niqe_features(restored)
+    return _niqe_tail(feat, mu.to(feat.device), cov.to(feat.device))
+
+
+def niqe_features(restored: torch.Tensor) -> torch.Tensor:
+    """The reference's ``distparam`` of every image: (B, blocks, 36) float64, blocks with columns outer and rows inner."""
+    _check_niqe(restored)
+    if restored.is_cuda:
+        return hip_niqe_features(restored)
+    return niqe_features_torch(restored)
+
+
+def _niqe_tail(feat: torch.Tensor, mu: torch.Tensor, cov: torch.Tensor) -> torch.Tensor:
+    """niqe.py:475-490 per image."""
+    out = []
+    for b, f in enumerate(feat):
+        rows = f[~torch.isnan(f).any(dim=1)]
+        if rows.shape[0] < 2:
+            raise ValueError(f"NIQE: image {b} has {rows.shape[0]} block(s) with defined features out of {f.shape[0]} (a flat image, "
+                             "or a single textured block): its feature covariance does not exist")
+        d = mu - torch.nanmean(f, dim=0)
+        inv = torch.linalg.pinv((cov + torch.cov(rows.t())) / 2)
+        out.append(torch.sqrt(d @ inv @ d))
+    return torch.stack(out)
+
+
+def _niqe_tables(Hc: int, Wc: int, device):
+    """Device copies of the grid and of the half-scale resize tables (cached)."""
+    from . import tasks
+
+    key = (str(device),)
+    if key not in _NIQE_DEVICE:
+        _NIQE_DEVICE[key] = niqe_grid().to(device).contiguous()
+    rows = tasks._device_tables((Hc, Hc // 2, 0.5, True), device)
+    cols = tasks._device_tables((Wc, Wc // 2, 0.5, True), device)
+    return _NIQE_DEVICE[key], rows, cols
+
+
+def hip_niqe_features(restored: torch.Tensor) -> torch.Tensor:
+    """One ``grl_image_niqe_features`` call (five launches): (B, blocks, 36) float64.  The image is read in place (any strides); the
+    library checks the arguments."""
+    from . import _lib
+
+    L = _lib.lib()
+    r = restored if restored.dtype == torch.float32 else restored.float()
+    B, _, H, W = r.shape
+    nbh, nbw = H // NIQE_BLOCK, W // NIQE_BLOCK
+    grid, (wh, ih), (ww, iw) = _niqe_tables(nbh * NIQE_BLOCK, nbw * NIQE_BLOCK, r.device)
+    ws_bytes = int(L.grl_image_niqe_workspace_bytes(B, H, W))
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=r.device)
+    out = torch.empty(B, nbh * nbw, NIQE_FEATURES, dtype=torch.float64, device=r.device)
+    args = _lib.GrlNiqeArgs(
+        img=r.data_ptr(), stride=(C.c_int64 * 4)(*r.stride()), shape=(C.c_int32 * 4)(*r.shape),
+        window=(C.c_double * 49)(*niqe_window().flatten().tolist()), grid=grid.data_ptr(), ngrid=grid.shape[1],
+        taps_h=wh.shape[1], taps_w=ww.shape[1], wh=wh.data_ptr(), ih=ih.data_ptr(), ww=ww.data_ptr(), iw=iw.data_ptr(),
+        workspace=ws.data_ptr(), workspace_bytes=ws_bytes, out=out.data_ptr())
+    _lib.check(L.grl_image_niqe_features(_lib.stream_ptr(), C.byref(args)), "grl_image_niqe_features")
+    return out
+
+
+# ---- NIQE, torch restatement (any device; the CPU path) ---------------------------------------------------------------------------
+def niqe_plane(restored: torch.Tensor) -> torch.Tensor:
+    """(B, 1, H, W) fp32 integer levels: the plane calculate_niqe scores (niqe.py:493-546) for what the validation step hands it,
+    ``tensor_round(output) * 255`` as a CHW **RGB** array.  For C = 3 the reference's to_y_channel assumes BGR (niqe.py:143-156,573),
+    so the plane is 24.966 R + 128.553 G + 65.481 B + 16 -- red and blue swapped against rgb2ycbcr.  The published numbers were
+    computed this way; it is reproduced rounding for rounding: the dot product in float64 on fp32 samples, / 255 cast to fp32,
+    x 255 in fp32, round half to even."""
+    k = (restored.float().clamp(0.0, 1.0) * 255.0).round()
+    if k.shape[1] == 1:
+        return k
+    u = ((k / 255.0) * 255.0 / 255.0).double()                    # tensor_round, x 255, to_y_channel's / 255, all fp32
+    y = (u[:, 0] * 24.966 + u[:, 1] * 128.553) + u[:, 2] * 65.481 + 16.0
+    return ((y / 255.0).float() * 255.0).round().unsqueeze(1)
+
+
+def _mscn(plane: torch.Tensor) -> torch.Tensor:
+    """(img - mu) / (sigma + 1) of ``plane`` (B, 1, h, w) in float64, window 7 x 7 with edge replication (niqe.py:447-455).  The
+    moments are taken of the differences to the centre sample, which changes nothing where the window has texture and gives the exact
+    zero the reference's fp32 ``mu`` gives where it is flat (csrc/niqe.hip, "Flat windows")."""
+    x = plane.double()
+    h, w = x.shape[-2:]
+    pad = F.pad(x, (3, 3, 3, 3), mode="replicate")
+    win = niqe_window()
+    s1, s2 = torch.zeros_like(x), torch.zeros_like(x)
+    for a in range(7):
+        for e in range(7):
+            d = pad[..., a : a + h, e : e + w] - x
+            s1 += float(win[a, e]) * d
+            s2 += float(win[a, e]) * (d * d)
+    sigma = torch.sqrt(torch.abs(s2 - s1 * s1))
+    return -s1 / (sigma + 1.0)
+
+
+def _aggd_features(blocks: torch.Tensor, grid: torch.Tensor) -> torch.Tensor:
+    """compute_feature (niqe.py:341-397) of (N, bs, bs) MSCN blocks: (N, 18) float64."""
+    q = [blocks] + [blocks * torch.roll(blocks, s, dims=(1, 2)) for s in _NIQE_SHIFTS]
+    q = torch.stack(q, 1).flatten(2)                              # (N, 5, bs * bs)
+    n = q.shape[-1]
+    neg, pos, sq = q < 0, q > 0, q * q
+    left = torch.sqrt((sq * neg).sum(-1) / neg.sum(-1))           # 0 / 0 = nan without negative samples, as the reference
+    right = torch.sqrt((sq * pos).sum(-1) / pos.sum(-1))
+    gammahat = left / right
+    rhat = (q.abs().sum(-1) / n) ** 2 / (sq.sum(-1) / n)
+    g2 = gammahat * gammahat
+    rhatnorm = (rhat * (g2 * gammahat + 1) * (gammahat + 1)) / ((g2 + 1) * (g2 + 1))
+    flat = rhatnorm.flatten()
+    idx = torch.empty_like(flat, dtype=torch.long)
+    for i in range(0, flat.numel(), 1024):                        # np.argmin((r_gam - rhatnorm) ** 2): the first minimum
+        idx[i : i + 1024] = torch.argmin((grid[1].unsqueeze(0) - flat[i : i + 1024].unsqueeze(1)) ** 2, dim=1)
+    idx = torch.where(torch.isnan(flat), torch.zeros_like(idx), idx).view_as(rhatnorm)   # all-nan distances: argmin answers 0
+    alpha, ga1, ga2, ga3 = grid[0][idx], grid[2][idx], grid[3][idx], grid[4][idx]
+    ratio = torch.sqrt(ga1 / ga3)
+    bl, br = left * ratio, right * ratio
+    mean = (br - bl) * (ga2 / ga1)
+    cols = [alpha[:, 0], (bl[:, 0] + br[:, 0]) / 2]
+    for k in range(1, 5):
+        cols += [alpha[:, k], mean[:, k], bl[:, k], br[:, k]]
+    return torch.stack(cols, 1)
+
+
+def niqe_features_torch(restored: torch.Tensor) -> torch.Tensor:
+    """niqe() up to ``distparam`` (niqe.py:400-473) in float64 torch, on the device of ``restored``: (B, blocks, 36)."""
+    from . import tasks
+
+    _check_niqe(restored)
+    B, _, H, W = restored.shape
+    nbh, nbw = H // NIQE_BLOCK, W // NIQE_BLOCK
+    yk = niqe_plane(restored)[..., : nbh * NIQE_BLOCK, : nbw * NIQE_BLOCK].contiguous()
+    grid = niqe_grid().to(restored.device)
+    feats = []
+    for plane, bs in ((yk, NIQE_BLOCK), (None, NIQE_BLOCK // 2)):
+        if plane is None:       # niqe.py:469-471: imresize(img / 255, 0.5) * 255 = imresize(img, 0.5) up to a rounding; kept in float64
+            Hc, Wc = yk.shape[-2:]
+            plane = tasks._torch_resize(yk, tasks.resize_tables(Hc, Hc // 2, 0.5, True), tasks.resize_tables(Wc, Wc // 2, 0.5, True))
+        m = _mscn(plane)
+        blocks = m.view(B, nbh, bs, nbw, bs).permute(0, 3, 1, 2, 4).reshape(B * nbw * nbh, bs, bs)
+        feats.append(_aggd_features(blocks, grid).view(B, nbw * nbh, NIQE_FEATURES // 2))
+    return torch.cat(feats, dim=2)

@@ -62,13 +62,16 @@ GEOMETRIES = {
     "deblur": dict(window_size=12, stripe_size=[48, 96], stripe_groups=[None, None], anchor_window_down_factor=4),
     # demosaicking Small (dm/grl.yaml:27-37, grl_test.md:11-15)
     "dm": dict(window_size=8, stripe_size=[32, 32], stripe_groups=[None, None], anchor_window_down_factor=4),
+    # blind / real-world SR Base (bsr/grl.yaml:53-67, grl_test.md:100-106); its tail is upsampler="nearest+conv"
+    "bsr": dict(window_size=16, stripe_size=[32, 64], stripe_groups=[None, None], anchor_window_down_factor=4),
 }
 
 _UPSAMPLER = {"tiny": "pixelshuffledirect", "small": "pixelshuffle", "base": "pixelshuffle"}
 
 
 def make_config(model: str, geometry: str, upscale: int = 1, img_size=64, **overrides) -> dict:
-    """kwargs for ``GRL(**cfg)`` (reference ctor: models/networks/grl.py:220-256)."""
+    """kwargs for ``GRL(**cfg)`` (reference ctor: models/networks/grl.py:220-256).  ``overrides`` replace any entry, e.g.
+    ``upsampler="nearest+conv"`` for the blind-SR checkpoint (the default tail is the model size's classical-SR one)."""
     cfg = dict(_COMMON)
     cfg.update(copy.deepcopy(MODELS[model]))
     cfg.update(copy.deepcopy(GEOMETRIES[geometry]))

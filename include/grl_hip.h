@@ -23,7 +23,7 @@ extern "C" {
 
 #define GRL_ERR_BAD_ARG (-1)
 #define GRL_ERR_UNSUPPORTED (-2)
-#define GRL_ABI_VERSION 25
+#define GRL_ABI_VERSION 26
 
 /* element kinds of activation / weight buffers */
 enum { GRL_DT_F32 = 0, GRL_DT_BF16 = 1, GRL_DT_F16 = 2 };
@@ -759,10 +759,49 @@ typedef struct GrlResizeArgs {
     const int32_t* iw;          /* [out_w][taps_w] input columns                                  */
     float* out;
     int32_t quantize;
-    int32_t reserved0;
+    int32_t out_f64;            /* ABI 26: != 0: out is double (N, C, out_h, out_w), the fp64 sums unrounded; not with quantize */
 } GrlResizeArgs;
 
 int grl_imresize(void* stream, const GrlResizeArgs* args);
+
+/* NIQE's feature matrix (ABI 26; the no-reference metric of blind / real-world SR validation, config/metric/restorer_niqe.yaml):
+ *   replaces  niqe() up to `distparam`       utils/metrics/niqe.py:400-473 (MSCN by two 7x7 convolutions, the imresize pyramid,
+ *             estimate_aggd_param / compute_feature  niqe.py:341-397       10 AGGD fits per 96 x 96 block in Python)
+ *             calculate_niqe's plane         niqe.py:493-546 on what NaturalImageQualityEvaluator.update hands it (niqe.py:566-574)
+ * img: fp32 (B, C, H, W) with arbitrary element strides, C = 1 or 3.  It is rounded to 8 bit on load (tensor_round, as the engine
+ * does before the metric, engines/base_gan.py:149-168).  C = 3: the plane is the reference's to_y_channel of a CHW RGB array, which
+ * assumes BGR (niqe.py:143-156,573): round(fl32((24.966 R + 128.553 G + 65.481 B + 16) / 255) * 255), the sum in float64 -- red
+ * and blue swapped against rgb2ycbcr, kept because the published numbers were computed this way.  C = 1: the rounded image.
+ * The plane is cropped (top-left) to nbh x nbw whole 96 x 96 blocks, nbh = H / 96, nbw = W / 96.  Scale 1 scores it; scale 2 scores
+ * imresize(plane / 255, 0.5) * 255, taken as imresize(plane, 0.5) and held in fp64 (grl_imresize with out_f64), resampled with the caller's tables for 96 nbh -> 48 nbh rows and 96 nbw -> 48 nbw
+ * columns (tasks.resize_tables).  Per block and scale: MSCN with `window` (7 x 7, edge replicate at the borders of
+ * the cropped plane), then the sums of the block and of its products with its four circularly shifted copies, all in fp64 in a
+ * fixed order (no atomics: two calls are bitwise equal), then the 18 features; alpha is the nearest point of `grid`'s r_gam row.
+ * out[b][block][36]: scale 1 then scale 2, blocks with columns outer and rows inner (niqe.py:458-465).  A block without negative or
+ * without positive samples has nan features where the reference has them.  Five launches on `stream`.
+ * Errors (GRL_ERR_BAD_ARG): a null pointer, C not 1 / 3, H or W below 96 (no block), B outside 1..65535, a negative stride, ngrid or
+ * taps < 1, misaligned pointers, workspace smaller than grl_image_niqe_workspace_bytes. */
+typedef struct GrlNiqeArgs {
+    const float* img;
+    int64_t stride[4];          /* element strides of dims b, c, h, w                                         */
+    int32_t shape[4];           /* B, C, H, W                                                                 */
+    double window[49];          /* fspecial('gaussian', 7, 7/6), row major                                    */
+    const double* grid;         /* [5][ngrid] device: gam = arange(0.2, 10.001, 0.001), r_gam (niqe.py:352-356), */
+                                /* gamma(1 / gam), gamma(2 / gam), gamma(3 / gam) (niqe.py:368-369,395)       */
+    int32_t ngrid;
+    int32_t taps_h, taps_w;     /* taps of the two half-scale tables                                          */
+    int32_t reserved0;
+    const double* wh;           /* [48 nbh][taps_h] as GrlResizeArgs                                          */
+    const int32_t* ih;
+    const double* ww;           /* [48 nbw][taps_w]                                                           */
+    const int32_t* iw;
+    void* workspace;            /* grl_image_niqe_workspace_bytes(B, H, W) bytes, 16-byte aligned, no initialisation */
+    int64_t workspace_bytes;
+    double* out;                /* [B][nbh * nbw][36]                                                         */
+} GrlNiqeArgs;
+
+int64_t grl_image_niqe_workspace_bytes(int32_t B, int32_t H, int32_t W);
+int grl_image_niqe_features(void* stream, const GrlNiqeArgs* args);
 
 /* Debug aid (ABI 21; no reference counterpart): fills the LDS of every CU with 0xFF bytes (fp32 / fp16 NaN) by a launch on
  * `stream`.  LDS keeps what the previous workgroup left in it; a kernel that reads LDS it has not written is otherwise right or

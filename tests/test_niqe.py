@@ -1,0 +1,185 @@
+"""NIQE (metrics.niqe, the metric group restorer_niqe) and the blind-SR task on the CPU: the float64 torch restatement against the
+reference fixtures of tools/make_golden_niqe.py, the C ABI of grl_image_niqe_features against the header, presets and CLI parsing."""
+import ctypes
+import json
+import os
+import subprocess
+
+import numpy as np
+import pytest
+import torch
+
+from grl_image_restoration_amd import _lib, evaluate as EV, make_config, metrics as M
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(ROOT, "tests", "golden", "niqe")
+PARAMS = os.path.join(GOLDEN, "niqe_pris_params.npz")
+
+# Bars.  Scores and features are compared with the float64 adjudication stored in the fixtures, never with the reference's fp32
+# value, which moves with its summation order.  What the reference itself shows on these fixtures (meta of niqe.npz: the reference's
+# fp32 run against the float64 run of the same functions): 1.2e-7, 1.9e-6, 3.6e-6, 3.5e-5 and, on rgb_192x288 where one alpha lands
+# on the neighbouring grid point, 1.233e-3.
+REF32_VS_REF64 = 1.233e-3          # the largest recorded gap (meta["largest_ref32_vs_ref64"], checked below)
+SCORE_BAR = 2 * REF32_VS_REF64     # factor 2 over it for the grid flips: one flipped alpha moved the score by the whole gap
+# Features, float64 against float64: a moment is a sum of 96 * 96 terms (relative rounding error below 9216 * 2^-53 = 1e-12); the
+# Eq. 8 mean is a difference of the two betas and can cancel by three digits, hence 1e-9 relative to (1e-3 + |feature|).
+FEATURE_BAR = 1e-9
+FEATURE_FLOOR = 1e-3
+# alpha is a nearest-grid-point search: a last-bit difference in a moment can move one feature of one block by one step
+GRID_STEP = 0.001
+GRID_FLIPS_PER_IMAGE = 1
+ALPHA_COLS = [0, 2, 6, 10, 14, 18, 20, 24, 28, 32]
+
+
+def golden(name):
+    z = np.load(os.path.join(GOLDEN, name + ".npz"))
+    return json.loads(str(z["meta"])), z
+
+
+def niqe_cases():
+    return sorted(golden("niqe")[0]["cases"])
+
+
+def case_image(z, name):
+    """Inputs are stored as integer levels (uint8, or int16 with levels outside 0..255): image = level / 255 in fp32."""
+    return torch.from_numpy(z[f"{name}__input"].astype(np.float32)) / 255.0
+
+
+def check_features(got, want, what):
+    """``got`` against ``want`` (both (B, blocks, 36) float64): nan positions equal, alphas equal up to GRID_FLIPS_PER_IMAGE single
+    steps per image, everything else within FEATURE_BAR (columns of a block whose alpha moved are skipped: they follow alpha)."""
+    got, want = torch.as_tensor(got).cpu(), torch.as_tensor(want).cpu()
+    assert got.shape == want.shape and got.dtype == torch.float64, (what, got.shape, want.shape)
+    assert torch.equal(torch.isnan(got), torch.isnan(want)), what
+    for b in range(got.shape[0]):
+        da = (got[b][:, ALPHA_COLS] - want[b][:, ALPHA_COLS]).abs()
+        moved = da > 0
+        assert int(moved.sum()) <= GRID_FLIPS_PER_IMAGE and float(da.max()) <= GRID_STEP * 1.0001, (what, b, int(moved.sum()), float(da.max()))
+        ok = torch.ones_like(got[b], dtype=torch.bool)
+        for blk, col in moved.nonzero().tolist():
+            c = ALPHA_COLS[col]
+            ok[blk, c : c + (2 if c % 18 == 0 else 4)] = False
+        err = ((got[b] - want[b]).abs() / (FEATURE_FLOOR + want[b].abs()))[ok & ~torch.isnan(want[b])]
+        assert float(err.max()) <= FEATURE_BAR, (what, b, float(err.max()))
+
+
+def test_recorded_reference_gap():
+    meta, _ = golden("niqe")
+    assert meta["y_mismatches"] == 0
+    assert abs(meta["largest_ref32_vs_ref64"] - REF32_VS_REF64) <= 1e-6
+    assert any(c["nan_rows"] > 0 for c in meta["cases"].values())
+
+
+@pytest.mark.parametrize("name", niqe_cases())
+def test_torch_restatement_matches_reference(name):
+    meta, z = golden("niqe")
+    x = case_image(z, name)
+    feat = M.niqe_features(x)
+    check_features(feat, z[f"{name}__distparam64"], name)
+    v = M.niqe(x, PARAMS)
+    gap = (v - torch.from_numpy(z[f"{name}__ref64"])).abs().max().item()
+    print(f"{name}: NIQE {v.tolist()}  |restatement - float64 reference| = {gap:.3e}")
+    assert v.dtype == torch.float64 and v.shape == (x.shape[0],) and gap <= SCORE_BAR, gap
+    via_group = M.image_metrics(x, None, "restorer_niqe", niqe_params=PARAMS)
+    assert list(via_group) == ["val_niqe"] and torch.equal(via_group["val_niqe"], v)
+
+
+def test_window_and_params():
+    with np.load(PARAMS) as f:
+        assert np.abs(M.niqe_window().numpy() - f["gaussian_window"]).max() < 1e-16
+        mu, cov = M.load_niqe_params({k: f[k] for k in f.files})
+    mu2, cov2 = M.load_niqe_params(PARAMS)
+    assert torch.equal(mu, mu2) and torch.equal(cov, cov2) and mu.shape == (36,)
+    assert M.niqe_grid().shape == (5, 9801)
+    assert M.NO_REFERENCE_GROUPS == {"restorer_niqe": ("val_niqe",)} and M.ALL_GROUPS["restorer_niqe"] == ("val_niqe",)
+    assert set(M.ALL_GROUPS) == set(M.GROUPS) | {"restorer_niqe"}
+    assert M.GROUPS["restorer"] == ("val_psnr", "val_psnr_y", "val_ssim", "val_ssim_y")
+
+
+def test_params_are_user_data(monkeypatch):
+    x = torch.rand(1, 3, 100, 100)
+    monkeypatch.delenv(M.NIQE_ENV, raising=False)
+    with pytest.raises(ValueError, match="GRL_NIQE_PARAMS"):
+        M.niqe(x)
+    with pytest.raises(ValueError, match="not found"):
+        M.niqe(x, os.path.join(GOLDEN, "missing.npz"))
+    monkeypatch.setenv(M.NIQE_ENV, PARAMS)
+    _, z = golden("niqe")
+    x = case_image(z, "rgb_192x288")
+    assert torch.equal(M.niqe(x), M.niqe(x, PARAMS))
+
+
+def test_flat_and_small_images_raise():
+    with pytest.raises(ValueError, match="flat"):
+        M.niqe(torch.full((1, 3, 200, 200), 0.5), PARAMS)
+    with pytest.raises(ValueError, match="flat"):
+        M.niqe(torch.zeros(1, 1, 192, 192), PARAMS)
+    with pytest.raises(ValueError, match="96"):
+        M.niqe(torch.rand(1, 3, 95, 300), PARAMS)
+    with pytest.raises(ValueError):
+        M.niqe(torch.rand(1, 2, 96, 96), PARAMS)
+
+
+def test_saturated_region_gives_nan_blocks():
+    """Flat windows at a level other than 0 (a burnt-out sky) give exactly zero MSCN, as in the reference's fp32 run."""
+    g = torch.Generator().manual_seed(3)
+    x = torch.rand(1, 1, 288, 288, generator=g)
+    x[..., 90:200, 90:200] = 1.0
+    f = M.niqe_features(x)[0]
+    assert torch.isnan(f[4]).any() and not torch.isnan(f[[0, 1, 2, 3, 5, 6, 7, 8]]).any()
+
+
+def test_niqe_args_layout_matches_header(tmp_path):
+    st = _lib.GrlNiqeArgs
+    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "grl_hip.h"', "int main(void) {",
+             'printf("size %zu\\n", sizeof(GrlNiqeArgs));']
+    lines += [f'printf("{f[0]} %zu\\n", offsetof(GrlNiqeArgs, {f[0]}));' for f in st._fields_]
+    lines += ["return 0; }"]
+    src, exe = tmp_path / "layout.c", tmp_path / "layout"
+    src.write_text("\n".join(lines))
+    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
+    out = dict(l.split() for l in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
+    assert int(out["size"]) == ctypes.sizeof(st)
+    for f in st._fields_:
+        assert int(out[f[0]]) == getattr(st, f[0]).offset, f[0]
+    assert "grl_image_niqe_features" in _lib.EXPORTS and "grl_image_niqe_workspace_bytes" in _lib.EXPORTS
+    assert _lib.ABI_VERSION >= 26
+
+
+def test_bsr_preset():
+    cfg = make_config("base", "bsr", upscale=4, upsampler="nearest+conv")
+    assert cfg["upsampler"] == "nearest+conv" and cfg["window_size"] == 16 and cfg["stripe_size"] == [32, 64]
+    assert cfg["stripe_groups"] == [None, None] and cfg["anchor_window_down_factor"] == 4 and cfg["embed_dim"] == 180
+    assert make_config("base", "bsr", upscale=4)["upsampler"] == "pixelshuffle"         # today's choice per model is the default
+    meta, _ = golden("bsr_pipeline")
+    from tools.make_golden_niqe import BSR_OVERRIDES
+
+    assert meta["cfg"] == make_config("tiny", "bsr", upscale=4, img_size=64, upsampler="nearest+conv", **BSR_OVERRIDES)
+
+
+def test_evaluate_cli_bsr_arguments(tmp_path, monkeypatch, capsys):
+    lq = tmp_path / "lq"
+    lq.mkdir()
+    monkeypatch.delenv(M.NIQE_ENV, raising=False)
+    assert "bsr" in EV.TASKS
+    with pytest.raises(SystemExit):                               # the pristine model is named neither way
+        EV.main(["--task", "bsr", "--lq", str(lq)])
+    err = capsys.readouterr().err
+    assert "--niqe-params" in err and "GRL_NIQE_PARAMS" in err
+    with pytest.raises(SystemExit):
+        EV.main(["--task", "bsr", "--lq", str(lq), "--niqe-params", str(tmp_path / "none.npz")])
+    assert "not found" in capsys.readouterr().err
+    with pytest.raises(SystemExit):
+        EV.main(["--task", "sr", "--lq", str(lq)])
+    assert "the following arguments are required: --gt" in capsys.readouterr().err
+    with pytest.raises(SystemExit):
+        EV.main(["--task", "bsr", "--lq", str(lq), "--gt", str(lq), "--niqe-params", PARAMS])
+    with pytest.raises(SystemExit):
+        EV.main(["--task", "bsr", "--lq", str(lq), "--metric", "restorer", "--niqe-params", PARAMS])
+    with pytest.raises(SystemExit):
+        EV.main(["--task", "bsr", "--niqe-params", PARAMS])
+    capsys.readouterr()
+    # without --gt, with the parameters: accepted by the parser; the empty folder is what stops it
+    with pytest.raises(ValueError, match="no images"):
+        EV.main(["--task", "bsr", "--model", "tiny", "--geometry", "bsr", "--upsampler", "nearest+conv", "--lq", str(lq),
+                 "--niqe-params", PARAMS, "--device", "cpu"])
