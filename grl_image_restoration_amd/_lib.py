@@ -7,6 +7,8 @@ returns an error, a RuntimeError is raised.  Build it with ``python __graft_entr
 import ctypes as C
 import os
 
+from . import switches as SW
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgrl_hip.so")
 ABI_VERSION = 26
@@ -679,7 +681,7 @@ def check(code: int, what: str):
         raise RuntimeError(f"libgrl_hip: {what} failed: {kind}")
 
 
-_DIRTY_LDS = os.environ.get("GRL_DIRTY_LDS", "0") == "1"
+_DIRTY_LDS = SW.on("GRL_DIRTY_LDS")
 
 
 def stream_ptr():

@@ -19,7 +19,6 @@ true-valued fp32 gradients.  The factor is chosen once per backward pass from th
 (``GradScaleTop``: one host read per step).
 """
 import math
-import os
 import threading
 import weakref
 from typing import Optional, Sequence
@@ -30,6 +29,7 @@ import torch.nn.functional as F
 
 from . import _lib as L
 from . import composite, ops
+from . import switches as SW
 
 _SIZES = (64, 96, 128, 192, 256, 384, 576, 768, 1152)   # widths both as N (n-tile chunks of 4/6/8) and as K (k-steps) of grl_linear_fwd
 
@@ -259,8 +259,8 @@ def _real(n: int, npad: int) -> bool:
     return n % 4 == 0 and n < npad and _REAL_WIDTHS[0]
 
 
-_REAL_WIDTHS = [os.environ.get("GRL_REAL_WIDTHS", "1") != "0"]
-_F16_HANDOVER = [os.environ.get("GRL_F16_HANDOVER", "1") != "0"]     # linear layers: fp16 operand copies for the weight gradient
+_REAL_WIDTHS = [SW.on("GRL_REAL_WIDTHS")]
+_F16_HANDOVER = [SW.on("GRL_F16_HANDOVER")]     # linear layers: fp16 operand copies for the weight gradient
 
 
 @torch.library.custom_op("grl::linear", mutates_args=())
@@ -660,7 +660,7 @@ class FanOut(torch.autograd.Function):
 
 
 def fan_out(x, n: int):
-    if x.is_cuda and x.requires_grad and os.environ.get("GRL_FAN_OUT", "1") != "0":
+    if x.is_cuda and x.requires_grad and SW.on("GRL_FAN_OUT"):
         return FanOut.apply(x, n)
     return (x,) * n
 
@@ -728,7 +728,7 @@ class SeResidualFn(torch.autograd.Function):
 def se_residual(x1, u, w1, b1, w2, b2, rows_per_image: int):
     """x1 + u * ChannelAttention-gate(u) on token matrices [B * rows_per_image, C]; w1 [Cmid, C], w2 [C, Cmid]."""
     C_ = u.shape[1]
-    if u.is_cuda and ops.se_mlp_ok(u[:1], w1) and C_ % 4 == 0 and os.environ.get("GRL_SE_KERNEL", "1") != "0":
+    if u.is_cuda and ops.se_mlp_ok(u[:1], w1) and C_ % 4 == 0 and SW.on("GRL_SE_KERNEL"):
         return SeResidualFn.apply(x1, u, w1, b1, w2, b2, rows_per_image)
     B = u.shape[0] // rows_per_image
     gate = se_gate(u.view(B, rows_per_image, C_).mean(dim=1), w1, b1, w2, b2)
@@ -737,7 +737,7 @@ def se_residual(x1, u, w1, b1, w2, b2, rows_per_image: int):
 
 def se_gate(pool, w1, b1, w2, b2):
     """The CAB's squeeze-excite gate from the pooled means (mixed_attn_block.py:956-963); w1 [Cmid, C], w2 [C, Cmid]."""
-    if pool.is_cuda and ops.se_mlp_ok(pool, w1) and os.environ.get("GRL_SE_KERNEL", "1") != "0":
+    if pool.is_cuda and ops.se_mlp_ok(pool, w1) and SW.on("GRL_SE_KERNEL"):
         return SeMlpFn.apply(pool, w1, b1, w2, b2)
     return torch.sigmoid(F.linear(F.relu(F.linear(pool, w1, b1)), w2, b2))
 

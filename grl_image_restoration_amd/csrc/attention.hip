@@ -800,7 +800,7 @@ extern "C" int grl_attention_fwd(void* stream, const GrlAttnArgs* args) {
     const bool split = p.q_lo != nullptr || p.k_lo != nullptr || p.v_lo != nullptr;
     if (p.o_lo != nullptr && p.out_dtype != GRL_DT_F16) return GRL_ERR_BAD_ARG;
     const bool lazy_ok = !split && p.k_one31 && p.head_dim <= 30 && p.ones_col != 31 && p.lazy_floor != nullptr;
-    static const int rows_off = getenv("GRL_ATTN_ROWS") ? atoi(getenv("GRL_ATTN_ROWS")) == 0 : 0;   // 0: round-2 fast kernels (A/B)
+    static const int rows_off = grl_env_int("GRL_ATTN_ROWS", 1) == 0;   // 0: round-2 fast kernels (A/B)
     // head_dim 32 (GRL-Small): no spare slot; the row-streaming kernel carries offset and denominator on the VALU instead
     const bool d32_ok = !split && p.head_dim == 32 && p.ones_col < 0 && p.lazy_floor != nullptr;
     const bool generic_only = getenv("GRL_ATTN_GENERIC") != nullptr;   // A/B knob, read per call (set: generic kernel only)

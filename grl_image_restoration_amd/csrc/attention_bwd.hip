@@ -687,14 +687,13 @@ extern "C" int grl_attention_bwd(void* stream, const GrlAttnBwdArgs* args) {
     GrlAttnBwdLaunch a_l;                               // the caller's arguments + the table-window sizes of the two launches
     a_l.fwd = a.fwd; a_l.d_o = a.d_o; a_l.d_q = a.d_q; a_l.d_k = a.d_k; a_l.d_v = a.d_v; a_l.d_table = a.d_table; a_l.g_scale = a.g_scale;
     a_l.d_table_fix = a.d_table_fix; a_l.d_o_ld = a.d_o_ld; a_l.tab_window = 0; a_l.tab_window_kv = 0;
-    static const int no_pre = getenv("GRL_ATTN_BWD_PREFETCH") ? atoi(getenv("GRL_ATTN_BWD_PREFETCH")) == 0 : 0;
+    static const int no_pre = grl_env_int("GRL_ATTN_BWD_PREFETCH", 1) == 0;
     a_l.no_prefetch = no_pre;
     const int Dw = p.q.ww + p.k.ww - 1;
     // Split launches (see attn_dq_kernel): when a launch has fewer workgroups than the chip has CUs and a long streamed dimension,
     // cut that dimension over several workgroups that accumulate with atomics.  Needs a destination this function can zero: dense
     // head planes [nh][tokens][32] (what the training path passes).  GRL_ATTN_BWD_SPLITS=1 disables, =n forces n parts on every launch, =-n caps the automatic choice at n (timing experiments).
-    const char* fs = getenv("GRL_ATTN_BWD_SPLITS");       // (read per call: the tests switch it)
-    const int force_splits = fs ? atoi(fs) : 0;
+    const int force_splits = grl_env_int("GRL_ATTN_BWD_SPLITS", 0);       // (read per call: the tests switch it)
     auto dense = [&](const GrlTokenGrid& g) {
         return g.ld == 32 && g.col0 == 0 && g.hstride == (int64_t)p.B * g.Himg * g.Wimg * 32;
     };

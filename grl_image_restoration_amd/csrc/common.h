@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #include "grl_hip_internal.h"
 
@@ -164,6 +165,19 @@ __device__ __forceinline__ float row16_sum(float v) {
     v += dpp_move<DPP_ROW_ROR4>(v);    // + the next quad
     v += dpp_move<DPP_ROW_ROR8>(v);    // + the other pair of quads
     return v;
+}
+
+// ---- environment switches read by the launchers (host only; the table of all GRL_* switches is grl_image_restoration_amd/switches.py) ----
+// Integer value of environment variable `name`, `dflt` when it is not set.  Each caller decides whether it reads once (function-local
+// static) or per call.
+inline int grl_env_int(const char* name, int dflt) {
+    const char* v = getenv(name);
+    return v ? atoi(v) : dflt;
+}
+// GRL_PERSIST_GRID: cap on the grid of the persistent kernels (tuning knob; 256 = one workgroup per CU)
+inline int grl_persist_grid_cap() {
+    static const int cap = grl_env_int("GRL_PERSIST_GRID", 256);
+    return cap;
 }
 
 #define GRL_CHECK_LAUNCH()                         \

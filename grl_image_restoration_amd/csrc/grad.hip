@@ -205,7 +205,7 @@ extern "C" int grl_gemm_tn(void* stream, const GrlGemmTnArgs* args) {
     if (p.splits <= 0 || p.splits * p.taps > 65535 || (p.c == nullptr && p.c_fix == nullptr)) return GRL_ERR_BAD_ARG;
     const dim3 grid((p.N + GT - 1) / GT, (p.K + (p.b_ones ? 1 : 0) + GT - 1) / GT, p.splits * p.taps);
     GrlGemmTnArgs q = p;
-    static const int plain_order = getenv("GRL_GEMM_TN_XCD") ? atoi(getenv("GRL_GEMM_TN_XCD")) == 0 : 0;
+    static const int plain_order = grl_env_int("GRL_GEMM_TN_XCD", 1) == 0;
     q.reserved0 = plain_order;         // (kernel-internal use of the reserved field: 1 = blockIdx order)
     hipLaunchKernelGGL(gemm_tn_kernel, grid, dim3(256), 0, (hipStream_t)stream, q);
     GRL_CHECK_LAUNCH();

@@ -311,7 +311,7 @@ int launch_ls(const GrlLinearArgs& p, hipStream_t st) {
     using G = LsGeom<KS>;
     const int nslabs = (p.Npad + LS_SLAB - 1) / LS_SLAB;
     const int ntiles = (p.M + LS_T - 1) / LS_T;
-    static const int cus = getenv("GRL_PERSIST_GRID") ? atoi(getenv("GRL_PERSIST_GRID")) : 256;
+    const int cus = grl_persist_grid_cap();
     int per_xcd = cus / (8 * nslabs);                       // walkers per XCD: one workgroup per CU
     if (per_xcd < 1) per_xcd = 1;
     if (per_xcd > (ntiles + 7) / 8) per_xcd = (ntiles + 7) / 8;

@@ -417,7 +417,7 @@ int launch_mlp(const TailP& p, hipStream_t st) {
     const size_t lds = 2 * (size_t)S::BUFP + (PROJ ? 8 : 3) * S::CP * sizeof(float) +
                        (size_t)((WV * 16 * (S::CP * 4 + 16) + 1023) / 1024) * 1024;
     const int ntiles = (p.M + WV * 16 - 1) / (WV * 16);
-    static const int cap = getenv("GRL_PERSIST_GRID") ? atoi(getenv("GRL_PERSIST_GRID")) : 256;   // tuning knob
+    const int cap = grl_persist_grid_cap();
     const int grid = ntiles < cap ? ntiles : cap;   // one persistent workgroup per CU
     auto kfn = mlp_kernel<KSTEPS, WV, PROJ>;
     hipError_t e = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);

@@ -180,8 +180,7 @@ int launch_qkv(const GrlQkvArgs& p, hipStream_t st) {
     using S = QkvShape<KSTEPS, SPC>;
     const size_t lds = 2 * (size_t)S::BUFP + (size_t)((TOK * 16 * (S::CP * 4 + 16) + 1023) / 1024) * 1024;
     const int ntiles = (p.M + TOK * 16 - 1) / (TOK * 16);
-    static const int cap0 = getenv("GRL_PERSIST_GRID") ? atoi(getenv("GRL_PERSIST_GRID")) : 256;   // tuning knob
-    const int cap = cap0 * (WV <= 4 ? 2 : 1);       // small workgroups: two per CU (or one beside a workgroup of another kernel)
+    const int cap = grl_persist_grid_cap();
     const int grid = ntiles < cap ? ntiles : cap;   // persistent workgroups
     auto kfn = qkv_kernel<KSTEPS, SPC, WV, TOK>;
     hipError_t e = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -193,10 +192,9 @@ int launch_qkv(const GrlQkvArgs& p, hipStream_t st) {
 
 template <int KSTEPS>
 int launch_qkv_k(const GrlQkvArgs& p, hipStream_t st) {
-    static const int small = getenv("GRL_QKV_SMALL") ? atoi(getenv("GRL_QKV_SMALL")) : 0;   // experiment: 64-token workgroups
-    static const int w16 = getenv("GRL_QKV_W16") ? atoi(getenv("GRL_QKV_W16")) : 1;       // 16 waves, slot-split (-5 % vs 8 waves)
+    static const int w16 = grl_env_int("GRL_QKV_W16", 1);   // 16 waves, slot-split (-5 % vs 8 waves); 0: the 8-wave kernel (A/B)
     if (p.nslots % 2 == 0 && w16) return launch_qkv<KSTEPS, 2, 16, 8>(p, st);
-    if (p.nslots % 2 == 0) return small ? launch_qkv<KSTEPS, 2, 4>(p, st) : launch_qkv<KSTEPS, 2, 8>(p, st);
+    if (p.nslots % 2 == 0) return launch_qkv<KSTEPS, 2, 8>(p, st);
     return launch_qkv<KSTEPS, 1, 8>(p, st);
 }
 

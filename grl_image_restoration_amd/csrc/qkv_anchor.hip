@@ -233,7 +233,7 @@ template <int KS>
 int launch_qa(const GrlQkvAnchorArgs& p, hipStream_t st) {
     using S = QaShape<KS>;
     const int ntiles = p.B * (p.H >> 1) * (p.W >> 6);
-    static const int cap = getenv("GRL_PERSIST_GRID") ? atoi(getenv("GRL_PERSIST_GRID")) : 256;   // tuning knob
+    const int cap = grl_persist_grid_cap();
     const int grid = ntiles < cap ? ntiles : cap;   // persistent workgroups
     auto kfn = qkv_anchor_kernel<KS>;
     hipError_t e = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, S::LDS);
@@ -883,7 +883,7 @@ extern "C" int grl_qkv_anchor_fwd(void* stream, const GrlQkvAnchorArgs* args) {
         if (p.Cpad != 192 || p.nslots != 18 || p.nanc != 3 || ((uintptr_t)p.lo_blob & 15) != 0) return GRL_ERR_UNSUPPORTED;
         return launch_qs(p, st);
     }
-    static const bool regs_off = getenv("GRL_QKV_REGS") && atoi(getenv("GRL_QKV_REGS")) == 0;
+    static const bool regs_off = grl_env_int("GRL_QKV_REGS", 1) == 0;
     if (p.Cpad == 192 && p.nslots + p.nanc == QR_SLOTS && !regs_off) return launch_qr(p, st);
     switch (p.Cpad / 16) {
         case 4: return launch_qa<4>(p, st);

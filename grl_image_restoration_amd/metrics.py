@@ -29,6 +29,7 @@ from typing import Dict, Optional, Tuple
 import torch
 import torch.nn.functional as F
 
+from . import switches as SW
 from .evaluate import rgb_to_y, shave, tensor_round
 
 GROUPS = {
@@ -230,7 +231,7 @@ def load_niqe_params(params=None) -> Tuple[torch.Tensor, torch.Tensor]:
     import numpy as np
 
     if params is None:
-        params = os.environ.get(NIQE_ENV)
+        params = SW.text(NIQE_ENV)
         if not params:
             raise ValueError(f"NIQE needs the pristine model (the reference's utils/metrics/niqe_pris_params.npz): pass its path as "
                              f"--niqe-params / niqe_params, or set the environment variable {NIQE_ENV}")

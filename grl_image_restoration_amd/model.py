@@ -10,7 +10,6 @@ the forward pass (grl.py:506-551) on MI355X through libgrl_hip.so.
 There is no CPU / eager fallback for the hot path: calling the model on CPU tensors raises.
 """
 import math
-import os
 from typing import Dict, List, Optional
 
 import torch
@@ -20,6 +19,7 @@ import torch.nn.functional as F
 from . import _lib as L
 from . import autograd as AG
 from . import ops, tables
+from . import switches as SW
 from .geometry import BlockGeo, block_schedule, pad_multiple, table_rows, to_2tuple
 
 LOG2E = tables.LOG2E
@@ -245,7 +245,7 @@ class GRL(nn.Module):
         #                                      fast + those splits 1.07e-3 -> calibrated (_calibrated_plan, 6 of 16 blocks split) 5.4e-4,
         #                                      +17 % time at 512x512; so narrow models with windows of 8 or less always calibrate
         #          GRL-Tiny                    high (fast + splits 6e-4 .. 8e-4, but 8e-3 at clamp scales)
-        precision = os.environ.get("GRL_PRECISION", precision)
+        precision = SW.text("GRL_PRECISION", default=precision)
         if precision not in ("auto", "fast", "high"):
             raise ValueError(f"precision={precision!r}: expected 'auto', 'fast' or 'high'")
         narrow = embed_dim < 160 or not upsampler
@@ -259,7 +259,7 @@ class GRL(nn.Module):
         # 1.04e-3 with W only -- but measured on the GPU the fixtures moved from 8.2e-4 to 8.8e-4 (deblur) and from 7.2e-4 to 9.0e-4
         # (Small) for 4-5 % of a step: not kept, the margin to the 1e-3 bar is worth more.)
         self.split_sites = ("stage_conv,after,last,cab0" if embed_dim >= 160 else "stage_conv,after,last") if narrow else ""
-        self.hiq_scale = float(os.environ.get("GRL_HIQ_SCALE", "50"))
+        self.hiq_scale = SW.num("GRL_HIQ_SCALE")
         if embed_dim % 2 or any((embed_dim // 2) % h for h in self.num_heads_window + self.num_heads_stripe):
             raise ValueError("embed_dim/2 must be divisible by the number of heads")
         if max((embed_dim // 2) // h for h in self.num_heads_window + self.num_heads_stripe) > 32:
@@ -507,7 +507,7 @@ class GRL(nn.Module):
         if not hi and CP in (64, 128, 192) and KA == CP and self.local_connection:   # + proj/norm1/CAB in front: one kernel per block tail
             pk["proj_blob"] = ops.pack_proj(Wop)
             # weights stationary in registers (csrc/tail_regs.hip, round 4): 255 against 290 us per 4 tiles; GRL_TAIL_REGS=0: streaming kernel
-            if CP == 192 and HP == 384 and C > 160 and os.environ.get("GRL_TAIL_REGS", "1") != "0":
+            if CP == 192 and HP == 384 and C > 160 and SW.on("GRL_TAIL_REGS"):
                 pk["tail_rblob"] = ops.pack_tail_regs(Wop, blk.mlp.fc1.weight.to(dev), blk.mlp.fc1.bias.to(dev), blk.mlp.fc2.weight.to(dev))
         if not hi and CP in (64, 128, 192):  # fused fc1 -> GELU -> fc2 -> norm2 -> residual kernel (csrc/mlp.hip)
             pk.update(mlp_blob=ops.pack_mlp(blk.mlp.fc1.weight.to(dev), blk.mlp.fc1.bias.to(dev), blk.mlp.fc2.weight.to(dev), CP, HP),
@@ -521,7 +521,7 @@ class GRL(nn.Module):
             coords = tables.coords_table(win, df, device=dev)
             bias = tables.bias_rows(m.cpb_mlp[0].weight.to(dev), m.cpb_mlp[0].bias.to(dev), m.cpb_mlp[2].weight.to(dev), coords)
             sw = lambda t: (t[1], t[0])
-            tr = (not hi and os.environ.get("GRL_ATTN_TRANSPOSE", "1") != "0"
+            tr = (not hi and SW.on("GRL_ATTN_TRANSPOSE")
                   and not ops.attention_rows_ok(q_win, k_win, q_sh, k_sh, masked, d)
                   and ops.attention_rows_ok(sw(q_win), sw(k_win), sw(q_sh), sw(k_sh), masked, d))
             if tr:
@@ -551,7 +551,7 @@ class GRL(nn.Module):
             if hi_c:
                 CmO = CmI   # fp32 mid tensor written by the plain store path: every channel of its row comes from the conv
             sp = 3 if hi_c else 1
-            sites = _split_sites(os.environ.get("GRL_SPLIT_SITES", self.split_sites))
+            sites = _split_sites(SW.text("GRL_SPLIT_SITES", default=self.split_sites))
             # the CAB's first conv on split operands: everything-split `high`; the fast path's per-site choice (see _plan); fp16 in the
             # auto-resolved `high` of a Base-width model (_high_cab_fp16: every other site is split there, so this one can afford it)
             pk["cab0_split"] = 3 if hi_c else (1 if hi else sites.get("cab0", 1))
@@ -564,7 +564,7 @@ class GRL(nn.Module):
                 se3_w=se[3].weight.detach().float().reshape(C, -1).to(dev).clone(),
                 se3_b=se[3].bias.detach().float().to(dev).clone(),
             )
-            if not hi_c and CP == 192 and Cm <= 48 and CmI >= 56 and os.environ.get("GRL_CAB_CONV2", "1") != "0":
+            if not hi_c and CP == 192 and Cm <= 48 and CmI >= 56 and SW.on("GRL_CAB_CONV2"):
                 pk["cab2_blob"], pk["cab2_bias"] = ops.pack_cab_conv2(c2.weight.to(dev), c2.bias.to(dev))   # csrc/cab_conv2.hip
         return pk
 
@@ -574,7 +574,7 @@ class GRL(nn.Module):
         (tools/precision_sites.py only ...) they are the least sensitive sites of the net -- conv1 3.4e-4 / 2.5e-4 (weights /
         input alone), conv2 1.9e-4 / 2.3e-4, against 1e-3 for the stage conv's weights alone -- and on split operands they were 41
         of a 188 ms forward.  An explicit precision='high' (and GRL-Tiny) keeps every contraction split.  GRL_HIGH_CAB=split|fp16."""
-        mode = os.environ.get("GRL_HIGH_CAB", "")
+        mode = SW.text("GRL_HIGH_CAB")
         if mode in ("split", "fp16"):
             return mode == "fp16"
         return self._precision_arg == "auto" and self.embed_dim >= 160
@@ -599,15 +599,16 @@ class GRL(nn.Module):
                     a = blk.attn
                     for t in (a.window_attn.attn_transform, a.stripe_attn.attn_transform1, a.stripe_attn.attn_transform2):
                         smax = max(smax, float(tables.clamped_scale(t.logit_scale).max()))
-            if smax <= float(os.environ.get("GRL_NARROW_HIGH_SCALE", "25")) and self.window_size[0] <= 8:
+            calibrate, high_scale = SW.on("GRL_CALIBRATE"), SW.num("GRL_NARROW_HIGH_SCALE")
+            if smax <= high_scale and self.window_size[0] <= 8:
                 # 8x8 windows (the demosaicking geometry): fp16 operands miss the 1e-3 bar even at random-init scales (GRL-Small
                 # 1.07e-3 against 7.1e-4 at the 16x16 denoising geometry), so the blocks are chosen by measurement here as well
-                if os.environ.get("GRL_CALIBRATE", "1") != "0":
+                if calibrate:
                     self._calibrate_narrow = True
-            elif smax > float(os.environ.get("GRL_NARROW_HIGH_SCALE", "25")):
+            elif smax > high_scale:
                 # round 6: not `high` throughout any more -- the blocks are chosen by measurement (_calibrated_plan), everything split
                 # only if the probe asks for it; GRL_CALIBRATE=0 restores the blanket rule
-                if os.environ.get("GRL_CALIBRATE", "1") == "0":
+                if not calibrate:
                     return "high"
                 self._calibrate_narrow = True
         return "fast"
@@ -621,7 +622,7 @@ class GRL(nn.Module):
         self.precision = self._resolve_precision()
         self.calibration = None
         if (self._precision_arg == "auto" and self.precision == "fast" and (not self._narrow or self._calibrate_narrow)
-                and os.environ.get("GRL_CALIBRATE", "1") != "0"):
+                and SW.on("GRL_CALIBRATE")):
             plan = self._calibrated_plan(x_size, dev, force=self._calibrate_narrow)
         else:
             plan = self._build_plan(x_size, dev, self.precision)
@@ -645,7 +646,7 @@ class GRL(nn.Module):
 
         # fast mode: convolutions named in GRL_SPLIT_SITES (stage_conv, after, last) still run on split operands -- per-site
         # precision for the models whose fast-mode error sits at the 1e-3 limit (tools/precision_sites.py)
-        sites = _split_sites(os.environ.get("GRL_SPLIT_SITES", self.split_sites))
+        sites = _split_sites(SW.text("GRL_SPLIT_SITES", default=self.split_sites))
         xs = {k: (3 if hi else sites.get(k, 1)) for k in ("stage_conv", "after", "last")}
 
         def pconv(conv, cin_pad, cout_pad, r=0, cg=0, site=None):
@@ -718,8 +719,8 @@ class GRL(nn.Module):
         self.calibration = info
         if not force and not any(fast["stages"][si]["blocks"][bi].get("hiq") for si, bi in blocks):
             return fast                       # random-init-like scales: fp16 operands hold 2e-4 (fixtures); nothing to measure
-        bar_rms = float(os.environ.get("GRL_CAL_RMS", "1.3e-4"))
-        bar_max = float(os.environ.get("GRL_CAL_MAX", "8.5e-4"))
+        bar_rms = SW.num("GRL_CAL_RMS")
+        bar_max = SW.num("GRL_CAL_MAX")
         H, W = x_size
         # the probe is a crop when the image is large and the block geometry does not depend on the image size
         ph, pw = min(H, 256 // self.pad_size * self.pad_size or self.pad_size), min(W, 256 // self.pad_size * self.pad_size or self.pad_size)
@@ -807,7 +808,7 @@ class GRL(nn.Module):
         # (GRL_SE_FOLD=1: conv2 + pool + squeeze-excite gate in one launch, the gate by the last workgroup of each image.  Measured
         # SLOWER in the two-stream bench, 88.1 against 82.6 ms/step: the serial tail of one workgroup per image holds the whole
         # launch, while the separate 10-us se_kernel hides behind the other tile group's kernels.  Kept as an option, off.)
-        if "cab2_blob" in pk and os.environ.get("GRL_SE_FOLD", "0") == "1":
+        if "cab2_blob" in pk and SW.on("GRL_SE_FOLD"):
             return ops.cab_conv2(mid, pk["cab2_blob"], pk["cab2_bias"], B, H, W,
                                  se=(pk["se1_w"], pk["se1_b"], pk["se3_w"], pk["se3_b"], self.embed_dim))
         elif "cab2_blob" in pk:
@@ -866,8 +867,8 @@ class GRL(nn.Module):
             return self._block_high(r, pk, geo, B, H, W)
         # q/k/v, anchors and the anchor-side values live as head planes [slot][token][32]: a key tile of 32
         # consecutive tokens is 2 KB contiguous for the attention kernel's staging loads
-        one_pass = "qa_blob" in pk and df == 2 and H % 2 == 0 and W % 64 == 0 and os.environ.get("GRL_QKV_ANCHOR", "1") != "0"
-        if pk.get("hiq") and one_pass and "qa_lo" in pk and os.environ.get("GRL_QKV_SPLIT", "1") != "0":
+        one_pass = "qa_blob" in pk and df == 2 and H % 2 == 0 and W % 64 == 0 and SW.on("GRL_QKV_ANCHOR")
+        if pk.get("hiq") and one_pass and "qa_lo" in pk and SW.on("GRL_QKV_SPLIT"):
             qkv, anc = ops.qkv_anchor(r, pk["qa_blob"], pk["qa_slots"][0], pk["qa_slots"][1], B, H, W, lo_blob=pk["qa_lo"])
         elif pk.get("hiq"):
             qkv = ops.linear(r, pk["qkv_w3"], pk["qkv_b"], epi=L.EPI_GROUPNORM, gscale=pk["qkv_gs"], planes=True, a_split=3, w_regs=pk.get("qkv_w3r"))
@@ -875,7 +876,7 @@ class GRL(nn.Module):
         elif one_pass:
             qkv, anc = ops.qkv_anchor(r, pk["qa_blob"], pk["qa_slots"][0], pk["qa_slots"][1], B, H, W)
         else:
-            if "qkv_blob" in pk and os.environ.get("GRL_STREAM_QKV", "1") != "0":
+            if "qkv_blob" in pk and SW.on("GRL_STREAM_QKV"):
                 qkv = ops.qkv(r, pk["qkv_blob"], pk["qkv_slots"])
             else:
                 qkv = ops.linear(r, pk["qkv_w"], pk["qkv_b"], epi=L.EPI_GROUPNORM, gscale=pk["qkv_gs"], planes=True)
@@ -883,7 +884,7 @@ class GRL(nn.Module):
         att = ops.empty(M, (nh_w + nh_s) * 32, dtype=ops.GEMM_DTYPE, device=dev)  # operand of the proj GEMM
         self._attention(qkv, anc, att, pk, geo, B, H, W)
         cab, gate = self._cab(r, pk, B, H, W, CP) if self.local_connection else (None, None)
-        if "proj_blob" in pk and "mlp_blob" in pk and H * W >= 128 and os.environ.get("GRL_FUSED_TAIL", "1") != "0":
+        if "proj_blob" in pk and "mlp_blob" in pk and H * W >= 128 and SW.on("GRL_FUSED_TAIL"):
             return ops.block_tail(att, r, cab, gate, H * W, pk["proj_blob"], pk["proj_b"], pk["n1_g"], pk["n1_b"], pk["mlp_blob"],
                                   pk["fc2_b"], pk["n2_g"], pk["n2_b"], Hpad=pk["mlp_hp"], n_real=C, res_scale=self.res_scale,
                                   rblob=pk.get("tail_rblob"))
@@ -892,7 +893,7 @@ class GRL(nn.Module):
                         ln_b=pk["n1_b"], n_real=C, res_scale=self.res_scale, resid=r, add2=cab, add2_scale=gate,
                         rows_per_image=H * W)
         # x = x + res_scale * norm2(mlp(x))                 (efficient.py:554)
-        if "mlp_blob" in pk and os.environ.get("GRL_FUSED_MLP", "1") != "0":
+        if "mlp_blob" in pk and SW.on("GRL_FUSED_MLP"):
             return ops.mlp(r1, pk["mlp_blob"], pk["fc2_b"], pk["n2_g"], pk["n2_b"], Hpad=pk["mlp_hp"], n_real=C,
                            res_scale=self.res_scale)
         h = ops.linear(r1, pk["fc1_w"], pk["fc1_b"], epi=L.EPI_GELU)
@@ -927,7 +928,7 @@ class GRL(nn.Module):
         # norm + residual (+ gated CAB branch) in the epilogue of the weights-stationary kernel where it takes the shape (a row of
         # <= 192 channels is one slab): the fp32 products p1 / p2 never reach memory
         fuse = (CP <= 192 and M % 32 == 0 and (H * W) % 32 == 0 and pk.get("proj_wr") is not None and pk.get("fc2_wr") is not None
-                and os.environ.get("GRL_HIGH_FUSE_LN", "1") != "0")
+                and SW.on("GRL_HIGH_FUSE_LN"))
         if fuse:
             r1 = ops.linear(att, pk["proj_w"], pk["proj_b"], epi=L.EPI_LN_RES, out_dtype=f32, a_split=3, w_regs=pk["proj_wr"],
                             ln_g=pk["n1_g"], ln_b=pk["n1_b"], n_real=C, res_scale=self.res_scale, resid=r, add2=cab, add2_scale=gate,
@@ -950,7 +951,7 @@ class GRL(nn.Module):
         n = self.stream_groups(B)
         if n > 1:
             return self._features_streams(t, plan, B, H, W, n)
-        check = os.environ.get("GRL_CHECK_RANGE", "0") == "1"   # debug: largest residual-stream magnitude per block (fp16 operand
+        check = SW.on("GRL_CHECK_RANGE")                        # debug: largest residual-stream magnitude per block (fp16 operand
         for si, st in enumerate(plan["stages"]):                # staging saturates at 65504; this reports how close a checkpoint gets)
             r = t
             for bi, pk in enumerate(st["blocks"]):
@@ -965,8 +966,8 @@ class GRL(nn.Module):
     def stream_groups(B: int) -> int:
         """Number of tile groups / HIP streams a batch of B tiles is processed in (GRL_SPLIT_STREAMS, default 2;
         measured on MI355X: 2 groups +6 % tiles/s over one stream, 4 groups are host-launch bound)."""
-        n = int(os.environ.get("GRL_SPLIT_STREAMS", "2"))
-        if os.environ.get("GRL_CHECK_RANGE", "0") == "1":
+        n = SW.num("GRL_SPLIT_STREAMS")
+        if SW.on("GRL_CHECK_RANGE"):
             return 1
         return n if n > 1 and B >= n and B % n == 0 else 1
 
@@ -1038,7 +1039,7 @@ class GRL(nn.Module):
         T, S, nh, d = x.shape
         dev = x.device
         cache = self.__dict__.setdefault("_coords_cache", {})
-        if ops.head_planes_ok(x, S) and os.environ.get("GRL_PLANES_KERNEL", "1") != "0" and not ops.deterministic():
+        if ops.head_planes_ok(x, S) and SW.on("GRL_PLANES_KERNEL") and not ops.deterministic():
             # round 6: one launch forward (normalise, scale, pad constants, permute, fp16 copy), one backward (csrc/planes.hip).
             # An expanded input (the anchors, used as scaled queries and as keys) is passed once: both slots read input slot 0.
             expanded = x.stride(1) == 0
@@ -1051,7 +1052,7 @@ class GRL(nn.Module):
             # (the fp32 planes are autograd's handle on the operands only -- every consumer takes the fp16 copies, f16= of the attention
             # op -- so the kernel does not write them: GRL_PLANES_WRITE32=1 restores the values)
             outs = AG.HeadPlanesFn.apply(xin, sc, tuple(0 if expanded else j for j in range(S)), tuple(s is None for s in scales),
-                                         tuple(int(c) for c in one_cols), os.environ.get("GRL_PLANES_WRITE32", "0") == "1")
+                                         tuple(int(c) for c in one_cols), SW.on("GRL_PLANES_WRITE32"))
             return outs[:S], outs[S:]
         key = ("planes_const", T, S, nh, d, tuple(s is None for s in scales), tuple(one_cols), str(dev))
         const = cache.get(key)
@@ -1156,7 +1157,7 @@ class GRL(nn.Module):
         qkv = AG.linear(r_q, a.qkv.body.weight, a.qkv.body.bias)                               # QKVProjection (mixed_attn_block.py:669-676)
         pooled = r_p.view(B, Ha, df, Wa, df, C).mean(dim=(2, 4)).reshape(B * Ha * Wa, C)        # AnchorLinear avg-pool (:727-736)
         anc = AG.linear(pooled, a.anchor.body[0].reduction.weight, a.anchor.body[0].reduction.bias).view(-1, nh_s, d_s)
-        same = (nh_w, d_w) == (nh_s, d_s) and os.environ.get("GRL_TRAIN_BATCHED_PLANES", "1") != "0"
+        same = (nh_w, d_w) == (nh_s, d_s) and SW.on("GRL_TRAIN_BATCHED_PLANES")
         if same:
             att = self._attention_train_batched(qkv, anc, a, geo, B, H, W, pre)
             return self._block_train_tail(r, att, blk, B, H, W, dp, r_c)
@@ -1248,7 +1249,7 @@ class GRL(nn.Module):
         # (round 6: the two branch outputs as token matrices [M, nh * 32]: one cat along the channels gives the projection's input --
         # _block_train_tail places the weight columns accordingly -- and the cat's backward hands each attention backward its column
         # block of the gradient in place; before: cat of the planes, permute, slice, copy, and zeros + copy + two copies back)
-        tm = os.environ.get("GRL_TRAIN_TOKEN_MAJOR", "1") != "0"
+        tm = SW.on("GRL_TRAIN_TOKEN_MAJOR")
         ow = AG.AttentionFn.apply(qw, kw, vw, tabs[0],
                                   dict(q=g_tok_w, k=g_tok_w, B=B, nh=nh, d=d, masked=sh > 0, floor=fw, prepared=True,
                                        f16=(qw16, kw16, vw16), token_major=tm))
@@ -1304,7 +1305,7 @@ class GRL(nn.Module):
         # Mlp (swin_v1_block.py:37-43): the GELU between fc1 and fc2 is taken by fc2's loader, its adjoint by the epilogue of fc2's
         # data-gradient launch (autograd.linear gelu_in; GRL_GELU_FUSED=0: the torch activation)
         h1 = AG.linear(x1, blk.mlp.fc1.weight, blk.mlp.fc1.bias)
-        if os.environ.get("GRL_GELU_FUSED", "1") != "0":
+        if SW.on("GRL_GELU_FUSED"):
             m = AG.linear(h1, blk.mlp.fc2.weight, blk.mlp.fc2.bias, gelu_in=True)
         else:
             m = AG.linear(F.gelu(h1), blk.mlp.fc2.weight, blk.mlp.fc2.bias)
@@ -1356,7 +1357,7 @@ class GRL(nn.Module):
 
         f = conv(x.permute(0, 2, 3, 1).reshape(B * H * W, Cin), self.conv_first)
         z = AG.layer_norm(f, self.norm_start.weight, self.norm_start.bias, 1e-5)
-        pre = self._train_tables(sched, x.device) if os.environ.get("GRL_TRAIN_BATCHED_PLANES", "1") != "0" else {}
+        pre = self._train_tables(sched, x.device) if SW.on("GRL_TRAIN_BATCHED_PLANES") else {}
         j = 0
         for si, stage in enumerate(self.layers):
             r = z
@@ -1419,7 +1420,7 @@ class GRL(nn.Module):
     def forward(self, x):
         """grl.py:506-551.  Eager launch sequence, or a captured HIP graph (``enable_graph`` / GRL_GRAPH=1)."""
         if getattr(self, "_use_graph", None) is None:
-            self._use_graph, self._graphs = os.environ.get("GRL_GRAPH", "0") == "1", {}
+            self._use_graph, self._graphs = SW.on("GRL_GRAPH"), {}
         if not (self._use_graph and x.is_cuda) or ops.profiling() or torch.is_grad_enabled():
             return self._forward_eager(x)
         key = (tuple(x.shape), x.dtype, str(x.device))
@@ -1448,7 +1449,7 @@ class GRL(nn.Module):
         if not x.is_cuda:
             # CPU tensor: the composite torch path (composite.py; SURVEY 8(b) "errors", BASELINE configs[0]).  Not a fallback of the
             # GPU path -- a CUDA tensor never gets here and still fails loudly below when the HIP library is missing.
-            if os.environ.get("GRL_NO_CPU_COMPOSITE", "0") == "1":
+            if SW.on("GRL_NO_CPU_COMPOSITE"):
                 raise RuntimeError("grl_image_restoration_amd.GRL: got a CPU tensor and GRL_NO_CPU_COMPOSITE=1 forbids the composite torch path "
                                    "(no CPU fallback)")
             if any(p.is_cuda for p in self.parameters()):

@@ -12,6 +12,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib as L
+from . import switches as SW
 
 GEMM_DTYPE = torch.float16  # operand / intermediate type of the linear and conv kernels (csrc/common.h: gemm_t)
 PLANE_DTYPE = torch.float16  # q / k / v / anchor head planes (attention operands)
@@ -24,7 +25,7 @@ _KIND = {torch.float32: L.DT_F32, torch.float16: L.DT_F16}
 # in the parity tests instead of depending on what the allocator handed out (zeros in a fresh process, another process's leftovers
 # in memory the driver recycled -- round 5's order-dependent failure of the captured training step).  The fill is an ordinary
 # launch on the current stream, so it is captured into a HIP graph with the step and re-poisons the buffer on every replay.
-_POISON = os.environ.get("GRL_POISON", "0") == "1"
+_POISON = SW.on("GRL_POISON")
 
 
 def set_poison(flag: bool) -> bool:
@@ -48,7 +49,7 @@ def deterministic() -> bool:
     the M slabs of the weight-gradient GEMM, the bias-table gradient of the attention backward -- are accumulated as 64-bit fixed
     point with integer atomics (integer addition commutes, fp32 addition does not), and the attention backward does not split
     its launches (grl_hip.h: GrlGemmTnArgs.c_fix, GrlAttnBwdArgs.d_table_fix).  Slower; read per call."""
-    return os.environ.get("GRL_DETERMINISTIC", "0") == "1"
+    return SW.on("GRL_DETERMINISTIC")
 
 
 # ---- one zero fill per backward pass -----------------------------------------------------------------------------------------
@@ -60,7 +61,7 @@ def deterministic() -> bool:
 # GRL_ZERO_ARENA=0: torch.zeros per buffer.
 _ARENA: dict = {}            # device index -> [buffer, next free element, elements requested in this pass, autograd graph-task id]
 _ARENA_SIZE: dict = {}       # device index -> elements the last complete pass requested
-_ARENA_ON = os.environ.get("GRL_ZERO_ARENA", "1") != "0"
+_ARENA_ON = SW.on("GRL_ZERO_ARENA")
 
 
 def _graph_task() -> int:
@@ -737,7 +738,7 @@ def conv3x3(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, B: int, H: int
     # Short-K layers (CAB conv2: 64 -> 192 channels, 9 tap steps in all) are epilogue/store dominated with one 104 KB-LDS
     # workgroup per CU; two launches of 96 output channels run two workgroups per CU whose store and MFMA phases
     # overlap (137 -> 101 us per 4 tiles).  Long-K layers (stage convs) lose from the split.  GRL_CONV_SPLIT overrides.
-    split = int(os.environ.get("GRL_CONV_SPLIT", "96" if CinP <= 64 and x_split == 1 else "0"))
+    split = SW.num("GRL_CONV_SPLIT", default=96 if CinP <= 64 and x_split == 1 else 0)
     if split and CoutP > split and CoutP % split == 0 and shuffle_r <= 1:
         step = split
     elif CoutP > 192:
@@ -852,7 +853,7 @@ def gemm_tn(a: torch.Tensor, b: torch.Tensor, N: int, K: int, *, taps: int = 1, 
     # ~1000 workgroups of >= 256 rows each; measured per shape with the XCD-aware tile order (tools/bench_gemm_tn.py, 512 / 768 /
     # 1024 / 1536 / 2048): the 3 x 3-tile proj gradient is fastest at 512 (42 against 51 us), the nine-tap 184 x 192 stage convolution
     # at 1536 (118 against 137), everything else at 1024
-    wgs = int(os.environ.get("GRL_GEMM_TN_WGS", "0")) or (512 if tiles <= 9 else (1536 if tiles >= 81 else 1024))
+    wgs = SW.num("GRL_GEMM_TN_WGS") or (512 if tiles <= 9 else (1536 if tiles >= 81 else 1024))
     splits = max(1, min((M + 255) // 256, (wgs + tiles - 1) // tiles))
     args = L.GrlGemmTnArgs(a=_ptr(a), lda=a.stride(0), b=_ptr(b), b_dtype=_KIND[b.dtype], ldb=b.stride(0), M=M, N=N, K=K, taps=taps,
                            H=H, W=W, splits=splits, a_scale=a_scale, out_scale=out_scale, c=None if det else _ptr(c), ldc=K,
@@ -933,7 +934,7 @@ def cpb_table_bwd(coords: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, w2: 
     return d_w1, d_b1, d_w2
 
 
-STAT_REPLICAS = int(os.environ.get("GRL_STAT_REPLICAS", "32"))     # copies of small cross-workgroup sums (LayerNorm dgamma / dbeta, plane scale gradients)
+STAT_REPLICAS = SW.num("GRL_STAT_REPLICAS")     # copies of small cross-workgroup sums (LayerNorm dgamma / dbeta, plane scale gradients)
 
 
 def layernorm_train(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float = 1e-5, resid: Optional[torch.Tensor] = None,
