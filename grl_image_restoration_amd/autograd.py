@@ -10,7 +10,7 @@ the forward AND the backward pass runs in libgrl_hip.so:
 (torch.library custom ops with registered autograd and fake kernels)
 
 and the element-wise glue between them (LayerNorm, GELU, L2 normalisation, logit scale, CPB-MLP, squeeze-excite, residuals,
-pixel shuffle) is ordinary differentiable torch code on the GPU (model.py: ``GRL._forward_train``).
+pixel shuffle) is ordinary differentiable torch code on the GPU (forward_train.py: ``forward``).
 
 Gradient range: the kernels contract fp16 operands.  An L1 loss over a 256x256 output produces gradients of ~1e-6, below the
 fp16 normal range, so the backward contractions multiply their gradient operand by a power of two on its way to fp16 and
@@ -479,7 +479,7 @@ conv3x3_op.register_autograd(_conv_backward, setup_context=_conv_setup)
 
 def _attn_operands(q, k, v, d, prepared, have=(None, None, None)):
     """fp16 copies of the head planes for the kernels.  ``prepared``: the caller has already put the constants into the pad
-    columns (GRL._to_planes: 1.0 in k's slot 31 and in v's column d) -- otherwise two index fills per call.  ``have``: copies the
+    columns (forward_train.to_planes: 1.0 in k's slot 31 and in v's column d) -- otherwise two index fills per call.  ``have``: copies the
     caller already made (of prepared planes)."""
     q16 = have[0] if have[0] is not None else q.detach().to(ops.PLANE_DTYPE)
     k16 = have[1] if have[1] is not None else k.detach().to(ops.PLANE_DTYPE)
@@ -502,7 +502,7 @@ def attention_op(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, table: torch
     (fp16 in the kernel): q = normalised * scale * log2e, k normalised, v raw; ``table`` from tables.kernel_table; ``floor`` from
     tables.lazy_floor; qgeo / kgeo = (Himg, Wimg, wh, ww, shy, shx).  Returns (fp32 planes [nh, q_tokens, 32], log2-sum-exp2,
     and the fp16 operand planes the kernel ran on -- kept for the backward pass instead of converting them again).
-    ``q16`` / ``k16`` / ``v16``: fp16 copies of (prepared) q / k / v the caller already has -- GRL._block_train converts the planes of
+    ``q16`` / ``k16`` / ``v16``: fp16 copies of (prepared) q / k / v the caller already has -- forward_train.block_train converts the planes of
     a whole block in one launch instead of three per attention call; the matching outputs are empty then (an op's outputs must not
     alias its inputs) and the backward takes the operands from the inputs.  ``token_major``: the output as a token matrix
     [q_tokens, nh * 32] instead of head planes -- what the projection behind the attention reads (round 6: the planes of the two

@@ -6,7 +6,7 @@ the HIP library is missing), and nothing here is timed or claimed as MI355X work
 without a GPU -- checkpoint conversion, a unit test of the surrounding engine, the reference's own CPU smoke run -- produces the
 reference's numbers instead of an exception.  The three contractions that are HIP kernels on the GPU (torch.ops.grl.linear /
 conv3x3 / attention, autograd.py) are written here as ordinary differentiable torch expressions on the SAME operand contract
-(channels-last token matrices, head planes [nh, tokens, 32], the kernel-domain bias table), so ``GRL._forward_train`` -- the one
+(channels-last token matrices, head planes [nh, tokens, 32], the kernel-domain bias table), so ``forward_train.forward`` -- the one
 statement of the network's data flow -- serves both devices.
 
 Attention semantics (mixed_attn_block_efficient.py:36-58, 77-94, 128-165, 215-270; ops.py:36-157, 308-375): cyclic shift by

@@ -78,6 +78,15 @@ class BlockGeo:
     def anchor_shift_size(self):
         return (self.stripe_shift_size[0] // self.df, self.stripe_shift_size[1] // self.df)
 
+    def grids(self, H: int, W: int):
+        """The token grids of the block's three attention launches on an H x W image, each as (rows, cols, window rows, window
+        cols, shift y, shift x): the window branch's tokens, the stripe branch's tokens, and the anchors (H / df x W / df)."""
+        ws, sh = self.window, self.window_shift
+        st, ss = self.stripe, self.stripe_shift_size
+        ast, ass = self.anchor_stripe, self.anchor_shift_size
+        return ((H, W, ws[0], ws[1], sh, sh), (H, W, st[0], st[1], ss[0], ss[1]),
+                (H // self.df, W // self.df, ast[0], ast[1], ass[0], ass[1]))
+
 
 def block_schedule(depths, num_heads_window, num_heads_stripe, window_size, stripe_size, stripe_groups,
                    stripe_shift: bool, df: int, x_size) -> List[List[BlockGeo]]:

@@ -20,7 +20,7 @@ _KIND = {torch.float32: L.DT_F32, torch.float16: L.DT_F16}
 
 
 # ---- uninitialised workspace ------------------------------------------------------------------------------------------
-# Every output / workspace tensor of the C-ABI wrappers (and of autograd.py / model.py) comes from here.  GRL_POISON=1 fills it with
+# Every output / workspace tensor of the C-ABI wrappers (and of autograd.py / forward_infer.py) comes from here.  GRL_POISON=1 fills it with
 # NaN (floating types) or 0x7f bytes first: a kernel that reads an element neither it nor a predecessor wrote turns up as a NaN
 # in the parity tests instead of depending on what the allocator handed out (zeros in a fresh process, another process's leftovers
 # in memory the driver recycled -- round 5's order-dependent failure of the captured training step).  The fill is an ordinary

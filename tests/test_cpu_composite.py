@@ -48,7 +48,7 @@ def test_cpu_path_is_differentiable_and_announced():
 
 def test_batched_plane_and_table_chains_equal_the_per_slot_chains(monkeypatch):
     """Round 5 builds the head planes of a block, and the bias tables / logit scales of all blocks, in batched chains
-    (GRL._block_planes / _train_tables / _residual).  Same loss and same gradients as the per-slot chains of round 4
+    (forward_train.block_planes / train_tables).  Same loss and same gradients as the per-slot chains of round 4
     (GRL_TRAIN_BATCHED_PLANES=0), here through the composite contractions on CPU at a checkpoint-like spread of logit scales, with
     DropPath on (both paths draw the same masks)."""
     from grl_image_restoration_amd import GRL, make_config

@@ -248,7 +248,7 @@ def test_graph_owns_its_plan_across_shapes_and_weight_updates():
 SEED_BARS = {
     # GRL-Base SR: fp16 operands sit AT the 1e-3 bar at these scales, weight draw by weight draw (round 5: 7.7e-4 / 5.9e-4 / 1.9e-3;
     # round 6, six draws: 7.3e-4, 1.6e-3, 6.3e-4, 5.5e-4, 8.3e-4, 1.2e-3).  Since round 6 `auto` MEASURES the weights it holds
-    # (GRL._calibrated_plan: a probe image through the all-split network and through the fp16-operand one) and moves the blocks whose
+    # (plan.calibrated_plan: a probe image through the all-split network and through the fp16-operand one) and moves the blocks whose
     # fp16 rounding costs the most to split operands until the probe passes: 0-11 of 40 blocks on these draws, 3.6e-4 .. 8.0e-4
     # against the float64 truth -- asserted at the north_star's 1e-3 like every fixture (the bar was 2.5e-3).
     "base_sr4": dict(auto_max=1e-3, auto_rms=2e-4, also_high=True),
@@ -324,20 +324,20 @@ def test_second_seeds_at_clamp_scales_vs_pinned_oracle(tag, seeds):
 
 
 def test_auto_precision_is_calibrated_once_per_weight_set(monkeypatch):
-    """precision='auto' on a wide SR model with checkpoint-like scales (GRL._calibrated_plan): the choice is made when the plan is
+    """precision='auto' on a wide SR model with checkpoint-like scales (plan.calibrated_plan): the choice is made when the plan is
     built -- a second forward re-uses it, new weights trigger a new measurement, GRL_CALIBRATE=0 keeps the fp16-operand rules of
     round 5 -- and the numbers it decided on are available to the caller."""
     import math
 
-    from grl_image_restoration_amd import GRL, make_config
+    from grl_image_restoration_amd import make_config, plan
 
     cfg = make_config("base", "sr_ckpt_df2", upscale=4, img_size=64)
     m, sd = _product(cfg, 15, logit_scale_mean=math.log(100.0))          # weight draw 15: fp16 operands alone give 1.2e-3
     m = m.to("cuda:0")
     lq = O.synthetic_pair("sr", (64, 64), 4, batch=1, seed=25)[0].to("cuda:0")
     builds = []
-    orig = GRL._build_plan
-    monkeypatch.setattr(GRL, "_build_plan", lambda self, *a, **k: (builds.append(a[2]), orig(self, *a, **k))[1])
+    orig = plan.build_plan
+    monkeypatch.setattr(plan, "build_plan", lambda model, *a, **k: (builds.append(a[2]), orig(model, *a, **k))[1])
     with torch.no_grad():
         y1 = m(lq)
         n1 = len(builds)

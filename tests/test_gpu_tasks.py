@@ -98,7 +98,7 @@ def _pipeline_model(**kw):
 # GRL-Small at the dm geometry against the reference's fp32 output (which is within 1.2e-6 of the same network on the exactly
 # demosaicked input, and moves by 4e-6 under a 2^-20 input perturbation).  Split operands (`high`) measured 4.6e-6 max / 9.9e-7 rms:
 # the attention kernels handle 8x8 windows / 32x32 stripes / anchors / 4 at head dim 32.  The default (`auto`) calibrates the blocks
-# of narrow models with 8x8 windows (model.py, _resolve_precision): measured 5.4e-4 max / 1.2e-4 rms (1.07e-3 on fp16 operands alone).
+# of narrow models with 8x8 windows (plan.py, resolve_precision): measured 5.4e-4 max / 1.2e-4 rms (1.07e-3 on fp16 operands alone).
 PIPELINE_BARS = {"high": (1e-5, 2e-6), "auto": (1e-3, 2e-4)}
 
 

@@ -298,8 +298,8 @@ def test_layernorm_train_kernels_match_torch(M, n):
 @pytest.mark.parametrize("T,nh,d,anchors", [(1000, 3, 30, False), (257, 3, 30, True), (512, 2, 32, False), (300, 2, 16, True)])
 def test_head_planes_kernels_match_the_torch_chain(T, nh, d, anchors, monkeypatch):
     """grl_head_planes_fwd / _bwd (csrc/planes.hip: normalise, scale, pad constants, permute, fp16 copy in one launch; dx and the
-    logit-scale gradients in another) against GRL._block_planes' torch chain (GRL_PLANES_KERNEL=0) in float64-checked fp32."""
-    from grl_image_restoration_amd import GRL, make_config
+    logit-scale gradients in another) against forward_train.block_planes' torch chain (GRL_PLANES_KERNEL=0) in float64-checked fp32."""
+    from grl_image_restoration_amd import GRL, forward_train, make_config
 
     m = GRL(**make_config("tiny", "yaml", upscale=2, img_size=16, depths=[1], num_heads_window=[2], num_heads_stripe=[2]))
     # (the training path leaves the fp32 planes unwritten -- nothing reads them, the attention op takes the fp16 copies -- this test
@@ -322,7 +322,7 @@ def test_head_planes_kernels_match_the_torch_chain(T, nh, d, anchors, monkeypatc
         x = x0.clone().requires_grad_(True)
         sa, sb = s_a.clone().requires_grad_(True), s_b.clone().requires_grad_(True)
         scales = (sa, ones) if anchors else (sa, ones, None, sb, ones, None)
-        p32, p16 = m._block_planes(x.expand(-1, 2, nh, d) if anchors else x, scales, one_cols)
+        p32, p16 = forward_train.block_planes(m, x.expand(-1, 2, nh, d) if anchors else x, scales, one_cols)
         assert len(p32) == len(p16) == S and all(t.shape == (nh, T, 32) for t in p32) and all(t.dtype == torch.float16 for t in p16)
         sum((a * b).sum() for a, b in zip(p32, grads)).backward()
         res[mode] = ([t.detach().clone() for t in p32], [t.detach().clone() for t in p16], x.grad.clone(), sa.grad.clone(),

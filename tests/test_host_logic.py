@@ -459,13 +459,13 @@ def test_transposed_view_is_the_same_attention_on_the_oracle():
 
 
 def test_split_site_spec_and_linear_split_blob_layout():
-    """model._split_sites ('name' = both operands split, 'name:x' = activations only) and ops.pack_linear_split: the register image
+    """plan._split_sites ('name' = both operands split, 'name:x' = activations only) and ops.pack_linear_split: the register image
     of include/grl_hip.h (GrlLinearArgs.w_regs) -- per slab of 192 columns and compute wave the hi, then the lo A fragments, lane l
     element e of k-step s = W[32 (6 slab + wave) + (l & 31)][16 s + 8 (l >> 5) + e], columns beyond Npad zero."""
     import torch
 
     from grl_image_restoration_amd import _lib, ops
-    from grl_image_restoration_amd.model import _split_sites
+    from grl_image_restoration_amd.plan import _split_sites
 
     assert _split_sites("stage_conv:x,after,last,cab0") == {"stage_conv": 2, "after": 3, "last": 3, "cab0": 3}
     assert _split_sites("") == {}
@@ -487,16 +487,16 @@ def test_split_site_spec_and_linear_split_blob_layout():
 
 
 def test_training_glue_shortcuts_equal_the_plain_torch_chains():
-    """Round-4 launch-count shortcuts of the training path, on the CPU: GRL._attn_table's single gather + scale equals
+    """Round-4 launch-count shortcuts of the training path, on the CPU: forward_train.attn_table's single gather + scale equals
     tables.kernel_table(16 * sigmoid(CPB-MLP)) on every entry a (query, key) pair can address (the pad entries repeat row 0 instead
-    of being zero), with the same gradient for the CPB-MLP; GRL._to_planes's single cat equals the pad + permute it replaced, with
+    of being zero), with the same gradient for the CPB-MLP; forward_train.to_planes's single cat equals the pad + permute it replaced, with
     the constants the attention kernel wants (k slot 31, v column d) in place."""
     import math
 
     import torch
     import torch.nn.functional as F
 
-    from grl_image_restoration_amd import GRL, make_config, tables
+    from grl_image_restoration_amd import GRL, forward_train, make_config, tables
 
     cfg = make_config("base", "sr_ckpt_df2", upscale=4, img_size=64, depths=[1], num_heads_window=[3], num_heads_stripe=[3])
     torch.manual_seed(3)
@@ -505,7 +505,7 @@ def test_training_glue_shortcuts_equal_the_plain_torch_chains():
     for tr, win, df in ((blk.attn.window_attn.attn_transform, (32, 32), 1), (blk.attn.stripe_attn.attn_transform1, (64, 64), 2)):
         coords = tables.coords_table(win, df, device="cpu")
         rows = coords.shape[0]
-        got = m._attn_table(tr, win, df, torch.device("cpu"))
+        got = forward_train.attn_table(m, tr, win, df, torch.device("cpu"))
         h = F.relu(F.linear(coords, tr.cpb_mlp[0].weight, tr.cpb_mlp[0].bias))
         want = tables.kernel_table(16.0 * torch.sigmoid(F.linear(h, tr.cpb_mlp[2].weight)))
         assert got.shape == want.shape and got.is_contiguous()
@@ -521,16 +521,16 @@ def test_training_glue_shortcuts_equal_the_plain_torch_chains():
 
     t = torch.randn(96, 3, 30, generator=torch.Generator().manual_seed(6), requires_grad=True)
     plain = F.pad(t, (0, 2)).permute(1, 0, 2).contiguous()
-    assert torch.equal(m._to_planes(t), plain)
-    k = m._to_planes(t, 31)
+    assert torch.equal(forward_train.to_planes(m, t), plain)
+    k = forward_train.to_planes(m, t, 31)
     assert torch.equal(k[..., :31], plain[..., :31]) and bool((k[..., 31] == 1).all())
-    v = m._to_planes(t, 30)
+    v = forward_train.to_planes(m, t, 30)
     assert torch.equal(v[..., :30], plain[..., :30]) and bool((v[..., 30] == 1).all()) and bool((v[..., 31] == 0).all())
     (g,) = torch.autograd.grad(k.sum(), t)
     assert bool((g == 1).all())                                                                        # the constant block takes no gradient
     t32 = torch.randn(64, 2, 32)
-    assert torch.equal(m._to_planes(t32, -1), t32.permute(1, 0, 2).contiguous())
-    assert math.isclose(float((m._to_planes(t, 31).sum() - plain.sum()).detach()), 96 * 3, rel_tol=1e-5)
+    assert torch.equal(forward_train.to_planes(m, t32, -1), t32.permute(1, 0, 2).contiguous())
+    assert math.isclose(float((forward_train.to_planes(m, t, 31).sum() - plain.sum()).detach()), 96 * 3, rel_tol=1e-5)
 
 
 def test_fused_adamw_capture_mode_bookkeeping():
@@ -604,10 +604,47 @@ def test_fused_adamw_capture_mode_keeps_addresses_and_follows_schedulers():
         opt.refresh_capture_hyper()
 
 
+def test_block_grids_are_the_tuples_the_launch_sequences_spelt_out():
+    """BlockGeo.grids returns the (rows, cols, window rows, window cols, shift y, shift x) tuples that the inference and the training
+    launch sequences each spelt out before: a shifted window block and a shifted stripe block of two schedules."""
+    from grl_image_restoration_amd import make_config
+    from grl_image_restoration_amd.geometry import block_schedule
+
+    for model, geom, side in (("base", "sr_ckpt_df2", 128), ("small", "dn_df4", 256)):
+        cfg = make_config(model, geom, img_size=side)
+        H, W = side, 2 * side
+        sched = block_schedule(cfg["depths"], cfg["num_heads_window"], cfg["num_heads_stripe"], cfg["window_size"], cfg["stripe_size"],
+                               cfg["stripe_groups"], cfg["stripe_shift"], cfg["anchor_window_down_factor"], (H, W))
+        shifted_window, shifted_stripe = sched[0][2], sched[0][3]         # block 2: both shifts, H stripes; block 3: stripes only, W stripes
+        assert shifted_window.window_shift > 0 and shifted_window.stripe_shift and shifted_stripe.stripe_shift
+        assert shifted_stripe.window_shift == 0 and shifted_stripe.stripe == tuple(cfg["stripe_size"])[::-1]
+        for geo in (shifted_window, shifted_stripe):
+            df = geo.df
+            Ha, Wa = H // df, W // df
+            ws, sh = geo.window, geo.window_shift
+            st, ss = geo.stripe, geo.stripe_shift_size
+            ast, ass = geo.anchor_stripe, geo.anchor_shift_size
+            assert geo.grids(H, W) == ((H, W, ws[0], ws[1], sh, sh), (H, W, st[0], st[1], ss[0], ss[1]),
+                                       (Ha, Wa, ast[0], ast[1], ass[0], ass[1]))
+    window, stripe, anchor = sched[0][2].grids(256, 512)                  # dn_df4: 16x16 windows, 64x128 stripes, anchors / 4
+    assert window == (256, 512, 16, 16, 8, 8) and stripe == (256, 512, 64, 128, 32, 64) and anchor == (64, 128, 16, 32, 8, 16)
+
+
+def test_training_floor_and_scale_helpers_equal_the_table_module():
+    """forward_train._floor on the already scaled value s * log2e is tables.lazy_floor(s); _scale is the clamped scale * log2e."""
+    import torch
+
+    from grl_image_restoration_amd import forward_train, tables
+
+    s = torch.tensor([0.5, 1.0, 7.3, 10.0, 69.3, 99.99, 100.0])
+    assert torch.equal(forward_train._floor(s * tables.LOG2E), tables.lazy_floor(s))
+    assert torch.equal(forward_train._scale(torch.tensor([1.0, 4.0, 5.0])), tables.clamped_scale(torch.tensor([1.0, 4.0, 5.0])) * tables.LOG2E)
+
+
 def test_calibration_predicts_the_blocks_to_split():
-    """GRL._calibrated_plan's variance bookkeeping (model.predicted_split_count): blocks are sorted by what their fp16 rounding
+    """plan.calibrated_plan's variance bookkeeping (plan.predicted_split_count): blocks are sorted by what their fp16 rounding
     costs, the cheapest stay on fp16 operands while the summed variance fits the bar."""
-    from grl_image_restoration_amd.model import predicted_split_count as psc
+    from grl_image_restoration_amd.plan import predicted_split_count as psc
 
     bar = 1.3e-4
     assert psc([], 0.0, bar) == 0

@@ -1,4 +1,4 @@
-"""What does `auto`'s block-by-block calibration (GRL._calibrated_plan) decide on checkpoint-like weight draws, what does the
+"""What does `auto`'s block-by-block calibration (plan.calibrated_plan) decide on checkpoint-like weight draws, what does the
 decision cost, and what error against the float64 truth results?  (diagnostic, GPU box; the truths are tests/golden/seeds/*)"""
 import json
 import math

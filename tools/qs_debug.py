@@ -13,11 +13,11 @@ with torch.no_grad():
         if n.endswith("logit_scale"): p_.fill_(math.log(100.0))
 B, H, W, CP = 4, 256, 256, 192
 plan = m._plan((H, W), torch.device("cuda"))
-pk = plan["stages"][0]["blocks"][2]
+pk = plan.stages[0].blocks[2]
 r = torch.randn(B * H * W, CP, device="cuda"); r[:, 180:] = 0
 lib = L.lib()
 buf = (C.c_ulonglong * 64)()
-run = lambda: ops.qkv_anchor(r, pk["qa_blob"], 18, 3, B, H, W, lo_blob=pk["qa_lo"])
+run = lambda: ops.qkv_anchor(r, pk.qa_blob, 18, 3, B, H, W, lo_blob=pk.qa_lo)
 for _ in range(3): run()
 lib.grl_qs_debug(buf, 1)
 N = 10

@@ -11,17 +11,17 @@ m = GRL(**cfg).eval().cuda()
 B, H, W, CP, C_ = 4, 256, 256, 192, 180
 M = B * H * W
 plan = m._plan((H, W), torch.device("cuda"))
-pk = plan["stages"][0]["blocks"][2]
+pk = plan.stages[0].blocks[2]
 blk0 = m.layers[0].blocks[2]
-pk["tail_rblob"] = ops.pack_tail_regs(pk["proj_w"].float(), blk0.mlp.fc1.weight, blk0.mlp.fc1.bias, blk0.mlp.fc2.weight)
+pk.tail_rblob = ops.pack_tail_regs(pk.proj_w.float(), blk0.mlp.fc1.weight, blk0.mlp.fc1.bias, blk0.mlp.fc2.weight)
 r = torch.randn(M, CP, device="cuda"); r[:, C_:] = 0
 att = torch.randn(M, CP, device="cuda").to(torch.float16)
 cab = torch.randn(M, CP, device="cuda").to(torch.float16); cab[:, C_:] = 0
 gate = torch.ones(B, CP, device="cuda")
 lib = L.lib()
 buf = (C.c_ulonglong * 64)()
-run = lambda: ops.block_tail(att, r, cab, gate, H * W, pk["proj_blob"], pk["proj_b"], pk["n1_g"], pk["n1_b"], pk["mlp_blob"], pk["fc2_b"], pk["n2_g"], pk["n2_b"],
-                             Hpad=pk["mlp_hp"], n_real=C_, rblob=pk["tail_rblob"])
+run = lambda: ops.block_tail(att, r, cab, gate, H * W, pk.proj_blob, pk.proj_b, pk.n1_g, pk.n1_b, pk.mlp_blob, pk.fc2_b, pk.n2_g, pk.n2_b,
+                             Hpad=pk.mlp_hp, n_real=C_, rblob=pk.tail_rblob)
 for _ in range(3): run()
 lib.grl_tr_debug(buf, 1)
 N = 10
