@@ -4,5 +4,8 @@ from .model import GRL  # noqa: F401
 from .optim import FusedAdamW  # noqa: F401
 from .train_graph import GraphedTrainStep  # noqa: F401
 from .presets import baseline_config, make_config  # noqa: F401
+from .data import PatchSampler, PatchStore  # noqa: F401
+from .train import charbonnier, multistep_warmup_lr  # noqa: F401
 
-__all__ = ["GRL", "FusedAdamW", "GraphedTrainStep", "make_config", "baseline_config"]
+__all__ = ["GRL", "FusedAdamW", "GraphedTrainStep", "make_config", "baseline_config", "PatchStore", "PatchSampler",
+           "charbonnier", "multistep_warmup_lr"]

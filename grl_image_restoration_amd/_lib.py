@@ -11,7 +11,7 @@ from . import switches as SW
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgrl_hip.so")
-ABI_VERSION = 26
+ABI_VERSION = 27
 DT_F32, DT_BF16, DT_F16 = 0, 1, 2
 
 EPI_PLAIN, EPI_GELU, EPI_GROUPNORM, EPI_LN_RES, EPI_GELU_GRAD = 0, 1, 2, 3, 4
@@ -61,6 +61,7 @@ EXPORTS = [
     "grl_imresize",
     "grl_image_niqe_workspace_bytes",
     "grl_image_niqe_features",
+    "grl_sample_patches",
     "grl_debug_dirty_lds",
     "grl_abi_version",
     "grl_build_info",
@@ -560,6 +561,19 @@ class GrlNiqeArgs(_Strict):
     ]
 
 
+class GrlPatchArgs(_Strict):
+    _fields_ = [
+        ("store", C.c_void_p),
+        ("offsets", C.c_void_p),
+        ("dims", C.c_void_p),
+        ("N", C.c_int32), ("C", C.c_int32),
+        ("work", C.c_void_p),
+        ("B", C.c_int32), ("P", C.c_int32), ("scale", C.c_int32),
+        ("reserved0", C.c_int32),
+        ("out", C.c_void_p),
+    ]
+
+
 _lib = None
 
 
@@ -669,6 +683,8 @@ def lib():
     L.grl_image_niqe_workspace_bytes.restype = C.c_int64
     L.grl_image_niqe_features.argtypes = [C.c_void_p, C.POINTER(GrlNiqeArgs)]
     L.grl_image_niqe_features.restype = C.c_int
+    L.grl_sample_patches.argtypes = [C.c_void_p, C.POINTER(GrlPatchArgs)]
+    L.grl_sample_patches.restype = C.c_int
     L.grl_debug_dirty_lds.argtypes = [C.c_void_p]
     L.grl_debug_dirty_lds.restype = C.c_int
     _lib = L

@@ -1,0 +1,278 @@
+"""Training batches from a device-resident image store: the reference's training data path without its host loop.
+
+  PatchStore     the training images as 8-bit H x W x C arrays back to back in ONE uint8 tensor, with a table of byte offsets and a
+                 table of (H, W): what the reference keeps per image in its HDF5 cache (data/datasets/base_image.py:333-354), here
+                 on the device
+  .sample        a work list (image, x, y, flags) -> (B, C, P scale, P scale) fp32 in [0, 1]: _pad_images, _sample_patches
+                 (base_image.py:276-293), _augment (base_image.py:356-372), ascontiguousarray and to_tensor
+                 (restoration_sr.py:111-115) for the whole batch
+  PatchSampler   the draws of one training batch (``random.Random``: image, _random_index of base_image.py:252-256, the three
+                 flips) and the task's (lq, gt) pair built from them
+
+CUDA stores go through ``grl_sample_patches`` of libgrl_hip.so (csrc/patches.hip): one launch per batch and store, the work list
+read from device memory, so the launch can be captured and replayed while the list changes.  There is no torch fallback for them.
+CPU stores take the plain torch restatement below; the two are bitwise equal (tests/test_gpu_patches.py), and both equal the
+reference's numpy chain (tests/test_patches.py): a value is ``float(v) / 255`` by IEEE division.
+
+Flags of a work-list entry: bit 0 reverses the rows (``x[::-1]``), bit 1 the columns (``x[:, ::-1]``), bit 2 swaps the two axes
+(``np.swapaxes(x, 0, 1)``), applied in that order after the crop.  The crop is rows ``x * scale .. x * scale + P * scale - 1`` and
+columns ``y * scale ..``; pixels outside the image are 0, which is the reference's bottom / right padding of images smaller than
+the patch.
+"""
+import ctypes as C
+import random
+from typing import List, Optional, Sequence
+
+import numpy as np
+import torch
+
+TASKS = ("sr", "sr_bicubic", "dn", "dm")
+FLIP_ROWS, FLIP_COLS, SWAP_AXES = 1, 2, 4
+
+
+class PatchStore:
+    def __init__(self, images: Sequence, device="cpu"):
+        """``images``: uint8 arrays (numpy or torch), each H x W x C or H x W, one channel count (1 or 3) for all of them."""
+        arrs = []
+        for im in images:
+            a = im.detach().cpu().numpy() if torch.is_tensor(im) else np.asarray(im)
+            if a.dtype != np.uint8:
+                raise TypeError(f"PatchStore holds 8-bit images, got {a.dtype}")
+            if a.ndim == 2:
+                a = a[:, :, None]
+            if a.ndim != 3 or a.shape[2] not in (1, 3) or a.shape[0] < 1 or a.shape[1] < 1:
+                raise ValueError(f"PatchStore: need H x W x C images with C = 1 or 3, got {a.shape}")
+            arrs.append(np.ascontiguousarray(a))
+        if not arrs:
+            raise ValueError("PatchStore: no images")
+        if len({a.shape[2] for a in arrs}) != 1:
+            raise ValueError("PatchStore: every image of a store has the same number of channels")
+        self.channels = int(arrs[0].shape[2])
+        self.dims = [(int(a.shape[0]), int(a.shape[1])) for a in arrs]
+        sizes = [a.size for a in arrs]
+        self.data = torch.from_numpy(np.concatenate([a.reshape(-1) for a in arrs]))
+        self._starts = [int(v) for v in np.concatenate([[0], np.cumsum(sizes)[:-1]])]
+        self.offsets = torch.tensor(self._starts, dtype=torch.int64)
+        self.dims_t = torch.tensor(self.dims, dtype=torch.int32)
+        self.to(device)
+
+    @classmethod
+    def from_folder(cls, folder: str, channels: int = 3, device="cpu") -> "PatchStore":
+        """Every image file of ``folder`` in sorted order, read as ``evaluate._read_image`` reads it (the same extensions, PIL's
+        ``convert("RGB")`` or ``convert("L")``), kept as 8 bit."""
+        from PIL import Image
+
+        from .evaluate import gt_images
+
+        mode = "L" if channels == 1 else "RGB"
+        return cls([np.asarray(Image.open(p).convert(mode), dtype=np.uint8) for p in gt_images(folder)], device)
+
+    def to(self, device) -> "PatchStore":
+        """Moves the store (in place) and returns it."""
+        self.data, self.offsets, self.dims_t = self.data.to(device), self.offsets.to(device), self.dims_t.to(device)
+        return self
+
+    @property
+    def device(self):
+        return self.data.device
+
+    def __len__(self):
+        return len(self.dims)
+
+    def image(self, n: int) -> torch.Tensor:
+        """Image ``n`` as an H x W x C uint8 view of the store."""
+        H, W = self.dims[n]
+        o = self._starts[n]
+        return self.data[o : o + H * W * self.channels].view(H, W, self.channels)
+
+    def sample(self, work: torch.Tensor, patch: int, scale: int = 1, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``work``: int32 (B, 4) on the store's device -- image, top row x, left column y, flags (module docstring).  Returns fp32
+        (B, C, patch * scale, patch * scale); ``out`` receives it when given (a static buffer of a captured step)."""
+        patch, scale = int(patch), int(scale)
+        if work.dtype != torch.int32 or work.dim() != 2 or work.shape[1] != 4 or work.shape[0] < 1 or not work.is_contiguous():
+            raise ValueError("work list: a contiguous int32 (B, 4) tensor")
+        if work.device != self.data.device:
+            raise ValueError(f"work list on {work.device}, store on {self.data.device}")
+        if patch < 1 or scale < 1:
+            raise ValueError(f"patch and scale must be positive, got {patch}, {scale}")
+        B, S = work.shape[0], patch * scale
+        if out is None:
+            out = torch.empty(B, self.channels, S, S, dtype=torch.float32, device=self.data.device)
+        elif out.shape != (B, self.channels, S, S) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != work.device:
+            raise ValueError("out: a contiguous fp32 (B, C, patch * scale, patch * scale) tensor on the store's device")
+        if self.data.is_cuda:
+            return self._hip_sample(work, patch, scale, out)
+        return self._torch_sample(work, patch, scale, out)
+
+    def _hip_sample(self, work, patch, scale, out):
+        from . import _lib
+
+        args = _lib.GrlPatchArgs(store=self.data.data_ptr(), offsets=self.offsets.data_ptr(), dims=self.dims_t.data_ptr(),
+                                 N=len(self), C=self.channels, work=work.data_ptr(), B=work.shape[0], P=patch, scale=scale,
+                                 out=out.data_ptr())
+        _lib.check(_lib.lib().grl_sample_patches(_lib.stream_ptr(), C.byref(args)), "grl_sample_patches")
+        return out
+
+    def _torch_sample(self, work, patch, scale, out):
+        """The reference's chain per sample in plain torch (any device): zero-padded crop, flips, axis swap, to_tensor."""
+        S = patch * scale
+        for b, (n, x, y, flags) in enumerate(work.tolist()):
+            if not 0 <= n < len(self):
+                raise IndexError(f"work list: image {n} of a store of {len(self)}")
+            img = self.image(n)
+            H, W = self.dims[n]
+            r0, c0 = x * scale, y * scale
+            crop = torch.zeros(S, S, self.channels, dtype=torch.uint8, device=img.device)
+            h, w = min(S, H - r0), min(S, W - c0)
+            if r0 < 0 or c0 < 0:
+                raise IndexError(f"work list: negative origin ({x}, {y})")
+            if h > 0 and w > 0:
+                crop[:h, :w] = img[r0 : r0 + h, c0 : c0 + w]
+            if flags & FLIP_ROWS:
+                crop = crop.flip(0)
+            if flags & FLIP_COLS:
+                crop = crop.flip(1)
+            if flags & SWAP_AXES:
+                crop = crop.transpose(0, 1)
+            out[b] = crop.permute(2, 0, 1).contiguous().to(torch.float32).div(255)
+        return out
+
+
+class PatchSampler:
+    """(lq, gt) training batches of a task from PatchStores.
+
+    Tasks (``scale`` is the SR factor, 1 for dn / dm):
+      sr          paired stores: LQ patch ``patch``, GT patch ``patch * scale`` at the same place (restoration_sr.py:97-123 with
+                  ``load_lr``); every GT image is ``scale`` times its LQ image
+      sr_bicubic  GT store only.  The LQ store is made once per image at construction: ``tasks.modcrop`` to the scale, then
+                  ``tasks.sr_lq`` (MATLAB bicubic, 8-bit quantised) on the store's device; the GT store is replaced by the cropped
+                  images; then sampled as ``sr``.  This is the QUANTISED LQ -- what an offline LR folder holds and what validation
+                  scores -- not the float LQ that restoration_sr.py:130-141 resizes per item without rounding
+      dn          ``lq = gt + sigma / 255 * randn`` from a ``torch.Generator`` on the store's device seeded with ``seed``; sigma is
+                  ``sigma``, or drawn per sample from ``sigma_range`` (restoration_dn.py:126-143, the training branch)
+      dm          ``lq = tasks.demosaic_gt(gt)`` (RGB, even ``patch``)
+
+    Draws, from ``random.Random(seed)``, per sample and in this order: ``randrange(N)`` for the image; ``randrange(H' - P + 1)``
+    and ``randrange(W' - P + 1)`` with H' = max(H, P), W' = max(W, P) the LQ-side size after the reference's padding
+    (_random_index on the padded image, base_image.py:252-256, 397-402); three ``random() < 0.5`` for the flags; with
+    ``sigma_range`` one ``uniform(lo, hi)``.
+    """
+
+    def __init__(self, task: str, gt_store: PatchStore, lq_store: Optional[PatchStore] = None, patch: int = 64, batch: int = 8,
+                 scale: int = 1, sigma: Optional[float] = None, sigma_range: Optional[Sequence[float]] = None, seed: int = 0):
+        if task not in TASKS:
+            raise ValueError(f"unknown task {task!r}: one of {TASKS}")
+        patch, batch, scale = int(patch), int(batch), int(scale)
+        if patch < 1 or batch < 1:
+            raise ValueError(f"patch and batch must be positive, got {patch}, {batch}")
+        if task in ("dn", "dm") and scale != 1:
+            raise ValueError(f"task {task} restores at scale 1, got {scale}")
+        if task in ("sr", "sr_bicubic") and scale < (2 if task == "sr_bicubic" else 1):
+            raise ValueError(f"task {task}: bad scale {scale}")
+        if task == "sr" and lq_store is None:
+            raise ValueError("task sr needs an LQ store")
+        if task != "sr" and lq_store is not None:
+            raise ValueError(f"task {task} builds its LQ from the GT store; an LQ store is not used")
+        if task == "dn" and (sigma is None) == (sigma_range is None):
+            raise ValueError("task dn needs sigma or sigma_range (one of them)")
+        if task != "dn" and (sigma is not None or sigma_range is not None):
+            raise ValueError(f"task {task} adds no noise")
+        if task == "dm" and (gt_store.channels != 3 or patch % 2 or patch < 4):
+            raise ValueError("task dm works on RGB patches with an even side of at least 4")
+        if task == "sr_bicubic":
+            gt_store, lq_store = _bicubic_stores(gt_store, scale)
+        if lq_store is not None:
+            if len(lq_store) != len(gt_store) or lq_store.channels != gt_store.channels or lq_store.device != gt_store.device:
+                raise ValueError("task sr: the two stores need the same number of images, channel count and device")
+            for n, ((h, w), (H, W)) in enumerate(zip(lq_store.dims, gt_store.dims)):
+                if (H, W) != (h * scale, w * scale):
+                    raise ValueError(f"task sr: image {n} is {h} x {w} (LQ) and {H} x {W} (GT), not a x{scale} pair")
+        self.task, self.gt_store, self.lq_store = task, gt_store, lq_store
+        self.patch, self.batch, self.scale = patch, batch, scale
+        self.sigma, self.sigma_range = sigma, (tuple(float(v) for v in sigma_range) if sigma_range is not None else None)
+        self.rng = random.Random(seed)
+        self.device = gt_store.device
+        self.gen = torch.Generator(device=self.device).manual_seed(int(seed)) if task == "dn" else None
+        self.work = torch.zeros(batch, 4, dtype=torch.int32, device=self.device)      # the device work list, rewritten in place
+
+    # ---- draws ---------------------------------------------------------------------------------------------------------------
+    def draw(self):
+        """One batch of draws: ([(image, x, y, flags)] * batch, [sigma] * batch or None)."""
+        sizes = (self.lq_store or self.gt_store).dims
+        P, work, sigmas = self.patch, [], []
+        for _ in range(self.batch):
+            n = self.rng.randrange(len(sizes))
+            H, W = max(sizes[n][0], P), max(sizes[n][1], P)
+            x = self.rng.randrange(0, H - P + 1)
+            y = self.rng.randrange(0, W - P + 1)
+            flags = sum(bit for bit in (FLIP_ROWS, FLIP_COLS, SWAP_AXES) if self.rng.random() < 0.5)
+            work.append((n, x, y, flags))
+            if self.sigma_range is not None:
+                sigmas.append(self.rng.uniform(*self.sigma_range))
+        return work, (sigmas if self.sigma_range is not None else None)
+
+    def rng_state(self):
+        """What a checkpoint keeps to continue the stream of batches: the draws' state and the noise generator's."""
+        return {"draws": self.rng.getstate(), "noise": self.gen.get_state().cpu() if self.gen is not None else None}
+
+    def set_rng_state(self, state):
+        self.rng.setstate(_as_rng_state(state["draws"]))
+        if self.gen is not None and state.get("noise") is not None:
+            self.gen.set_state(state["noise"].cpu())
+
+    # ---- batches -------------------------------------------------------------------------------------------------------------
+    def next(self, work=None, sigmas: Optional[Sequence[float]] = None):
+        """(lq, gt) on the store's device.  ``work``: an explicit work list (a sequence of (image, x, y, flags) or an int32 (B, 4)
+        tensor) instead of fresh draws; ``sigmas`` with it for dn with a sigma range."""
+        if work is None:
+            work, sigmas = self.draw()
+        if torch.is_tensor(work):
+            wt = work.to(device=self.device, dtype=torch.int32).contiguous()
+        else:
+            wt = torch.tensor([list(w) for w in work], dtype=torch.int32).reshape(-1, 4)
+            if wt.shape == self.work.shape:          # the sampler's own list, in place: a captured launch reads this address
+                self.work.copy_(wt)
+                wt = self.work
+            else:
+                wt = wt.to(self.device)
+        B = wt.shape[0]
+        if self.lq_store is not None:                # sr, and sr_bicubic after its stores were made
+            lq = self.lq_store.sample(wt, self.patch, 1)
+            gt = self.gt_store.sample(wt, self.patch, self.scale)
+            return lq, gt
+        gt = self.gt_store.sample(wt, self.patch, 1)
+        if self.task == "dm":
+            from . import tasks
+
+            return tasks.demosaic_gt(gt), gt
+        if self.sigma_range is not None:
+            if sigmas is None or len(sigmas) != B:
+                raise ValueError("dn with a sigma range: one sigma per sample of an explicit work list")
+            level = torch.tensor(list(sigmas), dtype=torch.float32).view(B, 1, 1, 1).to(self.device) / 255
+        else:
+            level = self.sigma / 255
+        noise = torch.randn(gt.shape, generator=self.gen, device=self.device, dtype=torch.float32)
+        return gt + noise * level, gt
+
+
+def _as_rng_state(s):
+    """``random.Random.setstate`` wants tuples; a state that went through a checkpoint may hold lists."""
+    return (s[0], tuple(s[1]), s[2])
+
+
+def _bicubic_stores(gt_store: PatchStore, scale: int):
+    """(cropped GT store, LQ store) for sr_bicubic: per image ``tasks.sr_lq`` of the GT cropped to a multiple of ``scale``, on the
+    store's device, rounded back to 8 bit (``sr_lq`` returns k / 255 exactly)."""
+    from . import tasks
+
+    gts: List[torch.Tensor] = []
+    lqs: List[torch.Tensor] = []
+    for n in range(len(gt_store)):
+        img = gt_store.image(n)
+        gt = tasks.modcrop(img.permute(2, 0, 1).unsqueeze(0), scale)
+        if gt.shape[-2] < scale or gt.shape[-1] < scale:
+            raise ValueError(f"sr_bicubic: image {n} ({img.shape[0]} x {img.shape[1]}) is smaller than the scale")
+        lq, _ = tasks.sr_lq(gt.to(torch.float32).div(255).contiguous(), scale)
+        lqs.append((lq[0] * 255).round().to(torch.uint8).permute(1, 2, 0).contiguous().cpu())
+        gts.append(gt[0].permute(1, 2, 0).contiguous().cpu())
+    return PatchStore(gts, gt_store.device), PatchStore(lqs, gt_store.device)

@@ -1,0 +1,277 @@
+"""Training from an image folder without Lightning / Hydra: the reference's training command around this package's step.
+
+Restates the pieces of the reference's training run that sit around ``model(x)``:
+
+  multistep_warmup_lr   optim/multi_steplr.py:22-30    linear warm-up, then torch's MultiStepLR as the reference runs it
+  charbonnier           losses/losses.py:53-56         (the default loss is L1, config/loss/l1.yaml)
+  the step              engines/base.py:221-236        forward, loss, backward, optimizer step: ``GraphedTrainStep`` (one captured
+                                                       HIP graph) with ``FusedAdamW``, or the same step eagerly with ``--eager``
+  the batches           data/datasets/*.py             ``data.PatchSampler`` over device-resident ``data.PatchStore``s
+  validation            engines/base.py:256-268        ``evaluate.evaluate_folder`` every ``--val-every`` steps
+  checkpoints           tools/trainer.py:93-115        the Lightning layout ``{"state_dict": {"model.<key>": tensor}}`` that
+                                                       ``evaluate.load_checkpoint`` and the reference read, plus ``step``,
+                                                       ``optimizer``, ``sampler_rng`` and ``args`` for ``--resume``
+
+    python -m grl_image_restoration_amd.train --task sr --scale 4 --model base --geometry sr_ckpt_df2 \\
+        --gt DIV2K/HR --lq DIV2K/LR_bicubic/X4 --patch 64 --batch 8 --steps 500000 \\
+        --milestones 250000+400000+450000+475000 --gamma 0.5 --out runs/sr_x4 --val-gt Set5/GTmod12 --val-lq Set5/LRbicx4
+    python -m grl_image_restoration_amd.train --task sr_bicubic --scale 2 --model small --geometry sr_ckpt_df4 --gt DIV2K/HR ...
+    python -m grl_image_restoration_amd.train --task dn --sigma 25 --model small --geometry dn_df4 --gt DFWB --ckpt dn_grl_small_c3s25.ckpt ...
+    python -m grl_image_restoration_amd.train --task dm --model small --geometry dm --gt DFWB ...
+
+Schedule.  ``multistep_warmup_lr(step, ...)`` is the learning rate of optimizer step ``step`` (0-based) when the reference's
+``MultiStepLRWarmup`` is stepped once per iteration.  During warm-up it is the reference's linear ramp.  After it, torch's
+``MultiStepLR.get_lr`` is the chained form -- the optimizer's CURRENT rate, times ``gamma`` at a milestone -- so the plateau is the
+LAST WARM-UP value ``init + (base - init) (W - 1) / W``, not ``base``, and a milestone inside the warm-up never fires.  That is what
+the reference trains with and what is restated here, value for value (tests/golden/train/lr_schedule.npz).  The rate is written
+into ``param_groups[*]["lr"]`` before each step; a captured step reads it from there (FusedAdamW.refresh_capture_hyper).
+
+Captured steps.  The first step is ``GraphedTrainStep``'s own eager warm-up step on the first batch (it updates the weights and
+counts as step 0); every later step replays the graph on the sampler's next batch.  ``charbonnier`` passes a non-zero
+``recalibrate_every``: its gradients shrink as the error does, and the captured step freezes the fp16 gradient operand scale
+(train_graph.py's docstring).  Validation runs between replays with the module in ``eval()``; the captured step stays valid -- a
+replay bumps the parameters' version counters, the inference plan keys on them, and the graph's own buffers are not touched by an
+eval forward -- so it is neither finished nor re-captured.  ``step.finish()`` runs before the optimizer state is read for a checkpoint.
+
+Data-parallel.  Under ``torchrun`` (torch.distributed initialised from the environment) the bare module goes to
+``GraphedTrainStep``, which owns the gradient all-reduce; each rank's sampler is seeded ``seed + rank``; rank 0 validates and
+writes checkpoints.  ``--eager`` is single-process only.
+"""
+import argparse
+import os
+from collections import Counter
+from typing import List, Optional, Sequence
+
+import torch
+
+from . import data as D
+
+
+def multistep_warmup_lr(step: int, base_lr: float, milestones: Sequence[int], gamma: float, warmup_iter: int = -1,
+                        warmup_init_lr: float = 0.0) -> float:
+    """The reference's ``MultiStepLRWarmup`` (optim/multi_steplr.py:22-30) after ``step`` scheduler steps, in its operation order
+    (module docstring: the plateau after a warm-up is the last warm-up value, as in the reference)."""
+    step = int(step)
+    if step < warmup_iter:
+        return warmup_init_lr + (base_lr - warmup_init_lr) / warmup_iter * step
+    lr = base_lr
+    if warmup_iter > 0:
+        lr = warmup_init_lr + (base_lr - warmup_init_lr) / warmup_iter * (warmup_iter - 1)
+    counts = Counter(int(m) for m in milestones)
+    for m in sorted(counts):                      # MultiStepLR.get_lr: lr * gamma ** (times m is listed) when last_epoch == m
+        if max(warmup_iter, 0) <= m <= step:
+            lr = lr * gamma ** counts[m]
+    return lr
+
+
+def charbonnier(x: torch.Tensor, y: torch.Tensor, eps: float = 1e-3) -> torch.Tensor:
+    """losses/losses.py:53-56."""
+    diff = x - y
+    return torch.mean(torch.sqrt((diff * diff) + (eps * eps)))
+
+
+def l1(x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    """torch.nn.L1Loss (config/loss/l1.yaml)."""
+    return (x - y).abs().mean()
+
+
+LOSSES = {"l1": l1, "charbonnier": charbonnier}
+RECALIBRATE_EVERY = 200        # captured Charbonnier steps: eager re-measurement of the gradient scale (train_graph.py)
+
+
+def save_checkpoint(path: str, model, optimizer, step: int, sampler: D.PatchSampler, args: dict):
+    obj = {"state_dict": {"model." + k: v.detach().cpu() for k, v in model.state_dict().items()},
+           "step": int(step), "optimizer": optimizer.state_dict(), "sampler_rng": sampler.rng_state(), "args": dict(args)}
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    torch.save(obj, path + ".tmp")
+    os.replace(path + ".tmp", path)
+    return path
+
+
+def _parser():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--task", default="sr", choices=D.TASKS,
+                    help="sr: paired folders --lq / --gt; sr_bicubic, dn, dm: the LQ is made from --gt on the device")
+    ap.add_argument("--gt", required=True, help="GT training folder")
+    ap.add_argument("--lq", default=None, help="LQ training folder (--task sr)")
+    ap.add_argument("--model", default="base", choices=["tiny", "small", "base"])
+    ap.add_argument("--geometry", default="sr_ckpt_df2", help="a key of presets.GEOMETRIES")
+    ap.add_argument("--depths", default=None, help="blocks per stage as a+b+c instead of the model size's (short experiments)")
+    ap.add_argument("--scale", type=int, default=None, help="4 by default for --task sr / sr_bicubic; 1 for dn / dm")
+    ap.add_argument("--channels", type=int, default=3, choices=[1, 3])
+    ap.add_argument("--upsampler", default=None, choices=["pixelshuffle", "pixelshuffledirect", "nearest+conv"])
+    ap.add_argument("--ckpt", default=None, help="start weights (a reference checkpoint); random init without it")
+    ap.add_argument("--patch", type=int, default=64, help="LQ patch side")
+    ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--steps", type=int, required=True, help="train until this many optimizer steps have been taken in total")
+    ap.add_argument("--lr", type=float, default=2e-4)
+    ap.add_argument("--weight-decay", type=float, default=1e-4)
+    ap.add_argument("--milestones", default="", help="a+b+c: steps at which the rate is multiplied by --gamma")
+    ap.add_argument("--gamma", type=float, default=0.5)
+    ap.add_argument("--warmup-iter", type=int, default=-1)
+    ap.add_argument("--warmup-init-lr", type=float, default=0.0)
+    ap.add_argument("--loss", default="l1", choices=sorted(LOSSES))
+    ap.add_argument("--sigma", type=float, default=None, help="--task dn: noise level on the 0..255 scale")
+    ap.add_argument("--sigma-range", type=float, nargs=2, default=None, metavar=("LO", "HI"), help="--task dn: a level per sample")
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--val-gt", default=None)
+    ap.add_argument("--val-lq", default=None)
+    ap.add_argument("--val-every", type=int, default=0)
+    ap.add_argument("--metric", default=None, help="a metric group of metrics.ALL_GROUPS instead of PSNR-Y")
+    ap.add_argument("--out", default=None, help="checkpoint folder")
+    ap.add_argument("--save-every", type=int, default=0)
+    ap.add_argument("--resume", default=None, help="a checkpoint of this command: weights, optimizer, step and sampler state")
+    ap.add_argument("--eager", action="store_true", help="no captured graph")
+    ap.add_argument("--device", default="cuda:0")
+    return ap
+
+
+def _check(ap, a):
+    if a.task == "sr" and a.lq is None:
+        ap.error("--lq is required with --task sr")
+    if a.task != "sr" and a.lq is not None:
+        ap.error(f"--task {a.task} builds its LQ from --gt; --lq is not used")
+    if a.task == "dn" and (a.sigma is None) == (a.sigma_range is None):
+        ap.error("--task dn needs --sigma or --sigma-range (one of them)")
+    if a.task != "dn" and (a.sigma is not None or a.sigma_range is not None):
+        ap.error(f"--task {a.task} adds no noise; --sigma / --sigma-range are not used")
+    if a.scale is None:
+        a.scale = 4 if a.task in ("sr", "sr_bicubic") else 1
+    if a.task in ("dn", "dm") and a.scale != 1:
+        ap.error(f"--task {a.task} restores at --scale 1")
+    if a.task == "sr_bicubic" and a.scale < 2:
+        ap.error("--task sr_bicubic needs a --scale above 1")
+    if a.scale < 1 or a.patch < 1 or a.batch < 1 or a.steps < 0:
+        ap.error("--scale, --patch and --batch must be positive")
+    if a.task == "dm" and (a.channels != 3 or a.patch % 2):
+        ap.error("--task dm works on RGB patches with an even --patch")
+    if a.val_every:
+        if a.val_gt is None:
+            ap.error("--val-every needs --val-gt")
+        if a.task == "sr" and a.val_lq is None:
+            ap.error("--task sr validates on --val-lq / --val-gt")
+        if a.task == "dn" and a.sigma is None:
+            ap.error("validation of --task dn needs a fixed --sigma")
+    if a.task != "sr" and a.val_lq is not None:
+        ap.error(f"--task {a.task} builds its validation LQ from --val-gt; --val-lq is not used")
+    if a.save_every and a.out is None:
+        ap.error("--save-every needs --out")
+    try:
+        a.milestone_list = [int(m) for m in a.milestones.split("+") if m != ""]
+        a.depth_list = [int(d) for d in a.depths.split("+")] if a.depths else None
+    except ValueError:
+        ap.error("--milestones and --depths are integers joined by +")
+    if a.metric is not None:
+        from .metrics import ALL_GROUPS
+
+        if a.metric not in ALL_GROUPS:
+            ap.error(f"--metric: one of {sorted(ALL_GROUPS)}")
+
+
+def main(argv: Optional[List[str]] = None):
+    """Returns {"steps", "losses", "lrs", "work", "val", "checkpoint"}: per step taken in this call its index, loss, rate and work
+    list; (step, result) of every validation; the last checkpoint written."""
+    import torch.distributed as dist
+
+    from . import GRL, FusedAdamW, GraphedTrainStep, make_config
+    from .evaluate import evaluate_folder, load_checkpoint
+
+    ap = _parser()
+    a = ap.parse_args(argv)
+    _check(ap, a)
+
+    rank, world = 0, 1
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1 and not dist.is_initialized():
+        dist.init_process_group("nccl" if a.device.startswith("cuda") else "gloo")
+    if dist.is_available() and dist.is_initialized():
+        rank, world = dist.get_rank(), dist.get_world_size()
+        if a.device.startswith("cuda"):
+            a.device = f"cuda:{int(os.environ.get('LOCAL_RANK', rank))}"
+        if a.eager and world > 1:
+            ap.error("--eager is single-process; the captured step owns the gradient all-reduce")
+    device = torch.device(a.device)
+    if device.type == "cuda":
+        torch.cuda.set_device(device)
+
+    over = {"upsampler": a.upsampler} if a.upsampler and a.scale > 1 else {}
+    if a.depth_list:
+        heads = make_config(a.model, a.geometry)["num_heads_window"][0]
+        over.update(depths=a.depth_list, num_heads_window=[heads] * len(a.depth_list), num_heads_stripe=[heads] * len(a.depth_list))
+    model = GRL(**make_config(a.model, a.geometry, upscale=a.scale, img_size=a.patch, in_channels=a.channels, **over))
+    resume = torch.load(a.resume, map_location="cpu", weights_only=False) if a.resume else None
+    if resume is not None:
+        load_checkpoint(model, resume)
+    elif a.ckpt:
+        load_checkpoint(model, a.ckpt)
+    model = model.to(device).train()
+
+    gt_store = D.PatchStore.from_folder(a.gt, a.channels, device)
+    lq_store = D.PatchStore.from_folder(a.lq, a.channels, device) if a.task == "sr" else None
+    sampler = D.PatchSampler(a.task, gt_store, lq_store, patch=a.patch, batch=a.batch, scale=a.scale, sigma=a.sigma,
+                             sigma_range=a.sigma_range, seed=a.seed + rank)
+
+    opt = FusedAdamW(model.parameters(), lr=a.lr, weight_decay=a.weight_decay)
+    start = 0
+    if resume is not None:
+        opt.load_state_dict(resume["optimizer"])
+        sampler.set_rng_state(resume["sampler_rng"])
+        start = int(resume["step"])
+
+    loss_fn = LOSSES[a.loss]
+    seen = []                                           # losses of eager calls (the captured step's warm-up step reports here)
+
+    def recorded(y, t):
+        loss = loss_fn(y, t)
+        if not seen:
+            seen.append(loss.detach())
+        return loss
+
+    lr_at = lambda n: multistep_warmup_lr(n, a.lr, a.milestone_list, a.gamma, a.warmup_iter, a.warmup_init_lr)
+    out = {"steps": [], "losses": [], "lrs": [], "work": [], "val": [], "checkpoint": None}
+    step_fn = None
+
+    def checkpoint(n):
+        if step_fn is not None:
+            step_fn.finish()
+        if rank == 0 and a.out is not None:
+            out["checkpoint"] = save_checkpoint(os.path.join(a.out, f"step_{n}.ckpt"), model, opt, n, sampler, vars(a))
+
+    for n in range(start, a.steps):
+        lr = lr_at(n)
+        for g in opt.param_groups:
+            g["lr"] = lr
+        work, sigmas = sampler.draw()
+        lq, gt = sampler.next(work, sigmas)
+        if a.eager:
+            opt.zero_grad(set_to_none=True)
+            loss = loss_fn(model(lq), gt)
+            loss.backward()
+            opt.step()
+        elif step_fn is None:
+            step_fn = GraphedTrainStep(model, opt, recorded, lq, gt, warmup=1,
+                                       recalibrate_every=RECALIBRATE_EVERY if a.loss == "charbonnier" else 0)
+            loss = seen[0]
+        else:
+            loss = step_fn(lq, gt)
+        loss = float(loss.detach())
+        out["steps"].append(n); out["losses"].append(loss); out["lrs"].append(lr); out["work"].append(work)
+        if rank == 0:
+            print(f"step {n:8d}  lr {lr:.3e}  loss {loss:.6f}", flush=True)
+        done = n + 1
+        if a.val_every and done % a.val_every == 0 and rank == 0:
+            model.eval()
+            with torch.no_grad():
+                v = evaluate_folder(model, a.val_lq, a.val_gt, a.scale, device=a.device, verbose=False, metric_group=a.metric,
+                                    channels=a.channels, task=a.task, sigma=a.sigma)
+            model.train()
+            out["val"].append((done, v))
+            print(f"step {n:8d}  validation {v}", flush=True)
+        if a.save_every and done % a.save_every == 0 and done != a.steps:
+            checkpoint(done)
+    if a.steps > start or resume is None:
+        checkpoint(max(a.steps, start))
+    return out
+
+
+if __name__ == "__main__":
+    main()

@@ -23,7 +23,7 @@ extern "C" {
 
 #define GRL_ERR_BAD_ARG (-1)
 #define GRL_ERR_UNSUPPORTED (-2)
-#define GRL_ABI_VERSION 26
+#define GRL_ABI_VERSION 27
 
 /* element kinds of activation / weight buffers */
 enum { GRL_DT_F32 = 0, GRL_DT_BF16 = 1, GRL_DT_F16 = 2 };
@@ -802,6 +802,34 @@ typedef struct GrlNiqeArgs {
 
 int64_t grl_image_niqe_workspace_bytes(int32_t B, int32_t H, int32_t W);
 int grl_image_niqe_features(void* stream, const GrlNiqeArgs* args);
+
+/* A batch of training patches cut out of a device-resident store of 8-bit images (ABI 27; the data path of training):
+ *   replaces  _pad_images / _sample_patches   data/datasets/base_image.py:276-293 (zero padding at the bottom / right, the crop)
+ *             _augment                        data/datasets/base_image.py:356-372 (x[::-1], x[:, ::-1], np.swapaxes(x, 0, 1))
+ *             ascontiguousarray + to_tensor   data/datasets/restoration_sr.py:111-115, restoration_dn.py:123-124
+ *             and the DataLoader's collation and host-to-device copy of the batch
+ * store: N images back to back, each H x W x C interleaved uint8 (C = 1 or 3, one value per store); offsets[n] is the first byte of
+ * image n, dims[n] = (H, W).  work[b] = (image index, x, y, flags), read from DEVICE memory by the kernel: the launch takes no
+ * per-sample scalar and stays valid inside a captured graph while the list's contents change.  With S = P * scale, sample b is the
+ * crop of rows x * scale .. x * scale + S - 1 and columns y * scale .. y * scale + S - 1 (pixels outside the image read as 0), then
+ * flags bit 0: rows reversed, bit 1: columns reversed, bit 2: the two axes swapped, in that order.  A paired LQ / GT batch is two
+ * calls over two stores with one work list (scale 1 and s).
+ * out: contiguous fp32 (B, C, S, S), 16-byte aligned; every value is float(v) / 255 by IEEE division (bitwise to_tensor).
+ * An image index outside 0 .. N - 1 yields a zero patch; offsets / dims are trusted.  One launch on `stream`.
+ * Errors (GRL_ERR_BAD_ARG): a null pointer, C not 1 / 3, N, B or P <= 0, scale < 1, out or work not 16-byte aligned, a grid beyond
+ * 2^31 - 1 workgroups. */
+typedef struct GrlPatchArgs {
+    const uint8_t* store;
+    const int64_t* offsets;     /* [N] byte offset of every image                               */
+    const int32_t* dims;        /* [N][2] H, W                                                  */
+    int32_t N, C;
+    const int32_t* work;        /* [B][4] image, x (top row), y (left column), flags            */
+    int32_t B, P, scale;
+    int32_t reserved0;
+    float* out;                 /* (B, C, P * scale, P * scale)                                 */
+} GrlPatchArgs;
+
+int grl_sample_patches(void* stream, const GrlPatchArgs* args);
 
 /* Debug aid (ABI 21; no reference counterpart): fills the LDS of every CU with 0xFF bytes (fp32 / fp16 NaN) by a launch on
  * `stream`.  LDS keeps what the previous workgroup left in it; a kernel that reads LDS it has not written is otherwise right or
