@@ -11,7 +11,7 @@ from . import switches as SW
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgrl_hip.so")
-ABI_VERSION = 27
+ABI_VERSION = 28
 DT_F32, DT_BF16, DT_F16 = 0, 1, 2
 
 EPI_PLAIN, EPI_GELU, EPI_GROUPNORM, EPI_LN_RES, EPI_GELU_GRAD = 0, 1, 2, 3, 4
@@ -62,6 +62,7 @@ EXPORTS = [
     "grl_image_niqe_workspace_bytes",
     "grl_image_niqe_features",
     "grl_sample_patches",
+    "grl_blur_depthwise",
     "grl_debug_dirty_lds",
     "grl_abi_version",
     "grl_build_info",
@@ -574,6 +575,20 @@ class GrlPatchArgs(_Strict):
     ]
 
 
+class GrlBlurArgs(_Strict):
+    _fields_ = [
+        ("x", C.c_void_p),
+        ("stride", C.c_int64 * 4),
+        ("N", C.c_int32), ("C", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+        ("taps", C.c_void_p),
+        ("K", C.c_int32), ("pad", C.c_int32),
+        ("add", C.c_void_p),
+        ("add_stride", C.c_int64 * 3),
+        ("out", C.c_void_p),
+        ("center", C.c_void_p),
+    ]
+
+
 _lib = None
 
 
@@ -685,6 +700,8 @@ def lib():
     L.grl_image_niqe_features.restype = C.c_int
     L.grl_sample_patches.argtypes = [C.c_void_p, C.POINTER(GrlPatchArgs)]
     L.grl_sample_patches.restype = C.c_int
+    L.grl_blur_depthwise.argtypes = [C.c_void_p, C.POINTER(GrlBlurArgs)]
+    L.grl_blur_depthwise.restype = C.c_int
     L.grl_debug_dirty_lds.argtypes = [C.c_void_p]
     L.grl_debug_dirty_lds.restype = C.c_int
     _lib = L

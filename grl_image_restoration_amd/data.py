@@ -26,7 +26,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 import torch
 
-TASKS = ("sr", "sr_bicubic", "dn", "dm")
+TASKS = ("sr", "sr_bicubic", "dn", "dm", "db")
 FLIP_ROWS, FLIP_COLS, SWAP_AXES = 1, 2, 4
 
 
@@ -151,21 +151,30 @@ class PatchSampler:
       dn          ``lq = gt + sigma / 255 * randn`` from a ``torch.Generator`` on the store's device seeded with ``seed``; sigma is
                   ``sigma``, or drawn per sample from ``sigma_range`` (restoration_dn.py:126-143, the training branch)
       dm          ``lq = tasks.demosaic_gt(gt)`` (RGB, even ``patch``)
+      db          non-blind deblurring (RGB).  With ``taps`` the (K, K) table of ``tasks.blur_taps``, the draws and the crop use the
+                  reference's enlarged patch P' = ``patch`` + K - 1 (restoration_db.py:19-21), so the zero padding of small images
+                  follows P' as well; then ONE ``tasks.blur`` launch over the valid region gives ``lq`` at ``patch``, with the
+                  noise added by the kernel, and ``gt`` as the centre crop of the P' patch (engines/base.py:131-142: blur with
+                  padding, then cut K // 2 from every side of input and target).  The noise is ``sigma / 255 * randn`` (``sigma``
+                  defaults to 2, db.yaml:8) at ``patch`` x ``patch`` from the sampler's seeded ``torch.Generator``, as for dn.  The
+                  reference draws its training noise from the unseeded ``np.random`` at P' x P' and crops it, so there is no
+                  stream to reproduce bit for bit; the distribution is the same
 
     Draws, from ``random.Random(seed)``, per sample and in this order: ``randrange(N)`` for the image; ``randrange(H' - P + 1)``
     and ``randrange(W' - P + 1)`` with H' = max(H, P), W' = max(W, P) the LQ-side size after the reference's padding
     (_random_index on the padded image, base_image.py:252-256, 397-402); three ``random() < 0.5`` for the flags; with
-    ``sigma_range`` one ``uniform(lo, hi)``.
+    ``sigma_range`` one ``uniform(lo, hi)``.  For db, P is P'.
     """
 
     def __init__(self, task: str, gt_store: PatchStore, lq_store: Optional[PatchStore] = None, patch: int = 64, batch: int = 8,
-                 scale: int = 1, sigma: Optional[float] = None, sigma_range: Optional[Sequence[float]] = None, seed: int = 0):
+                 scale: int = 1, sigma: Optional[float] = None, sigma_range: Optional[Sequence[float]] = None, seed: int = 0,
+                 taps: Optional[torch.Tensor] = None):
         if task not in TASKS:
             raise ValueError(f"unknown task {task!r}: one of {TASKS}")
         patch, batch, scale = int(patch), int(batch), int(scale)
         if patch < 1 or batch < 1:
             raise ValueError(f"patch and batch must be positive, got {patch}, {batch}")
-        if task in ("dn", "dm") and scale != 1:
+        if task in ("dn", "dm", "db") and scale != 1:
             raise ValueError(f"task {task} restores at scale 1, got {scale}")
         if task in ("sr", "sr_bicubic") and scale < (2 if task == "sr_bicubic" else 1):
             raise ValueError(f"task {task}: bad scale {scale}")
@@ -175,7 +184,17 @@ class PatchSampler:
             raise ValueError(f"task {task} builds its LQ from the GT store; an LQ store is not used")
         if task == "dn" and (sigma is None) == (sigma_range is None):
             raise ValueError("task dn needs sigma or sigma_range (one of them)")
-        if task != "dn" and (sigma is not None or sigma_range is not None):
+        if task == "db":
+            if taps is None or taps.dim() != 2 or taps.shape[0] != taps.shape[1] or taps.shape[0] % 2 == 0 or taps.shape[0] > 31:
+                raise ValueError("task db needs taps: the (K, K) fp32 table of tasks.blur_taps, K odd and at most 31")
+            if sigma_range is not None:
+                raise ValueError("task db adds noise at one fixed sigma")
+            if gt_store.channels != 3:
+                raise ValueError("task db works on RGB patches")
+            sigma = 2.0 if sigma is None else float(sigma)
+        elif taps is not None:
+            raise ValueError(f"task {task} does not blur; taps are not used")
+        if task not in ("dn", "db") and (sigma is not None or sigma_range is not None):
             raise ValueError(f"task {task} adds no noise")
         if task == "dm" and (gt_store.channels != 3 or patch % 2 or patch < 4):
             raise ValueError("task dm works on RGB patches with an even side of at least 4")
@@ -192,14 +211,16 @@ class PatchSampler:
         self.sigma, self.sigma_range = sigma, (tuple(float(v) for v in sigma_range) if sigma_range is not None else None)
         self.rng = random.Random(seed)
         self.device = gt_store.device
-        self.gen = torch.Generator(device=self.device).manual_seed(int(seed)) if task == "dn" else None
+        self.gen = torch.Generator(device=self.device).manual_seed(int(seed)) if task in ("dn", "db") else None
+        self.taps = taps.to(device=self.device, dtype=torch.float32).contiguous() if task == "db" else None
+        self.draw_patch = patch + (self.taps.shape[0] - 1 if task == "db" else 0)      # the side the draws and the crop use
         self.work = torch.zeros(batch, 4, dtype=torch.int32, device=self.device)      # the device work list, rewritten in place
 
     # ---- draws ---------------------------------------------------------------------------------------------------------------
     def draw(self):
         """One batch of draws: ([(image, x, y, flags)] * batch, [sigma] * batch or None)."""
         sizes = (self.lq_store or self.gt_store).dims
-        P, work, sigmas = self.patch, [], []
+        P, work, sigmas = self.draw_patch, [], []
         for _ in range(self.batch):
             n = self.rng.randrange(len(sizes))
             H, W = max(sizes[n][0], P), max(sizes[n][1], P)
@@ -221,9 +242,10 @@ class PatchSampler:
             self.gen.set_state(state["noise"].cpu())
 
     # ---- batches -------------------------------------------------------------------------------------------------------------
-    def next(self, work=None, sigmas: Optional[Sequence[float]] = None):
+    def next(self, work=None, sigmas: Optional[Sequence[float]] = None, noise: Optional[torch.Tensor] = None):
         """(lq, gt) on the store's device.  ``work``: an explicit work list (a sequence of (image, x, y, flags) or an int32 (B, 4)
-        tensor) instead of fresh draws; ``sigmas`` with it for dn with a sigma range."""
+        tensor) instead of fresh draws; ``sigmas`` with it for dn with a sigma range.  ``noise`` (db): a unit-variance
+        (B, 3, patch, patch) fp32 tensor used instead of the generator's draw (it is scaled by ``sigma / 255``)."""
         if work is None:
             work, sigmas = self.draw()
         if torch.is_tensor(work):
@@ -240,7 +262,16 @@ class PatchSampler:
             lq = self.lq_store.sample(wt, self.patch, 1)
             gt = self.gt_store.sample(wt, self.patch, self.scale)
             return lq, gt
-        gt = self.gt_store.sample(wt, self.patch, 1)
+        gt = self.gt_store.sample(wt, self.draw_patch, 1)
+        if self.task == "db":
+            from . import tasks
+
+            shape = (B, 3, self.patch, self.patch)
+            if noise is None:
+                noise = torch.randn(shape, generator=self.gen, device=self.device, dtype=torch.float32)
+            elif tuple(noise.shape) != shape or noise.dtype != torch.float32:
+                raise ValueError(f"db noise: an fp32 tensor of shape {shape}")
+            return tasks.blur(gt, self.taps, "valid", add=noise.to(self.device) * (self.sigma / 255), want_center=True)
         if self.task == "dm":
             from . import tasks
 

@@ -17,6 +17,9 @@ Restates, for the MI355X module, the three pieces of the reference's evaluation 
   task "sr_bicubic" classical SR scored from the GT folder alone: the GT is cropped to a multiple of the scale and the LQ is its
                     MATLAB-bicubic downscale, 8-bit quantised (``tasks.sr_lq``; restoration_sr.py:130-141,
                     utils/matlab_functions.py:91-188), made on the device
+  task "db"         non-blind deblurring (config/data_module/db.yaml): the GT cropped to multiples of 8 and blurred on the device with
+                    the Gaussian or a Levin09 kernel, zero padded (``tasks.db_lq``, one ``grl_blur_depthwise`` launch;
+                    engines/base.py:131-139), plus the data set's noise at sigma 2, seeded 0 for every image (restoration_db.py:40-43)
   task "bsr"        blind / real-world SR (config/experiment/bsr/grl.yaml): LQ images only, no GT (``with_gt: False``); the metric is
                     NIQE of the output (``metrics.niqe``, config/metric/restorer_niqe.yaml), against the pristine model the user
                     names with ``--niqe-params`` or the environment variable GRL_NIQE_PARAMS
@@ -29,6 +32,8 @@ Restates, for the MI355X module, the three pieces of the reference's evaluation 
         --ckpt dn_grl_small_c3s25.ckpt --gt kodak24 --noise-prefix Kodak24 --metric restorer
     python -m grl_image_restoration_amd.evaluate --task sr_bicubic --scale 4 --model base --geometry sr_ckpt_df2 \\
         --ckpt sr_grl_base_c3x4.ckpt --gt Set5/original --metric restorer
+    python -m grl_image_restoration_amd.evaluate --task db --model small --geometry dn_df4 --ckpt runs/db/step_400000.ckpt \\
+        --gt Set5/original [--blur-kernel real4 --blur-kernel-file Levin09.npy]
     python -m grl_image_restoration_amd.evaluate --task bsr --model base --geometry bsr --upsampler nearest+conv \\
         --ckpt bsr_grl_base.ckpt --lq RealSRSet --niqe-params niqe_pris_params.npz
 """
@@ -158,7 +163,7 @@ def evaluate_pairs(model, pairs: Iterable[Tuple[torch.Tensor, torch.Tensor]], sc
     return {k: sum(o[k] for o in out) / len(out) for k in out[0]}
 
 
-TASKS = ("sr", "dn", "dm", "sr_bicubic", "bsr")
+TASKS = ("sr", "dn", "dm", "sr_bicubic", "bsr", "db")
 
 
 def gt_images(gt_dir: str) -> List[str]:
@@ -170,23 +175,30 @@ def gt_images(gt_dir: str) -> List[str]:
 
 
 def task_inputs(gt_dir: str, task: str, channels: int = 3, sigma: Optional[float] = None, noise_prefix: Optional[str] = None,
-                device: str = "cuda:0", scale: int = 1):
-    """(file name, LQ, GT) for every image of ``gt_dir`` under a task that synthesises its input ("dn", "dm" or "sr_bicubic"), as the reference's
+                device: str = "cuda:0", scale: int = 1, taps: Optional[torch.Tensor] = None):
+    """(file name, LQ, GT) for every image of ``gt_dir`` under a task that synthesises its input ("dn", "dm", "sr_bicubic" or "db"), as the reference's
     validation sets do: GT read as 8 bit and cropped to multiples of 8; "dn" adds ``tasks.dn_noise`` at ``sigma`` (keyed by
     ``noise_prefix/<file name>``: the reference's test-set name, by default the folder's base name matched to it case-insensitively by
     ``tasks.dn_test_set_name``, and the path that the set's test.json lists; on the CPU, in fp32, as the data set does), "dm"
     runs ``tasks.demosaic_gt`` on ``device`` (RGB only).  "sr_bicubic" crops the GT to a multiple of ``scale`` instead (the
-    reference's ``modcrop(img_gt, self.scale)``, restoration_sr.py:130) and makes the LQ with ``tasks.sr_lq`` on ``device``."""
+    reference's ``modcrop(img_gt, self.scale)``, restoration_sr.py:130) and makes the LQ with ``tasks.sr_lq`` on ``device``.
+    "db" (RGB only) blurs the GT on ``device`` with ``taps`` (``tasks.blur_taps``; default: the Gaussian's) and adds
+    ``tasks.db_noise`` at ``sigma`` (default 2), made on the CPU and added by the blur kernel."""
     from . import tasks
 
-    if task not in ("dn", "dm", "sr_bicubic"):
-        raise ValueError(f"task {task!r} reads its LQ from a folder; synthesised tasks: dn, dm, sr_bicubic")
+    if task not in ("dn", "dm", "sr_bicubic", "db"):
+        raise ValueError(f"task {task!r} reads its LQ from a folder; synthesised tasks: dn, dm, sr_bicubic, db")
     if task == "sr_bicubic" and int(scale) < 2:
         raise ValueError(f"task sr_bicubic needs a scale above 1, got {scale}")
     if task == "dn" and sigma is None:
         raise ValueError("task dn needs a noise sigma")
-    if task == "dm" and channels != 3:
-        raise ValueError("task dm works on RGB images")
+    if task in ("dm", "db") and channels != 3:
+        raise ValueError(f"task {task} works on RGB images")
+    if task == "db":
+        if taps is None:
+            taps = tasks.blur_taps(tasks.gaussian_blur_kernel())
+        taps = taps.to(device)
+        sigma = 2.0 if sigma is None else sigma
     if noise_prefix is None:
         noise_prefix = tasks.dn_test_set_name(os.path.basename(os.path.normpath(gt_dir)))
     mode = "L" if channels == 1 else "RGB"
@@ -200,6 +212,8 @@ def task_inputs(gt_dir: str, task: str, channels: int = 3, sigma: Optional[float
         if task == "dn":
             noise = tasks.dn_noise(gt.shape[1:], sigma, tasks.dn_noise_key(f"{noise_prefix}/{name}"))
             lq = gt + noise.unsqueeze(0)
+        elif task == "db":
+            lq = tasks.db_lq(gt.to(device), taps, tasks.db_noise(gt.shape[1:], sigma).unsqueeze(0).to(device))
         else:
             lq = tasks.demosaic_gt(gt.to(device))
         yield name, lq, gt
@@ -207,10 +221,11 @@ def task_inputs(gt_dir: str, task: str, channels: int = 3, sigma: Optional[float
 
 def evaluate_folder(model, lq_dir: Optional[str], gt_dir: Optional[str], scale: int, tile: int = 0, overlap: int = 32,
                     device: str = "cuda:0", verbose: bool = True, metric_group: Optional[str] = None, channels: int = 3,
-                    task: str = "sr", sigma: Optional[float] = None, noise_prefix: Optional[str] = None, niqe_params=None):
+                    task: str = "sr", sigma: Optional[float] = None, noise_prefix: Optional[str] = None, niqe_params=None,
+                    taps: Optional[torch.Tensor] = None):
     """Mean PSNR-Y over the image pairs of two folders; with ``metric_group``, {metric name: mean} of that group.  ``channels`` 1
-    reads the images as grayscale.  ``task`` "dn" / "dm" ignores ``lq_dir`` and builds the LQ from the GT (``task_inputs``;
-    ``scale`` must be 1); so does "sr_bicubic", at a ``scale`` above 1.  ``task`` "bsr" reads ``lq_dir`` alone (``gt_dir`` is not used)
+    reads the images as grayscale.  ``task`` "dn" / "dm" / "db" ignores ``lq_dir`` and builds the LQ from the GT (``task_inputs``;
+    ``scale`` must be 1; ``taps``: the blur taps of "db", the Gaussian's by default); so does "sr_bicubic", at a ``scale`` above 1.  ``task`` "bsr" reads ``lq_dir`` alone (``gt_dir`` is not used)
     and returns {"val_niqe": mean}; ``niqe_params`` is the pristine model of ``metrics.niqe`` (also for "restorer_niqe" elsewhere)."""
     if task not in TASKS:
         raise ValueError(f"unknown task {task!r}: one of {TASKS}")
@@ -227,7 +242,7 @@ def evaluate_folder(model, lq_dir: Optional[str], gt_dir: Optional[str], scale: 
     else:
         if scale != 1:
             raise ValueError(f"task {task} restores at scale 1, got {scale}")
-        items = task_inputs(gt_dir, task, channels, sigma, noise_prefix, device)
+        items = task_inputs(gt_dir, task, channels, sigma, noise_prefix, device, taps=taps)
     vals = []
     for name, lq, gt in items:
         v = evaluate_pairs(model, [(lq, gt)], scale, tile, overlap, device, metric_group, niqe_params)
@@ -258,8 +273,8 @@ def main(argv: Optional[List[str]] = None):
     ap.add_argument("--model", default="base", choices=["tiny", "small", "base"])
     ap.add_argument("--geometry", default="sr_ckpt_df2", help="a key of presets.GEOMETRIES")
     ap.add_argument("--task", default="sr", choices=TASKS,
-                    help="sr: LQ images from --lq (SR, deblurring, JPEG); dn / dm / sr_bicubic: the LQ is made from --gt (denoising, "
-                         "demosaicking, classical SR by MATLAB-bicubic downscaling at --scale); bsr: LQ images from --lq, no --gt, "
+                    help="sr: LQ images from --lq (SR, deblurring, JPEG); dn / dm / sr_bicubic / db: the LQ is made from --gt (denoising, "
+                         "demosaicking, classical SR by MATLAB-bicubic downscaling at --scale, non-blind deblurring); bsr: LQ images from --lq, no --gt, "
                          "scored by NIQE")
     ap.add_argument("--scale", type=int, default=None, help="4 by default for --task sr / sr_bicubic / bsr; 1 for everything else")
     ap.add_argument("--upsampler", default=None, choices=["pixelshuffle", "pixelshuffledirect", "nearest+conv"],
@@ -276,7 +291,11 @@ def main(argv: Optional[List[str]] = None):
     ap.add_argument("--metric", default=None, choices=sorted(ALL_GROUPS),
                     help="report this metric group of the reference (config/metric/*.yaml) instead of PSNR-Y alone")
     ap.add_argument("--channels", type=int, default=3, choices=[1, 3], help="1: grayscale model and images (dn_*_c1, jpeg_*_c1)")
-    ap.add_argument("--sigma", type=float, default=None, help="--task dn: noise level on the 0..255 scale (15, 25, 50)")
+    ap.add_argument("--sigma", type=float, default=None, help="--task dn: noise level on the 0..255 scale (15, 25, 50); --task db: the same, default 2")
+    ap.add_argument("--blur-kernel", default="gaussian",
+                    help="--task db: gaussian (25 x 25, sigma 1.6) or real1 .. real8 (the Levin09 motion kernels, from --blur-kernel-file)")
+    ap.add_argument("--blur-kernel-file", default=None,
+                    help="--task db with real1 .. real8: the reference's utils/blur_kernels/Levin09.npy, or a 2-D .npy of that kernel")
     ap.add_argument("--noise-prefix", default=None,
                     help="--task dn: the reference's test-set name (Set12, BSD68, CBSD68, Kodak24, McMaster, Urban100; case matters) "
                          "that starts the noise seed key '<prefix>/<file name>'; a different prefix draws different noise.  Default: "
@@ -300,10 +319,24 @@ def main(argv: Optional[List[str]] = None):
         ap.error("--task dn needs --sigma")
     if a.scale is None:
         a.scale = 4 if a.task in ("sr", "sr_bicubic", "bsr") else 1
-    if a.task in ("dn", "dm") and a.scale != 1:
+    if a.task in ("dn", "dm", "db") and a.scale != 1:
         ap.error(f"--task {a.task} restores at --scale 1")
     if a.task == "sr_bicubic" and a.scale < 2:
         ap.error("--task sr_bicubic needs a --scale above 1")
+    taps = None
+    if a.task == "db":
+        from . import tasks
+
+        if a.channels != 3:
+            ap.error("--task db works on RGB images")
+        try:
+            taps = tasks.blur_taps(tasks.load_blur_kernel(a.blur_kernel, a.blur_kernel_file))
+        except (ValueError, OSError) as e:
+            ap.error(f"--blur-kernel: {e}")
+        if a.sigma is None:
+            a.sigma = 2.0
+    elif a.blur_kernel != "gaussian" or a.blur_kernel_file is not None:
+        ap.error(f"--blur-kernel / --blur-kernel-file belong to --task db, not {a.task}")
     niqe_params = None
     if a.metric == "restorer_niqe":
         from .metrics import load_niqe_params
@@ -318,7 +351,7 @@ def main(argv: Optional[List[str]] = None):
         load_checkpoint(model, a.ckpt)
     model = model.to(a.device)
     return evaluate_folder(model, a.lq, a.gt, a.scale, a.tile, a.overlap, a.device, metric_group=a.metric, channels=a.channels,
-                           task=a.task, sigma=a.sigma, noise_prefix=a.noise_prefix, niqe_params=niqe_params)
+                           task=a.task, sigma=a.sigma, noise_prefix=a.noise_prefix, niqe_params=niqe_params, taps=taps)
 
 
 if __name__ == "__main__":

@@ -13,6 +13,15 @@
   imresize       utils/matlab_functions.py:91-188   MATLAB's antialiased bicubic ``imresize`` of a batch, rows then columns
   sr_lq          data/datasets/restoration_sr.py:130-141   the classical-SR LQ of a GT batch: modcrop to the scale, imresize by
                                                     1 / scale, 8-bit quantisation (``tensor_round``: what an LQ image file holds)
+  gaussian_blur_kernel  utils/utils_deblur.py:54-65  MATLAB's ``fspecial('gaussian', 25, 1.6)``, float64
+  load_blur_kernel   utils/utils_deblur.py:116-125  the blur kernel of non-blind deblurring: the Gaussian, or kernel n of a Levin09 file
+                                                    that the user supplies (the package ships none)
+  blur_taps          utils/utils_deblur.py:127      the correlation taps handed to ``conv2d``: the fp32 kernel flipped over both axes
+  blur               engines/base.py:131-142        depthwise K x K correlation of an image batch with one tap table, zero padded
+                                                    ("same", validation) or the valid region ("valid", the training branch's crop),
+                                                    plus the noise; ``want_center`` also returns the cropped target
+  db_noise           data/datasets/restoration_db.py:40-43   the deblurring validation noise: numpy's generator seeded 0 for EVERY image
+  db_lq                                             the deblurring LQ of a GT batch: ``blur(gt, taps, "same", add=noise)``
 
 CUDA fp32 tensors go through ``grl_demosaic_matlab`` of libgrl_hip.so (csrc/demosaic.hip); there is no torch fallback for them.
 ``demosaic_gt`` on CUDA is a single launch that reads the RGB image in place on the RGGB lattice, without forming the mosaic.  CPU
@@ -20,11 +29,14 @@ tensors take the float64 torch restatement below, cast back to the input dtype. 
 weights are dyadic) and therefore bitwise equal to each other and to the reference run in float64.  The noise is CPU numpy by
 design: only the reference's own generator stream reproduces its denoising PSNRs.  ``imresize`` follows the same rule: CUDA fp32
 tensors go through ``grl_imresize`` (csrc/imresize.hip, one launch, fp64 sums, one rounding), CPU tensors through a float64 gather
-and sum by the same tables; the two agree to an fp32 rounding, not bitwise (cubic weights are not dyadic).
+and sum by the same tables; the two agree to an fp32 rounding, not bitwise (cubic weights are not dyadic).  ``blur`` on CUDA is one
+``grl_blur_depthwise`` launch (csrc/blur.hip: an fp32 fmaf chain per output in a fixed order, deterministic); on the CPU the taps are
+summed in float64 and rounded once.  The two agree within the forward error of a K x K-term fp32 sum, (K^2 + 2) 2^-24 max|x|.
 """
 import ctypes as C
 import hashlib
 import math
+from typing import Optional
 
 import numpy as np
 import torch
@@ -318,3 +330,137 @@ def sr_lq(gt: torch.Tensor, scale: int, quantize: bool = True):
     if lq.shape[-2] * scale != gtc.shape[-2] or lq.shape[-1] * scale != gtc.shape[-1]:
         raise RuntimeError(f"sr_lq: LQ {tuple(lq.shape[-2:])} x {scale} != GT {tuple(gtc.shape[-2:])}")
     return lq, gtc
+
+
+# ---- non-blind deblurring ------------------------------------------------------------------------------------------------------
+def gaussian_blur_kernel(size: int = 25, sigma: float = 1.6) -> torch.Tensor:
+    """MATLAB's ``fspecial('gaussian', size, sigma)`` as the reference runs it (utils_deblur.py:54-65), operation for operation in
+    float64: ``exp(-(x^2 + y^2) / (2 sigma^2))``, entries below ``eps * max`` zeroed (``eps`` is ``np.finfo(float).eps``: the
+    reference's ``scipy.finfo`` was an alias of it), divided by the sum.  (size, size) float64."""
+    siz = (size - 1.0) / 2.0
+    x, y = np.meshgrid(np.arange(-siz, siz + 1), np.arange(-siz, siz + 1))
+    h = np.exp(-(x * x + y * y) / (2 * sigma * sigma))
+    h[h < np.finfo(float).eps * h.max()] = 0
+    sumh = h.sum()
+    if sumh != 0:
+        h = h / sumh
+    return torch.from_numpy(h)
+
+
+def _check_blur_kernel(k: np.ndarray, what: str) -> np.ndarray:
+    k = np.asarray(k)
+    if k.dtype == object or k.ndim != 2 or k.shape[0] != k.shape[1] or k.shape[0] % 2 == 0 or not 1 <= k.shape[0] <= 31:
+        raise ValueError(f"{what}: a blur kernel is a square 2-D array with an odd side of 1 .. 31, got {k.dtype} {k.shape}")
+    return k.astype(np.float64)
+
+
+def load_blur_kernel(kernel_type: str = "gaussian", path=None) -> torch.Tensor:
+    """The (K, K) float64 blur kernel of ``config/data_module/db.yaml``'s ``kernel_type``, before the flip of ``blur_taps``:
+    "gaussian" is ``gaussian_blur_kernel()``; "real1" .. "real8" read kernel n from ``path``, a file the user supplies: the
+    reference's ``utils/blur_kernels/Levin09.npy`` (an object array (1, 8); only this layout is opened with ``allow_pickle``) or a
+    plain 2-D ``.npy`` holding that one kernel."""
+    if kernel_type == "gaussian":
+        return gaussian_blur_kernel()
+    if not (isinstance(kernel_type, str) and len(kernel_type) == 5 and kernel_type.startswith("real") and kernel_type[4] in "12345678"):
+        raise ValueError(f"unknown blur kernel {kernel_type!r}: gaussian or real1 .. real8")
+    if path is None:
+        raise ValueError(f"blur kernel {kernel_type} is read from a file (the reference's Levin09.npy, or a 2-D .npy); none was given")
+    try:
+        k = np.load(path, allow_pickle=False)
+    except ValueError:                                   # an object array: the reference's Levin09 layout
+        k = np.load(path, allow_pickle=True)
+        if k.dtype != object or k.shape != (1, 8):
+            raise ValueError(f"{path}: an object array of shape {k.shape}, not the (1, 8) Levin09 layout")
+        k = k[0, int(kernel_type[4]) - 1]
+    return torch.from_numpy(_check_blur_kernel(k, str(path)))
+
+
+def blur_taps(kernel) -> torch.Tensor:
+    """The (K, K) fp32 correlation taps the reference hands to ``conv2d`` (utils_deblur.py:127): the kernel cast to fp32 and flipped
+    over BOTH axes (``np.flip`` without an axis)."""
+    k = _check_blur_kernel(kernel.detach().cpu().numpy() if torch.is_tensor(kernel) else kernel, "blur_taps")
+    return torch.from_numpy(np.flip(k.astype(np.float32)).copy())
+
+
+def blur(x: torch.Tensor, taps: torch.Tensor, pad: str = "same", add: Optional[torch.Tensor] = None, want_center: bool = False):
+    """Depthwise correlation of an (N, C, H, W) fp32 batch with ONE (K, K) fp32 tap table for all channels, K odd and at most 31:
+    ``out = fl32(sum taps[ky][kx] * x[oy - p + ky][ox - p + kx]) + add``.  ``pad`` "same": p = K // 2, zeros outside, output H x W
+    (the reference's validation path); "valid": p = 0, output (H - K + 1) x (W - K + 1) (its training path: blur, then crop by
+    K // 2).  ``add``: an fp32 tensor that broadcasts to the output (the noise).  ``want_center`` ("valid" only): returns
+    ``(out, x[..., K//2 : K//2 + Ho, K//2 : K//2 + Wo])``, the cropped target, contiguous.  CUDA tensors take one
+    ``grl_blur_depthwise`` launch, in place on any strided view; CPU tensors sum in float64 and round once to fp32."""
+    if pad not in ("same", "valid"):
+        raise ValueError(f"blur: pad is 'same' or 'valid', got {pad!r}")
+    if x.dim() != 4 or x.shape[0] < 1 or x.shape[1] < 1 or x.shape[2] < 1 or x.shape[3] < 1:
+        raise ValueError(f"blur: need a non-empty (N, C, H, W) batch, got {tuple(x.shape)}")
+    if x.dtype != torch.float32 or taps.dtype != torch.float32:
+        raise TypeError(f"blur takes fp32 images and taps, got {x.dtype} and {taps.dtype}")
+    if taps.dim() != 2 or taps.shape[0] != taps.shape[1] or taps.shape[0] % 2 == 0 or taps.shape[0] > 31:
+        raise ValueError(f"blur: the taps are a square table with an odd side of at most 31, got {tuple(taps.shape)}")
+    K = taps.shape[0]
+    N, Cn, H, W = x.shape
+    if pad == "valid" and (H < K or W < K):
+        raise ValueError(f"blur: a {H} x {W} image has no valid region under a {K} x {K} kernel")
+    if want_center and pad != "valid":
+        raise ValueError("blur: the centre crop belongs to pad='valid'")
+    Ho, Wo = (H, W) if pad == "same" else (H - K + 1, W - K + 1)
+    if add is not None:
+        if add.dtype != torch.float32 or add.device != x.device:
+            raise TypeError("blur: add is an fp32 tensor on the image's device")
+        add = add.expand(N, Cn, Ho, Wo)
+    if x.is_cuda:
+        return hip_blur(x, taps.to(x.device), K // 2 if pad == "same" else 0, add, want_center)
+    p = K // 2 if pad == "same" else 0
+    w = taps.double().view(1, 1, K, K).expand(Cn, 1, K, K)
+    out = F.conv2d(x.double(), w, padding=p, groups=Cn).float()
+    if add is not None:
+        out = out + add
+    if want_center:
+        return out, x[..., K // 2 : K // 2 + Ho, K // 2 : K // 2 + Wo].contiguous()
+    return out
+
+
+def hip_blur(x: torch.Tensor, taps: torch.Tensor, pad: int, add: Optional[torch.Tensor] = None, want_center: bool = False):
+    """One ``grl_blur_depthwise`` launch: ``x`` an (N, C, H, W) fp32 CUDA tensor or view, ``taps`` (K, K) fp32 on its device, ``pad``
+    K // 2 or 0, ``add`` a view of the output's shape (any batch / channel / row strides; a column stride other than 1 is copied).
+    K, the padding and the sizes are checked by the library."""
+    from . import _lib
+
+    L = _lib.lib()
+    if x.dtype != torch.float32 or taps.dtype != torch.float32 or (add is not None and add.dtype != torch.float32):
+        raise TypeError(f"grl_blur_depthwise takes fp32 tensors, got {x.dtype}")
+    if taps.dim() != 2 or taps.shape[0] != taps.shape[1] or taps.device != x.device:
+        raise ValueError("blur taps: a square (K, K) table on the image's device")
+    taps = taps.contiguous()
+    K = taps.shape[0]
+    N, Cn, H, W = x.shape
+    Ho, Wo = H + 2 * pad - K + 1, W + 2 * pad - K + 1
+    shape = (N, Cn, max(Ho, 0), max(Wo, 0))
+    out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    center = torch.empty(shape, dtype=torch.float32, device=x.device) if want_center else None
+    add_ptr, add_stride = None, (0, 0, 0)
+    if add is not None:
+        if tuple(add.shape) != shape or add.device != x.device:
+            raise ValueError(f"blur add: shape {tuple(add.shape)}, the output is {shape}")
+        if add.stride(3) != 1 and Wo > 1:
+            add = add.contiguous()
+        add_ptr, add_stride = add.data_ptr(), add.stride()[:3]
+    args = _lib.GrlBlurArgs(x=x.data_ptr(), stride=(C.c_int64 * 4)(*x.stride()), N=N, C=Cn, H=H, W=W, taps=taps.data_ptr(), K=K,
+                            pad=pad, add=add_ptr, add_stride=(C.c_int64 * 3)(*add_stride), out=out.data_ptr(),
+                            center=center.data_ptr() if want_center else None)
+    _lib.check(L.grl_blur_depthwise(_lib.stream_ptr(), C.byref(args)), "grl_blur_depthwise")
+    return (out, center) if want_center else out
+
+
+def db_noise(shape, sigma: float) -> torch.Tensor:
+    """The reference's deblurring validation noise for one (C, H, W) image, bit for bit (restoration_db.py:40-43):
+    ``np.random.seed(0)`` before EVERY image -- unlike denoising, the same stream for all of them --
+    ``normal(0, sigma / 255, shape)`` in float64, cast to fp32 (CPU)."""
+    noise = np.random.RandomState(0).normal(0, sigma / 255.0, tuple(shape))
+    return torch.from_numpy(noise.astype(np.float32))
+
+
+def db_lq(gt: torch.Tensor, taps: torch.Tensor, noise: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The deblurring LQ of a GT batch as the engine builds it for validation (engines/base.py:131-139): the noise plus the GT
+    blurred with zero padding.  ``noise`` broadcasts to the batch and lives on the GT's device."""
+    return blur(gt, taps, "same", add=noise)

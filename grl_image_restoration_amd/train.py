@@ -18,6 +18,8 @@ Restates the pieces of the reference's training run that sit around ``model(x)``
     python -m grl_image_restoration_amd.train --task sr_bicubic --scale 2 --model small --geometry sr_ckpt_df4 --gt DIV2K/HR ...
     python -m grl_image_restoration_amd.train --task dn --sigma 25 --model small --geometry dn_df4 --gt DFWB --ckpt dn_grl_small_c3s25.ckpt ...
     python -m grl_image_restoration_amd.train --task dm --model small --geometry dm --gt DFWB ...
+    python -m grl_image_restoration_amd.train --task db --blur-kernel real4 --blur-kernel-file Levin09.npy --model small \\
+        --geometry dn_df4 --gt DFWB --val-gt Set5/original ...
 
 Schedule.  ``multistep_warmup_lr(step, ...)`` is the learning rate of optimizer step ``step`` (0-based) when the reference's
 ``MultiStepLRWarmup`` is stepped once per iteration.  During warm-up it is the reference's linear ramp.  After it, torch's
@@ -91,13 +93,13 @@ def save_checkpoint(path: str, model, optimizer, step: int, sampler: D.PatchSamp
 def _parser():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--task", default="sr", choices=D.TASKS,
-                    help="sr: paired folders --lq / --gt; sr_bicubic, dn, dm: the LQ is made from --gt on the device")
+                    help="sr: paired folders --lq / --gt; sr_bicubic, dn, dm, db: the LQ is made from --gt on the device")
     ap.add_argument("--gt", required=True, help="GT training folder")
     ap.add_argument("--lq", default=None, help="LQ training folder (--task sr)")
     ap.add_argument("--model", default="base", choices=["tiny", "small", "base"])
     ap.add_argument("--geometry", default="sr_ckpt_df2", help="a key of presets.GEOMETRIES")
     ap.add_argument("--depths", default=None, help="blocks per stage as a+b+c instead of the model size's (short experiments)")
-    ap.add_argument("--scale", type=int, default=None, help="4 by default for --task sr / sr_bicubic; 1 for dn / dm")
+    ap.add_argument("--scale", type=int, default=None, help="4 by default for --task sr / sr_bicubic; 1 for dn / dm / db")
     ap.add_argument("--channels", type=int, default=3, choices=[1, 3])
     ap.add_argument("--upsampler", default=None, choices=["pixelshuffle", "pixelshuffledirect", "nearest+conv"])
     ap.add_argument("--ckpt", default=None, help="start weights (a reference checkpoint); random init without it")
@@ -111,8 +113,12 @@ def _parser():
     ap.add_argument("--warmup-iter", type=int, default=-1)
     ap.add_argument("--warmup-init-lr", type=float, default=0.0)
     ap.add_argument("--loss", default="l1", choices=sorted(LOSSES))
-    ap.add_argument("--sigma", type=float, default=None, help="--task dn: noise level on the 0..255 scale")
+    ap.add_argument("--sigma", type=float, default=None, help="--task dn: noise level on the 0..255 scale; --task db: the same, default 2")
     ap.add_argument("--sigma-range", type=float, nargs=2, default=None, metavar=("LO", "HI"), help="--task dn: a level per sample")
+    ap.add_argument("--blur-kernel", default="gaussian",
+                    help="--task db: gaussian (25 x 25, sigma 1.6) or real1 .. real8 (the Levin09 motion kernels, from --blur-kernel-file)")
+    ap.add_argument("--blur-kernel-file", default=None,
+                    help="--task db with real1 .. real8: the reference's utils/blur_kernels/Levin09.npy, or a 2-D .npy of that kernel")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--val-gt", default=None)
     ap.add_argument("--val-lq", default=None)
@@ -133,11 +139,20 @@ def _check(ap, a):
         ap.error(f"--task {a.task} builds its LQ from --gt; --lq is not used")
     if a.task == "dn" and (a.sigma is None) == (a.sigma_range is None):
         ap.error("--task dn needs --sigma or --sigma-range (one of them)")
-    if a.task != "dn" and (a.sigma is not None or a.sigma_range is not None):
+    if a.task == "db":
+        if a.sigma_range is not None:
+            ap.error("--task db adds noise at one fixed --sigma")
+        if a.channels != 3:
+            ap.error("--task db works on RGB patches")
+        if a.sigma is None:
+            a.sigma = 2.0
+    elif a.blur_kernel != "gaussian" or a.blur_kernel_file is not None:
+        ap.error(f"--blur-kernel / --blur-kernel-file belong to --task db, not {a.task}")
+    if a.task not in ("dn", "db") and (a.sigma is not None or a.sigma_range is not None):
         ap.error(f"--task {a.task} adds no noise; --sigma / --sigma-range are not used")
     if a.scale is None:
         a.scale = 4 if a.task in ("sr", "sr_bicubic") else 1
-    if a.task in ("dn", "dm") and a.scale != 1:
+    if a.task in ("dn", "dm", "db") and a.scale != 1:
         ap.error(f"--task {a.task} restores at --scale 1")
     if a.task == "sr_bicubic" and a.scale < 2:
         ap.error("--task sr_bicubic needs a --scale above 1")
@@ -179,6 +194,14 @@ def main(argv: Optional[List[str]] = None):
     ap = _parser()
     a = ap.parse_args(argv)
     _check(ap, a)
+    taps = None
+    if a.task == "db":
+        from . import tasks
+
+        try:
+            taps = tasks.blur_taps(tasks.load_blur_kernel(a.blur_kernel, a.blur_kernel_file))
+        except (ValueError, OSError) as e:
+            ap.error(f"--blur-kernel: {e}")
 
     rank, world = 0, 1
     if int(os.environ.get("WORLD_SIZE", "1")) > 1 and not dist.is_initialized():
@@ -208,7 +231,7 @@ def main(argv: Optional[List[str]] = None):
     gt_store = D.PatchStore.from_folder(a.gt, a.channels, device)
     lq_store = D.PatchStore.from_folder(a.lq, a.channels, device) if a.task == "sr" else None
     sampler = D.PatchSampler(a.task, gt_store, lq_store, patch=a.patch, batch=a.batch, scale=a.scale, sigma=a.sigma,
-                             sigma_range=a.sigma_range, seed=a.seed + rank)
+                             sigma_range=a.sigma_range, seed=a.seed + rank, taps=taps)
 
     opt = FusedAdamW(model.parameters(), lr=a.lr, weight_decay=a.weight_decay)
     start = 0
@@ -262,7 +285,7 @@ def main(argv: Optional[List[str]] = None):
             model.eval()
             with torch.no_grad():
                 v = evaluate_folder(model, a.val_lq, a.val_gt, a.scale, device=a.device, verbose=False, metric_group=a.metric,
-                                    channels=a.channels, task=a.task, sigma=a.sigma)
+                                    channels=a.channels, task=a.task, sigma=a.sigma, taps=taps)
             model.train()
             out["val"].append((done, v))
             print(f"step {n:8d}  validation {v}", flush=True)

@@ -23,7 +23,7 @@ extern "C" {
 
 #define GRL_ERR_BAD_ARG (-1)
 #define GRL_ERR_UNSUPPORTED (-2)
-#define GRL_ABI_VERSION 27
+#define GRL_ABI_VERSION 28
 
 /* element kinds of activation / weight buffers */
 enum { GRL_DT_F32 = 0, GRL_DT_BF16 = 1, GRL_DT_F16 = 2 };
@@ -830,6 +830,37 @@ typedef struct GrlPatchArgs {
 } GrlPatchArgs;
 
 int grl_sample_patches(void* stream, const GrlPatchArgs* args);
+
+/* Depthwise K x K blur of an image batch (ABI 28; the LQ synthesis of non-blind deblurring, data module `db`):
+ *   replaces  input_ += F.conv2d(target, blur_kernel, groups=3, padding=(bkh, bkw))   engines/base.py:131-139
+ *             input_[:, :, bkh:-bkh, bkw:-bkw], target[:, :, bkh:-bkh, bkw:-bkw]        engines/base.py:140-142 (training)
+ * x: fp32 (N, C, H, W), read in place through four ELEMENT strides (batch, channel, row, column): crops, channels-last tensors.
+ * taps: K x K fp32 correlation taps in DEVICE memory, row major, one table for every plane (the reference repeats its kernel over the
+ * channels; utils/utils_deblur.py:127-128 has already flipped it); K odd, 1 .. 31.  The kernel reads them when it runs: no constant
+ * upload, no host synchronisation, so the launch can be captured and the table rewritten between replays.
+ * pad = K / 2: zero padding, out is (N, C, H, W) (validation).  pad = 0: the valid region, out is (N, C, H-K+1, W-K+1) (training: a
+ * (P+K-1)^2 patch gives a P^2 LQ).  out: contiguous fp32.
+ *   out[oy][ox] = fl32(sum_ky sum_kx taps[ky][kx] * x[oy - pad + ky][ox - pad + kx]) + add[oy][ox]
+ * one fp32 fmaf chain from 0 per output, ky outer and kx inner: deterministic, and independent of the tiling (a `valid` output is
+ * bitwise the `same` output at that place).  add (optional, the reference's noise): the output's shape, element strides add_stride
+ * (batch, channel, row) and unit column stride, added after the sum was rounded.  center (optional, pad = 0 only): contiguous fp32 of
+ * the output's shape that receives x[oy + K/2][ox + K/2], the reference's cropped target, from the tile already on chip.
+ * One launch on `stream`.
+ * Errors (GRL_ERR_BAD_ARG): a null x / taps / out, K even or outside 1 .. 31, pad neither 0 nor K / 2, H or W below K with pad = 0,
+ * center with pad != 0, a non-positive N, C, H or W, a pointer not 4-byte aligned, a grid beyond 2^31 - 1 workgroups. */
+typedef struct GrlBlurArgs {
+    const float* x;
+    int64_t stride[4];          /* element strides of batch, channel, row, column                */
+    int32_t N, C, H, W;
+    const float* taps;          /* [K][K] device                                                  */
+    int32_t K, pad;             /* pad: K / 2 (same size) or 0 (valid region)                     */
+    const float* add;           /* optional, the output's shape                                   */
+    int64_t add_stride[3];      /* element strides of batch, channel, row of add                  */
+    float* out;                 /* (N, C, H + 2 pad - K + 1, W + 2 pad - K + 1)                   */
+    float* center;              /* optional (pad = 0), the output's shape                         */
+} GrlBlurArgs;
+
+int grl_blur_depthwise(void* stream, const GrlBlurArgs* args);
 
 /* Debug aid (ABI 21; no reference counterpart): fills the LDS of every CU with 0xFF bytes (fp32 / fp16 NaN) by a launch on
  * `stream`.  LDS keeps what the previous workgroup left in it; a kernel that reads LDS it has not written is otherwise right or
