@@ -11,7 +11,7 @@ from . import switches as SW
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgrl_hip.so")
-ABI_VERSION = 28
+ABI_VERSION = 29
 DT_F32, DT_BF16, DT_F16 = 0, 1, 2
 
 EPI_PLAIN, EPI_GELU, EPI_GROUPNORM, EPI_LN_RES, EPI_GELU_GRAD = 0, 1, 2, 3, 4
@@ -63,6 +63,8 @@ EXPORTS = [
     "grl_image_niqe_features",
     "grl_sample_patches",
     "grl_blur_depthwise",
+    "grl_jpeg_workspace_bytes",
+    "grl_jpeg_roundtrip",
     "grl_debug_dirty_lds",
     "grl_abi_version",
     "grl_build_info",
@@ -589,6 +591,16 @@ class GrlBlurArgs(_Strict):
     ]
 
 
+class GrlJpegArgs(_Strict):
+    _fields_ = [
+        ("x", C.c_void_p),
+        ("quality", C.c_void_p),
+        ("N", C.c_int32), ("C", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+        ("workspace", C.c_void_p),
+        ("out", C.c_void_p),
+    ]
+
+
 _lib = None
 
 
@@ -702,6 +714,10 @@ def lib():
     L.grl_sample_patches.restype = C.c_int
     L.grl_blur_depthwise.argtypes = [C.c_void_p, C.POINTER(GrlBlurArgs)]
     L.grl_blur_depthwise.restype = C.c_int
+    L.grl_jpeg_workspace_bytes.argtypes = [C.c_int32] * 4
+    L.grl_jpeg_workspace_bytes.restype = C.c_int64
+    L.grl_jpeg_roundtrip.argtypes = [C.c_void_p, C.POINTER(GrlJpegArgs)]
+    L.grl_jpeg_roundtrip.restype = C.c_int
     L.grl_debug_dirty_lds.argtypes = [C.c_void_p]
     L.grl_debug_dirty_lds.restype = C.c_int
     _lib = L

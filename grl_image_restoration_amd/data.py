@@ -26,7 +26,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 import torch
 
-TASKS = ("sr", "sr_bicubic", "dn", "dm", "db")
+TASKS = ("sr", "sr_bicubic", "dn", "dm", "db", "jpeg")
 FLIP_ROWS, FLIP_COLS, SWAP_AXES = 1, 2, 4
 
 
@@ -160,21 +160,31 @@ class PatchSampler:
                   reference draws its training noise from the unseeded ``np.random`` at P' x P' and crops it, so there is no
                   stream to reproduce bit for bit; the distribution is the same
 
+      jpeg        JPEG artifact removal (restoration_jpeg.py:30-46), RGB or gray.  With a fixed ``quality`` (the reference's default,
+                  ``patchwise: False``) every image of the GT store is compressed WHOLE, once, at construction
+                  (``tasks.jpeg_roundtrip`` on the store's device) into an 8-bit LQ store, and the pair is sampled as ``sr`` at scale
+                  1: patches sit at arbitrary phases of the 8 x 8 block grid, and small images are zero padded after compression.
+                  With ``quality_range`` = (lo, hi) (``patchwise: True``) the GT patch is cropped and augmented first, a quality is
+                  drawn per sample, and ONE ``tasks.jpeg_roundtrip`` call compresses the batch of patches; the qualities sit in the
+                  sampler's own device tensor ``qualities``, so a captured step replays the call while they change.  Whole-image
+                  compression at a quality per sample is not built: it would recompress a whole image for every sample
+
     Draws, from ``random.Random(seed)``, per sample and in this order: ``randrange(N)`` for the image; ``randrange(H' - P + 1)``
     and ``randrange(W' - P + 1)`` with H' = max(H, P), W' = max(W, P) the LQ-side size after the reference's padding
     (_random_index on the padded image, base_image.py:252-256, 397-402); three ``random() < 0.5`` for the flags; with
-    ``sigma_range`` one ``uniform(lo, hi)``.  For db, P is P'.
+    ``sigma_range`` one ``uniform(lo, hi)``; with ``quality_range`` one ``randint(lo, hi)`` in that place.  For db, P is P'.
     """
 
     def __init__(self, task: str, gt_store: PatchStore, lq_store: Optional[PatchStore] = None, patch: int = 64, batch: int = 8,
                  scale: int = 1, sigma: Optional[float] = None, sigma_range: Optional[Sequence[float]] = None, seed: int = 0,
-                 taps: Optional[torch.Tensor] = None):
+                 taps: Optional[torch.Tensor] = None, quality: Optional[int] = None,
+                 quality_range: Optional[Sequence[int]] = None, patchwise: bool = True):
         if task not in TASKS:
             raise ValueError(f"unknown task {task!r}: one of {TASKS}")
         patch, batch, scale = int(patch), int(batch), int(scale)
         if patch < 1 or batch < 1:
             raise ValueError(f"patch and batch must be positive, got {patch}, {batch}")
-        if task in ("dn", "dm", "db") and scale != 1:
+        if task in ("dn", "dm", "db", "jpeg") and scale != 1:
             raise ValueError(f"task {task} restores at scale 1, got {scale}")
         if task in ("sr", "sr_bicubic") and scale < (2 if task == "sr_bicubic" else 1):
             raise ValueError(f"task {task}: bad scale {scale}")
@@ -196,10 +206,26 @@ class PatchSampler:
             raise ValueError(f"task {task} does not blur; taps are not used")
         if task not in ("dn", "db") and (sigma is not None or sigma_range is not None):
             raise ValueError(f"task {task} adds no noise")
+        if task == "jpeg":
+            if (quality is None) == (quality_range is None):
+                raise ValueError("task jpeg needs quality or quality_range (one of them)")
+            if quality_range is not None:
+                if not patchwise:
+                    raise ValueError("task jpeg with a quality per sample compresses the cropped patches (patchwise); whole-image "
+                                     "compression would recompress an image for every sample and is not built")
+                quality_range = tuple(int(v) for v in quality_range)
+                if len(quality_range) != 2 or not 1 <= quality_range[0] <= quality_range[1] <= 100:
+                    raise ValueError(f"task jpeg: quality_range is (lo, hi) with 1 <= lo <= hi <= 100, got {quality_range}")
+            elif not 1 <= int(quality) <= 100:
+                raise ValueError(f"task jpeg: quality is 1 .. 100, got {quality}")
+        elif quality is not None or quality_range is not None:
+            raise ValueError(f"task {task} does not compress; quality / quality_range are not used")
         if task == "dm" and (gt_store.channels != 3 or patch % 2 or patch < 4):
             raise ValueError("task dm works on RGB patches with an even side of at least 4")
         if task == "sr_bicubic":
             gt_store, lq_store = _bicubic_stores(gt_store, scale)
+        if task == "jpeg" and quality is not None:
+            lq_store = _jpeg_store(gt_store, int(quality))
         if lq_store is not None:
             if len(lq_store) != len(gt_store) or lq_store.channels != gt_store.channels or lq_store.device != gt_store.device:
                 raise ValueError("task sr: the two stores need the same number of images, channel count and device")
@@ -209,16 +235,20 @@ class PatchSampler:
         self.task, self.gt_store, self.lq_store = task, gt_store, lq_store
         self.patch, self.batch, self.scale = patch, batch, scale
         self.sigma, self.sigma_range = sigma, (tuple(float(v) for v in sigma_range) if sigma_range is not None else None)
+        self.quality, self.quality_range = (int(quality) if quality is not None else None), quality_range
         self.rng = random.Random(seed)
         self.device = gt_store.device
         self.gen = torch.Generator(device=self.device).manual_seed(int(seed)) if task in ("dn", "db") else None
         self.taps = taps.to(device=self.device, dtype=torch.float32).contiguous() if task == "db" else None
         self.draw_patch = patch + (self.taps.shape[0] - 1 if task == "db" else 0)      # the side the draws and the crop use
         self.work = torch.zeros(batch, 4, dtype=torch.int32, device=self.device)      # the device work list, rewritten in place
+        # the device quality list of jpeg with a range, rewritten in place like the work list
+        self.qualities = torch.zeros(batch, dtype=torch.int32, device=self.device) if quality_range is not None else None
 
     # ---- draws ---------------------------------------------------------------------------------------------------------------
     def draw(self):
-        """One batch of draws: ([(image, x, y, flags)] * batch, [sigma] * batch or None)."""
+        """One batch of draws: ([(image, x, y, flags)] * batch, [sigma] * batch or None); for jpeg with a quality range the second
+        list holds the qualities."""
         sizes = (self.lq_store or self.gt_store).dims
         P, work, sigmas = self.draw_patch, [], []
         for _ in range(self.batch):
@@ -230,7 +260,9 @@ class PatchSampler:
             work.append((n, x, y, flags))
             if self.sigma_range is not None:
                 sigmas.append(self.rng.uniform(*self.sigma_range))
-        return work, (sigmas if self.sigma_range is not None else None)
+            if self.quality_range is not None:
+                sigmas.append(self.rng.randint(*self.quality_range))
+        return work, (sigmas if self.sigma_range is not None or self.quality_range is not None else None)
 
     def rng_state(self):
         """What a checkpoint keeps to continue the stream of batches: the draws' state and the noise generator's."""
@@ -244,7 +276,8 @@ class PatchSampler:
     # ---- batches -------------------------------------------------------------------------------------------------------------
     def next(self, work=None, sigmas: Optional[Sequence[float]] = None, noise: Optional[torch.Tensor] = None):
         """(lq, gt) on the store's device.  ``work``: an explicit work list (a sequence of (image, x, y, flags) or an int32 (B, 4)
-        tensor) instead of fresh draws; ``sigmas`` with it for dn with a sigma range.  ``noise`` (db): a unit-variance
+        tensor) instead of fresh draws; ``sigmas`` with it for dn with a sigma range and for jpeg with a quality range (the
+        qualities).  ``noise`` (db): a unit-variance
         (B, 3, patch, patch) fp32 tensor used instead of the generator's draw (it is scaled by ``sigma / 255``)."""
         if work is None:
             work, sigmas = self.draw()
@@ -258,7 +291,7 @@ class PatchSampler:
             else:
                 wt = wt.to(self.device)
         B = wt.shape[0]
-        if self.lq_store is not None:                # sr, and sr_bicubic after its stores were made
+        if self.lq_store is not None:                # sr, and sr_bicubic / jpeg at a fixed quality after their stores were made
             lq = self.lq_store.sample(wt, self.patch, 1)
             gt = self.gt_store.sample(wt, self.patch, self.scale)
             return lq, gt
@@ -276,6 +309,18 @@ class PatchSampler:
             from . import tasks
 
             return tasks.demosaic_gt(gt), gt
+        if self.task == "jpeg":
+            from . import tasks
+
+            if sigmas is None or len(sigmas) != B:
+                raise ValueError("jpeg with a quality range: one quality per sample of an explicit work list")
+            q = torch.tensor([int(v) for v in sigmas], dtype=torch.int32)
+            if q.shape == self.qualities.shape:       # the sampler's own list, in place: a captured call reads this address
+                self.qualities.copy_(q)
+                q = self.qualities
+            else:
+                q = q.to(self.device)
+            return tasks.jpeg_roundtrip(gt, q), gt
         if self.sigma_range is not None:
             if sigmas is None or len(sigmas) != B:
                 raise ValueError("dn with a sigma range: one sigma per sample of an explicit work list")
@@ -307,3 +352,16 @@ def _bicubic_stores(gt_store: PatchStore, scale: int):
         lqs.append((lq[0] * 255).round().to(torch.uint8).permute(1, 2, 0).contiguous().cpu())
         gts.append(gt[0].permute(1, 2, 0).contiguous().cpu())
     return PatchStore(gts, gt_store.device), PatchStore(lqs, gt_store.device)
+
+
+def _jpeg_store(gt_store: PatchStore, quality: int) -> PatchStore:
+    """The LQ store of jpeg at a fixed quality: every image of the GT store through ``tasks.jpeg_roundtrip`` as a whole, on the
+    store's device, back to 8 bit (the round trip returns k / 255 exactly)."""
+    from . import tasks
+
+    lqs: List[torch.Tensor] = []
+    for n in range(len(gt_store)):
+        gt = gt_store.image(n).permute(2, 0, 1).unsqueeze(0).to(torch.float32).div(255).contiguous()
+        lq = tasks.jpeg_roundtrip(gt, quality)
+        lqs.append((lq[0] * 255).round().to(torch.uint8).permute(1, 2, 0).contiguous().cpu())
+    return PatchStore(lqs, gt_store.device)

@@ -20,6 +20,9 @@ Restates, for the MI355X module, the three pieces of the reference's evaluation 
   task "db"         non-blind deblurring (config/data_module/db.yaml): the GT cropped to multiples of 8 and blurred on the device with
                     the Gaussian or a Levin09 kernel, zero padded (``tasks.db_lq``, one ``grl_blur_depthwise`` launch;
                     engines/base.py:131-139), plus the data set's noise at sigma 2, seeded 0 for every image (restoration_db.py:40-43)
+  task "jpeg"       JPEG artifact removal (config/data_module/jpeg.yaml): the GT, NOT cropped (the validation branch samples at scale 1,
+                    base_image.py:403-404), compressed and decompressed on the device at ``quality`` (``tasks.jpeg_roundtrip``:
+                    libjpeg's arithmetic bit for bit; data/datasets/restoration_jpeg.py:62-79)
   task "bsr"        blind / real-world SR (config/experiment/bsr/grl.yaml): LQ images only, no GT (``with_gt: False``); the metric is
                     NIQE of the output (``metrics.niqe``, config/metric/restorer_niqe.yaml), against the pristine model the user
                     names with ``--niqe-params`` or the environment variable GRL_NIQE_PARAMS
@@ -34,6 +37,8 @@ Restates, for the MI355X module, the three pieces of the reference's evaluation 
         --ckpt sr_grl_base_c3x4.ckpt --gt Set5/original --metric restorer
     python -m grl_image_restoration_amd.evaluate --task db --model small --geometry dn_df4 --ckpt runs/db/step_400000.ckpt \\
         --gt Set5/original [--blur-kernel real4 --blur-kernel-file Levin09.npy]
+    python -m grl_image_restoration_amd.evaluate --task jpeg --quality 10 --model small --geometry jpeg --ckpt jpeg_grl_small_c3q10.ckpt \\
+        --gt LIVE1 --metric restorer_jpeg
     python -m grl_image_restoration_amd.evaluate --task bsr --model base --geometry bsr --upsampler nearest+conv \\
         --ckpt bsr_grl_base.ckpt --lq RealSRSet --niqe-params niqe_pris_params.npz
 """
@@ -163,7 +168,7 @@ def evaluate_pairs(model, pairs: Iterable[Tuple[torch.Tensor, torch.Tensor]], sc
     return {k: sum(o[k] for o in out) / len(out) for k in out[0]}
 
 
-TASKS = ("sr", "dn", "dm", "sr_bicubic", "bsr", "db")
+TASKS = ("sr", "dn", "dm", "sr_bicubic", "bsr", "db", "jpeg")
 
 
 def gt_images(gt_dir: str) -> List[str]:
@@ -175,19 +180,22 @@ def gt_images(gt_dir: str) -> List[str]:
 
 
 def task_inputs(gt_dir: str, task: str, channels: int = 3, sigma: Optional[float] = None, noise_prefix: Optional[str] = None,
-                device: str = "cuda:0", scale: int = 1, taps: Optional[torch.Tensor] = None):
-    """(file name, LQ, GT) for every image of ``gt_dir`` under a task that synthesises its input ("dn", "dm", "sr_bicubic" or "db"), as the reference's
+                device: str = "cuda:0", scale: int = 1, taps: Optional[torch.Tensor] = None, quality: Optional[int] = None):
+    """(file name, LQ, GT) for every image of ``gt_dir`` under a task that synthesises its input ("dn", "dm", "sr_bicubic", "db" or "jpeg"), as the reference's
     validation sets do: GT read as 8 bit and cropped to multiples of 8; "dn" adds ``tasks.dn_noise`` at ``sigma`` (keyed by
     ``noise_prefix/<file name>``: the reference's test-set name, by default the folder's base name matched to it case-insensitively by
     ``tasks.dn_test_set_name``, and the path that the set's test.json lists; on the CPU, in fp32, as the data set does), "dm"
     runs ``tasks.demosaic_gt`` on ``device`` (RGB only).  "sr_bicubic" crops the GT to a multiple of ``scale`` instead (the
     reference's ``modcrop(img_gt, self.scale)``, restoration_sr.py:130) and makes the LQ with ``tasks.sr_lq`` on ``device``.
     "db" (RGB only) blurs the GT on ``device`` with ``taps`` (``tasks.blur_taps``; default: the Gaussian's) and adds
-    ``tasks.db_noise`` at ``sigma`` (default 2), made on the CPU and added by the blur kernel."""
+    ``tasks.db_noise`` at ``sigma`` (default 2), made on the CPU and added by the blur kernel.  "jpeg" leaves the GT uncropped
+    and makes the LQ with ``tasks.jpeg_roundtrip`` at ``quality`` on ``device``."""
     from . import tasks
 
-    if task not in ("dn", "dm", "sr_bicubic", "db"):
-        raise ValueError(f"task {task!r} reads its LQ from a folder; synthesised tasks: dn, dm, sr_bicubic, db")
+    if task not in ("dn", "dm", "sr_bicubic", "db", "jpeg"):
+        raise ValueError(f"task {task!r} reads its LQ from a folder; synthesised tasks: dn, dm, sr_bicubic, db, jpeg")
+    if task == "jpeg" and (quality is None or not 1 <= int(quality) <= 100):
+        raise ValueError(f"task jpeg needs a quality of 1 .. 100, got {quality}")
     if task == "sr_bicubic" and int(scale) < 2:
         raise ValueError(f"task sr_bicubic needs a scale above 1, got {scale}")
     if task == "dn" and sigma is None:
@@ -208,6 +216,10 @@ def task_inputs(gt_dir: str, task: str, channels: int = 3, sigma: Optional[float
             gt = tasks.modcrop(_read_image(p, mode), int(scale)).contiguous()
             yield name, tasks.sr_lq(gt.to(device), int(scale))[0], gt
             continue
+        if task == "jpeg":
+            gt = _read_image(p, mode)
+            yield name, tasks.jpeg_roundtrip(gt.to(device), int(quality)), gt
+            continue
         gt = tasks.modcrop(_read_image(p, mode), 8).contiguous()
         if task == "dn":
             noise = tasks.dn_noise(gt.shape[1:], sigma, tasks.dn_noise_key(f"{noise_prefix}/{name}"))
@@ -222,10 +234,10 @@ def task_inputs(gt_dir: str, task: str, channels: int = 3, sigma: Optional[float
 def evaluate_folder(model, lq_dir: Optional[str], gt_dir: Optional[str], scale: int, tile: int = 0, overlap: int = 32,
                     device: str = "cuda:0", verbose: bool = True, metric_group: Optional[str] = None, channels: int = 3,
                     task: str = "sr", sigma: Optional[float] = None, noise_prefix: Optional[str] = None, niqe_params=None,
-                    taps: Optional[torch.Tensor] = None):
+                    taps: Optional[torch.Tensor] = None, quality: Optional[int] = None):
     """Mean PSNR-Y over the image pairs of two folders; with ``metric_group``, {metric name: mean} of that group.  ``channels`` 1
-    reads the images as grayscale.  ``task`` "dn" / "dm" / "db" ignores ``lq_dir`` and builds the LQ from the GT (``task_inputs``;
-    ``scale`` must be 1; ``taps``: the blur taps of "db", the Gaussian's by default); so does "sr_bicubic", at a ``scale`` above 1.  ``task`` "bsr" reads ``lq_dir`` alone (``gt_dir`` is not used)
+    reads the images as grayscale.  ``task`` "dn" / "dm" / "db" / "jpeg" ignores ``lq_dir`` and builds the LQ from the GT (``task_inputs``;
+    ``scale`` must be 1; ``taps``: the blur taps of "db", the Gaussian's by default; ``quality``: the JPEG quality of "jpeg"); so does "sr_bicubic", at a ``scale`` above 1.  ``task`` "bsr" reads ``lq_dir`` alone (``gt_dir`` is not used)
     and returns {"val_niqe": mean}; ``niqe_params`` is the pristine model of ``metrics.niqe`` (also for "restorer_niqe" elsewhere)."""
     if task not in TASKS:
         raise ValueError(f"unknown task {task!r}: one of {TASKS}")
@@ -242,7 +254,7 @@ def evaluate_folder(model, lq_dir: Optional[str], gt_dir: Optional[str], scale: 
     else:
         if scale != 1:
             raise ValueError(f"task {task} restores at scale 1, got {scale}")
-        items = task_inputs(gt_dir, task, channels, sigma, noise_prefix, device, taps=taps)
+        items = task_inputs(gt_dir, task, channels, sigma, noise_prefix, device, taps=taps, quality=quality)
     vals = []
     for name, lq, gt in items:
         v = evaluate_pairs(model, [(lq, gt)], scale, tile, overlap, device, metric_group, niqe_params)
@@ -273,8 +285,9 @@ def main(argv: Optional[List[str]] = None):
     ap.add_argument("--model", default="base", choices=["tiny", "small", "base"])
     ap.add_argument("--geometry", default="sr_ckpt_df2", help="a key of presets.GEOMETRIES")
     ap.add_argument("--task", default="sr", choices=TASKS,
-                    help="sr: LQ images from --lq (SR, deblurring, JPEG); dn / dm / sr_bicubic / db: the LQ is made from --gt (denoising, "
-                         "demosaicking, classical SR by MATLAB-bicubic downscaling at --scale, non-blind deblurring); bsr: LQ images from --lq, no --gt, "
+                    help="sr: LQ images from --lq (SR, deblurring, JPEG); dn / dm / sr_bicubic / db / jpeg: the LQ is made from --gt (denoising, "
+                         "demosaicking, classical SR by MATLAB-bicubic downscaling at --scale, non-blind deblurring, JPEG compression at "
+                         "--quality); bsr: LQ images from --lq, no --gt, "
                          "scored by NIQE")
     ap.add_argument("--scale", type=int, default=None, help="4 by default for --task sr / sr_bicubic / bsr; 1 for everything else")
     ap.add_argument("--upsampler", default=None, choices=["pixelshuffle", "pixelshuffledirect", "nearest+conv"],
@@ -296,6 +309,7 @@ def main(argv: Optional[List[str]] = None):
                     help="--task db: gaussian (25 x 25, sigma 1.6) or real1 .. real8 (the Levin09 motion kernels, from --blur-kernel-file)")
     ap.add_argument("--blur-kernel-file", default=None,
                     help="--task db with real1 .. real8: the reference's utils/blur_kernels/Levin09.npy, or a 2-D .npy of that kernel")
+    ap.add_argument("--quality", type=int, default=None, help="--task jpeg: the JPEG quality factor, 1 .. 100 (10, 20, 30, 40)")
     ap.add_argument("--noise-prefix", default=None,
                     help="--task dn: the reference's test-set name (Set12, BSD68, CBSD68, Kodak24, McMaster, Urban100; case matters) "
                          "that starts the noise seed key '<prefix>/<file name>'; a different prefix draws different noise.  Default: "
@@ -319,8 +333,12 @@ def main(argv: Optional[List[str]] = None):
         ap.error("--task dn needs --sigma")
     if a.scale is None:
         a.scale = 4 if a.task in ("sr", "sr_bicubic", "bsr") else 1
-    if a.task in ("dn", "dm", "db") and a.scale != 1:
+    if a.task in ("dn", "dm", "db", "jpeg") and a.scale != 1:
         ap.error(f"--task {a.task} restores at --scale 1")
+    if a.task == "jpeg" and (a.quality is None or not 1 <= a.quality <= 100):
+        ap.error("--task jpeg needs --quality, 1 .. 100")
+    if a.task != "jpeg" and a.quality is not None:
+        ap.error(f"--quality belongs to --task jpeg, not {a.task}")
     if a.task == "sr_bicubic" and a.scale < 2:
         ap.error("--task sr_bicubic needs a --scale above 1")
     taps = None
@@ -351,7 +369,8 @@ def main(argv: Optional[List[str]] = None):
         load_checkpoint(model, a.ckpt)
     model = model.to(a.device)
     return evaluate_folder(model, a.lq, a.gt, a.scale, a.tile, a.overlap, a.device, metric_group=a.metric, channels=a.channels,
-                           task=a.task, sigma=a.sigma, noise_prefix=a.noise_prefix, niqe_params=niqe_params, taps=taps)
+                           task=a.task, sigma=a.sigma, noise_prefix=a.noise_prefix, niqe_params=niqe_params, taps=taps,
+                           quality=a.quality)
 
 
 if __name__ == "__main__":

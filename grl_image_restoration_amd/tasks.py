@@ -22,6 +22,10 @@
                                                     plus the noise; ``want_center`` also returns the cropped target
   db_noise           data/datasets/restoration_db.py:40-43   the deblurring validation noise: numpy's generator seeded 0 for EVERY image
   db_lq                                             the deblurring LQ of a GT batch: ``blur(gt, taps, "same", add=noise)``
+  jpeg_tables        libjpeg's jpeg_set_quality           the two baseline quantisation tables of a quality, natural (row-major) order
+  jpeg_roundtrip     data/datasets/restoration_jpeg.py:62-79   the JPEG artifact-removal LQ: ``cv2.imencode(".jpg", img, [IMWRITE_JPEG_QUALITY,
+                                                    q])`` followed by ``cv2.imdecode``, restated as libjpeg's integer arithmetic (the
+                                                    entropy coding is lossless and left out)
 
 CUDA fp32 tensors go through ``grl_demosaic_matlab`` of libgrl_hip.so (csrc/demosaic.hip); there is no torch fallback for them.
 ``demosaic_gt`` on CUDA is a single launch that reads the RGB image in place on the RGGB lattice, without forming the mosaic.  CPU
@@ -32,6 +36,9 @@ tensors go through ``grl_imresize`` (csrc/imresize.hip, one launch, fp64 sums, o
 and sum by the same tables; the two agree to an fp32 rounding, not bitwise (cubic weights are not dyadic).  ``blur`` on CUDA is one
 ``grl_blur_depthwise`` launch (csrc/blur.hip: an fp32 fmaf chain per output in a fixed order, deterministic); on the CPU the taps are
 summed in float64 and rounded once.  The two agree within the forward error of a K x K-term fp32 sum, (K^2 + 2) 2^-24 max|x|.
+``jpeg_roundtrip`` on CUDA is one ``grl_jpeg_roundtrip`` call (csrc/jpeg.hip, two launches, int32); on the CPU ``_torch_jpeg``
+restates the same integer arithmetic in int64.  Both are libjpeg-turbo's defaults (4:2:0, ``JDCT_ISLOW``, baseline tables, fancy
+upsampling) bit for bit, so the two paths and the library agree in every byte.
 """
 import ctypes as C
 import hashlib
@@ -464,3 +471,185 @@ def db_lq(gt: torch.Tensor, taps: torch.Tensor, noise: Optional[torch.Tensor] = 
     """The deblurring LQ of a GT batch as the engine builds it for validation (engines/base.py:131-139): the noise plus the GT
     blurred with zero padding.  ``noise`` broadcasts to the batch and lives on the GT's device."""
     return blur(gt, taps, "same", add=noise)
+
+
+# ---- JPEG compression artifacts ------------------------------------------------------------------------------------------------
+# JPEG Annex K, tables K.1 (luminance) and K.2 (chrominance), natural order
+_JPEG_STD = (
+    (16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
+     18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112,
+     100, 103, 99),
+    (17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99)
+    + (99,) * 32,
+)
+
+
+def jpeg_tables(q: int) -> torch.Tensor:
+    """(2, 64) int64: the luminance and the chrominance quantisation table of quality ``q`` (clamped to 1 .. 100) in natural
+    (row-major) order, as libjpeg's ``jpeg_set_quality(q, force_baseline=TRUE)`` scales the Annex K tables."""
+    q = min(max(int(q), 1), 100)
+    s = 5000 // q if q < 50 else 200 - 2 * q
+    return ((torch.tensor(_JPEG_STD, dtype=torch.int64) * s + 50) // 100).clamp(1, 255)
+
+
+def _jpeg_qualities(quality, N: int) -> torch.Tensor:
+    """``quality`` (an int, or a sequence or integer tensor of length N) as an int32 (N,) tensor, unclamped, on its own device."""
+    if torch.is_tensor(quality):
+        if quality.dtype not in (torch.int32, torch.int64) or quality.dim() > 1:
+            raise TypeError("jpeg_roundtrip: a quality tensor is int32 with one entry per sample")
+        quality = quality.to(torch.int32).reshape(-1)
+    elif isinstance(quality, (int, np.integer)):
+        quality = torch.full((N,), int(quality), dtype=torch.int32)
+    else:
+        quality = torch.tensor([int(v) for v in quality], dtype=torch.int32)
+    if quality.shape[0] != N:
+        raise ValueError(f"jpeg_roundtrip: {quality.shape[0]} qualities for a batch of {N}")
+    return quality
+
+
+def jpeg_roundtrip(x: torch.Tensor, quality) -> torch.Tensor:
+    """JPEG compression and decompression of an (N, C, H, W) fp32 batch of 8-bit levels ``k / 255``, C = 3 (RGB) or 1, as
+    libjpeg-turbo does it with OpenCV's and Pillow's defaults: 4:2:0 chroma, the ``islow`` integer DCT, baseline tables, fancy
+    upsampling.  ``quality``: an int, or a sequence or int32 tensor with one entry per sample; values outside 1 .. 100 are
+    clamped.  Returns fp32 ``k' / 255``.  CUDA tensors take ``grl_jpeg_roundtrip`` (a quality tensor on the device is read by the
+    kernel when it runs, so a captured call follows later changes of it); CPU tensors take ``_torch_jpeg``."""
+    if x.dim() != 4 or x.shape[1] not in (1, 3) or min(x.shape) < 1:
+        raise ValueError(f"jpeg_roundtrip: need a non-empty (N, C, H, W) batch with C = 1 or 3, got {tuple(x.shape)}")
+    if x.dtype != torch.float32:
+        raise TypeError(f"jpeg_roundtrip takes fp32 images, got {x.dtype}")
+    q = _jpeg_qualities(quality, x.shape[0])
+    if x.is_cuda:
+        return hip_jpeg(x, q.to(x.device))
+    return _torch_jpeg(x, q.cpu())
+
+
+def hip_jpeg(x: torch.Tensor, quality: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One ``grl_jpeg_roundtrip`` call: ``x`` an (N, C, H, W) fp32 CUDA tensor, ``quality`` an int32 (N,) tensor on its device.  The
+    workspace of the decoded component planes is a fresh uint8 tensor.  The sizes are checked by the library."""
+    from . import _lib
+
+    L = _lib.lib()
+    if x.dtype != torch.float32 or quality.dtype != torch.int32:
+        raise TypeError(f"grl_jpeg_roundtrip takes fp32 images and int32 qualities, got {x.dtype} and {quality.dtype}")
+    if quality.device != x.device or quality.dim() != 1 or quality.shape[0] != x.shape[0]:
+        raise ValueError("jpeg qualities: an int32 (N,) tensor on the image's device")
+    x, quality = x.contiguous(), quality.contiguous()
+    N, Cn, H, W = x.shape
+    if out is None:
+        out = torch.empty_like(x)
+    elif out.shape != x.shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != x.device:
+        raise ValueError("out: a contiguous fp32 tensor of the input's shape on its device")
+    ws = torch.empty(max(int(L.grl_jpeg_workspace_bytes(N, Cn, H, W)), 1), dtype=torch.uint8, device=x.device)
+    args = _lib.GrlJpegArgs(x=x.data_ptr(), quality=quality.data_ptr(), N=N, C=Cn, H=H, W=W, workspace=ws.data_ptr(),
+                            out=out.data_ptr())
+    _lib.check(L.grl_jpeg_roundtrip(_lib.stream_ptr(), C.byref(args)), "grl_jpeg_roundtrip")
+    return out
+
+
+def _jd(x, n: int):
+    """libjpeg's DESCALE: a rounding arithmetic right shift."""
+    return (x + (1 << (n - 1))) >> n
+
+
+def _jpeg_fdct8(x: torch.Tensor, dim: int, first: bool) -> torch.Tensor:
+    """One 1-D pass of jfdctint.c along ``dim`` (length 8): the row pass (``first``) or the column pass."""
+    d = x.unbind(dim)
+    t0, t7, t1, t6 = d[0] + d[7], d[0] - d[7], d[1] + d[6], d[1] - d[6]
+    t2, t5, t3, t4 = d[2] + d[5], d[2] - d[5], d[3] + d[4], d[3] - d[4]
+    t10, t13, t11, t12 = t0 + t3, t0 - t3, t1 + t2, t1 - t2
+    n = 11 if first else 15
+    o = [None] * 8
+    o[0], o[4] = ((t10 + t11) << 2, (t10 - t11) << 2) if first else (_jd(t10 + t11, 2), _jd(t10 - t11, 2))
+    z1 = (t12 + t13) * 4433
+    o[2], o[6] = _jd(z1 + t13 * 6270, n), _jd(z1 - t12 * 15137, n)
+    z1, z2, z3, z4 = t4 + t7, t5 + t6, t4 + t6, t5 + t7
+    z5 = (z3 + z4) * 9633
+    t4, t5, t6, t7 = t4 * 2446, t5 * 16819, t6 * 25172, t7 * 12299
+    z1, z2, z3, z4 = z1 * -7373, z2 * -20995, z3 * -16069 + z5, z4 * -3196 + z5
+    o[7], o[5], o[3], o[1] = _jd(t4 + z1 + z3, n), _jd(t5 + z2 + z4, n), _jd(t6 + z2 + z3, n), _jd(t7 + z1 + z4, n)
+    return torch.stack(o, dim)
+
+
+def _jpeg_idct8(x: torch.Tensor, dim: int, first: bool) -> torch.Tensor:
+    """One 1-D pass of jidctint.c along ``dim``: the column pass (``first``, descale 11) or the row pass (descale 18)."""
+    d = x.unbind(dim)
+    z1 = (d[2] + d[6]) * 4433
+    t2, t3 = z1 - d[6] * 15137, z1 + d[2] * 6270
+    t0, t1 = (d[0] + d[4]) << 13, (d[0] - d[4]) << 13
+    t10, t13, t11, t12 = t0 + t3, t0 - t3, t1 + t2, t1 - t2
+    t0, t1, t2, t3 = d[7], d[5], d[3], d[1]
+    z1, z2, z3, z4 = t0 + t3, t1 + t2, t0 + t2, t1 + t3
+    z5 = (z3 + z4) * 9633
+    t0, t1, t2, t3 = t0 * 2446, t1 * 16819, t2 * 25172, t3 * 12299
+    z1, z2, z3, z4 = z1 * -7373, z2 * -20995, z3 * -16069 + z5, z4 * -3196 + z5
+    t0, t1, t2, t3 = t0 + z1 + z3, t1 + z2 + z4, t2 + z2 + z3, t3 + z1 + z4
+    n = 11 if first else 18
+    return torch.stack([_jd(t10 + t3, n), _jd(t11 + t2, n), _jd(t12 + t1, n), _jd(t13 + t0, n),
+                        _jd(t13 - t0, n), _jd(t12 - t1, n), _jd(t11 - t2, n), _jd(t10 - t3, n)], dim)
+
+
+def _jpeg_plane(p: torch.Tensor, Q: torch.Tensor) -> torch.Tensor:
+    """An (N, 8a, 8b) int64 component plane through forward DCT, quantisation with the (N, 64) table ``Q``, dequantisation and
+    inverse DCT, block by block; returns the decoded samples 0 .. 255."""
+    N, Hp, Wp = p.shape
+    b = p.view(N, Hp // 8, 8, Wp // 8, 8).permute(0, 1, 3, 2, 4) - 128          # (N, block row, block column, row, column)
+    c = _jpeg_fdct8(_jpeg_fdct8(b, 4, True), 3, False)
+    Q = Q.view(N, 1, 1, 8, 8)
+    v = Q * 8
+    m = c.abs() + (v >> 1)
+    k = torch.where(m >= v, torch.div(m, v, rounding_mode="floor"), torch.zeros_like(m)) * c.sign()
+    s = _jpeg_idct8(_jpeg_idct8(k * Q, 3, True), 4, False)
+    return (s + 128).clamp(0, 255).permute(0, 1, 3, 2, 4).reshape(N, Hp, Wp)
+
+
+def _edge_pad(p: torch.Tensor, Hp: int, Wp: int) -> torch.Tensor:
+    """(N, H, W) -> (N, Hp, Wp) by replicating the last row and column."""
+    N, H, W = p.shape
+    r = torch.arange(Hp).clamp(max=H - 1)
+    c = torch.arange(Wp).clamp(max=W - 1)
+    return p[:, r][:, :, c]
+
+
+def _torch_jpeg(x: torch.Tensor, quality: torch.Tensor) -> torch.Tensor:
+    """The round trip in plain torch int64, vectorised over the batch and the blocks (CPU)."""
+    N, Cn, H, W = x.shape
+    k = (x * 255.0).round().clamp(0, 255).to(torch.int64)
+    Q = torch.stack([jpeg_tables(int(q)) for q in quality.tolist()])                   # (N, 2, 64)
+    Hp, Wp = -(-H // 8) * 8, -(-W // 8) * 8
+    if Cn == 1:
+        return (_jpeg_plane(_edge_pad(k[:, 0], Hp, Wp), Q[:, 0])[:, None, :H, :W].to(torch.float32) / 255).contiguous()
+    R, G, B = k[:, 0], k[:, 1], k[:, 2]
+    Y = (19595 * R + 38470 * G + 7471 * B + 32768) >> 16
+    Cb = (-11059 * R - 21709 * G + 32768 * B + (128 << 16) + 32767) >> 16
+    Cr = (32768 * R - 27439 * G - 5329 * B + (128 << 16) + 32767) >> 16
+    Y = _jpeg_plane(_edge_pad(Y, Hp, Wp), Q[:, 0])[:, :H, :W]
+    h2, w2 = -(-H // 2), -(-W // 2)
+    Hc, Wc = -(-h2 // 8) * 8, -(-w2 // 8) * 8
+    bias = torch.tensor([1, 2]).repeat(Wc // 2)
+    planes = []
+    for p in (Cb, Cr):
+        f = _edge_pad(p, 2 * h2, 2 * Wc)                                               # full resolution: columns to 2 Wc, rows to 2 h2
+        d = (f[:, 0::2, 0::2] + f[:, 0::2, 1::2] + f[:, 1::2, 0::2] + f[:, 1::2, 1::2] + bias) >> 2
+        d = _jpeg_plane(_edge_pad(d, Hc, Wc), Q[:, 1])[:, :h2, :w2]                    # ... then the rows of the small plane to Hc
+        planes.append(_jpeg_upsample(d)[:, :H, :W])
+    cb, cr = planes[0] - 128, planes[1] - 128
+    rgb = torch.stack([Y + ((91881 * cr + 32768) >> 16), Y + ((-22554 * cb - 46802 * cr + 32768) >> 16),
+                       Y + ((116130 * cb + 32768) >> 16)], 1).clamp(0, 255)
+    return (rgb.to(torch.float32) / 255).contiguous()
+
+
+def _jpeg_upsample(d: torch.Tensor) -> torch.Tensor:
+    """libjpeg's h2v2 fancy ("triangle") upsampling of an (N, h2, w2) plane to (N, 2 h2, 2 w2).  A plane of at most two columns
+    (an image of at most four) is replicated 2 x 2 instead: libjpeg picks its plain upsampler there (jdsample.c, jinit_upsampler:
+    ``do_fancy && compptr->downsampled_width > 2``)."""
+    N, h2, w2 = d.shape
+    if w2 <= 2:
+        return d.repeat_interleave(2, 1).repeat_interleave(2, 2)
+    y = torch.arange(2 * h2)
+    r = y // 2
+    rn = torch.where(y % 2 == 0, r - 1, r + 1).clamp(0, h2 - 1)
+    s = 3 * d[:, r] + d[:, rn]                                                         # (N, 2 h2, w2)
+    c = torch.arange(w2)
+    even = (3 * s + s[:, :, (c - 1).clamp(min=0)] + 8) >> 4
+    odd = (3 * s + s[:, :, (c + 1).clamp(max=w2 - 1)] + 7) >> 4
+    return torch.stack([even, odd], 3).reshape(N, 2 * h2, 2 * w2)

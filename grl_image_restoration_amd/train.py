@@ -18,6 +18,7 @@ Restates the pieces of the reference's training run that sit around ``model(x)``
     python -m grl_image_restoration_amd.train --task sr_bicubic --scale 2 --model small --geometry sr_ckpt_df4 --gt DIV2K/HR ...
     python -m grl_image_restoration_amd.train --task dn --sigma 25 --model small --geometry dn_df4 --gt DFWB --ckpt dn_grl_small_c3s25.ckpt ...
     python -m grl_image_restoration_amd.train --task dm --model small --geometry dm --gt DFWB ...
+    python -m grl_image_restoration_amd.train --task jpeg --quality 10 --model small --geometry jpeg --patch 288 --gt DFWB --val-gt LIVE1 ...
     python -m grl_image_restoration_amd.train --task db --blur-kernel real4 --blur-kernel-file Levin09.npy --model small \\
         --geometry dn_df4 --gt DFWB --val-gt Set5/original ...
 
@@ -93,13 +94,13 @@ def save_checkpoint(path: str, model, optimizer, step: int, sampler: D.PatchSamp
 def _parser():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--task", default="sr", choices=D.TASKS,
-                    help="sr: paired folders --lq / --gt; sr_bicubic, dn, dm, db: the LQ is made from --gt on the device")
+                    help="sr: paired folders --lq / --gt; sr_bicubic, dn, dm, db, jpeg: the LQ is made from --gt on the device")
     ap.add_argument("--gt", required=True, help="GT training folder")
     ap.add_argument("--lq", default=None, help="LQ training folder (--task sr)")
     ap.add_argument("--model", default="base", choices=["tiny", "small", "base"])
     ap.add_argument("--geometry", default="sr_ckpt_df2", help="a key of presets.GEOMETRIES")
     ap.add_argument("--depths", default=None, help="blocks per stage as a+b+c instead of the model size's (short experiments)")
-    ap.add_argument("--scale", type=int, default=None, help="4 by default for --task sr / sr_bicubic; 1 for dn / dm / db")
+    ap.add_argument("--scale", type=int, default=None, help="4 by default for --task sr / sr_bicubic; 1 for dn / dm / db / jpeg")
     ap.add_argument("--channels", type=int, default=3, choices=[1, 3])
     ap.add_argument("--upsampler", default=None, choices=["pixelshuffle", "pixelshuffledirect", "nearest+conv"])
     ap.add_argument("--ckpt", default=None, help="start weights (a reference checkpoint); random init without it")
@@ -119,6 +120,11 @@ def _parser():
                     help="--task db: gaussian (25 x 25, sigma 1.6) or real1 .. real8 (the Levin09 motion kernels, from --blur-kernel-file)")
     ap.add_argument("--blur-kernel-file", default=None,
                     help="--task db with real1 .. real8: the reference's utils/blur_kernels/Levin09.npy, or a 2-D .npy of that kernel")
+    ap.add_argument("--quality", type=int, default=None,
+                    help="--task jpeg: the JPEG quality factor, 1 .. 100; every training image is compressed whole, once.  With "
+                         "--quality-range it is the quality of validation only")
+    ap.add_argument("--quality-range", type=int, nargs=2, default=None, metavar=("LO", "HI"),
+                    help="--task jpeg: a quality per sample, drawn after the crop; the patches are compressed, not the images")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--val-gt", default=None)
     ap.add_argument("--val-lq", default=None)
@@ -148,11 +154,20 @@ def _check(ap, a):
             a.sigma = 2.0
     elif a.blur_kernel != "gaussian" or a.blur_kernel_file is not None:
         ap.error(f"--blur-kernel / --blur-kernel-file belong to --task db, not {a.task}")
+    if a.task == "jpeg":
+        if a.quality is None and a.quality_range is None:
+            ap.error("--task jpeg needs --quality or --quality-range")
+        if a.quality is not None and not 1 <= a.quality <= 100:
+            ap.error("--quality is 1 .. 100")
+        if a.quality_range is not None and not 1 <= a.quality_range[0] <= a.quality_range[1] <= 100:
+            ap.error("--quality-range is LO HI with 1 <= LO <= HI <= 100")
+    elif a.quality is not None or a.quality_range is not None:
+        ap.error(f"--quality / --quality-range belong to --task jpeg, not {a.task}")
     if a.task not in ("dn", "db") and (a.sigma is not None or a.sigma_range is not None):
         ap.error(f"--task {a.task} adds no noise; --sigma / --sigma-range are not used")
     if a.scale is None:
         a.scale = 4 if a.task in ("sr", "sr_bicubic") else 1
-    if a.task in ("dn", "dm", "db") and a.scale != 1:
+    if a.task in ("dn", "dm", "db", "jpeg") and a.scale != 1:
         ap.error(f"--task {a.task} restores at --scale 1")
     if a.task == "sr_bicubic" and a.scale < 2:
         ap.error("--task sr_bicubic needs a --scale above 1")
@@ -167,6 +182,8 @@ def _check(ap, a):
             ap.error("--task sr validates on --val-lq / --val-gt")
         if a.task == "dn" and a.sigma is None:
             ap.error("validation of --task dn needs a fixed --sigma")
+        if a.task == "jpeg" and a.quality is None:
+            ap.error("validation of --task jpeg needs --quality next to --quality-range")
     if a.task != "sr" and a.val_lq is not None:
         ap.error(f"--task {a.task} builds its validation LQ from --val-gt; --val-lq is not used")
     if a.save_every and a.out is None:
@@ -231,7 +248,8 @@ def main(argv: Optional[List[str]] = None):
     gt_store = D.PatchStore.from_folder(a.gt, a.channels, device)
     lq_store = D.PatchStore.from_folder(a.lq, a.channels, device) if a.task == "sr" else None
     sampler = D.PatchSampler(a.task, gt_store, lq_store, patch=a.patch, batch=a.batch, scale=a.scale, sigma=a.sigma,
-                             sigma_range=a.sigma_range, seed=a.seed + rank, taps=taps)
+                             sigma_range=a.sigma_range, seed=a.seed + rank, taps=taps,
+                             quality=a.quality if a.quality_range is None else None, quality_range=a.quality_range)
 
     opt = FusedAdamW(model.parameters(), lr=a.lr, weight_decay=a.weight_decay)
     start = 0
@@ -285,7 +303,7 @@ def main(argv: Optional[List[str]] = None):
             model.eval()
             with torch.no_grad():
                 v = evaluate_folder(model, a.val_lq, a.val_gt, a.scale, device=a.device, verbose=False, metric_group=a.metric,
-                                    channels=a.channels, task=a.task, sigma=a.sigma, taps=taps)
+                                    channels=a.channels, task=a.task, sigma=a.sigma, taps=taps, quality=a.quality)
             model.train()
             out["val"].append((done, v))
             print(f"step {n:8d}  validation {v}", flush=True)

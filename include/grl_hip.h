@@ -23,7 +23,7 @@ extern "C" {
 
 #define GRL_ERR_BAD_ARG (-1)
 #define GRL_ERR_UNSUPPORTED (-2)
-#define GRL_ABI_VERSION 28
+#define GRL_ABI_VERSION 29
 
 /* element kinds of activation / weight buffers */
 enum { GRL_DT_F32 = 0, GRL_DT_BF16 = 1, GRL_DT_F16 = 2 };
@@ -861,6 +861,32 @@ typedef struct GrlBlurArgs {
 } GrlBlurArgs;
 
 int grl_blur_depthwise(void* stream, const GrlBlurArgs* args);
+
+/* JPEG compression and decompression of an image batch (ABI 29; the LQ synthesis of JPEG artifact removal, data module `jpeg`):
+ *   replaces  cv2.imencode(".jpg", img, [cv2.IMWRITE_JPEG_QUALITY, q]) + cv2.imdecode   data/datasets/restoration_jpeg.py:62-79
+ * The entropy coding is lossless and left out; everything else is libjpeg's integer arithmetic with the defaults that OpenCV and
+ * Pillow use (4:2:0 chroma, JDCT_ISLOW, baseline tables of jpeg_set_quality, fancy upsampling), restated in int32 bit for bit:
+ * RGB -> YCbCr, edge replication to whole blocks, 2 x 2 chroma averaging, forward DCT, quantisation, dequantisation, inverse DCT,
+ * triangle-filter chroma upsampling (plain replication for images of at most four columns, as libjpeg), YCbCr -> RGB.
+ * x: contiguous fp32 (N, C, H, W), C = 3 (RGB) or 1 (gray), values k / 255; the kernel takes k = rint(255 x) clamped to 0 .. 255.
+ * quality: [N] int32 in DEVICE memory, one per sample, clamped to 1 .. 100 as libjpeg clamps it.  The kernel reads it when it runs:
+ * a captured call stays valid while the qualities change.
+ * workspace: grl_jpeg_workspace_bytes(N, C, H, W) bytes, 8-byte aligned, no initialisation: the decoded 8-bit component planes (Y at
+ * 8 ceil(H / 8) x 8 ceil(W / 8); Cb and Cr at 8 ceil(ceil(H / 2) / 8) x 8 ceil(ceil(W / 2) / 8)).
+ * out: contiguous fp32 (N, C, H, W); every value is float(v) / 255 by IEEE division (bitwise to_tensor, as grl_sample_patches).
+ * Two launches on `stream` (the block pass and the merge pass); no allocation, no synchronisation.
+ * Errors (GRL_ERR_BAD_ARG): a null pointer, C not 1 / 3, a non-positive N, H or W, x / out / quality not 4-byte or workspace not
+ * 8-byte aligned, a grid beyond 2^31 - 1 workgroups.  grl_jpeg_workspace_bytes returns GRL_ERR_BAD_ARG for such sizes. */
+typedef struct GrlJpegArgs {
+    const float* x;             /* (N, C, H, W)                                                   */
+    const int32_t* quality;     /* [N] device                                                     */
+    int32_t N, C, H, W;
+    void* workspace;            /* grl_jpeg_workspace_bytes(N, C, H, W) bytes                     */
+    float* out;                 /* (N, C, H, W)                                                   */
+} GrlJpegArgs;
+
+int64_t grl_jpeg_workspace_bytes(int32_t N, int32_t C, int32_t H, int32_t W);
+int grl_jpeg_roundtrip(void* stream, const GrlJpegArgs* args);
 
 /* Debug aid (ABI 21; no reference counterpart): fills the LDS of every CU with 0xFF bytes (fp32 / fp16 NaN) by a launch on
  * `stream`.  LDS keeps what the previous workgroup left in it; a kernel that reads LDS it has not written is otherwise right or
