@@ -19,7 +19,13 @@
 //   * a weight that reaches 2^14 leaves the statement BEFORE the row's PV product; the offsets of the queries
 //     concerned are raised from the exact row maximum (compiler-generated cold code), O is rescaled and the row is
 //     redone; the maxima are taken over the rest of the chunk (round 4), so a chunk trips at most once.  The offsets start at
-//     the logit floor: the first chunk of a wave goes through the same code before its first row ("prime").
+//     the logit floor: the first chunk of a wave goes through the same code before its first row ("prime");
+//   * round 7, fewer trips at checkpoint-like scales without any added work: an offset move leaves the row maximum in
+//     (2^-3, 2^-2] (was (2^3, 2^4]): 16 binades under the 2^14 test instead of 10 -- weights under 2^-14 are fp16 sub-normals,
+//     which converts, MFMA and v_dot2c keep (ROWS_REST below) -- and a workgroup starts at the chunk that holds the key rows
+//     nearest to its queries, then wraps cyclically, so that the prime pass sees the keys its queries attend to most.
+//     tools/attn_trip_model.py replays both choices on the bench network: trips per wave 3.9 / 2.4 / 6.0 -> 1.9 / 0.7 / 3.0
+//     (window / tokens->anchors / anchors->tokens); profiles/r07_attention_trips.txt.
 // Timing-ablation switches of this file compute WRONG results by construction (they remove work to see what it costs).  They only
 // build together with -DGRL_ABLATION, which tools/attn_asm/build_variants_generic.sh passes for its throw-away variant libraries.
 #if !defined(GRL_ABLATION) && (defined(ROWS_ABL_NOBARRIER) || defined(ROWS_ABL_NODMA) || defined(ROWS_ABL_REPEAT))
@@ -42,8 +48,23 @@ constexpr int TBUF = 4096;            // bytes of one table-window buffer
 constexpr int TBUF_D32 = 8192;        // ... of the head_dim-32 instance (dn geometry: 16x32 anchors against 64x128 stripes need 6.6 KB)
 constexpr int rows_tbuf(bool d32) { return d32 ? TBUF_D32 : TBUF; }
 constexpr int rows_lds(bool d32) { return 4 * KBUF + 2 * rows_tbuf(d32); }
-constexpr float ROWS_REST = 4.0f;     // after an offset move the row maximum sits in (2^3, 2^4]
-constexpr float ROWS_EXTRA = 3.0f;    // ... unless up to this much more reaches the level where the overflow test can go (msafe)
+// Resting level (round 7): after an offset move the row maximum sits in (2^(ROWS_REST-1), 2^ROWS_REST], i.e. 14 - ROWS_REST binades
+// under the overflow test.  Weights under 2^-14 are fp16 sub-normals: the kernel runs with the compiler's default float mode
+// (fp16 denormals kept), v_cvt_pk_f16_f32 rounds into them and the fp16 MFMA / v_dot2c_f32_f16 read them as they are
+// (tests/test_gpu_attention_trips.py::test_denormal_weights), so below 2^-14 a weight has an ABSOLUTE error of 2^-25 instead of
+// a relative one of 2^-11.  Bound of what that costs: 1024 keys all rounding the same way move the denominator by 2^-15, so
+// the lowest level a row maximum may rest at is -3, i.e. in (2^-4, 2^-3]: at most 2^-11 = 4.9e-4 of the denominator, a third of
+// the tests' tolerance (random signs: 32 x less).  ROWS_REST - ROWS_EXTRA is that lowest level.
+// (-DROWS_REST_LEVEL / -DROWS_EXTRA_LEVEL / -DROWS_ORDER_TOP: the variant builds behind profiles/r07_attention_trips.txt.)
+#ifndef ROWS_REST_LEVEL
+#define ROWS_REST_LEVEL (-2)
+#endif
+#ifndef ROWS_EXTRA_LEVEL
+#define ROWS_EXTRA_LEVEL (ROWS_REST_LEVEL + 3 > 3 ? 3 : ROWS_REST_LEVEL + 3)
+#endif
+constexpr float ROWS_REST = (float)(ROWS_REST_LEVEL);
+constexpr float ROWS_EXTRA = (float)(ROWS_EXTRA_LEVEL);   // an offset this close under msafe (overflow test no longer needed) goes straight there
+static_assert(ROWS_EXTRA_LEVEL >= 0 && ROWS_REST_LEVEL - ROWS_EXTRA_LEVEL >= -3 && ROWS_REST_LEVEL <= 8, "resting level outside what the fp16 weights allow");
 
 struct RowsGeom {
     int qseg, units, upw, nqs;
@@ -209,7 +230,19 @@ __global__ __launch_bounds__(RW * 64, D32 ? 3 : 4) void attn_rows_kernel(GrlAttn
     __builtin_amdgcn_s_sleep(1);
     for (int i_ = 0; i_ < (int)(blockIdx.x >> 3 & 3) * 4; ++i_) __builtin_amdgcn_s_sleep(8);   // experiment: de-phase the workgroups of a CU
 #endif
-    prefetch(0, 0, 0);
+    // Chunk order (round 7): start at the chunk that holds the key rows nearest to the workgroup's queries (centre of its query rows
+    // and segments mapped to key coordinates: the same rows for window attention, x df / : df between anchors and tokens), then
+    // cyclically over (sk, hk0).  The prime pass takes the offsets from the first chunk, and the keys a query attends to most are
+    // the ones around it: fewer later chunks exceed what the first one set.  ROWS_ORDER_TOP: the old order, (0, 0) upward.
+    int sk_s = 0, hk_s = 0;
+#ifndef ROWS_ORDER_TOP
+    {
+        const int rc = ((hqa + hqb + 1) * p.k.wh) / (2 * p.q.wh * RROWS), sc = ((sga + sgb + 1) * p.k.ww) / (2 * p.q.ww);
+        hk_s = __builtin_amdgcn_readfirstlane(RROWS * (rc < nrc ? rc : nrc - 1));
+        sk_s = __builtin_amdgcn_readfirstlane(sc < (p.k.ww >> 5) ? sc : (p.k.ww >> 5) - 1);
+    }
+#endif
+    prefetch(sk_s, hk_s, 0);
 
     // lane parts of the LDS addresses.  K fragment of key l31 of a row: 16-B segment (2 * kstep + half) ^ sw of its 64-B row
     // (k-step 1: ^ 32, inside the statement); V^T through ds_read_b64_tr_b16; bias of (tile 0, key row): table entry
@@ -231,7 +264,7 @@ __global__ __launch_bounds__(RW * 64, D32 ? 3 : 4) void attn_rows_kernel(GrlAttn
     int poison = 0;  // wave-uniform: a row kept tripping (non-finite logits): the outputs of this wave's queries become NaN
     auto chunks = [&](auto border_tag) {
     constexpr bool BORDER = decltype(border_tag)::value;
-    int sk = 0, hk0 = 0;
+    int sk = sk_s, hk0 = hk_s;
     int nochk = 0;   // wave-uniform: every query's offset is within 13.5 of the head's logit bound, no weight can reach 2^14 any more
     DBG_T(t_loop);
     DBG_ADD(0, t_loop - t_start);
@@ -248,7 +281,7 @@ __global__ __launch_bounds__(RW * 64, D32 ? 3 : 4) void attn_rows_kernel(GrlAttn
         DBG_ADD(2, t_c2 - t_c1);
         const int sk_c = sk, hk_c = hk0;
         hk0 += RROWS;
-        if (hk0 == p.k.wh) { hk0 = 0; ++sk; }
+        if (hk0 == p.k.wh) { hk0 = 0; ++sk; if (sk == (p.k.ww >> 5)) sk = 0; }
 #ifndef ROWS_ABL_NODMA
         if (ch + 1 < nch) prefetch(sk, hk0, (ch + 1) & 1);
 #endif
@@ -368,7 +401,7 @@ __global__ __launch_bounds__(RW * 64, D32 ? 3 : 4) void attn_rows_kernel(GrlAttn
                 float d0 = fmaxf(0.f, __builtin_ceilf(mx0) - ROWS_REST), d1 = fmaxf(0.f, __builtin_ceilf(mx1) - ROWS_REST);
                 {
                     // offsets within ROWS_EXTRA of the level where the overflow test becomes unnecessary go there right away
-                    // (the row maximum then rests at 2^(ROWS_REST - ROWS_EXTRA) at worst: ample for fp16 weights)
+                    // (the row maximum then rests at 2^(ROWS_REST - ROWS_EXTRA) = 2^-3 at worst: the lowest level derived at ROWS_REST)
                     const float msafe = (float)msafe_i;
                     float m0, m1;   // the new offsets
                     if constexpr (D32) {
