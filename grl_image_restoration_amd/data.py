@@ -26,7 +26,8 @@ from typing import List, Optional, Sequence
 import numpy as np
 import torch
 
-TASKS = ("sr", "sr_bicubic", "dn", "dm", "db", "jpeg")
+from .task_rules import TRAIN_TASKS as TASKS, resolve
+
 FLIP_ROWS, FLIP_COLS, SWAP_AXES = 1, 2, 4
 
 
@@ -139,35 +140,17 @@ class PatchStore:
 
 
 class PatchSampler:
-    """(lq, gt) training batches of a task from PatchStores.
+    """(lq, gt) training batches of a task from PatchStores.  The tasks, what each accepts and its defaults:
+    ``task_rules.RULES`` (``scale`` is the SR factor, 1 for the tasks that restore at scale 1).  How each LQ is made:
 
-    Tasks (``scale`` is the SR factor, 1 for dn / dm):
-      sr          paired stores: LQ patch ``patch``, GT patch ``patch * scale`` at the same place (restoration_sr.py:97-123 with
-                  ``load_lr``); every GT image is ``scale`` times its LQ image
-      sr_bicubic  GT store only.  The LQ store is made once per image at construction: ``tasks.modcrop`` to the scale, then
-                  ``tasks.sr_lq`` (MATLAB bicubic, 8-bit quantised) on the store's device; the GT store is replaced by the cropped
-                  images; then sampled as ``sr``.  This is the QUANTISED LQ -- what an offline LR folder holds and what validation
-                  scores -- not the float LQ that restoration_sr.py:130-141 resizes per item without rounding
-      dn          ``lq = gt + sigma / 255 * randn`` from a ``torch.Generator`` on the store's device seeded with ``seed``; sigma is
-                  ``sigma``, or drawn per sample from ``sigma_range`` (restoration_dn.py:126-143, the training branch)
-      dm          ``lq = tasks.demosaic_gt(gt)`` (RGB, even ``patch``)
-      db          non-blind deblurring (RGB).  With ``taps`` the (K, K) table of ``tasks.blur_taps``, the draws and the crop use the
-                  reference's enlarged patch P' = ``patch`` + K - 1 (restoration_db.py:19-21), so the zero padding of small images
-                  follows P' as well; then ONE ``tasks.blur`` launch over the valid region gives ``lq`` at ``patch``, with the
-                  noise added by the kernel, and ``gt`` as the centre crop of the P' patch (engines/base.py:131-142: blur with
-                  padding, then cut K // 2 from every side of input and target).  The noise is ``sigma / 255 * randn`` (``sigma``
-                  defaults to 2, db.yaml:8) at ``patch`` x ``patch`` from the sampler's seeded ``torch.Generator``, as for dn.  The
-                  reference draws its training noise from the unseeded ``np.random`` at P' x P' and crops it, so there is no
-                  stream to reproduce bit for bit; the distribution is the same
-
-      jpeg        JPEG artifact removal (restoration_jpeg.py:30-46), RGB or gray.  With a fixed ``quality`` (the reference's default,
-                  ``patchwise: False``) every image of the GT store is compressed WHOLE, once, at construction
-                  (``tasks.jpeg_roundtrip`` on the store's device) into an 8-bit LQ store, and the pair is sampled as ``sr`` at scale
-                  1: patches sit at arbitrary phases of the 8 x 8 block grid, and small images are zero padded after compression.
-                  With ``quality_range`` = (lo, hi) (``patchwise: True``) the GT patch is cropped and augmented first, a quality is
-                  drawn per sample, and ONE ``tasks.jpeg_roundtrip`` call compresses the batch of patches; the qualities sit in the
-                  sampler's own device tensor ``qualities``, so a captured step replays the call while they change.  Whole-image
-                  compression at a quality per sample is not built: it would recompress a whole image for every sample
+      sr          paired stores: LQ patch ``patch``, GT patch ``patch * scale`` at the same place; every GT image is ``scale`` times
+                  its LQ image
+      sr_bicubic, jpeg at a fixed ``quality``
+                  GT store only.  The LQ store is made once per image at construction (``tasks.TRAIN_STORE_LQ`` on the store's
+                  device; sr_bicubic also replaces the GT store by the images cropped to the scale); then sampled as ``sr``
+      dn, dm, db, jpeg with ``quality_range``
+                  from the sampled GT batch (``tasks.TRAIN_PAIR``).  db (``taps``: the (K, K) table of ``tasks.blur_taps``) draws and
+                  crops at the enlarged patch ``patch`` + K - 1; whole-image compression at a quality per sample is not built
 
     Draws, from ``random.Random(seed)``, per sample and in this order: ``randrange(N)`` for the image; ``randrange(H' - P + 1)``
     and ``randrange(W' - P + 1)`` with H' = max(H, P), W' = max(W, P) the LQ-side size after the reference's padding
@@ -179,53 +162,19 @@ class PatchSampler:
                  scale: int = 1, sigma: Optional[float] = None, sigma_range: Optional[Sequence[float]] = None, seed: int = 0,
                  taps: Optional[torch.Tensor] = None, quality: Optional[int] = None,
                  quality_range: Optional[Sequence[int]] = None, patchwise: bool = True):
-        if task not in TASKS:
-            raise ValueError(f"unknown task {task!r}: one of {TASKS}")
+        from . import tasks
+
         patch, batch, scale = int(patch), int(batch), int(scale)
         if patch < 1 or batch < 1:
             raise ValueError(f"patch and batch must be positive, got {patch}, {batch}")
-        if task in ("dn", "dm", "db", "jpeg") and scale != 1:
-            raise ValueError(f"task {task} restores at scale 1, got {scale}")
-        if task in ("sr", "sr_bicubic") and scale < (2 if task == "sr_bicubic" else 1):
-            raise ValueError(f"task {task}: bad scale {scale}")
-        if task == "sr" and lq_store is None:
-            raise ValueError("task sr needs an LQ store")
-        if task != "sr" and lq_store is not None:
-            raise ValueError(f"task {task} builds its LQ from the GT store; an LQ store is not used")
-        if task == "dn" and (sigma is None) == (sigma_range is None):
-            raise ValueError("task dn needs sigma or sigma_range (one of them)")
-        if task == "db":
-            if taps is None or taps.dim() != 2 or taps.shape[0] != taps.shape[1] or taps.shape[0] % 2 == 0 or taps.shape[0] > 31:
-                raise ValueError("task db needs taps: the (K, K) fp32 table of tasks.blur_taps, K odd and at most 31")
-            if sigma_range is not None:
-                raise ValueError("task db adds noise at one fixed sigma")
-            if gt_store.channels != 3:
-                raise ValueError("task db works on RGB patches")
-            sigma = 2.0 if sigma is None else float(sigma)
-        elif taps is not None:
-            raise ValueError(f"task {task} does not blur; taps are not used")
-        if task not in ("dn", "db") and (sigma is not None or sigma_range is not None):
-            raise ValueError(f"task {task} adds no noise")
-        if task == "jpeg":
-            if (quality is None) == (quality_range is None):
-                raise ValueError("task jpeg needs quality or quality_range (one of them)")
-            if quality_range is not None:
-                if not patchwise:
-                    raise ValueError("task jpeg with a quality per sample compresses the cropped patches (patchwise); whole-image "
-                                     "compression would recompress an image for every sample and is not built")
-                quality_range = tuple(int(v) for v in quality_range)
-                if len(quality_range) != 2 or not 1 <= quality_range[0] <= quality_range[1] <= 100:
-                    raise ValueError(f"task jpeg: quality_range is (lo, hi) with 1 <= lo <= hi <= 100, got {quality_range}")
-            elif not 1 <= int(quality) <= 100:
-                raise ValueError(f"task jpeg: quality is 1 .. 100, got {quality}")
-        elif quality is not None or quality_range is not None:
-            raise ValueError(f"task {task} does not compress; quality / quality_range are not used")
-        if task == "dm" and (gt_store.channels != 3 or patch % 2 or patch < 4):
-            raise ValueError("task dm works on RGB patches with an even side of at least 4")
-        if task == "sr_bicubic":
-            gt_store, lq_store = _bicubic_stores(gt_store, scale)
-        if task == "jpeg" and quality is not None:
-            lq_store = _jpeg_store(gt_store, int(quality))
+        o = resolve(task, "sampler", scale=scale, channels=gt_store.channels, lq=lq_store is not None, sigma=sigma,
+                    sigma_range=sigma_range, taps=taps is not None, quality=quality, quality_range=quality_range, patch=patch,
+                    patchwise=patchwise)
+        if taps is not None and (taps.dim() != 2 or taps.shape[0] != taps.shape[1] or taps.shape[0] % 2 == 0 or taps.shape[0] > 31):
+            raise ValueError("taps: the (K, K) fp32 table of tasks.blur_taps, K odd and at most 31")
+        store_lq = tasks.TRAIN_STORE_LQ.get(task) if o.quality_range is None else None
+        if store_lq is not None:
+            gt_store, lq_store = _derived_stores(gt_store, lambda gt: store_lq(gt, o), scale if o.rule.crop == "scale" else 1)
         if lq_store is not None:
             if len(lq_store) != len(gt_store) or lq_store.channels != gt_store.channels or lq_store.device != gt_store.device:
                 raise ValueError("task sr: the two stores need the same number of images, channel count and device")
@@ -234,16 +183,17 @@ class PatchSampler:
                     raise ValueError(f"task sr: image {n} is {h} x {w} (LQ) and {H} x {W} (GT), not a x{scale} pair")
         self.task, self.gt_store, self.lq_store = task, gt_store, lq_store
         self.patch, self.batch, self.scale = patch, batch, scale
-        self.sigma, self.sigma_range = sigma, (tuple(float(v) for v in sigma_range) if sigma_range is not None else None)
-        self.quality, self.quality_range = (int(quality) if quality is not None else None), quality_range
+        self.sigma, self.sigma_range = o.sigma, (tuple(float(v) for v in sigma_range) if sigma_range is not None else None)
+        self.quality, self.quality_range = o.quality, o.quality_range
         self.rng = random.Random(seed)
         self.device = gt_store.device
-        self.gen = torch.Generator(device=self.device).manual_seed(int(seed)) if task in ("dn", "db") else None
-        self.taps = taps.to(device=self.device, dtype=torch.float32).contiguous() if task == "db" else None
-        self.draw_patch = patch + (self.taps.shape[0] - 1 if task == "db" else 0)      # the side the draws and the crop use
+        self.gen = torch.Generator(device=self.device).manual_seed(int(seed)) if o.rule.noise else None
+        self.taps = taps.to(device=self.device, dtype=torch.float32).contiguous() if taps is not None else None
+        self.draw_patch = patch + (self.taps.shape[0] - 1 if taps is not None else 0)   # the side the draws and the crop use
         self.work = torch.zeros(batch, 4, dtype=torch.int32, device=self.device)      # the device work list, rewritten in place
         # the device quality list of jpeg with a range, rewritten in place like the work list
         self.qualities = torch.zeros(batch, dtype=torch.int32, device=self.device) if quality_range is not None else None
+        self._pair = tasks.TRAIN_PAIR.get(task)
 
     # ---- draws ---------------------------------------------------------------------------------------------------------------
     def draw(self):
@@ -284,51 +234,21 @@ class PatchSampler:
         if torch.is_tensor(work):
             wt = work.to(device=self.device, dtype=torch.int32).contiguous()
         else:
-            wt = torch.tensor([list(w) for w in work], dtype=torch.int32).reshape(-1, 4)
-            if wt.shape == self.work.shape:          # the sampler's own list, in place: a captured launch reads this address
-                self.work.copy_(wt)
-                wt = self.work
-            else:
-                wt = wt.to(self.device)
-        B = wt.shape[0]
-        if self.lq_store is not None:                # sr, and sr_bicubic / jpeg at a fixed quality after their stores were made
+            wt = self.in_place(self.work, torch.tensor([list(w) for w in work], dtype=torch.int32).reshape(-1, 4))
+        if self.lq_store is not None:                # paired stores, given or made at construction
             lq = self.lq_store.sample(wt, self.patch, 1)
             gt = self.gt_store.sample(wt, self.patch, self.scale)
             return lq, gt
-        gt = self.gt_store.sample(wt, self.draw_patch, 1)
-        if self.task == "db":
-            from . import tasks
+        return self._pair(self, self.gt_store.sample(wt, self.draw_patch, 1), sigmas, noise)
 
-            shape = (B, 3, self.patch, self.patch)
-            if noise is None:
-                noise = torch.randn(shape, generator=self.gen, device=self.device, dtype=torch.float32)
-            elif tuple(noise.shape) != shape or noise.dtype != torch.float32:
-                raise ValueError(f"db noise: an fp32 tensor of shape {shape}")
-            return tasks.blur(gt, self.taps, "valid", add=noise.to(self.device) * (self.sigma / 255), want_center=True)
-        if self.task == "dm":
-            from . import tasks
-
-            return tasks.demosaic_gt(gt), gt
-        if self.task == "jpeg":
-            from . import tasks
-
-            if sigmas is None or len(sigmas) != B:
-                raise ValueError("jpeg with a quality range: one quality per sample of an explicit work list")
-            q = torch.tensor([int(v) for v in sigmas], dtype=torch.int32)
-            if q.shape == self.qualities.shape:       # the sampler's own list, in place: a captured call reads this address
-                self.qualities.copy_(q)
-                q = self.qualities
-            else:
-                q = q.to(self.device)
-            return tasks.jpeg_roundtrip(gt, q), gt
-        if self.sigma_range is not None:
-            if sigmas is None or len(sigmas) != B:
-                raise ValueError("dn with a sigma range: one sigma per sample of an explicit work list")
-            level = torch.tensor(list(sigmas), dtype=torch.float32).view(B, 1, 1, 1).to(self.device) / 255
-        else:
-            level = self.sigma / 255
-        noise = torch.randn(gt.shape, generator=self.gen, device=self.device, dtype=torch.float32)
-        return gt + noise * level, gt
+    @staticmethod
+    def in_place(own: torch.Tensor, t: torch.Tensor) -> torch.Tensor:
+        """``t`` (CPU) written into the sampler's own device list ``own`` when the shapes match -- a captured launch reads that
+        address -- else moved to its device."""
+        if t.shape == own.shape:
+            own.copy_(t)
+            return own
+        return t.to(own.device)
 
 
 def _as_rng_state(s):
@@ -336,32 +256,20 @@ def _as_rng_state(s):
     return (s[0], tuple(s[1]), s[2])
 
 
-def _bicubic_stores(gt_store: PatchStore, scale: int):
-    """(cropped GT store, LQ store) for sr_bicubic: per image ``tasks.sr_lq`` of the GT cropped to a multiple of ``scale``, on the
-    store's device, rounded back to 8 bit (``sr_lq`` returns k / 255 exactly)."""
+def _derived_stores(gt_store: PatchStore, degrade, crop: int = 1):
+    """(GT store, LQ store) of a task whose LQ is made once per image: every image of the GT store, cropped to a multiple of
+    ``crop``, through ``degrade`` as a whole on the store's device, and back to 8 bit (the front ends return k / 255 exactly).
+    With a crop the GT store is replaced by the cropped images."""
     from . import tasks
 
     gts: List[torch.Tensor] = []
     lqs: List[torch.Tensor] = []
     for n in range(len(gt_store)):
         img = gt_store.image(n)
-        gt = tasks.modcrop(img.permute(2, 0, 1).unsqueeze(0), scale)
-        if gt.shape[-2] < scale or gt.shape[-1] < scale:
-            raise ValueError(f"sr_bicubic: image {n} ({img.shape[0]} x {img.shape[1]}) is smaller than the scale")
-        lq, _ = tasks.sr_lq(gt.to(torch.float32).div(255).contiguous(), scale)
+        gt = tasks.modcrop(img.permute(2, 0, 1).unsqueeze(0), crop)
+        if gt.shape[-2] < crop or gt.shape[-1] < crop:
+            raise ValueError(f"image {n} ({img.shape[0]} x {img.shape[1]}) is smaller than the scale")
+        lq = degrade(gt.to(torch.float32).div(255).contiguous())
         lqs.append((lq[0] * 255).round().to(torch.uint8).permute(1, 2, 0).contiguous().cpu())
         gts.append(gt[0].permute(1, 2, 0).contiguous().cpu())
-    return PatchStore(gts, gt_store.device), PatchStore(lqs, gt_store.device)
-
-
-def _jpeg_store(gt_store: PatchStore, quality: int) -> PatchStore:
-    """The LQ store of jpeg at a fixed quality: every image of the GT store through ``tasks.jpeg_roundtrip`` as a whole, on the
-    store's device, back to 8 bit (the round trip returns k / 255 exactly)."""
-    from . import tasks
-
-    lqs: List[torch.Tensor] = []
-    for n in range(len(gt_store)):
-        gt = gt_store.image(n).permute(2, 0, 1).unsqueeze(0).to(torch.float32).div(255).contiguous()
-        lq = tasks.jpeg_roundtrip(gt, quality)
-        lqs.append((lq[0] * 255).round().to(torch.uint8).permute(1, 2, 0).contiguous().cpu())
-    return PatchStore(lqs, gt_store.device)
+    return (PatchStore(gts, gt_store.device) if crop > 1 else gt_store), PatchStore(lqs, gt_store.device)

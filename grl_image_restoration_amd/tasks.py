@@ -26,6 +26,9 @@
   jpeg_roundtrip     data/datasets/restoration_jpeg.py:62-79   the JPEG artifact-removal LQ: ``cv2.imencode(".jpg", img, [IMWRITE_JPEG_QUALITY,
                                                     q])`` followed by ``cv2.imdecode``, restated as libjpeg's integer arithmetic (the
                                                     entropy coding is lossless and left out)
+  VAL_LQ, TRAIN_STORE_LQ, TRAIN_PAIR                the LQ of each task from the front ends above, per side: a validation image, a
+                                                    training store made once, a training batch (at the end of the module; what a
+                                                    task accepts is ``task_rules.RULES``)
 
 CUDA fp32 tensors go through ``grl_demosaic_matlab`` of libgrl_hip.so (csrc/demosaic.hip); there is no torch fallback for them.
 ``demosaic_gt`` on CUDA is a single launch that reads the RGB image in place on the RGGB lattice, without forming the mosaic.  CPU
@@ -653,3 +656,78 @@ def _jpeg_upsample(d: torch.Tensor) -> torch.Tensor:
     even = (3 * s + s[:, :, (c - 1).clamp(min=0)] + 8) >> 4
     odd = (3 * s + s[:, :, (c + 1).clamp(max=w2 - 1)] + 7) >> 4
     return torch.stack([even, odd], 3).reshape(N, 2 * h2, 2 * w2)
+
+
+# ---- the LQ of each task: validation images, training stores, training batches ----------------------------------------------------
+# Validation (``evaluate.task_inputs``): (gt (1, C, H, W) on the CPU, already cropped by the rule; file name; the options resolved by
+# ``task_rules.resolve`` plus ``taps`` and ``noise_prefix``; device) -> lq.
+def _dn_val_lq(gt, name, o, device):
+    """The reference's seeded validation noise, keyed by ``<test set>/<file name>``; on the CPU, in fp32, as the data set does."""
+    return gt + dn_noise(gt.shape[1:], o.sigma, dn_noise_key(f"{o.noise_prefix}/{name}")).unsqueeze(0)
+
+
+def _db_val_lq(gt, name, o, device):
+    """Blurred on ``device`` with zero padding; the noise (seeded 0 for every image) is made on the CPU and added by the blur kernel."""
+    return db_lq(gt.to(device), o.taps, db_noise(gt.shape[1:], o.sigma).unsqueeze(0).to(device))
+
+
+VAL_LQ = {
+    "dn": _dn_val_lq,
+    "dm": lambda gt, name, o, device: demosaic_gt(gt.to(device)),
+    "sr_bicubic": lambda gt, name, o, device: sr_lq(gt.to(device), int(o.scale))[0],
+    "db": _db_val_lq,
+    "jpeg": lambda gt, name, o, device: jpeg_roundtrip(gt.to(device), o.quality),
+}
+
+# Training, once per image at construction (``data.PatchSampler``): (gt (1, C, H, W) fp32 on the store's device, cropped by the rule;
+# the sampler's resolved options) -> lq of 8-bit levels, kept as an 8-bit LQ store and then sampled like a paired folder.
+#   sr_bicubic  the QUANTISED LQ -- what an offline LR folder holds and what validation scores -- not the float LQ that
+#               restoration_sr.py:130-141 resizes per item without rounding
+#   jpeg        at a fixed quality (the reference's default, ``patchwise: False``) every image is compressed WHOLE: patches sit at
+#               arbitrary phases of the 8 x 8 block grid, and small images are zero padded after compression
+TRAIN_STORE_LQ = {
+    "sr_bicubic": lambda gt, o: sr_lq(gt, o.scale)[0],
+    "jpeg": lambda gt, o: jpeg_roundtrip(gt, o.quality),
+}
+
+
+# Training, per batch: (the sampler ``s``; gt (B, C, draw_patch, draw_patch); the per-sample draws or None; ``noise`` of ``next``)
+# -> (lq, gt).
+def _dn_pair(s, gt, sigmas, noise):
+    """``lq = gt + sigma / 255 * randn`` from the sampler's seeded generator; sigma fixed, or one per sample from the sigma range
+    (restoration_dn.py:126-143, the training branch)."""
+    if s.sigma_range is not None:
+        if sigmas is None or len(sigmas) != gt.shape[0]:
+            raise ValueError("dn with a sigma range: one sigma per sample of an explicit work list")
+        level = torch.tensor(list(sigmas), dtype=torch.float32).view(-1, 1, 1, 1).to(s.device) / 255
+    else:
+        level = s.sigma / 255
+    noise = torch.randn(gt.shape, generator=s.gen, device=s.device, dtype=torch.float32)
+    return gt + noise * level, gt
+
+
+def _db_pair(s, gt, sigmas, noise):
+    """``gt`` comes at the reference's enlarged patch P' = patch + K - 1 (restoration_db.py:19-21), so the zero padding of small
+    images follows P' as well; ONE ``blur`` launch over the valid region gives ``lq`` at ``patch`` with the noise added by the
+    kernel, and the target as the centre crop (engines/base.py:131-142).  The noise is ``sigma / 255 * randn`` at patch x patch from
+    the sampler's generator, or ``noise`` scaled the same way.  The reference draws its training noise from the unseeded
+    ``np.random`` at P' x P' and crops it, so there is no stream to reproduce bit for bit; the distribution is the same."""
+    shape = (gt.shape[0], 3, s.patch, s.patch)
+    if noise is None:
+        noise = torch.randn(shape, generator=s.gen, device=s.device, dtype=torch.float32)
+    elif tuple(noise.shape) != shape or noise.dtype != torch.float32:
+        raise ValueError(f"db noise: an fp32 tensor of shape {shape}")
+    return blur(gt, s.taps, "valid", add=noise.to(s.device) * (s.sigma / 255), want_center=True)
+
+
+def _jpeg_pair(s, gt, sigmas, noise):
+    """With a quality range (``patchwise: True``, restoration_jpeg.py:30-46) the patch is cropped and augmented first and ONE
+    ``jpeg_roundtrip`` call compresses the batch at a quality per sample; the qualities sit in the sampler's own device tensor, so
+    a captured step replays the call while they change."""
+    if sigmas is None or len(sigmas) != gt.shape[0]:
+        raise ValueError("jpeg with a quality range: one quality per sample of an explicit work list")
+    q = s.in_place(s.qualities, torch.tensor([int(v) for v in sigmas], dtype=torch.int32))
+    return jpeg_roundtrip(gt, q), gt
+
+
+TRAIN_PAIR = {"dn": _dn_pair, "dm": lambda s, gt, sigmas, noise: (demosaic_gt(gt), gt), "db": _db_pair, "jpeg": _jpeg_pair}

@@ -48,6 +48,7 @@ from typing import List, Optional, Sequence
 import torch
 
 from . import data as D
+from .task_rules import add_task_arguments, load_taps, resolve_arguments
 
 
 def multistep_warmup_lr(step: int, base_lr: float, milestones: Sequence[int], gamma: float, warmup_iter: int = -1,
@@ -93,16 +94,10 @@ def save_checkpoint(path: str, model, optimizer, step: int, sampler: D.PatchSamp
 
 def _parser():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("--task", default="sr", choices=D.TASKS,
-                    help="sr: paired folders --lq / --gt; sr_bicubic, dn, dm, db, jpeg: the LQ is made from --gt on the device")
+    add_task_arguments(ap, D.TASKS)
     ap.add_argument("--gt", required=True, help="GT training folder")
     ap.add_argument("--lq", default=None, help="LQ training folder (--task sr)")
-    ap.add_argument("--model", default="base", choices=["tiny", "small", "base"])
-    ap.add_argument("--geometry", default="sr_ckpt_df2", help="a key of presets.GEOMETRIES")
     ap.add_argument("--depths", default=None, help="blocks per stage as a+b+c instead of the model size's (short experiments)")
-    ap.add_argument("--scale", type=int, default=None, help="4 by default for --task sr / sr_bicubic; 1 for dn / dm / db / jpeg")
-    ap.add_argument("--channels", type=int, default=3, choices=[1, 3])
-    ap.add_argument("--upsampler", default=None, choices=["pixelshuffle", "pixelshuffledirect", "nearest+conv"])
     ap.add_argument("--ckpt", default=None, help="start weights (a reference checkpoint); random init without it")
     ap.add_argument("--patch", type=int, default=64, help="LQ patch side")
     ap.add_argument("--batch", type=int, default=8)
@@ -114,15 +109,7 @@ def _parser():
     ap.add_argument("--warmup-iter", type=int, default=-1)
     ap.add_argument("--warmup-init-lr", type=float, default=0.0)
     ap.add_argument("--loss", default="l1", choices=sorted(LOSSES))
-    ap.add_argument("--sigma", type=float, default=None, help="--task dn: noise level on the 0..255 scale; --task db: the same, default 2")
     ap.add_argument("--sigma-range", type=float, nargs=2, default=None, metavar=("LO", "HI"), help="--task dn: a level per sample")
-    ap.add_argument("--blur-kernel", default="gaussian",
-                    help="--task db: gaussian (25 x 25, sigma 1.6) or real1 .. real8 (the Levin09 motion kernels, from --blur-kernel-file)")
-    ap.add_argument("--blur-kernel-file", default=None,
-                    help="--task db with real1 .. real8: the reference's utils/blur_kernels/Levin09.npy, or a 2-D .npy of that kernel")
-    ap.add_argument("--quality", type=int, default=None,
-                    help="--task jpeg: the JPEG quality factor, 1 .. 100; every training image is compressed whole, once.  With "
-                         "--quality-range it is the quality of validation only")
     ap.add_argument("--quality-range", type=int, nargs=2, default=None, metavar=("LO", "HI"),
                     help="--task jpeg: a quality per sample, drawn after the crop; the patches are compressed, not the images")
     ap.add_argument("--seed", type=int, default=0)
@@ -139,53 +126,13 @@ def _parser():
 
 
 def _check(ap, a):
-    if a.task == "sr" and a.lq is None:
-        ap.error("--lq is required with --task sr")
-    if a.task != "sr" and a.lq is not None:
-        ap.error(f"--task {a.task} builds its LQ from --gt; --lq is not used")
-    if a.task == "dn" and (a.sigma is None) == (a.sigma_range is None):
-        ap.error("--task dn needs --sigma or --sigma-range (one of them)")
-    if a.task == "db":
-        if a.sigma_range is not None:
-            ap.error("--task db adds noise at one fixed --sigma")
-        if a.channels != 3:
-            ap.error("--task db works on RGB patches")
-        if a.sigma is None:
-            a.sigma = 2.0
-    elif a.blur_kernel != "gaussian" or a.blur_kernel_file is not None:
-        ap.error(f"--blur-kernel / --blur-kernel-file belong to --task db, not {a.task}")
-    if a.task == "jpeg":
-        if a.quality is None and a.quality_range is None:
-            ap.error("--task jpeg needs --quality or --quality-range")
-        if a.quality is not None and not 1 <= a.quality <= 100:
-            ap.error("--quality is 1 .. 100")
-        if a.quality_range is not None and not 1 <= a.quality_range[0] <= a.quality_range[1] <= 100:
-            ap.error("--quality-range is LO HI with 1 <= LO <= HI <= 100")
-    elif a.quality is not None or a.quality_range is not None:
-        ap.error(f"--quality / --quality-range belong to --task jpeg, not {a.task}")
-    if a.task not in ("dn", "db") and (a.sigma is not None or a.sigma_range is not None):
-        ap.error(f"--task {a.task} adds no noise; --sigma / --sigma-range are not used")
-    if a.scale is None:
-        a.scale = 4 if a.task in ("sr", "sr_bicubic") else 1
-    if a.task in ("dn", "dm", "db", "jpeg") and a.scale != 1:
-        ap.error(f"--task {a.task} restores at --scale 1")
-    if a.task == "sr_bicubic" and a.scale < 2:
-        ap.error("--task sr_bicubic needs a --scale above 1")
-    if a.scale < 1 or a.patch < 1 or a.batch < 1 or a.steps < 0:
-        ap.error("--scale, --patch and --batch must be positive")
-    if a.task == "dm" and (a.channels != 3 or a.patch % 2):
-        ap.error("--task dm works on RGB patches with an even --patch")
-    if a.val_every:
-        if a.val_gt is None:
-            ap.error("--val-every needs --val-gt")
-        if a.task == "sr" and a.val_lq is None:
-            ap.error("--task sr validates on --val-lq / --val-gt")
-        if a.task == "dn" and a.sigma is None:
-            ap.error("validation of --task dn needs a fixed --sigma")
-        if a.task == "jpeg" and a.quality is None:
-            ap.error("validation of --task jpeg needs --quality next to --quality-range")
-    if a.task != "sr" and a.val_lq is not None:
-        ap.error(f"--task {a.task} builds its validation LQ from --val-gt; --val-lq is not used")
+    if a.val_every and a.val_gt is None:
+        ap.error("--val-every needs --val-gt")
+    o = resolve_arguments(ap, a, "train", sigma_range=a.sigma_range, quality_range=a.quality_range, patch=a.patch,
+                          val=bool(a.val_every), val_lq=a.val_lq is not None)
+    a.scale, a.sigma = o.scale, o.sigma
+    if a.patch < 1 or a.batch < 1 or a.steps < 0:
+        ap.error("--patch and --batch must be positive")
     if a.save_every and a.out is None:
         ap.error("--save-every needs --out")
     try:
@@ -211,14 +158,7 @@ def main(argv: Optional[List[str]] = None):
     ap = _parser()
     a = ap.parse_args(argv)
     _check(ap, a)
-    taps = None
-    if a.task == "db":
-        from . import tasks
-
-        try:
-            taps = tasks.blur_taps(tasks.load_blur_kernel(a.blur_kernel, a.blur_kernel_file))
-        except (ValueError, OSError) as e:
-            ap.error(f"--blur-kernel: {e}")
+    taps = load_taps(ap, a)
 
     rank, world = 0, 1
     if int(os.environ.get("WORLD_SIZE", "1")) > 1 and not dist.is_initialized():
@@ -246,7 +186,7 @@ def main(argv: Optional[List[str]] = None):
     model = model.to(device).train()
 
     gt_store = D.PatchStore.from_folder(a.gt, a.channels, device)
-    lq_store = D.PatchStore.from_folder(a.lq, a.channels, device) if a.task == "sr" else None
+    lq_store = D.PatchStore.from_folder(a.lq, a.channels, device) if a.lq is not None else None
     sampler = D.PatchSampler(a.task, gt_store, lq_store, patch=a.patch, batch=a.batch, scale=a.scale, sigma=a.sigma,
                              sigma_range=a.sigma_range, seed=a.seed + rank, taps=taps,
                              quality=a.quality if a.quality_range is None else None, quality_range=a.quality_range)
