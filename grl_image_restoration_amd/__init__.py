@@ -6,6 +6,8 @@ from .train_graph import GraphedTrainStep  # noqa: F401
 from .presets import baseline_config, make_config  # noqa: F401
 from .data import PatchSampler, PatchStore  # noqa: F401
 from .train import charbonnier, multistep_warmup_lr  # noqa: F401
+from .image8 import ImageWriter, pack8  # noqa: F401
+from .restore import restore_folder  # noqa: F401
 
 __all__ = ["GRL", "FusedAdamW", "GraphedTrainStep", "make_config", "baseline_config", "PatchStore", "PatchSampler",
-           "charbonnier", "multistep_warmup_lr"]
+           "charbonnier", "multistep_warmup_lr", "pack8", "ImageWriter", "restore_folder"]

@@ -11,7 +11,7 @@ from . import switches as SW
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgrl_hip.so")
-ABI_VERSION = 29
+ABI_VERSION = 30
 DT_F32, DT_BF16, DT_F16 = 0, 1, 2
 
 EPI_PLAIN, EPI_GELU, EPI_GROUPNORM, EPI_LN_RES, EPI_GELU_GRAD = 0, 1, 2, 3, 4
@@ -65,6 +65,7 @@ EXPORTS = [
     "grl_blur_depthwise",
     "grl_jpeg_workspace_bytes",
     "grl_jpeg_roundtrip",
+    "grl_image_pack8",
     "grl_debug_dirty_lds",
     "grl_abi_version",
     "grl_build_info",
@@ -601,6 +602,16 @@ class GrlJpegArgs(_Strict):
     ]
 
 
+class GrlPack8Args(_Strict):
+    _fields_ = [
+        ("x", C.c_void_p),
+        ("stride", C.c_int64 * 4),
+        ("N", C.c_int32), ("C", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+        ("rep", C.c_int32),
+        ("out", C.c_void_p),
+    ]
+
+
 _lib = None
 
 
@@ -718,6 +729,8 @@ def lib():
     L.grl_jpeg_workspace_bytes.restype = C.c_int64
     L.grl_jpeg_roundtrip.argtypes = [C.c_void_p, C.POINTER(GrlJpegArgs)]
     L.grl_jpeg_roundtrip.restype = C.c_int
+    L.grl_image_pack8.argtypes = [C.c_void_p, C.POINTER(GrlPack8Args)]
+    L.grl_image_pack8.restype = C.c_int
     L.grl_debug_dirty_lds.argtypes = [C.c_void_p]
     L.grl_debug_dirty_lds.restype = C.c_int
     _lib = L

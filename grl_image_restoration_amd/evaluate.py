@@ -29,8 +29,10 @@ Restates, for the MI355X module, the three pieces of the reference's evaluation 
         --gt LIVE1 --metric restorer_jpeg
     python -m grl_image_restoration_amd.evaluate --task bsr --model base --geometry bsr --upsampler nearest+conv \\
         --ckpt bsr_grl_base.ckpt --lq RealSRSet --niqe-params niqe_pris_params.npz
+    ... --save-dir results [--save-gt]    also writes results/X4/<data set>/<stem>_{LQ,HQ,GT}.png (image8.py), as the reference does
 """
 import argparse
+import contextlib
 import os
 from typing import Dict, Iterable, List, Optional, Tuple
 
@@ -131,16 +133,18 @@ def image_pairs(lq_dir: str, gt_dir: str) -> List[Tuple[str, str]]:
 
 @torch.no_grad()
 def evaluate_pairs(model, pairs: Iterable[Tuple[torch.Tensor, torch.Tensor]], scale: int, tile: int = 0, overlap: int = 32,
-                   device: str = "cuda:0", metric_group: Optional[str] = None, niqe_params=None):
+                   device: str = "cuda:0", metric_group: Optional[str] = None, niqe_params=None, on_result=None):
     """PSNR-Y of ``model`` on (lq, gt) tensors in [0, 1], (1,3,h,w) / (1,3,h*scale,w*scale): a list, one value per pair.
     ``tile > 0`` uses the reference's tiled inference (engines/base.py:90-116) through ``tiling.forward_tiled``.
     With ``metric_group`` (a key of ``metrics.ALL_GROUPS``): {metric name: mean over the pairs} of that group instead.  ``gt`` may be
-    None for the group "restorer_niqe", which scores the output alone against ``niqe_params``."""
+    None for the group "restorer_niqe", which scores the output alone against ``niqe_params``.  ``on_result(index, lq, sr, gt)`` is
+    called for every pair with the tensors on ``device``, after ``sr`` and ``gt`` were cropped to each other and before the metrics:
+    the images the reference saves (engines/base.py:259-264, before ``shave``)."""
     from . import tiling
     from .metrics import image_metrics
 
     out = []
-    for lq, gt in pairs:
+    for index, (lq, gt) in enumerate(pairs):
         lq = lq.to(device)
         if tile and tile < min(lq.shape[-2:]):
             sr = tiling.forward_tiled(model, lq, tile, overlap, scale)
@@ -152,6 +156,8 @@ def evaluate_pairs(model, pairs: Iterable[Tuple[torch.Tensor, torch.Tensor]], sc
         else:
             gt = gt.to(sr.device)[..., : sr.shape[-2], : sr.shape[-1]]
             sr = sr[..., : gt.shape[-2], : gt.shape[-1]]
+        if on_result is not None:
+            on_result(index, lq, sr, gt)
         if metric_group is None:
             out.append(float(psnr_y(sr, gt, scale)))
         else:
@@ -196,13 +202,18 @@ def task_inputs(gt_dir: str, task: str, channels: int = 3, sigma: Optional[float
 def evaluate_folder(model, lq_dir: Optional[str], gt_dir: Optional[str], scale: int, tile: int = 0, overlap: int = 32,
                     device: str = "cuda:0", verbose: bool = True, metric_group: Optional[str] = None, channels: int = 3,
                     task: str = "sr", sigma: Optional[float] = None, noise_prefix: Optional[str] = None, niqe_params=None,
-                    taps: Optional[torch.Tensor] = None, quality: Optional[int] = None):
+                    taps: Optional[torch.Tensor] = None, quality: Optional[int] = None, save_dir: Optional[str] = None,
+                    save_gt: bool = False, save_workers: int = 4):
     """Mean PSNR-Y over the image pairs of two folders; with ``metric_group``, {metric name: mean} of that group.  ``channels`` 1
     reads the images as grayscale.  A ``task`` that synthesises its input ignores ``lq_dir`` and builds the LQ from the GT
     (``task_inputs``, with ``sigma``, ``taps``, ``quality`` and ``scale`` as the task's rule takes them).  A task without a ground
     truth ("bsr") reads ``lq_dir`` alone (``gt_dir`` is not used) and returns {"val_niqe": mean}; ``niqe_params`` is the pristine
-    model of ``metrics.niqe`` (also for "restorer_niqe" elsewhere)."""
-    rule = resolve(task, "evaluate_folder", scale=scale, channels=channels, sigma=sigma, quality=quality).rule
+    model of ``metrics.niqe`` (also for "restorer_niqe" elsewhere).  With ``save_dir`` every image is also written as 8-bit PNG under
+    the reference's layout (``image8.save_paths``): ``<stem>_HQ.png`` the restored image, ``<stem>_LQ.png`` the model's input
+    (enlarged ``scale`` times by replication, as the reference saves it), and with ``save_gt`` ``<stem>_GT.png``; the files are complete
+    when the call returns.  The metrics do not depend on it."""
+    o = resolve(task, "evaluate_folder", scale=scale, channels=channels, sigma=sigma, quality=quality)
+    rule = o.rule
     mode = "L" if channels == 1 else "RGB"
     if rule.lq_from == "gt":
         items = task_inputs(gt_dir, task, channels, sigma, noise_prefix, device, scale, taps, quality)
@@ -213,13 +224,28 @@ def evaluate_folder(model, lq_dir: Optional[str], gt_dir: Optional[str], scale: 
             raise ValueError(f"task {task} has no ground truth: its metric group is restorer_niqe, not {metric_group!r}")
         metric_group = "restorer_niqe"
         items = ((os.path.relpath(p, lq_dir), _read_image(p, mode), None) for p in gt_images(lq_dir))
-    vals = []
-    for name, lq, gt in items:
-        v = evaluate_pairs(model, [(lq, gt)], scale, tile, overlap, device, metric_group, niqe_params)
-        v = v[0] if metric_group is None else v
-        vals.append(v)
-        if verbose:
-            print(f"{name:32s} {_columns(v)}")
+    vals, writer, save = [], contextlib.nullcontext(), None
+    if save_dir is not None:
+        from .image8 import ImageWriter, save_paths
+
+        dataset = os.path.basename(os.path.normpath(gt_dir if rule.has_gt else lq_dir))
+        writer = ImageWriter(save_workers)
+
+        def save(name, lq, sr, gt):
+            paths = save_paths(save_dir, task, name, scale, o.sigma, o.quality, dataset)
+            os.makedirs(os.path.dirname(paths["HQ"]), exist_ok=True)
+            writer.write(paths["HQ"], sr.float())
+            writer.write(paths["LQ"], lq, rep=scale)
+            if save_gt and gt is not None:
+                writer.write(paths["GT"], gt)
+    with writer:                                          # closed, every file in place, before the mean is returned
+        for name, lq, gt in items:
+            on_result = None if save is None else (lambda i, lq_, sr_, gt_, name=name: save(name, lq_, sr_, gt_))
+            v = evaluate_pairs(model, [(lq, gt)], scale, tile, overlap, device, metric_group, niqe_params, on_result)
+            v = v[0] if metric_group is None else v
+            vals.append(v)
+            if verbose:
+                print(f"{name:32s} {_columns(v)}")
     if metric_group is None:
         mean = sum(vals) / len(vals)
     else:
@@ -251,6 +277,10 @@ def _parser():
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--metric", default=None, choices=sorted(ALL_GROUPS),
                     help="report this metric group of the reference (config/metric/*.yaml) instead of PSNR-Y alone")
+    ap.add_argument("--save-dir", default=None,
+                    help="also write every restored image (<stem>_HQ.png) and the model's input (<stem>_LQ.png) as 8-bit PNG under "
+                         "DIR/X<scale> | Sigma<sigma> | QF<quality>/<data set>/, the reference's layout")
+    ap.add_argument("--save-gt", action="store_true", help="with --save-dir: also write <stem>_GT.png")
     ap.add_argument("--noise-prefix", default=None,
                     help="--task dn: the reference's test-set name (Set12, BSD68, CBSD68, Kodak24, McMaster, Urban100; case matters) "
                          "that starts the noise seed key '<prefix>/<file name>'; a different prefix draws different noise.  Default: "
@@ -296,7 +326,7 @@ def main(argv: Optional[List[str]] = None):
     model = model.to(a.device)
     return evaluate_folder(model, a.lq, a.gt, a.scale, a.tile, a.overlap, a.device, metric_group=a.metric, channels=a.channels,
                            task=a.task, sigma=a.sigma, noise_prefix=a.noise_prefix, niqe_params=niqe_params, taps=taps,
-                           quality=a.quality)
+                           quality=a.quality, save_dir=a.save_dir, save_gt=a.save_gt)
 
 
 if __name__ == "__main__":

@@ -1,0 +1,97 @@
+"""Restores a folder of degraded images that have no ground truth: every image of --lq goes through the model, whole or tiled, and
+is written as ``<out>/<stem><suffix>.png``.  Nothing is synthesised and nothing is scored (``evaluate`` does that); the 8-bit pack
+and the PNG writer are ``image8.pack8`` / ``image8.ImageWriter``, the rounding is the reference's (engines/base.py:259-264,545-550).
+
+    python -m grl_image_restoration_amd.restore --model base --geometry sr_ckpt_df2 --scale 4 --ckpt sr_grl_base_c3x4.ckpt \\
+        --lq photos --out restored [--tile 256 --overlap 32]
+    python -m grl_image_restoration_amd.restore --model small --geometry dn_df4 --ckpt dn_grl_small_c3s25.ckpt --lq noisy --out clean
+"""
+import argparse
+import os
+from concurrent.futures import ThreadPoolExecutor
+from typing import List, Optional
+
+import torch
+
+from .evaluate import _read_image, gt_images, load_checkpoint
+from .image8 import ImageWriter
+
+
+@torch.no_grad()
+def restore_folder(model, lq_dir: str, out_dir: str, scale: int = 1, tile: int = 0, overlap: int = 32, device: str = "cuda:0",
+                   channels: int = 3, suffix: str = "_HQ", workers: int = 4, compress_level: int = 6, verbose: bool = False) -> List[str]:
+    """Writes ``<out_dir>/<stem><suffix>.png`` for every image of ``lq_dir`` in sorted order and returns the paths; every file is
+    complete when the call returns.  ``tile > 0`` restores images larger than the tile through ``tiling.forward_tiled``.  One reader
+    thread decodes the next image while the device works on the current one; ``workers`` threads compress the PNGs."""
+    from . import tiling
+
+    files = gt_images(lq_dir)
+    mode = "L" if channels == 1 else "RGB"
+    os.makedirs(out_dir, exist_ok=True)
+    paths = []
+    with ThreadPoolExecutor(max_workers=1, thread_name_prefix="grl-image-reader") as reader, \
+            ImageWriter(workers, compress_level) as writer:
+        ahead = reader.submit(_read_image, files[0], mode)
+        for i, f in enumerate(files):
+            lq = ahead.result()
+            if i + 1 < len(files):
+                ahead = reader.submit(_read_image, files[i + 1], mode)
+            lq = lq.to(device)
+            if tile and tile < min(lq.shape[-2:]):
+                sr = tiling.forward_tiled(model, lq, tile, overlap, scale)
+            else:
+                sr = model(lq)
+            path = os.path.join(out_dir, os.path.splitext(os.path.basename(f))[0] + suffix + ".png")
+            writer.write(path, sr.float())
+            paths.append(path)
+            if verbose:
+                print(f"{os.path.basename(f):32s} -> {path}")
+    return paths
+
+
+def _parser():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--lq", required=True, help="folder of degraded images")
+    ap.add_argument("--out", required=True, help="folder the restored images are written to (created)")
+    ap.add_argument("--ckpt", default=None, help="reference checkpoint (.ckpt / .pth); random init without it")
+    ap.add_argument("--model", default="base", choices=["tiny", "small", "base"])
+    ap.add_argument("--geometry", required=True, help="a key of presets.GEOMETRIES")
+    ap.add_argument("--scale", type=int, default=1, help="the model's upscaling factor; SR checkpoints need theirs (2, 3, 4)")
+    ap.add_argument("--channels", type=int, default=3, choices=[1, 3], help="1: grayscale model and images")
+    ap.add_argument("--upsampler", default=None, choices=["pixelshuffle", "pixelshuffledirect", "nearest+conv"],
+                    help="the reconstruction tail; default: the model size's classical-SR tail (bsr_grl_base.ckpt: nearest+conv)")
+    ap.add_argument("--depths", default=None, help="blocks per stage as a+b+c instead of the model size's (short experiments)")
+    ap.add_argument("--tile", type=int, default=0)
+    ap.add_argument("--overlap", type=int, default=32)
+    ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--suffix", default="_HQ", help="written files are <stem><suffix>.png")
+    ap.add_argument("--workers", type=int, default=4, help="PNG writer threads (at most 8)")
+    ap.add_argument("--compress-level", type=int, default=6, choices=range(10), metavar="0..9")
+    return ap
+
+
+def main(argv: Optional[List[str]] = None):
+    from . import GRL, make_config
+
+    ap = _parser()
+    a = ap.parse_args(argv)
+    if a.scale < 1:
+        ap.error("--scale is at least 1")
+    try:
+        depths = [int(d) for d in a.depths.split("+")] if a.depths else None
+    except ValueError:
+        ap.error("--depths are integers joined by +")
+    over = {"upsampler": a.upsampler} if a.upsampler and a.scale > 1 else {}
+    if depths:
+        heads = make_config(a.model, a.geometry)["num_heads_window"][0]
+        over.update(depths=depths, num_heads_window=[heads] * len(depths), num_heads_stripe=[heads] * len(depths))
+    model = GRL(**make_config(a.model, a.geometry, upscale=a.scale, in_channels=a.channels, **over)).eval()
+    if a.ckpt:
+        load_checkpoint(model, a.ckpt)
+    model = model.to(a.device)
+    return restore_folder(model, a.lq, a.out, a.scale, a.tile, a.overlap, a.device, a.channels, a.suffix, a.workers,
+                          a.compress_level, verbose=True)
+
+
+if __name__ == "__main__":
+    main()

@@ -25,23 +25,26 @@ class TaskRule:
     sigma_range: bool = False           # training may draw a sigma per sample
     taps: bool = False                  # takes a blur kernel
     quality: bool = False               # takes a JPEG quality, or for training a quality range
+    save_tag: Optional[str] = None      # saved images go under X<scale> ("scale"), Sigma<sigma> ("sigma"), QF<quality> ("quality") or
+                                        # straight under the data set's name (None): engines/base.py:504-524
 
 
 RULES = {
     "sr": TaskRule("classical SR from an LQ / GT folder pair (also deblurring and JPEG from folders): config/experiment/sr, "
-                   "data/datasets/restoration_sr.py:97-123 with load_lr", lq_from="folder", default_scale=4, max_scale=None),
+                   "data/datasets/restoration_sr.py:97-123 with load_lr", lq_from="folder", default_scale=4, max_scale=None, save_tag="scale"),
     "dn": TaskRule("denoising: config/data_module/dn.yaml; training noise restoration_dn.py:126-143, seeded validation noise :133-143",
-                   crop=8, noise=True, sigma_range=True),
+                   crop=8, noise=True, sigma_range=True, save_tag="sigma"),
     "dm": TaskRule("demosaicking: restoration_dm.py:25-35 (mosaic), engines/base.py:126-128 (dm_matlab before the model)",
                    crop=8, rgb_only=True, even_patch=True),
     "sr_bicubic": TaskRule("classical SR from the GT alone, LQ by MATLAB bicubic: restoration_sr.py:130-141, utils/matlab_functions.py:91-188",
-                           default_scale=4, min_scale=2, max_scale=None, crop="scale"),
+                           default_scale=4, min_scale=2, max_scale=None, crop="scale", save_tag="scale"),
     "bsr": TaskRule("blind / real-world SR, LQ images only, NIQE: config/experiment/bsr/grl.yaml (with_gt: False), "
-                    "config/metric/restorer_niqe.yaml", lq_from="folder", has_gt=False, trainable=False, default_scale=4, max_scale=None),
+                    "config/metric/restorer_niqe.yaml", lq_from="folder", has_gt=False, trainable=False, default_scale=4, max_scale=None,
+                    save_tag="scale"),
     "db": TaskRule("non-blind deblurring: config/data_module/db.yaml, restoration_db.py:19-21,40-43, engines/base.py:131-142",
                    crop=8, rgb_only=True, noise=True, sigma_default=2.0, taps=True),
     "jpeg": TaskRule("JPEG artifact removal: config/data_module/jpeg.yaml, restoration_jpeg.py:30-46,62-79; validation is not cropped "
-                     "(base_image.py:403-404)", quality=True),
+                     "(base_image.py:403-404)", quality=True, save_tag="quality"),
 }
 TASKS = tuple(RULES)
 # the order data.TASKS has had since the tasks were added: the SR tasks, then the tasks at scale 1

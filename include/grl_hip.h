@@ -23,7 +23,7 @@ extern "C" {
 
 #define GRL_ERR_BAD_ARG (-1)
 #define GRL_ERR_UNSUPPORTED (-2)
-#define GRL_ABI_VERSION 29
+#define GRL_ABI_VERSION 30
 
 /* element kinds of activation / weight buffers */
 enum { GRL_DT_F32 = 0, GRL_DT_BF16 = 1, GRL_DT_F16 = 2 };
@@ -887,6 +887,29 @@ typedef struct GrlJpegArgs {
 
 int64_t grl_jpeg_workspace_bytes(int32_t N, int32_t C, int32_t H, int32_t W);
 int grl_jpeg_roundtrip(void* stream, const GrlJpegArgs* args);
+
+/* 8-bit pack of an image batch for saving (ABI 30; the validation images the reference writes, save_images: True):
+ *   replaces  tensor_round(img, 1.0)                                  utils/utils_image.py:30-33, engines/base.py:259-261
+ *             F.interpolate(tn_input, scale_factor=scale)             engines/base.py:529-530 (rep = scale: the LQ of the SR tasks)
+ *             to_pil_image(tn[0].detach())                            engines/base.py:545-554 (float tensor: mul(255).byte(), HWC)
+ * x: fp32 (N, C, H, W), C = 1 or 3, read in place through four ELEMENT strides (batch, channel, row, column): a crop such as
+ * sr[..., :h, :w] needs no copy.  rep: 1 .. 8, every source pixel becomes a rep x rep block (nearest upscale, never materialised).
+ * out: contiguous uint8 (N, H rep, W rep, C), 4-byte aligned.
+ *   out[n][y][x][c] = uint8(rint(clamp(x[n][c][y / rep][x / rep], 0, 1) * 255.0f))
+ * rint rounds half to even, as torch.round; the multiply is one fp32 multiply of the clamped value.  NaN gives 0 (the reference's
+ * result for it is undefined); -inf gives 0 and +inf gives 255.
+ * One launch on `stream`; no allocation, no synchronisation.
+ * Errors (GRL_ERR_BAD_ARG, nothing is launched): a null args / x / out, C not 1 / 3, a non-positive N, H or W, rep outside 1 .. 8,
+ * x or out not 4-byte aligned, an output of 2^31 bytes or more, a grid beyond 2^31 - 1 workgroups. */
+typedef struct GrlPack8Args {
+    const float* x;
+    int64_t stride[4];          /* element strides of batch, channel, row, column                */
+    int32_t N, C, H, W;
+    int32_t rep;                /* 1 .. 8                                                         */
+    uint8_t* out;               /* (N, H rep, W rep, C)                                           */
+} GrlPack8Args;
+
+int grl_image_pack8(void* stream, const GrlPack8Args* args);
 
 /* Debug aid (ABI 21; no reference counterpart): fills the LDS of every CU with 0xFF bytes (fp32 / fp16 NaN) by a launch on
  * `stream`.  LDS keeps what the previous workgroup left in it; a kernel that reads LDS it has not written is otherwise right or
