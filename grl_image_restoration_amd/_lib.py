@@ -11,7 +11,7 @@ from . import switches as SW
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgrl_hip.so")
-ABI_VERSION = 30
+ABI_VERSION = 31
 DT_F32, DT_BF16, DT_F16 = 0, 1, 2
 
 EPI_PLAIN, EPI_GELU, EPI_GROUPNORM, EPI_LN_RES, EPI_GELU_GRAD = 0, 1, 2, 3, 4
@@ -66,6 +66,8 @@ EXPORTS = [
     "grl_jpeg_workspace_bytes",
     "grl_jpeg_roundtrip",
     "grl_image_pack8",
+    "grl_usm_workspace_bytes",
+    "grl_usm_sharp",
     "grl_debug_dirty_lds",
     "grl_abi_version",
     "grl_build_info",
@@ -612,6 +614,19 @@ class GrlPack8Args(_Strict):
     ]
 
 
+class GrlUsmArgs(_Strict):
+    _fields_ = [
+        ("x", C.c_void_p),
+        ("taps", C.c_void_p),
+        ("N", C.c_int32), ("C", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+        ("K", C.c_int32),
+        ("quantise", C.c_int32),
+        ("weight", C.c_float), ("threshold", C.c_float),
+        ("workspace", C.c_void_p),
+        ("out", C.c_void_p),
+    ]
+
+
 _lib = None
 
 
@@ -731,6 +746,10 @@ def lib():
     L.grl_jpeg_roundtrip.restype = C.c_int
     L.grl_image_pack8.argtypes = [C.c_void_p, C.POINTER(GrlPack8Args)]
     L.grl_image_pack8.restype = C.c_int
+    L.grl_usm_workspace_bytes.argtypes = [C.c_int32] * 4
+    L.grl_usm_workspace_bytes.restype = C.c_int64
+    L.grl_usm_sharp.argtypes = [C.c_void_p, C.POINTER(GrlUsmArgs)]
+    L.grl_usm_sharp.restype = C.c_int
     L.grl_debug_dirty_lds.argtypes = [C.c_void_p]
     L.grl_debug_dirty_lds.restype = C.c_int
     _lib = L

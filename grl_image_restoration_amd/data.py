@@ -144,7 +144,13 @@ class PatchSampler:
     ``task_rules.RULES`` (``scale`` is the SR factor, 1 for the tasks that restore at scale 1).  How each LQ is made:
 
       sr          paired stores: LQ patch ``patch``, GT patch ``patch * scale`` at the same place; every GT image is ``scale`` times
-                  its LQ image
+                  its LQ image.  With ``usm`` the GT store is replaced at construction by its USM-sharpened 8-bit twin: every image
+                  through ``tasks.usm_sharp`` whole, once, on the store's device, and back to 8 bit by ``image8.pack8`` (the
+                  reference's ``use_usm_pixel`` target, restoration_bsr.py:56-59,103-104, engines/base_psnr.py:39-41).  The LQ
+                  store, the draws, the work list and the generator are untouched: a seed gives the same crops with and without
+                  it.  The one deliberate difference from the reference's bsr path: the target is rounded to 8 bits (at most
+                  1 / 510 off), and it is sharpened on the whole image rather than on a 400 x 400 crop, so a patch carries no
+                  reflected crop border
       sr_bicubic, jpeg at a fixed ``quality``
                   GT store only.  The LQ store is made once per image at construction (``tasks.TRAIN_STORE_LQ`` on the store's
                   device; sr_bicubic also replaces the GT store by the images cropped to the scale); then sampled as ``sr``
@@ -161,7 +167,7 @@ class PatchSampler:
     def __init__(self, task: str, gt_store: PatchStore, lq_store: Optional[PatchStore] = None, patch: int = 64, batch: int = 8,
                  scale: int = 1, sigma: Optional[float] = None, sigma_range: Optional[Sequence[float]] = None, seed: int = 0,
                  taps: Optional[torch.Tensor] = None, quality: Optional[int] = None,
-                 quality_range: Optional[Sequence[int]] = None, patchwise: bool = True):
+                 quality_range: Optional[Sequence[int]] = None, patchwise: bool = True, usm: bool = False):
         from . import tasks
 
         patch, batch, scale = int(patch), int(batch), int(scale)
@@ -169,12 +175,14 @@ class PatchSampler:
             raise ValueError(f"patch and batch must be positive, got {patch}, {batch}")
         o = resolve(task, "sampler", scale=scale, channels=gt_store.channels, lq=lq_store is not None, sigma=sigma,
                     sigma_range=sigma_range, taps=taps is not None, quality=quality, quality_range=quality_range, patch=patch,
-                    patchwise=patchwise)
+                    patchwise=patchwise, usm=usm)
         if taps is not None and (taps.dim() != 2 or taps.shape[0] != taps.shape[1] or taps.shape[0] % 2 == 0 or taps.shape[0] > 31):
             raise ValueError("taps: the (K, K) fp32 table of tasks.blur_taps, K odd and at most 31")
         store_lq = tasks.TRAIN_STORE_LQ.get(task) if o.quality_range is None else None
         if store_lq is not None:
             gt_store, lq_store = _derived_stores(gt_store, lambda gt: store_lq(gt, o), scale if o.rule.crop == "scale" else 1)
+        if usm:
+            gt_store = _usm_store(gt_store)
         if lq_store is not None:
             if len(lq_store) != len(gt_store) or lq_store.channels != gt_store.channels or lq_store.device != gt_store.device:
                 raise ValueError("task sr: the two stores need the same number of images, channel count and device")
@@ -273,3 +281,17 @@ def _derived_stores(gt_store: PatchStore, degrade, crop: int = 1):
         lqs.append((lq[0] * 255).round().to(torch.uint8).permute(1, 2, 0).contiguous().cpu())
         gts.append(gt[0].permute(1, 2, 0).contiguous().cpu())
     return (PatchStore(gts, gt_store.device) if crop > 1 else gt_store), PatchStore(lqs, gt_store.device)
+
+
+def _usm_store(gt_store: PatchStore) -> PatchStore:
+    """The store of the USM-sharpened images: every image whole through ``tasks.usm_sharp`` on the store's device, packed back to
+    8 bit by ``image8.pack8``."""
+    from . import tasks
+    from .image8 import pack8
+
+    out: List[torch.Tensor] = []
+    for n in range(len(gt_store)):
+        # k / 255 by IEEE division, on the host: torch divides a CUDA tensor by a scalar through the reciprocal
+        x = gt_store.image(n).cpu().permute(2, 0, 1).unsqueeze(0).to(torch.float32).div(255).contiguous()
+        out.append(pack8(tasks.usm_sharp(x.to(gt_store.device)))[0].cpu())
+    return PatchStore(out, gt_store.device)

@@ -29,6 +29,8 @@ Restates, for the MI355X module, the three pieces of the reference's evaluation 
         --gt LIVE1 --metric restorer_jpeg
     python -m grl_image_restoration_amd.evaluate --task bsr --model base --geometry bsr --upsampler nearest+conv \\
         --ckpt bsr_grl_base.ckpt --lq RealSRSet --niqe-params niqe_pris_params.npz
+    python -m grl_image_restoration_amd.evaluate --model base --geometry bsr_psnr --upsampler nearest+conv --scale 4 \\
+        --ckpt bsr_psnr.ckpt --lq Set5/LRbicx4 --gt Set5/GTmod12 --usm-gt      scores against the USM-sharpened GT (val.use_usm: True)
     ... --save-dir results [--save-gt]    also writes results/X4/<data set>/<stem>_{LQ,HQ,GT}.png (image8.py), as the reference does
 """
 import argparse
@@ -203,7 +205,7 @@ def evaluate_folder(model, lq_dir: Optional[str], gt_dir: Optional[str], scale: 
                     device: str = "cuda:0", verbose: bool = True, metric_group: Optional[str] = None, channels: int = 3,
                     task: str = "sr", sigma: Optional[float] = None, noise_prefix: Optional[str] = None, niqe_params=None,
                     taps: Optional[torch.Tensor] = None, quality: Optional[int] = None, save_dir: Optional[str] = None,
-                    save_gt: bool = False, save_workers: int = 4):
+                    save_gt: bool = False, save_workers: int = 4, usm_gt: bool = False):
     """Mean PSNR-Y over the image pairs of two folders; with ``metric_group``, {metric name: mean} of that group.  ``channels`` 1
     reads the images as grayscale.  A ``task`` that synthesises its input ignores ``lq_dir`` and builds the LQ from the GT
     (``task_inputs``, with ``sigma``, ``taps``, ``quality`` and ``scale`` as the task's rule takes them).  A task without a ground
@@ -211,14 +213,22 @@ def evaluate_folder(model, lq_dir: Optional[str], gt_dir: Optional[str], scale: 
     model of ``metrics.niqe`` (also for "restorer_niqe" elsewhere).  With ``save_dir`` every image is also written as 8-bit PNG under
     the reference's layout (``image8.save_paths``): ``<stem>_HQ.png`` the restored image, ``<stem>_LQ.png`` the model's input
     (enlarged ``scale`` times by replication, as the reference saves it), and with ``save_gt`` ``<stem>_GT.png``; the files are complete
-    when the call returns.  The metrics do not depend on it."""
-    o = resolve(task, "evaluate_folder", scale=scale, channels=channels, sigma=sigma, quality=quality)
+    when the call returns.  The metrics do not depend on it.  ``usm_gt`` (task "sr" only; ValueError elsewhere): every GT is cropped
+    to a multiple of ``scale`` and sharpened by ``tasks.usm_sharp(..., quantise=True)`` on ``device`` before anything else sees it,
+    as the reference's validation set does under ``use_usm`` (restoration_sr.py:94,105-109, base_image.py:404): the metrics are
+    taken against the sharpened GT and ``save_gt`` writes it."""
+    o = resolve(task, "evaluate_folder", scale=scale, channels=channels, sigma=sigma, quality=quality, usm=usm_gt)
     rule = o.rule
     mode = "L" if channels == 1 else "RGB"
     if rule.lq_from == "gt":
         items = task_inputs(gt_dir, task, channels, sigma, noise_prefix, device, scale, taps, quality)
     elif rule.has_gt:
         items = ((os.path.basename(lq_p), _read_image(lq_p, mode), _read_image(gt_p, mode)) for lq_p, gt_p in image_pairs(lq_dir, gt_dir))
+        if usm_gt:
+            from . import tasks
+
+            items = ((name, lq, tasks.usm_sharp(tasks.modcrop(gt, int(scale)).contiguous().to(device), quantise=True))
+                     for name, lq, gt in items)
     else:
         if metric_group not in (None, "restorer_niqe"):
             raise ValueError(f"task {task} has no ground truth: its metric group is restorer_niqe, not {metric_group!r}")
@@ -281,6 +291,9 @@ def _parser():
                     help="also write every restored image (<stem>_HQ.png) and the model's input (<stem>_LQ.png) as 8-bit PNG under "
                          "DIR/X<scale> | Sigma<sigma> | QF<quality>/<data set>/, the reference's layout")
     ap.add_argument("--save-gt", action="store_true", help="with --save-dir: also write <stem>_GT.png")
+    ap.add_argument("--usm-gt", action="store_true",
+                    help="--task sr: score against the USM-sharpened GT (the reference's val.use_usm: True of bsr/grl_psnr.yaml); the "
+                         "GT is cropped to a multiple of --scale first, and --save-gt writes the sharpened image")
     ap.add_argument("--noise-prefix", default=None,
                     help="--task dn: the reference's test-set name (Set12, BSD68, CBSD68, Kodak24, McMaster, Urban100; case matters) "
                          "that starts the noise seed key '<prefix>/<file name>'; a different prefix draws different noise.  Default: "
@@ -300,7 +313,7 @@ def _check(ap, a):
         if a.metric not in (None, "restorer_niqe"):
             ap.error(f"--task {a.task} is scored by --metric restorer_niqe")
         a.metric = "restorer_niqe"
-    o = resolve_arguments(ap, a, "evaluate")
+    o = resolve_arguments(ap, a, "evaluate", usm=a.usm_gt)
     a.scale, a.sigma = o.scale, o.sigma
 
 
@@ -326,7 +339,7 @@ def main(argv: Optional[List[str]] = None):
     model = model.to(a.device)
     return evaluate_folder(model, a.lq, a.gt, a.scale, a.tile, a.overlap, a.device, metric_group=a.metric, channels=a.channels,
                            task=a.task, sigma=a.sigma, noise_prefix=a.noise_prefix, niqe_params=niqe_params, taps=taps,
-                           quality=a.quality, save_dir=a.save_dir, save_gt=a.save_gt)
+                           quality=a.quality, save_dir=a.save_dir, save_gt=a.save_gt, usm_gt=a.usm_gt)
 
 
 if __name__ == "__main__":

@@ -64,6 +64,8 @@ GEOMETRIES = {
     "dm": dict(window_size=8, stripe_size=[32, 32], stripe_groups=[None, None], anchor_window_down_factor=4),
     # blind / real-world SR Base (bsr/grl.yaml:53-67, grl_test.md:100-106); its tail is upsampler="nearest+conv"
     "bsr": dict(window_size=16, stripe_size=[32, 64], stripe_groups=[None, None], anchor_window_down_factor=4),
+    # blind / real-world SR Base, the PSNR stage trained on USM-sharpened targets (bsr/grl_psnr.yaml:9-10,35-46); nearest+conv tail
+    "bsr_psnr": dict(window_size=16, stripe_size=[64, 64], stripe_groups=[None, None], anchor_window_down_factor=4),
     # JPEG artifact removal (jpeg/grl/grl_p288.yaml:37-46)
     "jpeg": dict(window_size=36, stripe_size=[72, 144], stripe_groups=[None, None], anchor_window_down_factor=4),
 }

@@ -25,13 +25,15 @@ class TaskRule:
     sigma_range: bool = False           # training may draw a sigma per sample
     taps: bool = False                  # takes a blur kernel
     quality: bool = False               # takes a JPEG quality, or for training a quality range
+    usm: bool = False                   # the GT may be USM-sharpened (use_usm / use_usm_pixel: restoration_sr.py:94,105-109)
     save_tag: Optional[str] = None      # saved images go under X<scale> ("scale"), Sigma<sigma> ("sigma"), QF<quality> ("quality") or
                                         # straight under the data set's name (None): engines/base.py:504-524
 
 
 RULES = {
     "sr": TaskRule("classical SR from an LQ / GT folder pair (also deblurring and JPEG from folders): config/experiment/sr, "
-                   "data/datasets/restoration_sr.py:97-123 with load_lr", lq_from="folder", default_scale=4, max_scale=None, save_tag="scale"),
+                   "data/datasets/restoration_sr.py:97-123 with load_lr; USM-sharpened GT: config/experiment/bsr/grl_psnr.yaml:26-33",
+                   lq_from="folder", default_scale=4, max_scale=None, usm=True, save_tag="scale"),
     "dn": TaskRule("denoising: config/data_module/dn.yaml; training noise restoration_dn.py:126-143, seeded validation noise :133-143",
                    crop=8, noise=True, sigma_range=True, save_tag="sigma"),
     "dm": TaskRule("demosaicking: restoration_dm.py:25-35 (mosaic), engines/base.py:126-128 (dm_matlab before the model)",
@@ -53,12 +55,13 @@ SYNTHESISED = tuple(t for t in RULES if RULES[t].lq_from == "gt")
 
 
 def resolve(task, where, *, scale=None, channels=3, lq=False, sigma=None, sigma_range=None, taps=False, quality=None,
-            quality_range=None, patch=None, patchwise=True, val=False, val_lq=False):
+            quality_range=None, patch=None, patchwise=True, val=False, val_lq=False, usm=False, val_usm=False):
     """Checks the options of one call against ``RULES[task]``, fills the defaults and returns them as a namespace (``rule``,
     ``scale``, ``sigma``, ``sigma_range``, ``quality``, ``quality_range``).  Raises ValueError.  ``where`` is the caller: "evaluate" /
     "train" (the command lines), "evaluate_folder", "task_inputs", "sampler".  ``lq`` / ``taps``: whether an LQ folder or store / a blur
-    kernel was given; ``val`` / ``val_lq`` (train): validation is on / has an LQ folder.  Where the callers have always differed,
-    the difference is a branch on ``where`` below, marked "kept".
+    kernel was given; ``val`` / ``val_lq`` (train): validation is on / has an LQ folder; ``usm`` / ``val_usm``: the GT (of training:
+    the targets; of evaluation and of train's validation: the scored GT) is sharpened by ``tasks.usm_sharp``.  Where the callers
+    have always differed, the difference is a branch on ``where`` below, marked "kept".
     """
     training, library_eval = where in ("train", "sampler"), where in ("evaluate_folder", "task_inputs")
     r = RULES.get(task)
@@ -74,6 +77,10 @@ def resolve(task, where, *, scale=None, channels=3, lq=False, sigma=None, sigma_
             raise ValueError(f"task {task} builds its LQ from the GT; an LQ folder (--lq, --val-lq) or store is not used")
         if val and r.lq_from == "folder" and not val_lq:
             raise ValueError(f"task {task} validates on --val-lq / --val-gt")
+
+    if (usm or val_usm) and not r.usm:
+        raise ValueError(f"task {task} has no USM-sharpened GT (--usm-gt, --usm, --val-usm, usm, usm_gt): only "
+                         f"{', '.join(t for t in RULES if RULES[t].usm)} reads a GT folder next to its LQ")
 
     if scale is None:
         scale = r.default_scale

@@ -26,6 +26,10 @@
   jpeg_roundtrip     data/datasets/restoration_jpeg.py:62-79   the JPEG artifact-removal LQ: ``cv2.imencode(".jpg", img, [IMWRITE_JPEG_QUALITY,
                                                     q])`` followed by ``cv2.imdecode``, restated as libjpeg's integer arithmetic (the
                                                     entropy coding is lossless and left out)
+  usm_taps           cv2.getGaussianKernel(K, 0)         the 1-D Gaussian of ``usm_sharp``: K = 51, sigma = 8 at the reference's radius 50
+  usm_sharp          utils/utils_bsr/utils_usm.py:34-60  unsharp-mask sharpening of a GT batch (``cv2.GaussianBlur`` twice, reflect-101
+                                                    borders): the target of the real-world-SR PSNR stage, restoration_sr.py:105-109
+                                                    (validation, ``use_usm``) and restoration_bsr.py:56-59 (training, ``use_usm_pixel``)
   VAL_LQ, TRAIN_STORE_LQ, TRAIN_PAIR                the LQ of each task from the front ends above, per side: a validation image, a
                                                     training store made once, a training batch (at the end of the module; what a
                                                     task accepts is ``task_rules.RULES``)
@@ -41,7 +45,10 @@ and sum by the same tables; the two agree to an fp32 rounding, not bitwise (cubi
 summed in float64 and rounded once.  The two agree within the forward error of a K x K-term fp32 sum, (K^2 + 2) 2^-24 max|x|.
 ``jpeg_roundtrip`` on CUDA is one ``grl_jpeg_roundtrip`` call (csrc/jpeg.hip, two launches, int32); on the CPU ``_torch_jpeg``
 restates the same integer arithmetic in int64.  Both are libjpeg-turbo's defaults (4:2:0, ``JDCT_ISLOW``, baseline tables, fancy
-upsampling) bit for bit, so the two paths and the library agree in every byte.
+upsampling) bit for bit, so the two paths and the library agree in every byte.  ``usm_sharp`` on CUDA is one ``grl_usm_sharp`` call
+(csrc/usm.hip, two launches, fp32 fmaf chains in a fixed order); on the CPU the two blurs and the mask are float64.  The two agree
+within the forward error of two 51-term fp32 chains wherever the masks agree; bit equality with OpenCV's summation order is not
+claimed.
 """
 import ctypes as C
 import hashlib
@@ -656,6 +663,122 @@ def _jpeg_upsample(d: torch.Tensor) -> torch.Tensor:
     even = (3 * s + s[:, :, (c - 1).clamp(min=0)] + 8) >> 4
     odd = (3 * s + s[:, :, (c + 1).clamp(max=w2 - 1)] + 7) >> 4
     return torch.stack([even, odd], 3).reshape(N, 2 * h2, 2 * w2)
+
+
+# ---- USM-sharpened targets ----------------------------------------------------------------------------------------------------
+# cv2.getGaussianKernel(n, sigma <= 0) returns these fixed tables for n <= 7 (imgproc/src/smooth.dispatch.cpp, small_gaussian_tab)
+_SMALL_GAUSSIAN = {1: (1.0,), 3: (0.25, 0.5, 0.25), 5: (0.0625, 0.25, 0.375, 0.25, 0.0625),
+                   7: (0.03125, 0.109375, 0.21875, 0.28125, 0.21875, 0.109375, 0.03125)}
+_USM_TAPS = {}
+
+
+def usm_taps(radius: int = 50) -> torch.Tensor:
+    """The (K,) fp32 taps of ``usm_sharp``'s blur: ``cv2.getGaussianKernel(K, 0)`` restated, K = ``radius``, plus one when it is
+    even (utils_usm.py:50-51: 50 -> 51).  ``sigma = 0.3 ((K - 1) / 2 - 1) + 0.8`` (8.0 at K = 51), ``exp(-(i - (K - 1) / 2)^2 /
+    (2 sigma^2))`` normalised by its sum in float64, then cast to fp32, as ``cv2.GaussianBlur`` builds its fp32 filter; K <= 7 are
+    OpenCV's fixed tables.  K is at most 63, what ``grl_usm_sharp`` takes."""
+    K = int(radius) + (1 if int(radius) % 2 == 0 else 0)
+    if not 1 <= K <= 63:
+        raise ValueError(f"usm_taps: the kernel size is 1 .. 63, got {K} (radius {radius})")
+    if K in _SMALL_GAUSSIAN:
+        return torch.tensor(_SMALL_GAUSSIAN[K], dtype=torch.float32)
+    sigma = 0.3 * ((K - 1) * 0.5 - 1) + 0.8
+    i = np.arange(K, dtype=np.float64) - (K - 1) * 0.5
+    k = np.exp(-(i * i) / (2 * sigma * sigma))
+    return torch.from_numpy((k / k.sum()).astype(np.float32))
+
+
+def usm_device_taps(radius: int, device) -> torch.Tensor:
+    """``usm_taps(radius)`` on ``device``, made once per radius and device.  The first call copies the table from the host, which a
+    stream capture does not allow: it raises there instead of breaking the capture; call it (or ``usm_sharp``) once before."""
+    key = (int(radius), str(torch.device(device)))
+    if key not in _USM_TAPS:
+        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f"usm_sharp: the taps of radius {radius} are not on {device} yet and cannot be copied there during a "
+                               "stream capture; call tasks.usm_device_taps(radius, device) or usm_sharp once before capturing")
+        _USM_TAPS[key] = usm_taps(radius).to(device)
+    return _USM_TAPS[key]
+
+
+def usm_sharp(x: torch.Tensor, weight: float = 0.5, radius: int = 50, threshold: float = 10.0, quantise: bool = False,
+              parts: bool = False):
+    """The reference's ``usm_sharp`` (utils_usm.py:34-60) on an (N, C, H, W) fp32 batch in [0, 1], C = 1 or 3, every plane on its own:
+
+        blur = G(x);  res = x - blur;  m = |res| * 255 > threshold;  soft = G(m)
+        out  = soft * clamp(x + weight * res, 0, 1) + (1 - soft) * x
+
+    G is the separable ``usm_taps(radius)`` blur with reflect-101 borders (``cv2.GaussianBlur``'s default), reflected as often as a
+    side shorter than K / 2 needs.  ``quantise``: the result as 8-bit levels / 255 (``single2uint`` then ``to_tensor``,
+    restoration_sr.py:108-115), bitwise ``image8.pack8`` of the plain result divided by 255.  ``parts``: returns
+    ``(out, blur, m)``.  CUDA tensors take one ``grl_usm_sharp`` call (two launches, fp32 fmaf chains; there is no fallback); CPU
+    tensors take the torch restatement: blur, mask and blend in float64, the result rounded once to fp32.  The call can be captured
+    once the taps are on the device (``usm_device_taps``: any earlier call with this radius, or that function itself)."""
+    if x.dim() != 4 or x.shape[1] not in (1, 3) or min(x.shape) < 1:
+        raise ValueError(f"usm_sharp: need a non-empty (N, C, H, W) batch with C = 1 or 3, got {tuple(x.shape)}")
+    if x.dtype != torch.float32:
+        raise TypeError(f"usm_sharp takes fp32 images, got {x.dtype}")
+    if x.is_cuda:
+        return hip_usm(x, usm_device_taps(radius, x.device), weight, threshold, quantise, parts)
+    return _torch_usm(x, usm_taps(radius), weight, threshold, quantise, parts)
+
+
+def hip_usm(x: torch.Tensor, taps: torch.Tensor, weight: float = 0.5, threshold: float = 10.0, quantise: bool = False,
+            parts: bool = False, out: Optional[torch.Tensor] = None):
+    """One ``grl_usm_sharp`` call: ``x`` an (N, C, H, W) fp32 CUDA tensor, ``taps`` (K,) fp32 on its device (read by the kernels when
+    they run).  The workspace is a fresh tensor; ``parts`` returns its two halves, blur and the 0 / 1 mask, next to the result.  K and
+    the sizes are checked by the library."""
+    from . import _lib
+
+    L = _lib.lib()
+    if x.dtype != torch.float32 or taps.dtype != torch.float32:
+        raise TypeError(f"grl_usm_sharp takes fp32 tensors, got {x.dtype} and {taps.dtype}")
+    if taps.dim() != 1 or taps.device != x.device:
+        raise ValueError("usm taps: a (K,) table on the image's device")
+    x, taps = x.contiguous(), taps.contiguous()
+    N, Cn, H, W = x.shape
+    if out is None:
+        out = torch.empty_like(x)
+    elif out.shape != x.shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != x.device:
+        raise ValueError("out: a contiguous fp32 tensor of the input's shape on its device")
+    ws = torch.empty((2,) + tuple(x.shape), dtype=torch.float32, device=x.device)
+    if int(L.grl_usm_workspace_bytes(N, Cn, H, W)) != ws.numel() * 4:
+        raise ValueError(f"grl_usm_sharp does not take a batch of shape {tuple(x.shape)}")
+    args = _lib.GrlUsmArgs(x=x.data_ptr(), taps=taps.data_ptr(), N=N, C=Cn, H=H, W=W, K=taps.shape[0], quantise=int(bool(quantise)),
+                           weight=float(weight), threshold=float(threshold), workspace=ws.data_ptr(), out=out.data_ptr())
+    _lib.check(L.grl_usm_sharp(_lib.stream_ptr(), C.byref(args)), "grl_usm_sharp")
+    return (out, ws[0], ws[1]) if parts else out
+
+
+def _reflect101(n: int, half: int) -> torch.Tensor:
+    """Source index of positions -half .. n - 1 + half under cv2's BORDER_REFLECT_101, reflected repeatedly."""
+    if n == 1:
+        return torch.zeros(1 + 2 * half, dtype=torch.int64)
+    p = 2 * (n - 1)
+    j = torch.arange(-half, n + half, dtype=torch.int64) % p
+    return torch.where(j >= n, p - j, j)
+
+
+def _usm_blur64(a: torch.Tensor, taps: torch.Tensor) -> torch.Tensor:
+    """The separable blur of a float64 (N, C, H, W) batch with float64 taps, rows then columns."""
+    N, Cn, H, W = a.shape
+    K = taps.shape[0]
+    a = a.reshape(N * Cn, 1, H, W)
+    a = F.conv2d(a[..., _reflect101(W, K // 2)], taps.view(1, 1, 1, K))
+    a = F.conv2d(a[..., _reflect101(H, K // 2), :], taps.view(1, 1, K, 1))
+    return a.reshape(N, Cn, H, W)
+
+
+def _torch_usm(x, taps, weight, threshold, quantise, parts):
+    x64, t64 = x.double(), taps.double()
+    blur = _usm_blur64(x64, t64)
+    res = x64 - blur
+    mask = (res.abs() * 255.0 > float(threshold)).double()
+    soft = _usm_blur64(mask, t64)
+    sharp = (x64 + float(weight) * res).clamp(0.0, 1.0)
+    out = (soft * sharp + (1.0 - soft) * x64).float()
+    if quantise:
+        out = _round8(out)
+    return (out, blur, mask) if parts else out
 
 
 # ---- the LQ of each task: validation images, training stores, training batches ----------------------------------------------------

@@ -15,6 +15,8 @@ Restates the pieces of the reference's training run that sit around ``model(x)``
     python -m grl_image_restoration_amd.train --task sr --scale 4 --model base --geometry sr_ckpt_df2 \\
         --gt DIV2K/HR --lq DIV2K/LR_bicubic/X4 --patch 64 --batch 8 --steps 500000 \\
         --milestones 250000+400000+450000+475000 --gamma 0.5 --out runs/sr_x4 --val-gt Set5/GTmod12 --val-lq Set5/LRbicx4
+    python -m grl_image_restoration_amd.train --task sr --scale 4 --model base --geometry bsr_psnr --upsampler nearest+conv \\
+        --usm --val-usm --weight-decay 0 --gt pairs/GT --lq pairs/LQ --val-gt Set5/GTmod12 --val-lq Set5/LRbicx4 ...
     python -m grl_image_restoration_amd.train --task sr_bicubic --scale 2 --model small --geometry sr_ckpt_df4 --gt DIV2K/HR ...
     python -m grl_image_restoration_amd.train --task dn --sigma 25 --model small --geometry dn_df4 --gt DFWB --ckpt dn_grl_small_c3s25.ckpt ...
     python -m grl_image_restoration_amd.train --task dm --model small --geometry dm --gt DFWB ...
@@ -112,6 +114,10 @@ def _parser():
     ap.add_argument("--sigma-range", type=float, nargs=2, default=None, metavar=("LO", "HI"), help="--task dn: a level per sample")
     ap.add_argument("--quality-range", type=int, nargs=2, default=None, metavar=("LO", "HI"),
                     help="--task jpeg: a quality per sample, drawn after the crop; the patches are compressed, not the images")
+    ap.add_argument("--usm", action="store_true",
+                    help="--task sr: train against USM-sharpened targets (the reference's use_usm_pixel: True of bsr/grl_psnr.yaml); "
+                         "every GT image is sharpened whole, once")
+    ap.add_argument("--val-usm", action="store_true", help="--task sr: validate against the USM-sharpened GT (val.use_usm: True)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--val-gt", default=None)
     ap.add_argument("--val-lq", default=None)
@@ -129,7 +135,7 @@ def _check(ap, a):
     if a.val_every and a.val_gt is None:
         ap.error("--val-every needs --val-gt")
     o = resolve_arguments(ap, a, "train", sigma_range=a.sigma_range, quality_range=a.quality_range, patch=a.patch,
-                          val=bool(a.val_every), val_lq=a.val_lq is not None)
+                          val=bool(a.val_every), val_lq=a.val_lq is not None, usm=a.usm, val_usm=a.val_usm)
     a.scale, a.sigma = o.scale, o.sigma
     if a.patch < 1 or a.batch < 1 or a.steps < 0:
         ap.error("--patch and --batch must be positive")
@@ -189,7 +195,7 @@ def main(argv: Optional[List[str]] = None):
     lq_store = D.PatchStore.from_folder(a.lq, a.channels, device) if a.lq is not None else None
     sampler = D.PatchSampler(a.task, gt_store, lq_store, patch=a.patch, batch=a.batch, scale=a.scale, sigma=a.sigma,
                              sigma_range=a.sigma_range, seed=a.seed + rank, taps=taps,
-                             quality=a.quality if a.quality_range is None else None, quality_range=a.quality_range)
+                             quality=a.quality if a.quality_range is None else None, quality_range=a.quality_range, usm=a.usm)
 
     opt = FusedAdamW(model.parameters(), lr=a.lr, weight_decay=a.weight_decay)
     start = 0
@@ -243,7 +249,7 @@ def main(argv: Optional[List[str]] = None):
             model.eval()
             with torch.no_grad():
                 v = evaluate_folder(model, a.val_lq, a.val_gt, a.scale, device=a.device, verbose=False, metric_group=a.metric,
-                                    channels=a.channels, task=a.task, sigma=a.sigma, taps=taps, quality=a.quality)
+                                    channels=a.channels, task=a.task, sigma=a.sigma, taps=taps, quality=a.quality, usm_gt=a.val_usm)
             model.train()
             out["val"].append((done, v))
             print(f"step {n:8d}  validation {v}", flush=True)

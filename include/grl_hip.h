@@ -23,7 +23,7 @@ extern "C" {
 
 #define GRL_ERR_BAD_ARG (-1)
 #define GRL_ERR_UNSUPPORTED (-2)
-#define GRL_ABI_VERSION 30
+#define GRL_ABI_VERSION 31
 
 /* element kinds of activation / weight buffers */
 enum { GRL_DT_F32 = 0, GRL_DT_BF16 = 1, GRL_DT_F16 = 2 };
@@ -910,6 +910,41 @@ typedef struct GrlPack8Args {
 } GrlPack8Args;
 
 int grl_image_pack8(void* stream, const GrlPack8Args* args);
+
+/* Unsharp-mask sharpening of an image batch (ABI 31; the sharpened GT of the real-world-SR PSNR stage, `use_usm` / `use_usm_pixel`):
+ *   replaces  usm_sharp(img, weight=0.5, radius=50, threshold=10)    utils/utils_bsr/utils_usm.py:34-60 (cv2.GaussianBlur twice)
+ *             USMSharp.forward                                        utils/utils_bsr/utils_usm.py:63-82 (its torch twin)
+ *             uint2single + usm_sharp + single2uint on the GT         data/datasets/restoration_sr.py:105-109 (validation)
+ *             self.usm_sharpener(gt)                                  data/datasets/restoration_bsr.py:56-59, 103-104 (training)
+ * x, out: contiguous fp32 (N, C, H, W), C = 1 or 3; every (n, c) plane is treated on its own, all arithmetic is fp32.
+ * taps: [K] fp32 in DEVICE memory (cv2.getGaussianKernel(K, 0); the reference's K is 51), K odd, 1 .. 63.  The kernels read them when
+ * they run: no constant upload, no host synchronisation, so the call can be captured and the taps rewritten between replays.
+ *   idx(i, n)  = reflect-101 (cv2's default border), reflected repeatedly: n == 1 -> 0; else j = i mod 2(n-1); j >= n ? 2(n-1) - j : j
+ *   G(a)[y][x] = column pass(row pass(a)), each pass one fp32 fmaf chain from 0 over taps t = 0 .. K-1 reading a[idx(. + t - K/2)]
+ *   blur = G(x);  res = x - blur;  m = (fabsf(res) * 255.0f > threshold) ? 1.0f : 0.0f
+ *   soft = G(m);  sharp = clamp(x + weight * res, 0, 1);  out = soft * sharp + (1 - soft) * x        (each operation rounded once)
+ *   quantise != 0:  out = float(rint(clamp(out, 0, 1) * 255.0f)) / 255   (half to even, IEEE division: single2uint, then to_tensor;
+ *                   bitwise grl_image_pack8 of the plain result divided by 255)
+ * The result of a plane does not depend on the tiling or on where the plane sits in the batch.
+ * workspace: grl_usm_workspace_bytes(N, C, H, W) bytes, 4-byte aligned, no initialisation.  After the call it holds blur, then m,
+ * each contiguous fp32 (N, C, H, W).
+ * Two launches on `stream` (x -> blur, m; then m, x, blur -> out); no allocation, no synchronisation.
+ * Errors (GRL_ERR_BAD_ARG, nothing is launched): a null args / x / taps / workspace / out, C not 1 / 3, K even or outside 1 .. 63, a
+ * non-positive N, H or W, H or W above 2^30, a pointer not 4-byte aligned, a grid beyond 2^31 - 1 workgroups.
+ * grl_usm_workspace_bytes returns GRL_ERR_BAD_ARG for such sizes. */
+typedef struct GrlUsmArgs {
+    const float* x;             /* (N, C, H, W)                                                   */
+    const float* taps;          /* [K] device                                                     */
+    int32_t N, C, H, W;
+    int32_t K;                  /* odd, 1 .. 63                                                   */
+    int32_t quantise;           /* != 0: 8-bit levels / 255                                       */
+    float weight, threshold;    /* the reference: 0.5, 10                                         */
+    void* workspace;            /* grl_usm_workspace_bytes(N, C, H, W) bytes                      */
+    float* out;                 /* (N, C, H, W)                                                   */
+} GrlUsmArgs;
+
+int64_t grl_usm_workspace_bytes(int32_t N, int32_t C, int32_t H, int32_t W);
+int grl_usm_sharp(void* stream, const GrlUsmArgs* args);
 
 /* Debug aid (ABI 21; no reference counterpart): fills the LDS of every CU with 0xFF bytes (fp32 / fp16 NaN) by a launch on
  * `stream`.  LDS keeps what the previous workgroup left in it; a kernel that reads LDS it has not written is otherwise right or
