@@ -11,7 +11,7 @@ from . import switches as SW
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgrl_hip.so")
-ABI_VERSION = 31
+ABI_VERSION = 32
 DT_F32, DT_BF16, DT_F16 = 0, 1, 2
 
 EPI_PLAIN, EPI_GELU, EPI_GROUPNORM, EPI_LN_RES, EPI_GELU_GRAD = 0, 1, 2, 3, 4
@@ -68,6 +68,8 @@ EXPORTS = [
     "grl_image_pack8",
     "grl_usm_workspace_bytes",
     "grl_usm_sharp",
+    "grl_cv_resize",
+    "grl_blur_items",
     "grl_debug_dirty_lds",
     "grl_abi_version",
     "grl_build_info",
@@ -627,6 +629,31 @@ class GrlUsmArgs(_Strict):
     ]
 
 
+class GrlCvResizeArgs(_Strict):
+    _fields_ = [
+        ("src", C.c_void_p),
+        ("dst", C.c_void_p),
+        ("src_elems", C.c_int64), ("dst_elems", C.c_int64),
+        ("items", C.c_void_p),
+        ("n_items", C.c_int32), ("C", C.c_int32),
+        ("max_ho", C.c_int32), ("max_wo", C.c_int32),
+    ]
+
+
+class GrlBlurItemsArgs(_Strict):
+    _fields_ = [
+        ("src", C.c_void_p),
+        ("dst", C.c_void_p),
+        ("taps", C.c_void_p),
+        ("src_elems", C.c_int64), ("dst_elems", C.c_int64), ("taps_elems", C.c_int64),
+        ("items", C.c_void_p),
+        ("n_items", C.c_int32), ("C", C.c_int32),
+        ("max_ho", C.c_int32), ("max_wo", C.c_int32),
+        ("max_K", C.c_int32),
+        ("reserved0", C.c_int32),
+    ]
+
+
 _lib = None
 
 
@@ -750,6 +777,10 @@ def lib():
     L.grl_usm_workspace_bytes.restype = C.c_int64
     L.grl_usm_sharp.argtypes = [C.c_void_p, C.POINTER(GrlUsmArgs)]
     L.grl_usm_sharp.restype = C.c_int
+    L.grl_cv_resize.argtypes = [C.c_void_p, C.POINTER(GrlCvResizeArgs)]
+    L.grl_cv_resize.restype = C.c_int
+    L.grl_blur_items.argtypes = [C.c_void_p, C.POINTER(GrlBlurItemsArgs)]
+    L.grl_blur_items.restype = C.c_int
     L.grl_debug_dirty_lds.argtypes = [C.c_void_p]
     L.grl_debug_dirty_lds.restype = C.c_int
     _lib = L

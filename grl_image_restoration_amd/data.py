@@ -151,6 +151,15 @@ class PatchSampler:
                   it.  The one deliberate difference from the reference's bsr path: the target is rounded to 8 bits (at most
                   1 / 510 off), and it is sharpened on the whole image rather than on a 400 x 400 crop, so a patch carries no
                   reflected crop border
+      sr with ``degrade``
+                  GT store only, scale 2 or 4: the reference's real-world-SR data path (restoration_bsr.py:83-110).  Per sample a
+                  ``degrade_crop`` x ``degrade_crop`` crop of a GT image is drawn (image, position and flags as for every task, at
+                  the crop size), with ``usm`` sharpened by ``tasks.usm_sharp`` -- the sharpened CROP is the degradation's input
+                  and the target (restoration_bsr.py:103-110), not a whole-image store as on the paired path -- and run through a
+                  freshly drawn ``bsr_degrade.draw_plan`` by ``bsr_degrade.apply_plans``; then one patch position is drawn in the
+                  crop / scale LQ and the aligned (lq, gt) patches are cut.  Images smaller than the crop are refused at
+                  construction: the store would pad them with zeros where the reference reflects them.  What is not built
+                  (camera noise, colour jitter): bsr_degrade's docstring
       sr_bicubic, jpeg at a fixed ``quality``
                   GT store only.  The LQ store is made once per image at construction (``tasks.TRAIN_STORE_LQ`` on the store's
                   device; sr_bicubic also replaces the GT store by the images cropped to the scale); then sampled as ``sr``
@@ -162,12 +171,15 @@ class PatchSampler:
     and ``randrange(W' - P + 1)`` with H' = max(H, P), W' = max(W, P) the LQ-side size after the reference's padding
     (_random_index on the padded image, base_image.py:252-256, 397-402); three ``random() < 0.5`` for the flags; with
     ``sigma_range`` one ``uniform(lo, hi)``; with ``quality_range`` one ``randint(lo, hi)`` in that place.  For db, P is P'.
+    With ``degrade``, P is the crop, and in that place come the draws of ``bsr_degrade.draw_plan`` and then
+    ``randrange(crop / scale - patch + 1)`` twice, the row and the column of the LQ patch.
     """
 
     def __init__(self, task: str, gt_store: PatchStore, lq_store: Optional[PatchStore] = None, patch: int = 64, batch: int = 8,
                  scale: int = 1, sigma: Optional[float] = None, sigma_range: Optional[Sequence[float]] = None, seed: int = 0,
                  taps: Optional[torch.Tensor] = None, quality: Optional[int] = None,
-                 quality_range: Optional[Sequence[int]] = None, patchwise: bool = True, usm: bool = False):
+                 quality_range: Optional[Sequence[int]] = None, patchwise: bool = True, usm: bool = False, degrade: bool = False,
+                 degrade_crop: int = 400):
         from . import tasks
 
         patch, batch, scale = int(patch), int(batch), int(scale)
@@ -175,13 +187,18 @@ class PatchSampler:
             raise ValueError(f"patch and batch must be positive, got {patch}, {batch}")
         o = resolve(task, "sampler", scale=scale, channels=gt_store.channels, lq=lq_store is not None, sigma=sigma,
                     sigma_range=sigma_range, taps=taps is not None, quality=quality, quality_range=quality_range, patch=patch,
-                    patchwise=patchwise, usm=usm)
+                    patchwise=patchwise, usm=usm, degrade=degrade, degrade_crop=degrade_crop if degrade else None)
         if taps is not None and (taps.dim() != 2 or taps.shape[0] != taps.shape[1] or taps.shape[0] % 2 == 0 or taps.shape[0] > 31):
             raise ValueError("taps: the (K, K) fp32 table of tasks.blur_taps, K odd and at most 31")
         store_lq = tasks.TRAIN_STORE_LQ.get(task) if o.quality_range is None else None
         if store_lq is not None:
             gt_store, lq_store = _derived_stores(gt_store, lambda gt: store_lq(gt, o), scale if o.rule.crop == "scale" else 1)
-        if usm:
+        if degrade:
+            small = [n for n, (H, W) in enumerate(gt_store.dims) if H < o.degrade_crop or W < o.degrade_crop]
+            if small:
+                raise ValueError(f"degrade: image {small[0]} ({gt_store.dims[small[0]][0]} x {gt_store.dims[small[0]][1]}) is smaller than "
+                                 f"the crop {o.degrade_crop}; the store pads with zeros where the reference reflects")
+        elif usm:
             gt_store = _usm_store(gt_store)
         if lq_store is not None:
             if len(lq_store) != len(gt_store) or lq_store.channels != gt_store.channels or lq_store.device != gt_store.device:
@@ -195,9 +212,12 @@ class PatchSampler:
         self.quality, self.quality_range = o.quality, o.quality_range
         self.rng = random.Random(seed)
         self.device = gt_store.device
-        self.gen = torch.Generator(device=self.device).manual_seed(int(seed)) if o.rule.noise else None
+        self.gen = torch.Generator(device=self.device).manual_seed(int(seed)) if o.rule.noise or degrade else None
+        self.degrade, self.degrade_crop, self.usm = bool(degrade), o.degrade_crop, bool(usm)
         self.taps = taps.to(device=self.device, dtype=torch.float32).contiguous() if taps is not None else None
         self.draw_patch = patch + (self.taps.shape[0] - 1 if taps is not None else 0)   # the side the draws and the crop use
+        if degrade:
+            self.draw_patch = o.degrade_crop
         self.work = torch.zeros(batch, 4, dtype=torch.int32, device=self.device)      # the device work list, rewritten in place
         # the device quality list of jpeg with a range, rewritten in place like the work list
         self.qualities = torch.zeros(batch, dtype=torch.int32, device=self.device) if quality_range is not None else None
@@ -206,7 +226,8 @@ class PatchSampler:
     # ---- draws ---------------------------------------------------------------------------------------------------------------
     def draw(self):
         """One batch of draws: ([(image, x, y, flags)] * batch, [sigma] * batch or None); for jpeg with a quality range the second
-        list holds the qualities."""
+        list holds the qualities, with ``degrade`` per sample (plan, row, column): the plan of ``bsr_degrade.draw_plan`` and the
+        place of the LQ patch."""
         sizes = (self.lq_store or self.gt_store).dims
         P, work, sigmas = self.draw_patch, [], []
         for _ in range(self.batch):
@@ -220,7 +241,12 @@ class PatchSampler:
                 sigmas.append(self.rng.uniform(*self.sigma_range))
             if self.quality_range is not None:
                 sigmas.append(self.rng.randint(*self.quality_range))
-        return work, (sigmas if self.sigma_range is not None or self.quality_range is not None else None)
+            if self.degrade:
+                from .bsr_degrade import draw_plan
+
+                plan, room = draw_plan(self.rng, self.scale, self.degrade_crop), self.degrade_crop // self.scale - self.patch + 1
+                sigmas.append((plan, self.rng.randrange(room), self.rng.randrange(room)))
+        return work, (sigmas if self.sigma_range is not None or self.quality_range is not None or self.degrade else None)
 
     def rng_state(self):
         """What a checkpoint keeps to continue the stream of batches: the draws' state and the noise generator's."""
@@ -235,7 +261,7 @@ class PatchSampler:
     def next(self, work=None, sigmas: Optional[Sequence[float]] = None, noise: Optional[torch.Tensor] = None):
         """(lq, gt) on the store's device.  ``work``: an explicit work list (a sequence of (image, x, y, flags) or an int32 (B, 4)
         tensor) instead of fresh draws; ``sigmas`` with it for dn with a sigma range and for jpeg with a quality range (the
-        qualities).  ``noise`` (db): a unit-variance
+        qualities) and for ``degrade`` (the (plan, row, column) per sample).  ``noise`` (db): a unit-variance
         (B, 3, patch, patch) fp32 tensor used instead of the generator's draw (it is scaled by ``sigma / 255``)."""
         if work is None:
             work, sigmas = self.draw()
@@ -243,11 +269,29 @@ class PatchSampler:
             wt = work.to(device=self.device, dtype=torch.int32).contiguous()
         else:
             wt = self.in_place(self.work, torch.tensor([list(w) for w in work], dtype=torch.int32).reshape(-1, 4))
+        if self.degrade:
+            return self._degraded(wt, sigmas)
         if self.lq_store is not None:                # paired stores, given or made at construction
             lq = self.lq_store.sample(wt, self.patch, 1)
             gt = self.gt_store.sample(wt, self.patch, self.scale)
             return lq, gt
         return self._pair(self, self.gt_store.sample(wt, self.draw_patch, 1), sigmas, noise)
+
+    def _degraded(self, wt, extras):
+        """The batch of ``degrade``: crops, their optional sharpening, the pipeline, the aligned patches."""
+        from . import tasks
+        from .bsr_degrade import apply_plans
+
+        if extras is None or len(extras) != wt.shape[0]:
+            raise ValueError("degrade: one (plan, row, column) per sample next to an explicit work list")
+        crops = self.gt_store.sample(wt, self.degrade_crop, 1)
+        if self.usm:
+            crops = tasks.usm_sharp(crops)
+        full = apply_plans(crops, [e[0] for e in extras], self.gen)
+        P, s = self.patch, self.scale
+        lq = torch.stack([full[b, :, r : r + P, c : c + P] for b, (_, r, c) in enumerate(extras)])
+        gt = torch.stack([crops[b, :, r * s : (r + P) * s, c * s : (c + P) * s] for b, (_, r, c) in enumerate(extras)])
+        return lq, gt
 
     @staticmethod
     def in_place(own: torch.Tensor, t: torch.Tensor) -> torch.Tensor:

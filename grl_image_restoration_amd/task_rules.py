@@ -26,6 +26,7 @@ class TaskRule:
     taps: bool = False                  # takes a blur kernel
     quality: bool = False               # takes a JPEG quality, or for training a quality range
     usm: bool = False                   # the GT may be USM-sharpened (use_usm / use_usm_pixel: restoration_sr.py:94,105-109)
+    degrade: bool = False               # training may make its LQ on the fly by the blind-SR degradation (restoration_bsr.py:83-110)
     save_tag: Optional[str] = None      # saved images go under X<scale> ("scale"), Sigma<sigma> ("sigma"), QF<quality> ("quality") or
                                         # straight under the data set's name (None): engines/base.py:504-524
 
@@ -33,7 +34,7 @@ class TaskRule:
 RULES = {
     "sr": TaskRule("classical SR from an LQ / GT folder pair (also deblurring and JPEG from folders): config/experiment/sr, "
                    "data/datasets/restoration_sr.py:97-123 with load_lr; USM-sharpened GT: config/experiment/bsr/grl_psnr.yaml:26-33",
-                   lq_from="folder", default_scale=4, max_scale=None, usm=True, save_tag="scale"),
+                   lq_from="folder", default_scale=4, max_scale=None, usm=True, degrade=True, save_tag="scale"),
     "dn": TaskRule("denoising: config/data_module/dn.yaml; training noise restoration_dn.py:126-143, seeded validation noise :133-143",
                    crop=8, noise=True, sigma_range=True, save_tag="sigma"),
     "dm": TaskRule("demosaicking: restoration_dm.py:25-35 (mosaic), engines/base.py:126-128 (dm_matlab before the model)",
@@ -55,13 +56,17 @@ SYNTHESISED = tuple(t for t in RULES if RULES[t].lq_from == "gt")
 
 
 def resolve(task, where, *, scale=None, channels=3, lq=False, sigma=None, sigma_range=None, taps=False, quality=None,
-            quality_range=None, patch=None, patchwise=True, val=False, val_lq=False, usm=False, val_usm=False):
+            quality_range=None, patch=None, patchwise=True, val=False, val_lq=False, usm=False, val_usm=False, degrade=False,
+            degrade_crop=None):
     """Checks the options of one call against ``RULES[task]``, fills the defaults and returns them as a namespace (``rule``,
     ``scale``, ``sigma``, ``sigma_range``, ``quality``, ``quality_range``).  Raises ValueError.  ``where`` is the caller: "evaluate" /
     "train" (the command lines), "evaluate_folder", "task_inputs", "sampler".  ``lq`` / ``taps``: whether an LQ folder or store / a blur
     kernel was given; ``val`` / ``val_lq`` (train): validation is on / has an LQ folder; ``usm`` / ``val_usm``: the GT (of training:
     the targets; of evaluation and of train's validation: the scored GT) is sharpened by ``tasks.usm_sharp``.  Where the callers
-    have always differed, the difference is a branch on ``where`` below, marked "kept".
+    have always differed, the difference is a branch on ``where`` below, marked "kept".  ``degrade`` (training): the LQ is made per
+    sample from a ``degrade_crop`` x ``degrade_crop`` GT crop (default 400) by ``bsr_degrade``; then no LQ folder or store is given,
+    the scale is 2 or 4, the images have three channels, the crop is a multiple of 4 and at least 4 * scale, and ``patch`` is at
+    most crop / scale.  The namespace also carries ``degrade_crop`` (None without ``degrade``).
     """
     training, library_eval = where in ("train", "sampler"), where in ("evaluate_folder", "task_inputs")
     r = RULES.get(task)
@@ -69,9 +74,17 @@ def resolve(task, where, *, scale=None, channels=3, lq=False, sigma=None, sigma_
         raise ValueError(f"unknown task {task!r}: one of {TRAIN_TASKS if training else TASKS}")
     if where == "task_inputs" and r.lq_from != "gt":
         raise ValueError(f"task {task!r} reads its LQ from a folder; synthesised tasks: {', '.join(SYNTHESISED)}")
+    if degrade:
+        if not training or not r.degrade:
+            raise ValueError(f"task {task} has no on-the-fly degradation (--degrade, degrade): only training of "
+                             f"{', '.join(t for t in RULES if RULES[t].degrade)} makes its LQ that way")
+        if lq:
+            raise ValueError(f"task {task} with degrade makes its LQ from the GT crops; an LQ folder (--lq) or store is not used")
+    elif degrade_crop is not None:
+        raise ValueError("degrade_crop (--degrade-crop) belongs to degrade (--degrade)")
     # kept: evaluate_folder ignores an LQ folder that the evaluate command line refuses
     if not library_eval:
-        if r.lq_from == "folder" and not lq:
+        if r.lq_from == "folder" and not lq and not degrade:
             raise ValueError(f"task {task} needs an LQ folder (--lq) or store")
         if r.lq_from == "gt" and (lq or val_lq):
             raise ValueError(f"task {task} builds its LQ from the GT; an LQ folder (--lq, --val-lq) or store is not used")
@@ -89,6 +102,16 @@ def resolve(task, where, *, scale=None, channels=3, lq=False, sigma=None, sigma_
     if checked and not r.min_scale <= scale <= (r.max_scale or scale):
         raise ValueError(f"task {task} restores at scale 1, got {scale}" if r.max_scale == 1 else
                          f"task {task} needs a scale of at least {r.min_scale}, got {scale}")
+    if degrade:
+        degrade_crop = 400 if degrade_crop is None else int(degrade_crop)
+        if scale not in (2, 4):
+            raise ValueError(f"task {task} with degrade is built for scales 2 and 4, got {scale}")
+        if channels != 3:
+            raise ValueError(f"task {task} with degrade works on RGB images (the correlated noise has a 3 x 3 covariance)")
+        if degrade_crop % 4 or degrade_crop < 4 * scale:
+            raise ValueError(f"task {task}: the degradation crop is a multiple of 4 and at least 4 * scale = {4 * scale}, got {degrade_crop}")
+        if patch is not None and patch > degrade_crop // scale:
+            raise ValueError(f"task {task}: a patch of {patch} does not fit the degraded crop of {degrade_crop // scale}")
     # kept: the evaluate command line checks the channels of db alone; dm on gray images fails later, in task_inputs
     if r.rgb_only and channels != 3 and (where != "evaluate" or r.taps):
         raise ValueError(f"task {task} works on RGB images")
@@ -135,7 +158,8 @@ def resolve(task, where, *, scale=None, channels=3, lq=False, sigma=None, sigma_
                 raise ValueError(f"task {task}: quality is 1 .. 100, got {quality}")
         elif val:
             raise ValueError(f"validation of task {task} needs a quality next to the quality range")
-    return SimpleNamespace(rule=r, scale=scale, sigma=sigma, sigma_range=sigma_range, quality=quality, quality_range=quality_range)
+    return SimpleNamespace(rule=r, scale=scale, sigma=sigma, sigma_range=sigma_range, quality=quality, quality_range=quality_range,
+                           degrade_crop=degrade_crop)
 
 
 # ---- the command lines ------------------------------------------------------------------------------------------------------------

@@ -17,6 +17,8 @@ Restates the pieces of the reference's training run that sit around ``model(x)``
         --milestones 250000+400000+450000+475000 --gamma 0.5 --out runs/sr_x4 --val-gt Set5/GTmod12 --val-lq Set5/LRbicx4
     python -m grl_image_restoration_amd.train --task sr --scale 4 --model base --geometry bsr_psnr --upsampler nearest+conv \\
         --usm --val-usm --weight-decay 0 --gt pairs/GT --lq pairs/LQ --val-gt Set5/GTmod12 --val-lq Set5/LRbicx4 ...
+    python -m grl_image_restoration_amd.train --task sr --scale 4 --model base --geometry bsr_psnr --upsampler nearest+conv \\
+        --degrade --usm --weight-decay 0 --gt DF2K/HR --val-gt frozen/GT --val-lq frozen/LQ ...      (no --lq: bsr_degrade makes it)
     python -m grl_image_restoration_amd.train --task sr_bicubic --scale 2 --model small --geometry sr_ckpt_df4 --gt DIV2K/HR ...
     python -m grl_image_restoration_amd.train --task dn --sigma 25 --model small --geometry dn_df4 --gt DFWB --ckpt dn_grl_small_c3s25.ckpt ...
     python -m grl_image_restoration_amd.train --task dm --model small --geometry dm --gt DFWB ...
@@ -117,6 +119,12 @@ def _parser():
     ap.add_argument("--usm", action="store_true",
                     help="--task sr: train against USM-sharpened targets (the reference's use_usm_pixel: True of bsr/grl_psnr.yaml); "
                          "every GT image is sharpened whole, once")
+    ap.add_argument("--degrade", action="store_true",
+                    help="--task sr at scale 2 or 4, without --lq: the LQ of every sample is made on the device from a GT crop by the "
+                         "blind-SR degradation (bsr_degrade: the reference's degradation_sr2, a fresh one per draw); with --usm the "
+                         "crop is sharpened first and is the target")
+    ap.add_argument("--degrade-crop", type=int, default=None,
+                    help="--degrade: side of the GT crop that is degraded (default 400, the reference's; a multiple of 4)")
     ap.add_argument("--val-usm", action="store_true", help="--task sr: validate against the USM-sharpened GT (val.use_usm: True)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--val-gt", default=None)
@@ -135,8 +143,9 @@ def _check(ap, a):
     if a.val_every and a.val_gt is None:
         ap.error("--val-every needs --val-gt")
     o = resolve_arguments(ap, a, "train", sigma_range=a.sigma_range, quality_range=a.quality_range, patch=a.patch,
-                          val=bool(a.val_every), val_lq=a.val_lq is not None, usm=a.usm, val_usm=a.val_usm)
-    a.scale, a.sigma = o.scale, o.sigma
+                          val=bool(a.val_every), val_lq=a.val_lq is not None, usm=a.usm, val_usm=a.val_usm, degrade=a.degrade,
+                          degrade_crop=a.degrade_crop)
+    a.scale, a.sigma, a.degrade_crop = o.scale, o.sigma, o.degrade_crop
     if a.patch < 1 or a.batch < 1 or a.steps < 0:
         ap.error("--patch and --batch must be positive")
     if a.save_every and a.out is None:
@@ -195,7 +204,8 @@ def main(argv: Optional[List[str]] = None):
     lq_store = D.PatchStore.from_folder(a.lq, a.channels, device) if a.lq is not None else None
     sampler = D.PatchSampler(a.task, gt_store, lq_store, patch=a.patch, batch=a.batch, scale=a.scale, sigma=a.sigma,
                              sigma_range=a.sigma_range, seed=a.seed + rank, taps=taps,
-                             quality=a.quality if a.quality_range is None else None, quality_range=a.quality_range, usm=a.usm)
+                             quality=a.quality if a.quality_range is None else None, quality_range=a.quality_range, usm=a.usm,
+                             **(dict(degrade=True, degrade_crop=a.degrade_crop) if a.degrade else {}))
 
     opt = FusedAdamW(model.parameters(), lr=a.lr, weight_decay=a.weight_decay)
     start = 0

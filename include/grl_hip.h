@@ -23,7 +23,7 @@ extern "C" {
 
 #define GRL_ERR_BAD_ARG (-1)
 #define GRL_ERR_UNSUPPORTED (-2)
-#define GRL_ABI_VERSION 31
+#define GRL_ABI_VERSION 32
 
 /* element kinds of activation / weight buffers */
 enum { GRL_DT_F32 = 0, GRL_DT_BF16 = 1, GRL_DT_F16 = 2 };
@@ -945,6 +945,79 @@ typedef struct GrlUsmArgs {
 
 int64_t grl_usm_workspace_bytes(int32_t N, int32_t C, int32_t H, int32_t W);
 int grl_usm_sharp(void* stream, const GrlUsmArgs* args);
+
+/* The two image kernels of the blind-SR degradation pipeline (ABI 32; the on-the-fly LQ of real-world SR training,
+ * bsr_degrade.py).  Inside one batch every sample has its own size, taps and mode, so both work on an ITEM LIST in DEVICE memory,
+ * the idiom of grl_sample_patches: one launch serves all items of a call, nothing is allocated, the host does not synchronise, and
+ * the launch stays valid inside a captured graph while the list's contents change.  An item names a source image, contiguous fp32
+ * (C, h, w) at an ELEMENT offset into the source arena, and a destination image, contiguous fp32 at an element offset into the
+ * destination arena; the two arenas may be one buffer as long as no item's destination overlaps any item's source.  The result of
+ * an item does not depend on which other items share the launch.
+ * What the host can see is checked on the host (GRL_ERR_BAD_ARG, nothing is launched).  The sizes, offsets and parameters of an item
+ * exist in the device table only; for them the HOST WRAPPER VOUCHES: that max_ho / max_wo (and max_K) are at least every item's
+ * output size (and K) -- the grid is sized from them, surplus workgroups leave, and an item beyond them would be computed only
+ * where the grid reaches -- and that the destinations of a call do not overlap.  Everything else the kernel checks itself: an item
+ * whose source or destination does not lie inside src_elems / dst_elems (its taps inside taps_elems), or whose size, mode, K or
+ * stride is out of range, is skipped whole, so no list content makes the kernels read or write outside the buffers.
+ *
+ * grl_cv_resize: OpenCV's resize, INTER_LINEAR / INTER_CUBIC / INTER_AREA
+ *   replaces  cv2.resize(img, (int(1/2 w), int(1/2 h)), interpolation=random.choice([1, 2, 3]))        utils/utils_bsr/utils_sisr.py:299-303
+ *             cv2.resize(img, (int(1/sf1 w), int(1/sf1 h)), interpolation=random.choice([1, 2, 3]))    utils/utils_bsr/utils_sisr.py:350-354
+ *             cv2.resize(img, (int(1/sf a), int(1/sf b)), interpolation=random.choice([1, 2, 3]))      utils/utils_bsr/utils_sisr.py:416-420
+ * items[i] = {src_off, dst_off, h, w, ho, wo, interp, 0}: (C, h, w) -> (C, ho, wo); interp 1, 2, 3 are cv2.INTER_LINEAR, INTER_CUBIC,
+ * INTER_AREA.  Per axis, scale = n / no; coordinates and weights in float64, each weight rounded once to fp32; tap indices outside
+ * the image clamp to the edge:
+ *   linear  f = (d + 0.5) scale - 0.5, i = floor(f), t = f - i; i < 0: i = 0, t = 0; i >= n - 1: i = n - 1, t = 0; taps i, i + 1: 1 - t, t
+ *   cubic   the same f, i, t without the clamps; taps i - 1 .. i + 2, A = -0.75: c0 = ((A(t+1) - 5A)(t+1) + 8A)(t+1) - 4A,
+ *           c1 = ((A+2)t - (A+3))t^2 + 1, c2 = c1's form at 1 - t, c3 = 1 - c0 - c1 - c2
+ *   area    h >= ho and w >= wo: the coverage table -- f1 = d scale, f2 = f1 + scale, cell = min(scale, n - f1), s1 = ceil(f1),
+ *           s2 = min(floor(f2), n - 1), s1 = min(s1, s2); (s1 - f1) / cell on s1 - 1 if s1 - f1 > 1e-3; 1 / cell on s1 .. s2 - 1;
+ *           min(min(f2 - s2, 1), cell) / cell on s2 if f2 - s2 > 1e-3
+ *           otherwise: the linear taps (and clamps) with i = floor(d scale), t = (d + 1) - (i + 1) / scale, t = 0 if t <= 0 else
+ *           t - floor(t), on both axes
+ *   out[oy][ox] = chain_ky wy[ky] * fl32(chain_kx wx[kx] * src[iy(ky)][ix(kx)]), each chain an fp32 fmaf chain from 0 in ascending tap
+ *   order: the horizontal pass, then the vertical one.
+ * This is OpenCV's sampling rule with float64 coordinates.  OpenCV rounds the coordinate to fp32 first, which moves a weight by up to
+ * n * 2^-24; equality with OpenCV's bytes is not claimed.
+ * Errors (GRL_ERR_BAD_ARG): a null args / src / dst / items, C not 1 / 3, a non-positive n_items, max_ho, max_wo, src_elems or
+ * dst_elems, max_ho or max_wo above 2^20, more than 65535 items, src / dst not 4-byte or items not 8-byte aligned. */
+typedef struct GrlCvResizeArgs {
+    const float* src;           /* source arena                                                   */
+    float* dst;                 /* destination arena                                              */
+    int64_t src_elems, dst_elems; /* their lengths in floats: no item reads / writes beyond them  */
+    const int64_t* items;       /* [n_items][8] device: src_off, dst_off, h, w, ho, wo, interp, 0 */
+    int32_t n_items, C;
+    int32_t max_ho, max_wo;     /* host-known maxima of ho, wo over the items (vouched for)       */
+} GrlCvResizeArgs;
+
+int grl_cv_resize(void* stream, const GrlCvResizeArgs* args);
+
+/* grl_blur_items: K x K blur with scipy's `mirror` boundary, per-item taps and a stride
+ *   replaces  ndimage.filters.convolve(img, np.expand_dims(k, axis=2), mode="mirror")                  utils/utils_bsr/utils_sisr.py:341-343, 410-412
+ *             ndimage.filters.convolve(img, k_shifted[..., None], mode="mirror"); img[0::sf, 0::sf]     utils/utils_bsr/utils_sisr.py:359-362
+ * items[i] = {src_off, dst_off, h, w, K, s, taps_off, 0}: (C, h, w) -> (C, ceil(h / s), ceil(w / s)); K odd, 1 .. max_K <= 31; s >= 1;
+ * the item's K x K fp32 taps, row major, at element taps_off of `taps`.  One tap table serves the item's channels.
+ *   out[oy][ox] = sum over ky (outer), kx (inner) of taps[ky][kx] * x[m(oy s - K/2 + ky, h)][m(ox s - K/2 + kx, w)]
+ *   m(i, n): scipy's mirror (reflect-101), folded as often as needed: n == 1 -> 0; else j = i mod 2(n-1); j >= n ? 2(n-1) - j : j
+ * (after a large downscale the image is smaller than the kernel).  One fp32 fmaf chain from 0 in that order, as grl_blur_depthwise.
+ * The taps are CORRELATION taps: ndimage.convolve convolves, so the caller passes the kernel flipped over both axes
+ * (tasks.blur_taps).  Only the strided outputs are computed.
+ * Errors (GRL_ERR_BAD_ARG): a null args / src / dst / taps / items, C not 1 / 3, max_K even or outside 1 .. 31, a non-positive n_items,
+ * max_ho, max_wo, src_elems, dst_elems or taps_elems, max_ho or max_wo above 2^20, n_items * C above 65535, src / dst / taps not
+ * 4-byte or items not 8-byte aligned. */
+typedef struct GrlBlurItemsArgs {
+    const float* src;           /* source arena                                                   */
+    float* dst;                 /* destination arena                                              */
+    const float* taps;          /* taps buffer, device                                            */
+    int64_t src_elems, dst_elems, taps_elems;
+    const int64_t* items;       /* [n_items][8] device: src_off, dst_off, h, w, K, s, taps_off, 0 */
+    int32_t n_items, C;
+    int32_t max_ho, max_wo;     /* host-known maxima of ceil(h / s), ceil(w / s) (vouched for)    */
+    int32_t max_K;              /* host-known maximum of K: odd, 1 .. 31                          */
+    int32_t reserved0;
+} GrlBlurItemsArgs;
+
+int grl_blur_items(void* stream, const GrlBlurItemsArgs* args);
 
 /* Debug aid (ABI 21; no reference counterpart): fills the LDS of every CU with 0xFF bytes (fp32 / fp16 NaN) by a launch on
  * `stream`.  LDS keeps what the previous workgroup left in it; a kernel that reads LDS it has not written is otherwise right or

@@ -1,0 +1,207 @@
+"""GPU tests of ``grl_cv_resize`` (csrc/cvresize.hip) and ``grl_blur_items`` (csrc/blur_items.hip) through ``bsr_degrade``, of the
+pipeline on the device and of ``PatchSampler(degrade=True)``.  The yardsticks, the fixture and the derivation of ``resize_bound`` and
+``blur_bound``: tests/test_degrade.py's docstring.  In short, with u = 2^-24 and inputs in [0, 1]: a resized value is within
+(n_x + n_y + 8) u of the float64 CPU path (n: the taps per axis), twice that for cubic; a blurred value within (K^2 + 2) u of scipy's
+float64 ``convolve(mode="mirror")``.
+
+The pipeline test (blur and resize stages only) walks every plan and carries the bound from stage to stage: a stage with weights of
+absolute sum S per axis (1, or at most 1.375 for cubic) passes an input error e on as at most S^2 e <= 2 e and adds its own bound;
+MATLAB's imresize by 1 / 2 (fp64 sums on the device, rounded once; its bicubic weights have an absolute sum below 1.25 per axis) passes
+1.6 e on and adds 2 u; a clip passes e on unchanged.  The CPU path rounds every stage's float64 result to fp32 once: u more per stage.
+"""
+import ctypes as C
+import random
+
+import numpy as np
+import pytest
+import torch
+
+from grl_image_restoration_amd import PatchSampler, PatchStore, _lib, bsr_degrade as B, tasks as T
+from tests.test_degrade import U24, blur_bound, fixture, resize_bound
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+
+# (shape, (ho, wo)) of the mixed resize launch, each at interp 1, 2 and 3; the last two area cases are upscales
+RESIZE_CASES = [((3, 37, 53), (9, 13)), ((3, 37, 53), (74, 106)), ((3, 36, 48), (12, 16)), ((3, 1, 9), (1, 4)), ((3, 8, 1), (3, 1)),
+                ((3, 50, 50), (100, 100))]
+GRAY_CASE = ((1, 70, 150), (33, 71))
+
+
+@pytest.fixture(scope="module")
+def fx():
+    return fixture()
+
+
+@pytest.fixture(scope="module")
+def resize_items():
+    """(images on the CPU, sizes, interps) of the mixed launch, and the float64 CPU results, computed once."""
+    g = torch.Generator().manual_seed(5)
+    imgs, sizes, interps = [], [], []
+    for shape, size in RESIZE_CASES:
+        x = torch.rand(*shape, generator=g)
+        for ip in (1, 2, 3):
+            imgs.append(x)
+            sizes.append(size)
+            interps.append(ip)
+    want = B.cv_resize([x.double() for x in imgs], sizes, interps)
+    return imgs, sizes, interps, want
+
+
+def test_resize_mixed_launch_against_the_float64_path(resize_items):
+    imgs, sizes, interps, want = resize_items
+    got = B.cv_resize([x.to(DEV) for x in imgs], sizes, interps)
+    torch.cuda.synchronize()
+    for x, size, ip, g, w in zip(imgs, sizes, interps, got, want):
+        b = resize_bound(ip, x.shape[1], x.shape[2], *size)
+        err = float((g.double().cpu() - w).abs().max())
+        print(f"{tuple(x.shape)} -> {size} interp {ip}: max|err| = {err:.3e} = {err / U24:.2f} u, bound {b / U24:.0f} u")
+        assert g.shape == w.shape and g.dtype == torch.float32 and err <= b
+    # one channel: a launch of its own (C belongs to the call)
+    shape, size = GRAY_CASE
+    x = torch.rand(*shape, generator=torch.Generator().manual_seed(6))
+    for ip, g, w in zip((1, 2, 3), B.cv_resize([x.to(DEV)] * 3, [size] * 3, [1, 2, 3]), B.cv_resize([x.double()] * 3, [size] * 3, [1, 2, 3])):
+        err = float((g.double().cpu() - w).abs().max())
+        print(f"{shape} -> {size} interp {ip}: max|err| = {err / U24:.2f} u")
+        assert err <= resize_bound(ip, shape[1], shape[2], *size)
+
+
+def test_resize_item_alone_equals_the_item_in_the_mixed_list(resize_items):
+    imgs, sizes, interps, _ = resize_items
+    mixed = B.cv_resize([x.to(DEV) for x in imgs], sizes, interps)
+    for i in (0, 2, 4, 5, 8, 11, 14, 17):
+        alone = B.cv_resize([imgs[i].to(DEV)], [sizes[i]], [interps[i]])[0]
+        assert torch.equal(alone, mixed[i]), i
+
+
+def test_blur_mixed_launch_against_the_fixture(fx):
+    for Cn in (3, 1):
+        names = [n for n in fx.blur if fx.blur[n]["x"].shape[0] == Cn]
+        got = B.blur_items([fx.blur[n]["x"].to(DEV) for n in names], [fx.blur[n]["taps"] for n in names], [fx.blur[n]["stride"] for n in names])
+        torch.cuda.synchronize()
+        for n, g in zip(names, got):
+            c = fx.blur[n]
+            err, b = np.abs(g.double().cpu().numpy() - c["out"]).max(), blur_bound(c["K"], c["x"])
+            print(f"{n}: max|err| = {err:.3e} = {err / U24:.1f} u, bound {b / U24:.0f} u")
+            assert g.shape == c["out"].shape and g.dtype == torch.float32 and err <= b
+        if Cn == 3:
+            for n, g in zip(names, got):
+                c = fx.blur[n]
+                alone = B.blur_items([c["x"].to(DEV)], [c["taps"]], [c["stride"]])[0]
+                assert torch.equal(alone, g), n
+
+
+def _refused(fn, struct, fields):
+    """The call returns GRL_ERR_BAD_ARG and leaves a sentinel-filled destination untouched.  ``dst`` absent: the sentinel buffer."""
+    out = torch.full((3 * 8 * 8,), -7.0, device=DEV)
+    fields = dict({"dst": out.data_ptr()}, **fields)
+    code = fn(_lib.stream_ptr(), C.byref(struct(**fields)))
+    torch.cuda.synchronize()
+    assert code == -1 and bool((out == -7.0).all()), fields
+
+
+def test_bad_arguments_launch_nothing():
+    L = _lib.lib()
+    src = torch.rand(3 * 8 * 8, device=DEV)
+    taps = torch.rand(9, device=DEV)
+    ri = torch.tensor([[0, 0, 8, 8, 8, 8, 1, 0]], dtype=torch.int64, device=DEV)
+    bi = torch.tensor([[0, 0, 8, 8, 3, 1, 0, 0]], dtype=torch.int64, device=DEV)
+    good_r = dict(src=src.data_ptr(), src_elems=192, dst_elems=192, items=ri.data_ptr(), n_items=1, C=3, max_ho=8, max_wo=8)
+    good_b = dict(src=src.data_ptr(), taps=taps.data_ptr(), src_elems=192, dst_elems=192, taps_elems=9, items=bi.data_ptr(), n_items=1,
+                  C=3, max_ho=8, max_wo=8, max_K=3)
+    bad_common = [dict(src=None), dict(items=None), dict(dst=None), dict(C=2), dict(C=0), dict(n_items=0), dict(n_items=-1), dict(max_ho=0),
+                  dict(max_wo=-3), dict(src_elems=0), dict(dst_elems=0), dict(src=src.data_ptr() + 2), dict(items=ri.data_ptr() + 4)]
+    for bad in bad_common:
+        _refused(L.grl_cv_resize, _lib.GrlCvResizeArgs, dict(good_r, **bad))
+    for bad in bad_common + [dict(taps=None), dict(max_K=4), dict(max_K=33), dict(max_K=0), dict(taps_elems=0), dict(taps=taps.data_ptr() + 1)]:
+        if bad.get("items") is not None:
+            bad = dict(items=bi.data_ptr() + 4)
+        _refused(L.grl_blur_items, _lib.GrlBlurItemsArgs, dict(good_b, **bad))
+    assert L.grl_cv_resize(_lib.stream_ptr(), None) == -1 and L.grl_blur_items(_lib.stream_ptr(), None) == -1
+    # what only the device table holds: an item that does not fit the arenas, or with a mode / K out of range, is skipped whole
+    out = torch.full((192,), -7.0, device=DEV)
+    for row in ([0, 64, 8, 8, 8, 8, 1, 0], [64, 0, 8, 8, 8, 8, 1, 0], [0, 0, 8, 8, 8, 8, 4, 0], [0, 0, 8, 8, 0, 8, 1, 0], [0, -1, 8, 8, 8, 8, 1, 0]):
+        t = torch.tensor([row], dtype=torch.int64, device=DEV)
+        assert L.grl_cv_resize(_lib.stream_ptr(), C.byref(_lib.GrlCvResizeArgs(**dict(good_r, dst=out.data_ptr(), items=t.data_ptr())))) == 0
+    for row in ([0, 64, 8, 8, 3, 1, 0, 0], [0, 0, 8, 8, 2, 1, 0, 0], [0, 0, 8, 8, 5, 1, 0, 0], [0, 0, 8, 8, 3, 0, 0, 0], [0, 0, 8, 8, 3, 1, 1, 0]):
+        t = torch.tensor([row], dtype=torch.int64, device=DEV)
+        assert L.grl_blur_items(_lib.stream_ptr(), C.byref(_lib.GrlBlurItemsArgs(**dict(good_b, dst=out.data_ptr(), items=t.data_ptr())))) == 0
+    torch.cuda.synchronize()
+    assert bool((out == -7.0).all())
+
+
+def _pipeline_bound(plan, crop):
+    """The bound of the module docstring carried through one plan of blur / resize / clip / imresize ops."""
+    e, size = 0.0, crop
+    for op in plan:
+        if op["op"] == "resize":
+            e = 2 * e + resize_bound(op["interp"], size, size, op["size"], op["size"]) + U24
+        elif op["op"] == "blur":
+            e = e + (op["kernel"].shape[0] ** 2 + 2) * U24 + U24
+        elif op["op"] == "imresize_half":
+            e = 1.6 * e + 2 * U24 + U24
+        elif op["op"] not in ("clip", "jpeg_final"):
+            raise AssertionError(op["op"])
+        size = op["size"]
+    return e
+
+
+def test_apply_plans_blur_and_resize_stages_against_the_cpu():
+    rng = random.Random(4)
+    plans = [B.draw_plan(rng, 4, 64, stages=(0, 1, 5, 6)) for _ in range(4)]
+    x = torch.rand(4, 3, 64, 64, generator=torch.Generator().manual_seed(2))
+    _, want, q = B.apply_plans(x, plans, parts=True)
+    out, got, qd = B.apply_plans(x.to(DEV), plans, parts=True)
+    assert got.shape == want.shape == (4, 3, 16, 16) and torch.equal(q, qd.cpu())
+    for b, plan in enumerate(plans):
+        err, bound = float((got[b].cpu().double() - want[b].double()).abs().max()), _pipeline_bound(plan, 64)
+        print(f"sample {b}: {[op['op'] for op in plan]} max|err| = {err / U24:.1f} u, bound {bound / U24:.0f} u")
+        assert err <= bound
+    assert torch.equal(out, T.jpeg_roundtrip(got, q))
+
+
+@pytest.fixture(scope="module")
+def store():
+    g = np.random.RandomState(1)
+    return [g.randint(0, 256, (h, w, 3)).astype(np.uint8) for h, w in ((70, 80), (64, 96), (90, 64))]
+
+
+def test_full_pipeline_on_a_cuda_store(store):
+    st = PatchStore(store, DEV)
+    rng = random.Random(9)
+    work = torch.tensor([[n % 3, 0, 0, n % 8] for n in range(6)], dtype=torch.int32, device=DEV)
+    x = st.sample(work, 64, 1)
+    plans = [B.draw_plan(rng, 4, 64) for _ in range(6)]
+    run = lambda seed: B.apply_plans(x, plans, torch.Generator(device=DEV).manual_seed(seed), parts=True)
+    out, pre, q = run(0)
+    assert out.shape == (6, 3, 16, 16) and out.dtype == torch.float32 and out.is_cuda
+    assert 0 <= float(out.min()) and float(out.max()) <= 1 and 0 <= float(pre.min()) and float(pre.max()) <= 1
+    k = out.cpu() * 255
+    assert torch.equal(k.round().div(255), out.cpu()), "the k / 255 grid"
+    assert torch.equal(out, T.jpeg_roundtrip(pre, q)) and q.tolist() == [p[-1]["quality"] for p in plans]
+    again = run(0)
+    assert torch.equal(again[0], out) and torch.equal(again[1], pre)
+    assert not torch.equal(run(1)[1], pre)
+
+
+def test_sampler_with_degrade_on_the_device(store):
+    make = lambda dev, **kw: PatchSampler("sr", PatchStore(store, dev), degrade=True, degrade_crop=64, patch=8, scale=4, batch=4, seed=5, **kw)
+    plain = lambda e: [([{k: (v.tolist() if isinstance(v, np.ndarray) else v) for k, v in op.items()} for op in p], r, c) for p, r, c in e]
+    for usm in (False, True):
+        s, cpu = make(DEV, usm=usm), make("cpu", usm=usm)
+        work, extras = s.draw()
+        cwork, cextras = cpu.draw()
+        assert work == cwork and plain(extras) == plain(cextras), "CPU and CUDA samplers make identical draws"
+        state = s.rng_state()
+        lq, gt = s.next(work, extras)
+        assert lq.shape == (4, 3, 8, 8) and gt.shape == (4, 3, 32, 32) and lq.is_cuda and gt.is_cuda
+        crops = s.gt_store.sample(torch.tensor(work, dtype=torch.int32, device=DEV), 64, 1)
+        if usm:
+            crops = T.usm_sharp(crops)
+        gen = torch.Generator(device=DEV)
+        gen.set_state(state["noise"])
+        full = B.apply_plans(crops, [e[0] for e in extras], gen)
+        for b, (_, r, c) in enumerate(extras):
+            assert torch.equal(gt[b], crops[b, :, 4 * r : 4 * r + 32, 4 * c : 4 * c + 32])
+            assert torch.equal(lq[b], full[b, :, r : r + 8, c : c + 8])
+        assert s.draw()[0] == cpu.draw()[0]

@@ -1,0 +1,193 @@
+"""Times the blind-SR degradation on the GPU: ``grl_cv_resize`` alone and ``grl_blur_items`` alone (eight 3 x 400 x 400 items per
+launch, the item tables already on the device), and ``bsr_degrade.apply_plans`` for a batch of 8 crops of 400 at scale 4 with the plans
+of ``random.Random(0)`` -- host work included: grouping the plans, uploading item tables and taps, the per-sample noise expressions.
+Kernels: warm-up, then the median over --reps measurements, each the time between two device events around --inner back-to-back
+launches, divided by --inner.  The pipeline: the median wall-clock time of --reps synchronised calls, and where it goes by kind of op
+(each kind timed with a synchronisation around it in one extra pass, so the shares are upper bounds).  The kernels are first checked
+against the float64 CPU path within the bounds of tests/test_degrade.py.  With --train-step, the captured training step of bench.py's
+training leg (GRL-Base x4, batch 8 of 64 x 64 LQ, L1, FusedAdamW) is timed in the same process for scale.  One JSON line per
+measurement, printed and written to --out.
+
+    python tools/bench_degrade.py [--reps 20] [--warmup 3] [--inner 10] [--train-step] [--out profiles/degrade_bench_line.json]
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import random
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+from grl_image_restoration_amd import _lib, bsr_degrade as B, tasks as T  # noqa: E402
+from tools.bench_metrics import _median_ms  # noqa: E402
+
+U24 = 2.0 ** -24
+N, CROP, SCALE = 8, 400, 4
+SLOT = 3 * CROP * CROP
+
+
+def _resize_case(dev):
+    """Eight crops -> 100 .. 310 with the three modes in turn (stage 1's range of sizes), and 400 -> 100 area (stage 6)."""
+    sizes = [100, 130, 160, 190, 220, 250, 280, 310]
+    items = [(b * SLOT, b * SLOT, CROP, CROP, s, s, 1 + b % 3, 0) for b, s in enumerate(sizes)]
+    return items, B._items_tensor(items, dev)
+
+
+def _blur_case(dev, K, stride):
+    g = torch.Generator().manual_seed(K)
+    taps = torch.rand(N, K, K, generator=g)
+    taps = (taps / taps.sum((1, 2), keepdim=True)).to(dev)
+    items = [(b * SLOT, b * SLOT, CROP, CROP, K, stride, b * K * K, 0) for b in range(N)]
+    return items, B._items_tensor(items, dev), taps
+
+
+def _check(x):
+    """Both kernels against the float64 CPU path on two of the eight items: (resize error / bound, blur error / bound)."""
+    imgs = [x[0].cpu(), x[1].cpu()]
+    sizes, interps = [(100, 100), (130, 130)], [3, 2]
+    got = B.cv_resize([i.cuda() for i in imgs], sizes, interps)
+    want = B.cv_resize([i.double() for i in imgs], sizes, interps)
+    r = 0.0
+    for g, w, ip, s in zip(got, want, interps, sizes):
+        ny, nx = B.resize_taps(ip, CROP, CROP, *s)
+        r = max(r, float((g.double().cpu() - w).abs().max()) / ((nx + ny + 8) * U24 * (2 if ip == 2 else 1)))
+    taps = torch.rand(25, 25, generator=torch.Generator().manual_seed(1))
+    taps = taps / taps.sum()
+    got = B.blur_items([imgs[0].cuda()], [taps], [4])[0]
+    want = B.blur_items([imgs[0].double()], [taps.double()], [4])[0]
+    return r, float((got.double().cpu() - want).abs().max()) / ((625 + 2) * U24)
+
+
+def _train_step_ms(steps):
+    from grl_image_restoration_amd import GRL, FusedAdamW, GraphedTrainStep, baseline_config
+
+    cfg = baseline_config(5)
+    g = torch.Generator().manual_seed(100)
+    lq = torch.rand(8, 3, 64, 64, generator=g).cuda()
+    gt = torch.rand(8, 3, 64 * cfg["upscale"], 64 * cfg["upscale"], generator=g).cuda()
+    torch.manual_seed(0)
+    model = GRL(**cfg).cuda().train()
+    opt = FusedAdamW(model.parameters(), lr=2e-4, weight_decay=1e-4)
+    step = GraphedTrainStep(model, opt, lambda y, t: (y - t).abs().mean(), lq, gt, warmup=1)
+    for _ in range(2):
+        step(lq, gt)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        step(lq, gt)
+    torch.cuda.synchronize()
+    ms = (time.perf_counter() - t0) / steps * 1e3
+    step.finish()
+    return ms
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--inner", type=int, default=10)
+    ap.add_argument("--train-step", action="store_true", help="also time the captured training step of bench.py's training leg")
+    ap.add_argument("--train-steps", type=int, default=5)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "degrade_bench_line.json"))
+    a = ap.parse_args(argv)
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_degrade needs the GPU")
+    dev = torch.device("cuda:0")
+    L = _lib.lib()
+    name = torch.cuda.get_device_name(0)
+    x = torch.rand(N, 3, CROP, CROP, generator=torch.Generator().manual_seed(0)).to(dev)
+    src, dst = x.reshape(-1).contiguous(), torch.empty(N * SLOT, dtype=torch.float32, device=dev)
+    r_ok, b_ok = _check(x)
+    lines = []
+
+    def emit(line):
+        line = dict(line, device=name, reps=a.reps, inner=a.inner)
+        print(json.dumps(line), flush=True)
+        lines.append(json.dumps(line))
+
+    items, table = _resize_case(dev)
+    args = _lib.GrlCvResizeArgs(src=src.data_ptr(), dst=dst.data_ptr(), src_elems=src.numel(), dst_elems=dst.numel(), items=table.data_ptr(),
+                                n_items=N, C=3, max_ho=max(i[4] for i in items), max_wo=max(i[5] for i in items))
+
+    def resize():
+        for _ in range(a.inner):
+            _lib.check(L.grl_cv_resize(_lib.stream_ptr(), C.byref(args)), "grl_cv_resize")
+
+    k = [t / a.inner for t in _median_ms(resize, a.reps, a.warmup)]
+    emit({"workload": "grl_cv_resize: 8 items 3x400x400 -> 100 .. 310, linear / cubic / area in turn, one launch",
+          "hip_us_median": round(k[0] * 1e3, 2), "hip_us_min": round(k[1] * 1e3, 2), "hip_us_max": round(k[2] * 1e3, 2),
+          "error_over_bound_vs_cpu": round(r_ok, 3)})
+    for K, stride in ((25, 1), (25, 4), (9, 1)):
+        items, table, taps = _blur_case(dev, K, stride)
+        bargs = _lib.GrlBlurItemsArgs(src=src.data_ptr(), dst=dst.data_ptr(), taps=taps.data_ptr(), src_elems=src.numel(), dst_elems=dst.numel(),
+                                      taps_elems=taps.numel(), items=table.data_ptr(), n_items=N, C=3, max_ho=-(-CROP // stride),
+                                      max_wo=-(-CROP // stride), max_K=K)
+
+        def blur():
+            for _ in range(a.inner):
+                _lib.check(L.grl_blur_items(_lib.stream_ptr(), C.byref(bargs)), "grl_blur_items")
+
+        k = [t / a.inner for t in _median_ms(blur, a.reps, a.warmup)]
+        emit({"workload": f"grl_blur_items: 8 items 3x400x400, K = {K}, stride {stride}, one launch", "hip_us_median": round(k[0] * 1e3, 2),
+              "hip_us_min": round(k[1] * 1e3, 2), "hip_us_max": round(k[2] * 1e3, 2), "error_over_bound_vs_cpu": round(b_ok, 3)})
+
+    rng = random.Random(0)
+    plans = [B.draw_plan(rng, SCALE, CROP) for _ in range(N)]
+    gen = torch.Generator(device=dev).manual_seed(0)
+    ts = []
+    for i in range(a.warmup + a.reps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = B.apply_plans(x, plans, gen)
+        torch.cuda.synchronize()
+        if i >= a.warmup:
+            ts.append((time.perf_counter() - t0) * 1e3)
+    ts.sort()
+    assert out.shape == (N, 3, CROP // SCALE, CROP // SCALE)
+
+    # where the time goes: every kind of op wrapped with a synchronisation on both sides, in one extra pass
+    spent = {}
+
+    def timed(kind, fn):
+        def wrapper(*args, **kw):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            r = fn(*args, **kw)
+            torch.cuda.synchronize()
+            spent[kind] = spent.get(kind, 0.0) + (time.perf_counter() - t0) * 1e3
+            return r
+        return wrapper
+
+    saved = (B._run_resize, B._run_blur, B.add_noise, T.jpeg_roundtrip, T.imresize)
+    B._run_resize, B._run_blur, B.add_noise = timed("resize", saved[0]), timed("blur", saved[1]), timed("noise", saved[2])
+    T.jpeg_roundtrip, T.imresize = timed("jpeg", saved[3]), timed("imresize", saved[4])
+    try:
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        B.apply_plans(x, plans, gen)
+        torch.cuda.synchronize()
+        total = (time.perf_counter() - t0) * 1e3
+    finally:
+        B._run_resize, B._run_blur, B.add_noise, T.jpeg_roundtrip, T.imresize = saved
+    spent["other (clips, copies, host)"] = max(total - sum(spent.values()), 0.0)
+    line = {"workload": f"apply_plans: batch {N}, crop {CROP}, scale {SCALE}, plans of random.Random(0), host work included",
+            "ms_median": round(ts[len(ts) // 2], 3), "ms_min": round(ts[0], 3), "ms_max": round(ts[-1], 3),
+            "ops": sorted({op["op"] for p in plans for op in p}),
+            "ms_by_kind_synchronised": {k: round(v, 3) for k, v in sorted(spent.items(), key=lambda kv: -kv[1])}}
+    if a.train_step:
+        line["train_step_ms"] = round(_train_step_ms(a.train_steps), 2)
+        line["share_of_train_step"] = round(line["ms_median"] / line["train_step_ms"], 4)
+    emit(line)
+    with open(a.out, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    if r_ok > 1 or b_ok > 1:
+        raise SystemExit("bench_degrade: a kernel is outside its derived bound")
+
+
+if __name__ == "__main__":
+    main()
