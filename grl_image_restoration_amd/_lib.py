@@ -16,66 +16,6 @@ DT_F32, DT_BF16, DT_F16 = 0, 1, 2
 
 EPI_PLAIN, EPI_GELU, EPI_GROUPNORM, EPI_LN_RES, EPI_GELU_GRAD = 0, 1, 2, 3, 4
 
-# every symbol include/grl_hip.h declares (tests check the .so exports all of them)
-EXPORTS = [
-    "grl_linear_fwd",
-    "grl_linear_split_blob_bytes",
-    "grl_mlp_fwd",
-    "grl_mlp_blob_bytes",
-    "grl_block_tail_fwd",
-    "grl_proj_blob_bytes",
-    "grl_tail_regs_blob_bytes",
-    "grl_qkv_fwd",
-    "grl_qkv_blob_bytes",
-    "grl_qkv_anchor_fwd",
-    "grl_qkv_anchor_lo_blob_bytes",
-    "grl_qkv_anchor_blob_bytes",
-    "grl_cab_conv2_fwd",
-    "grl_cab_conv2_blob_bytes",
-    "grl_attention_fwd",
-    "grl_attention_rows_geometry_ok",
-    "grl_layernorm_fwd",
-    "grl_layernorm_res_fwd",
-    "grl_conv3x3_fwd",
-    "grl_conv3x3_num_workgroups",
-    "grl_se_scale_fwd",
-    "grl_gemm_tn",
-    "grl_attention_bwd",
-    "grl_adamw_step",
-    "grl_layernorm_train_fwd",
-    "grl_layernorm_bwd",
-    "grl_pack_conv3x3",
-    "grl_pack_linear",
-    "grl_sum4",
-    "grl_se_mlp_fwd",
-    "grl_se_mlp_bwd",
-    "grl_se_colsum",
-    "grl_se_apply",
-    "grl_head_planes_fwd",
-    "grl_head_planes_bwd",
-    "grl_cpb_table_fwd",
-    "grl_cpb_table_bwd",
-    "grl_image_metrics_workspace_bytes",
-    "grl_image_metrics",
-    "grl_demosaic_matlab",
-    "grl_imresize",
-    "grl_image_niqe_workspace_bytes",
-    "grl_image_niqe_features",
-    "grl_sample_patches",
-    "grl_blur_depthwise",
-    "grl_jpeg_workspace_bytes",
-    "grl_jpeg_roundtrip",
-    "grl_image_pack8",
-    "grl_usm_workspace_bytes",
-    "grl_usm_sharp",
-    "grl_cv_resize",
-    "grl_blur_items",
-    "grl_debug_dirty_lds",
-    "grl_abi_version",
-    "grl_build_info",
-]
-
-
 class _Strict(C.Structure):
     """ctypes silently turns unknown keyword arguments into plain attributes (leaving the C field
     zero); refuse them instead."""
@@ -654,6 +594,75 @@ class GrlBlurItemsArgs(_Strict):
     ]
 
 
+_I32, _I64, _PTR = C.c_int32, C.c_int64, C.c_void_p
+
+
+def _launch(args_struct):
+    """int f(void* stream, const GrlXArgs* args): the shape of almost every entry point."""
+    return (C.c_int, [_PTR, C.POINTER(args_struct)])
+
+
+# every symbol include/grl_hip.h declares, in the header's order: name -> (restype, argtypes).  lib() applies this table;
+# tests/test_abi.py compares it with the prototypes of the header.
+SIGNATURES = {
+    "grl_linear_fwd": _launch(GrlLinearArgs),
+    "grl_linear_split_blob_bytes": (_I64, [_I32, _I32]),
+    "grl_mlp_fwd": _launch(GrlMlpArgs),
+    "grl_mlp_blob_bytes": (_I64, [_I32, _I32]),
+    "grl_block_tail_fwd": _launch(GrlTailArgs),
+    "grl_tail_regs_blob_bytes": (_I64, []),
+    "grl_proj_blob_bytes": (_I64, [_I32]),
+    "grl_qkv_fwd": _launch(GrlQkvArgs),
+    "grl_qkv_blob_bytes": (_I64, [_I32, _I32]),
+    "grl_qkv_anchor_fwd": _launch(GrlQkvAnchorArgs),
+    "grl_qkv_anchor_blob_bytes": (_I64, [_I32, _I32, _I32]),
+    "grl_qkv_anchor_lo_blob_bytes": (_I64, [_I32, _I32]),
+    "grl_attention_fwd": _launch(GrlAttnArgs),
+    "grl_attention_rows_geometry_ok": (C.c_int, [C.POINTER(GrlAttnArgs)]),
+    "grl_conv3x3_fwd": _launch(GrlConvArgs),
+    "grl_conv3x3_num_workgroups": (C.c_int, [_I32, _I32, _I32]),
+    "grl_cab_conv2_fwd": _launch(GrlCabConv2Args),
+    "grl_cab_conv2_blob_bytes": (_I64, []),
+    "grl_se_scale_fwd": (C.c_int, [_PTR, _PTR] + [_I32] * 6 + [_PTR] * 5),
+    "grl_layernorm_fwd": (C.c_int, [_PTR, _PTR, _I64, _PTR, _I64, _PTR, _PTR, _I32, _I32, _I32, C.c_float]),
+    "grl_layernorm_res_fwd": _launch(GrlLnResArgs),
+    "grl_gemm_tn": _launch(GrlGemmTnArgs),
+    "grl_attention_bwd": _launch(GrlAttnBwdArgs),
+    "grl_adamw_step": _launch(GrlAdamWArgs),
+    "grl_layernorm_train_fwd": _launch(GrlLnTrainArgs),
+    "grl_layernorm_bwd": _launch(GrlLnTrainArgs),
+    "grl_pack_conv3x3": (C.c_int, [_PTR] * 5 + [_I32] * 5),
+    "grl_pack_linear": (C.c_int, [_PTR] * 6 + [_I32] * 4),
+    "grl_sum4": (C.c_int, [_PTR] * 6 + [_I64]),
+    "grl_head_planes_fwd": _launch(GrlPlanesArgs),
+    "grl_head_planes_bwd": _launch(GrlPlanesArgs),
+    "grl_se_mlp_fwd": _launch(GrlSeMlpArgs),
+    "grl_se_mlp_bwd": _launch(GrlSeMlpArgs),
+    "grl_se_colsum": _launch(GrlSeRowsArgs),
+    "grl_se_apply": _launch(GrlSeRowsArgs),
+    "grl_cpb_table_fwd": _launch(GrlCpbArgs),
+    "grl_cpb_table_bwd": _launch(GrlCpbArgs),
+    "grl_image_metrics_workspace_bytes": (_I64, [_I32] * 4),
+    "grl_image_metrics": _launch(GrlMetricArgs),
+    "grl_demosaic_matlab": _launch(GrlDemosaicArgs),
+    "grl_imresize": _launch(GrlResizeArgs),
+    "grl_image_niqe_workspace_bytes": (_I64, [_I32] * 3),
+    "grl_image_niqe_features": _launch(GrlNiqeArgs),
+    "grl_sample_patches": _launch(GrlPatchArgs),
+    "grl_blur_depthwise": _launch(GrlBlurArgs),
+    "grl_jpeg_workspace_bytes": (_I64, [_I32] * 4),
+    "grl_jpeg_roundtrip": _launch(GrlJpegArgs),
+    "grl_image_pack8": _launch(GrlPack8Args),
+    "grl_usm_workspace_bytes": (_I64, [_I32] * 4),
+    "grl_usm_sharp": _launch(GrlUsmArgs),
+    "grl_cv_resize": _launch(GrlCvResizeArgs),
+    "grl_blur_items": _launch(GrlBlurItemsArgs),
+    "grl_debug_dirty_lds": (C.c_int, [_PTR]),
+    "grl_abi_version": (C.c_int, []),
+    "grl_build_info": (C.c_char_p, []),
+}
+EXPORTS = list(SIGNATURES)
+
 _lib = None
 
 
@@ -669,120 +678,11 @@ def lib():
             "There is no CPU/PyTorch fallback for the hot path."
         )
     L = C.CDLL(LIB_PATH)
-    L.grl_abi_version.restype = C.c_int
-    if L.grl_abi_version() != ABI_VERSION:
+    if L.grl_abi_version() != ABI_VERSION:      # int f(void): right under ctypes' defaults, before the table is applied
         raise RuntimeError(f"stale {LIB_PATH}: ABI {L.grl_abi_version()} != {ABI_VERSION}; rebuild")
-    L.grl_build_info.restype = C.c_char_p
-    L.grl_linear_fwd.argtypes = [C.c_void_p, C.POINTER(GrlLinearArgs)]
-    L.grl_linear_fwd.restype = C.c_int
-    L.grl_linear_split_blob_bytes.argtypes = [C.c_int32, C.c_int32]
-    L.grl_linear_split_blob_bytes.restype = C.c_int64
-    L.grl_mlp_fwd.argtypes = [C.c_void_p, C.POINTER(GrlMlpArgs)]
-    L.grl_mlp_fwd.restype = C.c_int
-    L.grl_mlp_blob_bytes.argtypes = [C.c_int32, C.c_int32]
-    L.grl_mlp_blob_bytes.restype = C.c_int64
-    L.grl_block_tail_fwd.argtypes = [C.c_void_p, C.POINTER(GrlTailArgs)]
-    L.grl_block_tail_fwd.restype = C.c_int
-    L.grl_proj_blob_bytes.argtypes = [C.c_int32]
-    L.grl_proj_blob_bytes.restype = C.c_int64
-    L.grl_tail_regs_blob_bytes.argtypes = []
-    L.grl_tail_regs_blob_bytes.restype = C.c_int64
-    L.grl_qkv_fwd.argtypes = [C.c_void_p, C.POINTER(GrlQkvArgs)]
-    L.grl_qkv_fwd.restype = C.c_int
-    L.grl_qkv_blob_bytes.argtypes = [C.c_int32, C.c_int32]
-    L.grl_qkv_blob_bytes.restype = C.c_int64
-    L.grl_qkv_anchor_fwd.argtypes = [C.c_void_p, C.POINTER(GrlQkvAnchorArgs)]
-    L.grl_qkv_anchor_fwd.restype = C.c_int
-    L.grl_qkv_anchor_blob_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
-    L.grl_qkv_anchor_blob_bytes.restype = C.c_int64
-    L.grl_qkv_anchor_lo_blob_bytes.argtypes = [C.c_int32, C.c_int32]
-    L.grl_qkv_anchor_lo_blob_bytes.restype = C.c_int64
-    L.grl_cab_conv2_fwd.argtypes = [C.c_void_p, C.POINTER(GrlCabConv2Args)]
-    L.grl_cab_conv2_fwd.restype = C.c_int
-    L.grl_cab_conv2_blob_bytes.argtypes = []
-    L.grl_cab_conv2_blob_bytes.restype = C.c_int64
-    L.grl_attention_fwd.argtypes = [C.c_void_p, C.POINTER(GrlAttnArgs)]
-    L.grl_attention_fwd.restype = C.c_int
-    L.grl_attention_rows_geometry_ok.argtypes = [C.POINTER(GrlAttnArgs)]
-    L.grl_attention_rows_geometry_ok.restype = C.c_int
-    L.grl_layernorm_fwd.argtypes = [
-        C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
-        C.c_int32, C.c_int32, C.c_int32, C.c_float,
-    ]
-    L.grl_layernorm_fwd.restype = C.c_int
-    L.grl_layernorm_res_fwd.argtypes = [C.c_void_p, C.POINTER(GrlLnResArgs)]
-    L.grl_layernorm_res_fwd.restype = C.c_int
-    L.grl_conv3x3_fwd.argtypes = [C.c_void_p, C.POINTER(GrlConvArgs)]
-    L.grl_conv3x3_fwd.restype = C.c_int
-    L.grl_conv3x3_num_workgroups.argtypes = [C.c_int32, C.c_int32, C.c_int32]
-    L.grl_conv3x3_num_workgroups.restype = C.c_int
-    L.grl_se_scale_fwd.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
-                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.grl_se_scale_fwd.restype = C.c_int
-    L.grl_gemm_tn.argtypes = [C.c_void_p, C.POINTER(GrlGemmTnArgs)]
-    L.grl_gemm_tn.restype = C.c_int
-    L.grl_attention_bwd.argtypes = [C.c_void_p, C.POINTER(GrlAttnBwdArgs)]
-    L.grl_attention_bwd.restype = C.c_int
-    L.grl_adamw_step.argtypes = [C.c_void_p, C.POINTER(GrlAdamWArgs)]
-    L.grl_adamw_step.restype = C.c_int
-    L.grl_layernorm_train_fwd.argtypes = [C.c_void_p, C.POINTER(GrlLnTrainArgs)]
-    L.grl_layernorm_train_fwd.restype = C.c_int
-    L.grl_layernorm_bwd.argtypes = [C.c_void_p, C.POINTER(GrlLnTrainArgs)]
-    L.grl_layernorm_bwd.restype = C.c_int
-    L.grl_pack_conv3x3.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
-    L.grl_pack_conv3x3.restype = C.c_int
-    L.grl_pack_linear.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
-    L.grl_pack_linear.restype = C.c_int
-    L.grl_sum4.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
-    L.grl_sum4.restype = C.c_int
-    L.grl_se_mlp_fwd.argtypes = [C.c_void_p, C.POINTER(GrlSeMlpArgs)]
-    L.grl_se_mlp_fwd.restype = C.c_int
-    L.grl_se_mlp_bwd.argtypes = [C.c_void_p, C.POINTER(GrlSeMlpArgs)]
-    L.grl_se_mlp_bwd.restype = C.c_int
-    L.grl_se_colsum.argtypes = [C.c_void_p, C.POINTER(GrlSeRowsArgs)]
-    L.grl_se_colsum.restype = C.c_int
-    L.grl_se_apply.argtypes = [C.c_void_p, C.POINTER(GrlSeRowsArgs)]
-    L.grl_se_apply.restype = C.c_int
-    L.grl_head_planes_fwd.argtypes = [C.c_void_p, C.POINTER(GrlPlanesArgs)]
-    L.grl_head_planes_fwd.restype = C.c_int
-    L.grl_head_planes_bwd.argtypes = [C.c_void_p, C.POINTER(GrlPlanesArgs)]
-    L.grl_head_planes_bwd.restype = C.c_int
-    L.grl_cpb_table_fwd.argtypes = [C.c_void_p, C.POINTER(GrlCpbArgs)]
-    L.grl_cpb_table_fwd.restype = C.c_int
-    L.grl_cpb_table_bwd.argtypes = [C.c_void_p, C.POINTER(GrlCpbArgs)]
-    L.grl_cpb_table_bwd.restype = C.c_int
-    L.grl_image_metrics_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32]
-    L.grl_image_metrics_workspace_bytes.restype = C.c_int64
-    L.grl_image_metrics.argtypes = [C.c_void_p, C.POINTER(GrlMetricArgs)]
-    L.grl_image_metrics.restype = C.c_int
-    L.grl_demosaic_matlab.argtypes = [C.c_void_p, C.POINTER(GrlDemosaicArgs)]
-    L.grl_demosaic_matlab.restype = C.c_int
-    L.grl_imresize.argtypes = [C.c_void_p, C.POINTER(GrlResizeArgs)]
-    L.grl_imresize.restype = C.c_int
-    L.grl_image_niqe_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
-    L.grl_image_niqe_workspace_bytes.restype = C.c_int64
-    L.grl_image_niqe_features.argtypes = [C.c_void_p, C.POINTER(GrlNiqeArgs)]
-    L.grl_image_niqe_features.restype = C.c_int
-    L.grl_sample_patches.argtypes = [C.c_void_p, C.POINTER(GrlPatchArgs)]
-    L.grl_sample_patches.restype = C.c_int
-    L.grl_blur_depthwise.argtypes = [C.c_void_p, C.POINTER(GrlBlurArgs)]
-    L.grl_blur_depthwise.restype = C.c_int
-    L.grl_jpeg_workspace_bytes.argtypes = [C.c_int32] * 4
-    L.grl_jpeg_workspace_bytes.restype = C.c_int64
-    L.grl_jpeg_roundtrip.argtypes = [C.c_void_p, C.POINTER(GrlJpegArgs)]
-    L.grl_jpeg_roundtrip.restype = C.c_int
-    L.grl_image_pack8.argtypes = [C.c_void_p, C.POINTER(GrlPack8Args)]
-    L.grl_image_pack8.restype = C.c_int
-    L.grl_usm_workspace_bytes.argtypes = [C.c_int32] * 4
-    L.grl_usm_workspace_bytes.restype = C.c_int64
-    L.grl_usm_sharp.argtypes = [C.c_void_p, C.POINTER(GrlUsmArgs)]
-    L.grl_usm_sharp.restype = C.c_int
-    L.grl_cv_resize.argtypes = [C.c_void_p, C.POINTER(GrlCvResizeArgs)]
-    L.grl_cv_resize.restype = C.c_int
-    L.grl_blur_items.argtypes = [C.c_void_p, C.POINTER(GrlBlurItemsArgs)]
-    L.grl_blur_items.restype = C.c_int
-    L.grl_debug_dirty_lds.argtypes = [C.c_void_p]
-    L.grl_debug_dirty_lds.restype = C.c_int
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = L
     return L
 
@@ -806,3 +706,10 @@ def stream_ptr():
     if _DIRTY_LDS:
         check(lib().grl_debug_dirty_lds(s), "grl_debug_dirty_lds")
     return s
+
+
+def launch(name: str, args):
+    """Calls entry point `name` of the shape int f(void* stream, const GrlXArgs* args) on the current stream and raises under
+    that same name unless it returns 0."""
+    fn = getattr(lib(), name)
+    check(fn(stream_ptr(), C.byref(args)), name)

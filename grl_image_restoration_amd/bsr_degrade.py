@@ -27,7 +27,6 @@ writes a frozen validation set: every image centre-cropped and degraded once, ``
 two folders as they are.
 """
 import argparse
-import ctypes as C
 import functools
 import math
 import os
@@ -166,7 +165,7 @@ def hip_cv_resize(src: torch.Tensor, dst: torch.Tensor, items, Cn: int) -> None:
     args = _lib.GrlCvResizeArgs(src=src.data_ptr(), dst=dst.data_ptr(), src_elems=src.numel(), dst_elems=dst.numel(),
                                 items=t.data_ptr(), n_items=len(items), C=Cn, max_ho=max(it[4] for it in items),
                                 max_wo=max(it[5] for it in items))
-    _lib.check(_lib.lib().grl_cv_resize(_lib.stream_ptr(), C.byref(args)), "grl_cv_resize")
+    _lib.launch("grl_cv_resize", args)
 
 
 # ---- blur -------------------------------------------------------------------------------------------------------------------------
@@ -232,7 +231,7 @@ def hip_blur_items(src: torch.Tensor, dst: torch.Tensor, taps: torch.Tensor, ite
                                  dst_elems=dst.numel(), taps_elems=taps.numel(), items=t.data_ptr(), n_items=len(items), C=Cn,
                                  max_ho=max(-(-it[2] // it[5]) for it in items), max_wo=max(-(-it[3] // it[5]) for it in items),
                                  max_K=max(it[4] for it in items))
-    _lib.check(_lib.lib().grl_blur_items(_lib.stream_ptr(), C.byref(args)), "grl_blur_items")
+    _lib.launch("grl_blur_items", args)
 
 
 # ---- the blur kernels (host, float64) ---------------------------------------------------------------------------------------------

@@ -19,7 +19,6 @@ Flags of a work-list entry: bit 0 reverses the rows (``x[::-1]``), bit 1 the col
 columns ``y * scale ..``; pixels outside the image are 0, which is the reference's bottom / right padding of images smaller than
 the patch.
 """
-import ctypes as C
 import random
 from typing import List, Optional, Sequence
 
@@ -111,7 +110,7 @@ class PatchStore:
         args = _lib.GrlPatchArgs(store=self.data.data_ptr(), offsets=self.offsets.data_ptr(), dims=self.dims_t.data_ptr(),
                                  N=len(self), C=self.channels, work=work.data_ptr(), B=work.shape[0], P=patch, scale=scale,
                                  out=out.data_ptr())
-        _lib.check(_lib.lib().grl_sample_patches(_lib.stream_ptr(), C.byref(args)), "grl_sample_patches")
+        _lib.launch("grl_sample_patches", args)
         return out
 
     def _torch_sample(self, work, patch, scale, out):

@@ -49,10 +49,9 @@ def pack8(x: torch.Tensor, rep: int = 1) -> torch.Tensor:
         return _torch_pack8(x, rep)
     from . import _lib
 
-    L = _lib.lib()
     out = torch.empty((N, H * rep, W * rep, Cn), dtype=torch.uint8, device=x.device)
     args = _lib.GrlPack8Args(x=x.data_ptr(), stride=(C.c_int64 * 4)(*x.stride()), N=N, C=Cn, H=H, W=W, rep=rep, out=out.data_ptr())
-    _lib.check(L.grl_image_pack8(_lib.stream_ptr(), C.byref(args)), "grl_image_pack8")
+    _lib.launch("grl_image_pack8", args)
     return out
 
 

@@ -116,7 +116,7 @@ def hip_image_metrics(restored: torch.Tensor, target: torch.Tensor, border: int,
         target=t.data_ptr(), target_stride=(C.c_int64 * 4)(*t.stride()), target_shape=(C.c_int32 * 4)(*t.shape),
         border=border, metrics=bits, taps=(C.c_double * 11)(*taps.tolist()), y_coef=(C.c_float * 3)(*ycoef.tolist()),
         workspace=ws.data_ptr(), workspace_bytes=ws_bytes, out=out.data_ptr())
-    _lib.check(L.grl_image_metrics(_lib.stream_ptr(), C.byref(args)), "grl_image_metrics")
+    _lib.launch("grl_image_metrics", args)
     return out
 
 
@@ -319,7 +319,7 @@ def hip_niqe_features(restored: torch.Tensor) -> torch.Tensor:
         window=(C.c_double * 49)(*niqe_window().flatten().tolist()), grid=grid.data_ptr(), ngrid=grid.shape[1],
         taps_h=wh.shape[1], taps_w=ww.shape[1], wh=wh.data_ptr(), ih=ih.data_ptr(), ww=ww.data_ptr(), iw=iw.data_ptr(),
         workspace=ws.data_ptr(), workspace_bytes=ws_bytes, out=out.data_ptr())
-    _lib.check(L.grl_image_niqe_features(_lib.stream_ptr(), C.byref(args)), "grl_image_niqe_features")
+    _lib.launch("grl_image_niqe_features", args)
     return out
 
 

@@ -294,7 +294,7 @@ def linear(
         assert resid is not None and resid.dtype == torch.float32 and resid.stride(1) == 1 and resid.stride(0) % 4 == 0 and out.dtype == torch.float32
         assert resid.shape[0] >= M and resid.shape[1] >= (n_store if n_store > 0 else Npad)
     with _timed(f"linear {Kpad}->{Npad}" if _PROFILE is not None else "linear"):
-        L.check(L.lib().grl_linear_fwd(L.stream_ptr(), C.byref(args)), "grl_linear_fwd")
+        L.launch("grl_linear_fwd", args)
     return out
 
 
@@ -372,7 +372,7 @@ def qkv(x: torch.Tensor, blob: torch.Tensor, nslots: int, out: Optional[torch.Te
     args = L.GrlQkvArgs(x=_ptr(x), ldx=x.stride(0), blob=_ptr(blob), M=M, Cpad=Cpad, nslots=nslots, out=_ptr(out),
                         out_plane_stride=M * 32)
     with _timed("qkv"):
-        L.check(L.lib().grl_qkv_fwd(L.stream_ptr(), C.byref(args)), "grl_qkv_fwd")
+        L.launch("grl_qkv_fwd", args)
     return out
 
 
@@ -449,7 +449,7 @@ def qkv_anchor(x: torch.Tensor, blob: torch.Tensor, nslots: int, nanc: int, B: i
     args = L.GrlQkvAnchorArgs(x=_ptr(x), ldx=x.stride(0), B=B, H=H, W=W, Cpad=Cpad, blob=_ptr(blob), nslots=nslots, nanc=nanc,
                               out=_ptr(out), out_plane_stride=M * 32, anc=_ptr(anc), anc_plane_stride=(M // 4) * 32, lo_blob=_ptr(lo_blob))
     with _timed("qkv_anchor"):
-        L.check(L.lib().grl_qkv_anchor_fwd(L.stream_ptr(), C.byref(args)), "grl_qkv_anchor_fwd")
+        L.launch("grl_qkv_anchor_fwd", args)
     return out, (anc if nanc > 0 else None)
 
 
@@ -520,7 +520,7 @@ def block_tail(att: torch.Tensor, x: torch.Tensor, cab: torch.Tensor, gate: torc
                          n1_b=_ptr(n1_b), blob=_ptr(blob), M=M, Cpad=Cpad, Hpad=Hpad, b2=_ptr(b2), n2_g=_ptr(n2_g), n2_b=_ptr(n2_b),
                          n_real=n_real, ln_eps=ln_eps, res_scale=res_scale, out=_ptr(out), ldo=out.stride(0), rblob=_ptr(rblob))
     with _timed("block_tail"):
-        L.check(L.lib().grl_block_tail_fwd(L.stream_ptr(), C.byref(args)), "grl_block_tail_fwd")
+        L.launch("grl_block_tail_fwd", args)
     return out
 
 
@@ -537,7 +537,7 @@ def mlp(x: torch.Tensor, blob: torch.Tensor, b2: torch.Tensor, ln_g: torch.Tenso
     args = L.GrlMlpArgs(x=_ptr(x), ldx=x.stride(0), blob=_ptr(blob), M=M, Cpad=Cpad, Hpad=Hpad, b2=_ptr(b2), ln_g=_ptr(ln_g),
                         ln_b=_ptr(ln_b), n_real=n_real, ln_eps=ln_eps, res_scale=res_scale, out=_ptr(out), ldo=out.stride(0))
     with _timed("mlp"):
-        L.check(L.lib().grl_mlp_fwd(L.stream_ptr(), C.byref(args)), "grl_mlp_fwd")
+        L.launch("grl_mlp_fwd", args)
     return out
 
 
@@ -588,7 +588,7 @@ def attention_rows_ok(q_win, k_win, q_shift, k_shift, masked: bool, head_dim: in
     args = L.GrlAttnArgs(q=gq, k=gk, v=gk, o=gq, B=1, nh=1, nwy=1, nwx=1, table=None,
                          trows=(q_win[0] + k_win[0] - 1) * (q_win[1] + k_win[1] - 1), tstride=0, masked=int(masked),
                          ones_col=head_dim if head_dim < 32 else -1, head_dim=head_dim, out_dtype=L.DT_F16, k_one31=0)
-    return bool(L.lib().grl_attention_rows_geometry_ok(C.byref(args)))
+    return bool(L.lib().grl_attention_rows_geometry_ok(args))
 
 
 def transpose_table(bias: torch.Tensor, q_win, k_win) -> torch.Tensor:
@@ -632,7 +632,7 @@ def attention(q: TokenGrid, k: TokenGrid, v: TokenGrid, o: TokenGrid, *, B: int,
                          lse=_ptr(lse), lse_stride=lse.stride(0) if lse is not None else 0,
                          q_lo=twin(q, q_lo), k_lo=twin(k, k_lo), v_lo=twin(v, v_lo), o_lo=twin(o, o_lo), lazy_ceil=_ptr(lazy_ceil))
     with _timed(f"attention q{q.wh}x{q.ww} k{k.wh}x{k.ww}" if _PROFILE is not None else "attention"):
-        L.check(L.lib().grl_attention_fwd(L.stream_ptr(), C.byref(args)), "grl_attention_fwd")
+        L.launch("grl_attention_fwd", args)
     return o.t
 
 
@@ -665,7 +665,7 @@ def layernorm_res(x: torch.Tensor, resid: torch.Tensor, gamma: torch.Tensor, bet
                           rows_per_image=rows_per_image, M=x.shape[0], n_real=n_real, n_pad=n_pad, eps=eps, res_scale=res_scale,
                           y=_ptr(out), ldy=out.stride(0))
     with _timed("layernorm_res"):
-        L.check(L.lib().grl_layernorm_res_fwd(L.stream_ptr(), C.byref(args)), "grl_layernorm_res_fwd")
+        L.launch("grl_layernorm_res_fwd", args)
     return out
 
 
@@ -729,9 +729,8 @@ def conv3x3(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, B: int, H: int
     if out is None:
         out = empty(rows, cols, dtype=out_dtype, device=x.device)
     pool = None
-    lib = L.lib()
     if want_pool:
-        nwg = lib.grl_conv3x3_num_workgroups(B, H, W)
+        nwg = L.lib().grl_conv3x3_num_workgroups(B, H, W)
         pool = empty(nwg, CoutP, dtype=torch.float32, device=x.device)
     # at most 192 output channels per launch; larger layers are split on the channel axis
     step = CoutP
@@ -764,7 +763,7 @@ def conv3x3(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, B: int, H: int
             x_cols=x_cols, n_store=ns,
         )
         with _timed(f"conv3x3 {CinP}->{CoutP} {H}x{W}" if _PROFILE is not None else "conv3x3"):
-            L.check(lib.grl_conv3x3_fwd(L.stream_ptr(), C.byref(args)), "grl_conv3x3_fwd")
+            L.launch("grl_conv3x3_fwd", args)
     return (out, pool) if want_pool else out
 
 
@@ -813,7 +812,7 @@ def cab_conv2(x: torch.Tensor, blob: torch.Tensor, bias: torch.Tensor, B: int, H
         args.se_w1, args.se_b1, args.se_w2, args.se_b2 = _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2)
         args.se_c, args.se_mid, args.inv_hw = C_, w1.shape[0], 1.0 / (H * W)
     with _timed("cab_conv2"):
-        L.check(L.lib().grl_cab_conv2_fwd(L.stream_ptr(), C.byref(args)), "grl_cab_conv2_fwd")
+        L.launch("grl_cab_conv2_fwd", args)
     return out, (gate if se is not None else pool)
 
 
@@ -860,7 +859,7 @@ def gemm_tn(a: torch.Tensor, b: torch.Tensor, N: int, K: int, *, taps: int = 1, 
                            c_tap_stride=N * K, c_fix=_ptr(c) if det else None, b_ones=int(b_ones),
                            c_bias=None if det else _ptr(cb), c_bias_fix=_ptr(cb) if det else None, a_dtype=_KIND[a.dtype])
     with _timed("gemm_tn"):
-        L.check(L.lib().grl_gemm_tn(L.stream_ptr(), C.byref(args)), "grl_gemm_tn")
+        L.launch("grl_gemm_tn", args)
     if det:
         c = (c.double() * (out_scale * 2.0 ** -30)).float()
         cb = (cb.double() * (out_scale * 2.0 ** -30)).float() if b_ones else None
@@ -895,7 +894,7 @@ def attention_bwd(q: TokenGrid, k: TokenGrid, v: TokenGrid, o: TokenGrid, d_o: t
     args = L.GrlAttnBwdArgs(fwd=fwd, d_o=_ptr(d_o), d_q=_ptr(d_q), d_k=_ptr(d_k), d_v=_ptr(d_v), d_table=_ptr(d_table), g_scale=g_scale,
                             d_table_fix=_ptr(fix), d_o_ld=d_o_ld)
     with _timed("attention_bwd"):
-        L.check(L.lib().grl_attention_bwd(L.stream_ptr(), C.byref(args)), "grl_attention_bwd")
+        L.launch("grl_attention_bwd", args)
     if fix is not None:
         d_table = (fix.double() * (2.0 ** -32 / g_scale)).float()
     return d_q, d_k, d_v, d_table
@@ -915,7 +914,7 @@ def cpb_table(coords: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, w2: torc
     out = empty(G, nh, rows4, dtype=torch.float32, device=coords.device)
     args = L.GrlCpbArgs(coords=_ptr(cs), w1=_ptr(a), b1=_ptr(b), w2=_ptr(c), out=_ptr(out), G=G, rows=rows, rows4=rows4, nh=nh, hidden=hid)
     with _timed("cpb_table"):
-        L.check(L.lib().grl_cpb_table_fwd(L.stream_ptr(), C.byref(args)), "grl_cpb_table_fwd")
+        L.launch("grl_cpb_table_fwd", args)
     return out
 
 
@@ -930,7 +929,7 @@ def cpb_table_bwd(coords: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, w2: 
     args = L.GrlCpbArgs(coords=_ptr(cs), w1=_ptr(a), b1=_ptr(b), w2=_ptr(c), d_out=_ptr(g), d_w1=_ptr(d_w1), d_b1=_ptr(d_b1), d_w2=_ptr(d_w2),
                         G=G, rows=rows, rows4=rows4, nh=nh, hidden=hid)
     with _timed("cpb_table_bwd"):
-        L.check(L.lib().grl_cpb_table_bwd(L.stream_ptr(), C.byref(args)), "grl_cpb_table_bwd")
+        L.launch("grl_cpb_table_bwd", args)
     return d_w1, d_b1, d_w2
 
 
@@ -956,7 +955,7 @@ def layernorm_train(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, ep
                             M=M, n=n, eps=eps, resid=_ptr(resid), ldr=resid.stride(0) if resid is not None else 0,
                             row_scale=_ptr(row_scale), rows_per_image=rows_per_image, alpha=alpha if resid is not None else 0.0)
     with _timed("layernorm_train"):
-        L.check(L.lib().grl_layernorm_train_fwd(L.stream_ptr(), C.byref(args)), "grl_layernorm_train_fwd")
+        L.launch("grl_layernorm_train_fwd", args)
     return y, mean, rstd
 
 
@@ -976,7 +975,7 @@ def layernorm_bwd(dy: torch.Tensor, x: torch.Tensor, mean: torch.Tensor, rstd: t
                             dx=_ptr(dx), lddx=n, dgamma=_ptr(dgb[0]), dbeta=_ptr(dgb[1]), M=M, n=n, eps=0.0,
                             row_scale=_ptr(row_scale), rows_per_image=rows_per_image, alpha=alpha, stat_replicas=R)
     with _timed("layernorm_bwd"):
-        L.check(L.lib().grl_layernorm_bwd(L.stream_ptr(), C.byref(args)), "grl_layernorm_bwd")
+        L.launch("grl_layernorm_bwd", args)
     dgb = dgb.sum(1) if R > 1 else dgb[:, 0]
     return dx, dgb[0], dgb[1]
 
@@ -1008,7 +1007,7 @@ def head_planes(x: torch.Tensor, scale: torch.Tensor, src, raw, one_cols, write3
     args = _planes_args(x, scale, src, raw, one_cols, [False] * S_out)
     args.out32, args.out16 = (_ptr(out32) if write32 else None), _ptr(out16)
     with _timed("head_planes"):
-        L.check(L.lib().grl_head_planes_fwd(L.stream_ptr(), C.byref(args)), "grl_head_planes_fwd")
+        L.launch("grl_head_planes_fwd", args)
     return out32, out16
 
 
@@ -1028,7 +1027,7 @@ def head_planes_bwd(x: torch.Tensor, scale: torch.Tensor, src, raw, one_cols, gr
             args.dy[s_] = g.data_ptr()
     args.dx, args.dscale = _ptr(dx), _ptr(dscale)
     with _timed("head_planes_bwd"):
-        L.check(L.lib().grl_head_planes_bwd(L.stream_ptr(), C.byref(args)), "grl_head_planes_bwd")
+        L.launch("grl_head_planes_bwd", args)
     return dx, (dscale.sum(0) if R > 1 else dscale[0])
 
 
@@ -1076,7 +1075,7 @@ def se_mlp(pool: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, w2: torch.Ten
     hidden = empty(B, Cmid, dtype=torch.float32, device=pool.device)
     args = L.GrlSeMlpArgs(pool=_ptr(ts[0]), w1=_ptr(ts[1]), b1=_ptr(ts[2]), w2=_ptr(ts[3]), b2=_ptr(ts[4]), gate=_ptr(gate), hidden=_ptr(hidden),
                           B=B, C=C_, Cmid=Cmid)
-    L.check(L.lib().grl_se_mlp_fwd(L.stream_ptr(), C.byref(args)), "grl_se_mlp_fwd")
+    L.launch("grl_se_mlp_fwd", args)
     return gate, hidden
 
 
@@ -1096,7 +1095,7 @@ def se_mlp_bwd(d_gate: torch.Tensor, pool: torch.Tensor, gate: torch.Tensor, hid
     args = L.GrlSeMlpArgs(pool=_ptr(pl), w1=_ptr(w1c), w2=_ptr(w2c), gate=_ptr(gate), hidden=_ptr(hidden), d_gate=_ptr(dg), d_pool=_ptr(d_pool),
                           d_w1=_ptr(d_w1), d_b1=_ptr(d_b1), d_w2=_ptr(d_w2), d_b2=_ptr(d_b2), B=B, C=C_, Cmid=Cmid,
                           b1=_ptr(d_b1), b2=_ptr(d_b2), parallel=int(par))     # (b1 / b2 are not read by the backward kernel; non-null for the argument check)
-    L.check(L.lib().grl_se_mlp_bwd(L.stream_ptr(), C.byref(args)), "grl_se_mlp_bwd")
+    L.launch("grl_se_mlp_bwd", args)
     return d_pool, d_w1, d_b1, d_w2, d_b2
 
 
@@ -1112,7 +1111,7 @@ def se_colsum(a: torch.Tensor, rows_per_image: int, k: float = 1.0, f: Optional[
     out = zeros_f32((M // rows_per_image) * C_, a.device).view(M // rows_per_image, C_)
     args = L.GrlSeRowsArgs(a=_ptr(a), lda=a.stride(0), f=_ptr(f), ldf=f.stride(0) if f is not None else 0, out=_ptr(out), ldo=C_, k=k,
                            M=M, C=C_, rows_per_image=rows_per_image)
-    L.check(L.lib().grl_se_colsum(L.stream_ptr(), C.byref(args)), "grl_se_colsum")
+    L.launch("grl_se_colsum", args)
     return out
 
 
@@ -1127,7 +1126,7 @@ def se_apply(a: torch.Tensor, g: torch.Tensor, rows_per_image: int, f: Optional[
     out = empty(M, C_, dtype=torch.float32, device=a.device)
     args = L.GrlSeRowsArgs(a=_ptr(a), lda=a.stride(0), f=_ptr(f), ldf=f.stride(0) if f is not None else 0, g=_ptr(g), h=_ptr(h), out=_ptr(out),
                            ldo=C_, k=k, M=M, C=C_, rows_per_image=rows_per_image)
-    L.check(L.lib().grl_se_apply(L.stream_ptr(), C.byref(args)), "grl_se_apply")
+    L.launch("grl_se_apply", args)
     return out
 
 

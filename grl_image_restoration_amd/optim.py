@@ -7,7 +7,6 @@ parameter group in ONE launch of ``grl_adamw_step`` (csrc/grad.hip): a host-buil
 in device memory.  fp32 parameters on the GPU; CPU parameters take the same update as plain torch arithmetic (``_step_cpu``: like the
 model's composite path it exists so that a module built without a GPU steps instead of raising -- never reached by GPU tensors).
 """
-import ctypes as C
 from typing import Iterable
 
 import torch
@@ -184,7 +183,7 @@ class FusedAdamW(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        lib = L.lib()
+        L.lib()    # a missing or stale library is an error even when every group is on the CPU
         for gi, group in enumerate(self.param_groups):
             plist = [p for p in group["params"] if p.grad is not None]
             if not plist:
@@ -236,7 +235,7 @@ class FusedAdamW(torch.optim.Optimizer):
                 bias_corrections_dev=bc_dev.data_ptr() if bc_dev is not None else None,
                 hyper_dev=self._hyper_dev[gi].data_ptr() if (self._step_dev is not None and gi in self._hyper_dev) else None,
             )
-            L.check(lib.grl_adamw_step(L.stream_ptr(), C.byref(args)), "grl_adamw_step")
+            L.launch("grl_adamw_step", args)
             # the kernel wrote through raw pointers: tell autograd (and GRL's plan version stamp) that the tensors changed in place
             torch.autograd.graph.increment_version(plist)
         return loss

@@ -115,7 +115,6 @@ def hip_demosaic(planes) -> torch.Tensor:
     by the library."""
     from . import _lib
 
-    L = _lib.lib()
     p0 = planes[0]
     if any(p.dtype != torch.float32 for p in planes):
         raise TypeError(f"grl_demosaic_matlab takes fp32 tensors, got {p0.dtype}")
@@ -125,7 +124,7 @@ def hip_demosaic(planes) -> torch.Tensor:
     out = torch.empty(N, 3, 2 * h, 2 * w, dtype=torch.float32, device=p0.device)
     args = _lib.GrlDemosaicArgs(plane=(C.c_void_p * 4)(*[p.data_ptr() for p in planes]), stride=(C.c_int64 * 3)(*p0.stride()),
                                 N=N, h=h, w=w, out=out.data_ptr())
-    _lib.check(L.grl_demosaic_matlab(_lib.stream_ptr(), C.byref(args)), "grl_demosaic_matlab")
+    _lib.launch("grl_demosaic_matlab", args)
     return out
 
 
@@ -318,7 +317,6 @@ def hip_resize(img: torch.Tensor, rows, cols, quantize: bool = False) -> torch.T
     indices) on the same device, (out_len, taps) each.  The sizes are checked by the library."""
     from . import _lib
 
-    L = _lib.lib()
     if img.dtype != torch.float32:
         raise TypeError(f"grl_imresize takes fp32 tensors, got {img.dtype}")
     (wh, ih), (ww, iw) = rows, cols
@@ -332,7 +330,7 @@ def hip_resize(img: torch.Tensor, rows, cols, quantize: bool = False) -> torch.T
                               out_h=wh.shape[0], out_w=ww.shape[0], taps_h=wh.shape[1], taps_w=ww.shape[1],
                               wh=wh.data_ptr(), ih=ih.data_ptr(), ww=ww.data_ptr(), iw=iw.data_ptr(), out=out.data_ptr(),
                               quantize=int(bool(quantize)))
-    _lib.check(L.grl_imresize(_lib.stream_ptr(), C.byref(args)), "grl_imresize")
+    _lib.launch("grl_imresize", args)
     return out
 
 
@@ -443,7 +441,6 @@ def hip_blur(x: torch.Tensor, taps: torch.Tensor, pad: int, add: Optional[torch.
     K, the padding and the sizes are checked by the library."""
     from . import _lib
 
-    L = _lib.lib()
     if x.dtype != torch.float32 or taps.dtype != torch.float32 or (add is not None and add.dtype != torch.float32):
         raise TypeError(f"grl_blur_depthwise takes fp32 tensors, got {x.dtype}")
     if taps.dim() != 2 or taps.shape[0] != taps.shape[1] or taps.device != x.device:
@@ -465,7 +462,7 @@ def hip_blur(x: torch.Tensor, taps: torch.Tensor, pad: int, add: Optional[torch.
     args = _lib.GrlBlurArgs(x=x.data_ptr(), stride=(C.c_int64 * 4)(*x.stride()), N=N, C=Cn, H=H, W=W, taps=taps.data_ptr(), K=K,
                             pad=pad, add=add_ptr, add_stride=(C.c_int64 * 3)(*add_stride), out=out.data_ptr(),
                             center=center.data_ptr() if want_center else None)
-    _lib.check(L.grl_blur_depthwise(_lib.stream_ptr(), C.byref(args)), "grl_blur_depthwise")
+    _lib.launch("grl_blur_depthwise", args)
     return (out, center) if want_center else out
 
 
@@ -552,7 +549,7 @@ def hip_jpeg(x: torch.Tensor, quality: torch.Tensor, out: Optional[torch.Tensor]
     ws = torch.empty(max(int(L.grl_jpeg_workspace_bytes(N, Cn, H, W)), 1), dtype=torch.uint8, device=x.device)
     args = _lib.GrlJpegArgs(x=x.data_ptr(), quality=quality.data_ptr(), N=N, C=Cn, H=H, W=W, workspace=ws.data_ptr(),
                             out=out.data_ptr())
-    _lib.check(L.grl_jpeg_roundtrip(_lib.stream_ptr(), C.byref(args)), "grl_jpeg_roundtrip")
+    _lib.launch("grl_jpeg_roundtrip", args)
     return out
 
 
@@ -745,7 +742,7 @@ def hip_usm(x: torch.Tensor, taps: torch.Tensor, weight: float = 0.5, threshold:
         raise ValueError(f"grl_usm_sharp does not take a batch of shape {tuple(x.shape)}")
     args = _lib.GrlUsmArgs(x=x.data_ptr(), taps=taps.data_ptr(), N=N, C=Cn, H=H, W=W, K=taps.shape[0], quantise=int(bool(quantise)),
                            weight=float(weight), threshold=float(threshold), workspace=ws.data_ptr(), out=out.data_ptr())
-    _lib.check(L.grl_usm_sharp(_lib.stream_ptr(), C.byref(args)), "grl_usm_sharp")
+    _lib.launch("grl_usm_sharp", args)
     return (out, ws[0], ws[1]) if parts else out
 
 

@@ -9,10 +9,8 @@ gamma_n <= (n + 0.04) u.  The final add of the noise rounds once more: at most u
 noise at sigma 2.  Together: |err| <= (K^2 + 2) 2^-24 max(1, max|x|).  The CPU path sums in float64 and rounds once, so it sits
 within an fp32 ulp of the float64 LQ; the bound is the one the fp32 device kernel is held to as well.  The reference's own fp32 LQ
 carries the same error, so against it twice the bound is allowed."""
-import ctypes
 import os
 import random
-import subprocess
 
 import numpy as np
 import pytest
@@ -21,7 +19,6 @@ import torch
 from grl_image_restoration_amd import PatchSampler, PatchStore, _lib, data as D, evaluate as EV, tasks as T, train
 from tests.test_tasks import golden
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LEVIN = {"real4": "levin_4", "real5": "levin_5"}
 
 
@@ -163,21 +160,10 @@ def test_blur_argument_errors():
     assert torch.equal(T.blur(x, one), x)                                     # K = 1
 
 
-def test_blur_args_layout_matches_header_and_abi(tmp_path):
-    st = _lib.GrlBlurArgs
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "grl_hip.h"', "int main(void) {",
-             'printf("size %zu\\n", sizeof(GrlBlurArgs));']
-    lines += [f'printf("{f[0]} %zu\\n", offsetof(GrlBlurArgs, {f[0]}));' for f in st._fields_]
-    lines += ['printf("abi %d\\n", (int)GRL_ABI_VERSION);', "return 0; }"]
-    src = tmp_path / "layout.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    out = dict(l.split() for l in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
-    assert int(out["size"]) == ctypes.sizeof(st)
-    for f in st._fields_:
-        assert int(out[f[0]]) == getattr(st, f[0]).offset, f[0]
-    assert _lib.ABI_VERSION >= 28 and int(out["abi"]) == _lib.ABI_VERSION
+def test_blur_args_layout_matches_header_and_abi():
+    """The layout of GrlBlurArgs is compared with the header in tests/test_abi.py, like every struct's;
+    what is particular to this entry point stays here."""
+    assert _lib.ABI_VERSION >= 28
     assert "grl_blur_depthwise" in _lib.EXPORTS
 
 

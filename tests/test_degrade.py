@@ -17,11 +17,9 @@ The bounds of the fp32 kernels, used by tests/test_gpu_degrade.py, with u = 2^-2
   * ``blur_bound``: tests/test_blur.py's ``bound``: (K^2 + 2) u for a K^2-term fmaf chain with positive taps of sum 1 (+- K^2 u / 2
     after their rounding to fp32, inside the + 2).
 """
-import ctypes
 import json
 import os
 import random
-import subprocess
 
 import numpy as np
 import pytest
@@ -409,22 +407,10 @@ def test_train_and_the_frozen_set_on_the_cpu(tmp_path, capsys):
 
 
 # ---- the C ABI --------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", ["GrlCvResizeArgs", "GrlBlurItemsArgs"])
-def test_args_layout_matches_header_and_abi(tmp_path, name):
-    st = getattr(_lib, name)
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "grl_hip.h"', "int main(void) {",
-             f'printf("size %zu\\n", sizeof({name}));']
-    lines += [f'printf("{f[0]} %zu\\n", offsetof({name}, {f[0]}));' for f in st._fields_]
-    lines += ['printf("abi %d\\n", (int)GRL_ABI_VERSION);', "return 0; }"]
-    src = tmp_path / "layout.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    out = dict(l.split() for l in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
-    assert int(out["size"]) == ctypes.sizeof(st)
-    for f in st._fields_:
-        assert int(out[f[0]]) == getattr(st, f[0]).offset, f[0]
-    assert _lib.ABI_VERSION >= 32 and int(out["abi"]) == _lib.ABI_VERSION
+def test_args_layout_matches_header_and_abi():
+    """The layouts of GrlCvResizeArgs and GrlBlurItemsArgs are compared with the header in tests/test_abi.py, like every struct's;
+    what is particular to this entry point stays here."""
+    assert _lib.ABI_VERSION >= 32
     assert "grl_cv_resize" in _lib.EXPORTS and "grl_blur_items" in _lib.EXPORTS
     header = open(os.path.join(ROOT, "include", "grl_hip.h")).read()
     assert "utils_sisr.py:350-354" in header and "utils_sisr.py:359-362" in header and "VOUCHES" in header

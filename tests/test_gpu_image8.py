@@ -102,6 +102,12 @@ def test_bad_arguments_raise_without_a_fault():
     assert torch.equal(out[: 2 * 5 * 7 * 3].view(2, 5, 7, 3).cpu(), I._torch_pack8(x.cpu(), 1)) and int(out[210:].sum()) == 0
 
 
+def test_launch_names_the_entry_point_it_called():
+    """_lib.launch checks the return code under the name it looked up: the library refuses the null pointers before any launch."""
+    with pytest.raises(RuntimeError, match="grl_image_pack8 failed: bad argument"):
+        _lib.launch("grl_image_pack8", _lib.GrlPack8Args())
+
+
 def test_image_writer_on_cuda_tensors_reuses_its_buffers(tmp_path):
     """Eight images through two workers and four staging buffers; an image is overwritten on the device right after its write."""
     g = torch.Generator().manual_seed(4)

@@ -1,9 +1,7 @@
 """Saving restored images on the CPU (image8.py, restore.py, evaluate's --save-dir).  ``pack8`` is pinned bit for bit against
 tests/golden/tasks/image8.npz, which tools/make_golden_image8.py wrote with the reference's own ``tensor_round`` followed by the calls
 of ``_save_images`` (engines/base.py:529-550).  Every comparison is integer equality."""
-import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -97,21 +95,10 @@ def test_nan_gives_zero_and_arguments_are_checked():
     assert G.pack8 is I.pack8 and G.ImageWriter is I.ImageWriter and G.restore_folder is restore.restore_folder
 
 
-def test_pack8_args_layout_matches_header_and_abi(tmp_path):
-    st = _lib.GrlPack8Args
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "grl_hip.h"', "int main(void) {",
-             'printf("size %zu\\n", sizeof(GrlPack8Args));']
-    lines += [f'printf("{f[0]} %zu\\n", offsetof(GrlPack8Args, {f[0]}));' for f in st._fields_]
-    lines += ['printf("abi %d\\n", (int)GRL_ABI_VERSION);', "return 0; }"]
-    src = tmp_path / "layout.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    out = dict(l.split() for l in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
-    assert int(out["size"]) == ctypes.sizeof(st)
-    for f in st._fields_:
-        assert int(out[f[0]]) == getattr(st, f[0]).offset, f[0]
-    assert _lib.ABI_VERSION >= 30 and int(out["abi"]) == _lib.ABI_VERSION
+def test_pack8_args_layout_matches_header_and_abi():
+    """The layout of GrlPack8Args is compared with the header in tests/test_abi.py, like every struct's;
+    what is particular to this entry point stays here."""
+    assert _lib.ABI_VERSION >= 30
     assert "grl_image_pack8" in _lib.EXPORTS
     header = open(os.path.join(ROOT, "include", "grl_hip.h")).read()
     assert "utils/utils_image.py:30-33" in header and "engines/base.py:529-530" in header and "NaN gives 0" in header

@@ -4,11 +4,9 @@ integer arithmetic, so every comparison with the library is ``torch.equal``: aga
 tools/make_jpeg_golden.py wrote from the same library (never skipped).  OpenCV, which the reference calls
 (data/datasets/restoration_jpeg.py:62-79), runs libjpeg-turbo with the same defaults: 4:2:0, JDCT_ISLOW, baseline tables, fancy
 upsampling."""
-import ctypes
 import io
 import os
 import random
-import subprocess
 
 import numpy as np
 import pytest
@@ -153,21 +151,10 @@ def test_tables_are_the_decoded_files():
             assert list(qt[k]) == natural[k].tolist(), (q, k)
 
 
-def test_jpeg_args_layout_matches_header_and_abi(tmp_path):
-    st = _lib.GrlJpegArgs
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "grl_hip.h"', "int main(void) {",
-             'printf("size %zu\\n", sizeof(GrlJpegArgs));']
-    lines += [f'printf("{f[0]} %zu\\n", offsetof(GrlJpegArgs, {f[0]}));' for f in st._fields_]
-    lines += ['printf("abi %d\\n", (int)GRL_ABI_VERSION);', "return 0; }"]
-    src = tmp_path / "layout.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    out = dict(l.split() for l in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
-    assert int(out["size"]) == ctypes.sizeof(st)
-    for f in st._fields_:
-        assert int(out[f[0]]) == getattr(st, f[0]).offset, f[0]
-    assert _lib.ABI_VERSION >= 29 and int(out["abi"]) == _lib.ABI_VERSION
+def test_jpeg_args_layout_matches_header_and_abi():
+    """The layout of GrlJpegArgs is compared with the header in tests/test_abi.py, like every struct's;
+    what is particular to this entry point stays here."""
+    assert _lib.ABI_VERSION >= 29
     assert "grl_jpeg_roundtrip" in _lib.EXPORTS and "grl_jpeg_workspace_bytes" in _lib.EXPORTS
     header = open(os.path.join(ROOT, "include", "grl_hip.h")).read()
     assert "restoration_jpeg.py:62-79" in header

@@ -2,10 +2,8 @@
 restatement of the reference's chain (_pad_images, _random_index, _sample_patches, _augment of data/datasets/base_image.py and
 torchvision's to_tensor), the draw order, the learning-rate schedule against the reference's class and recorded values, the
 Charbonnier loss, the ABI entry, and the four tasks' batches."""
-import ctypes
 import os
 import random
-import subprocess
 
 import numpy as np
 import pytest
@@ -170,21 +168,10 @@ def test_charbonnier_value_and_gradient():
     assert abs(float(charbonnier(y, y, eps=0.5)) - 0.5) < 1e-7
 
 
-def test_patch_args_layout_matches_header_and_abi(tmp_path):
-    st = _lib.GrlPatchArgs
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "grl_hip.h"', "int main(void) {",
-             'printf("size %zu\\n", sizeof(GrlPatchArgs));']
-    lines += [f'printf("{f[0]} %zu\\n", offsetof(GrlPatchArgs, {f[0]}));' for f in st._fields_]
-    lines += ['printf("abi %d\\n", (int)GRL_ABI_VERSION);', "return 0; }"]
-    src = tmp_path / "layout.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    out = dict(l.split() for l in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
-    assert int(out["size"]) == ctypes.sizeof(st)
-    for f in st._fields_:
-        assert int(out[f[0]]) == getattr(st, f[0]).offset, f[0]
-    assert _lib.ABI_VERSION >= 27 and int(out["abi"]) == _lib.ABI_VERSION
+def test_patch_args_layout_matches_header_and_abi():
+    """The layout of GrlPatchArgs is compared with the header in tests/test_abi.py, like every struct's;
+    what is particular to this entry point stays here."""
+    assert _lib.ABI_VERSION >= 27
     assert "grl_sample_patches" in _lib.EXPORTS
 
 

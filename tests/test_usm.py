@@ -19,10 +19,8 @@ Tolerances (u = 2^-24, gamma_n = n u / (1 - n u), |x| <= 1, the taps are positiv
     most tap_max^2 and the result by at most tap_max^2 * 0.5: the bound is 6.4e-6 + U tap_max^2 0.5.  The float64 result at
     threshold 10 is restated below in numpy from the recorded blur.
 """
-import ctypes
 import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -135,21 +133,10 @@ def test_usm_sharp_refuses_what_it_cannot_take():
         T.usm_sharp(torch.zeros(1, 3, 8, 8, dtype=torch.float64))
 
 
-def test_usm_args_layout_matches_header_and_abi(tmp_path):
-    st = _lib.GrlUsmArgs
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "grl_hip.h"', "int main(void) {",
-             'printf("size %zu\\n", sizeof(GrlUsmArgs));']
-    lines += [f'printf("{f[0]} %zu\\n", offsetof(GrlUsmArgs, {f[0]}));' for f in st._fields_]
-    lines += ['printf("abi %d\\n", (int)GRL_ABI_VERSION);', "return 0; }"]
-    src = tmp_path / "layout.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    out = dict(l.split() for l in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
-    assert int(out["size"]) == ctypes.sizeof(st)
-    for f in st._fields_:
-        assert int(out[f[0]]) == getattr(st, f[0]).offset, f[0]
-    assert _lib.ABI_VERSION >= 31 and int(out["abi"]) == _lib.ABI_VERSION
+def test_usm_args_layout_matches_header_and_abi():
+    """The layout of GrlUsmArgs is compared with the header in tests/test_abi.py, like every struct's;
+    what is particular to this entry point stays here."""
+    assert _lib.ABI_VERSION >= 31
     assert "grl_usm_sharp" in _lib.EXPORTS and "grl_usm_workspace_bytes" in _lib.EXPORTS
     header = open(os.path.join(ROOT, "include", "grl_hip.h")).read()
     assert "utils/utils_bsr/utils_usm.py:34-60" in header and "restoration_sr.py:105-109" in header
