@@ -260,7 +260,6 @@ def _real(n: int, npad: int) -> bool:
 
 
 _REAL_WIDTHS = [SW.on("GRL_REAL_WIDTHS")]
-_F16_HANDOVER = [SW.on("GRL_F16_HANDOVER")]     # linear layers: fp16 operand copies for the weight gradient
 
 
 @torch.library.custom_op("grl::linear", mutates_args=())
@@ -282,7 +281,7 @@ def linear_op(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor], one_c
         _leave_operand(x, xa)
     if gelu_in:
         kw["a_gelu"] = True
-    if w.requires_grad and _F16_HANDOVER[0] and K % 4 == 0:
+    if w.requires_grad and K % 4 == 0:
         # the fp16 operand [x | 1 | 0] the kernel contracts, kept for the weight gradient INSTEAD of x: grl_gemm_tn then reads 2-byte
         # values from 16-byte aligned rows once per output tile instead of converting the fp32 matrix every time (and the saved
         # activation is half the size)
@@ -660,7 +659,7 @@ class FanOut(torch.autograd.Function):
 
 
 def fan_out(x, n: int):
-    if x.is_cuda and x.requires_grad and SW.on("GRL_FAN_OUT"):
+    if x.is_cuda and x.requires_grad:
         return FanOut.apply(x, n)
     return (x,) * n
 

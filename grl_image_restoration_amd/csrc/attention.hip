@@ -800,13 +800,13 @@ extern "C" int grl_attention_fwd(void* stream, const GrlAttnArgs* args) {
     const bool split = p.q_lo != nullptr || p.k_lo != nullptr || p.v_lo != nullptr;
     if (p.o_lo != nullptr && p.out_dtype != GRL_DT_F16) return GRL_ERR_BAD_ARG;
     const bool lazy_ok = !split && p.k_one31 && p.head_dim <= 30 && p.ones_col != 31 && p.lazy_floor != nullptr;
-    static const int rows_off = grl_env_int("GRL_ATTN_ROWS", 1) == 0;   // 0: round-2 fast kernels (A/B)
     // head_dim 32 (GRL-Small): no spare slot; the row-streaming kernel carries offset and denominator on the VALU instead
     const bool d32_ok = !split && p.head_dim == 32 && p.ones_col < 0 && p.lazy_floor != nullptr;
-    const bool generic_only = getenv("GRL_ATTN_GENERIC") != nullptr;   // A/B knob, read per call (set: generic kernel only)
-    if ((lazy_ok || d32_ok) && !rows_off && !generic_only && grl_attn_rows_supported(p)) return grl_attn_rows_launch(p, st);
+    if ((lazy_ok || d32_ok) && grl_attn_rows_supported(p)) return grl_attn_rows_launch(p, st);
+    // the round-2 tile kernel: 32-aligned geometries that the row-streaming kernel declines (anchors against the 64x128 stripes of
+    // the dn geometries at head_dim <= 30: their table window does not fit its buffer)
     if (lazy_ok && !p.q.transposed && p.ones_col >= 0 && (p.q.ww % 32) == 0 && (p.k.ww % 32) == 0 && (p.q.wh % 2) == 0 &&
-        (p.k.wh % 8) == 0 && fast_lds_bytes(p, 1) <= 160 * 1024 && !generic_only)
+        (p.k.wh % 8) == 0 && fast_lds_bytes(p, 1) <= 160 * 1024)
         return launch_fast(p, st);
     // query blocks of equal size: 288 anchors are 2 x 3 waves (192 + 96 queries), not 4 waves + a workgroup that stages every
     // key chunk for 32 queries

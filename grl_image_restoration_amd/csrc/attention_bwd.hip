@@ -33,7 +33,6 @@ namespace {
 struct GrlAttnBwdLaunch : GrlAttnBwdArgs {
     int32_t tab_window;      // floats of a table window in attn_dq_kernel's LDS (table and histogram)
     int32_t tab_window_kv;   // ... in attn_dkv_kernel's
-    int32_t no_prefetch;     // GRL_ATTN_BWD_PREFETCH=0: attn_dq_kernel stages every chunk behind its loads (A/B timing)
 };
 
 constexpr int QT = 2;            // tiles (32 queries resp. keys) per wave
@@ -289,7 +288,7 @@ __global__ __launch_bounds__(256) void attn_dq_kernel(GrlAttnBwdLaunch a, int sp
     // Round 6: with the full 256 threads a chunk is two (key, 16-byte segment) items per thread, and their K / V loads for chunk ch + 1
     // are ISSUED before the tiles of chunk ch are computed (16 registers); the LDS stores follow behind the next barrier.  Before, every
     // chunk began with the full global-load latency in front of its first tile -- with one wave per SIMD nothing else covers it.
-    const bool pre = nthreads == 256 && !a.no_prefetch;
+    const bool pre = nthreads == 256;
     const int ch_end = (sp + 1) * nchunks / splits;
     f16x8 pk[2], pv[2];
     int prid[2];
@@ -687,8 +686,6 @@ extern "C" int grl_attention_bwd(void* stream, const GrlAttnBwdArgs* args) {
     GrlAttnBwdLaunch a_l;                               // the caller's arguments + the table-window sizes of the two launches
     a_l.fwd = a.fwd; a_l.d_o = a.d_o; a_l.d_q = a.d_q; a_l.d_k = a.d_k; a_l.d_v = a.d_v; a_l.d_table = a.d_table; a_l.g_scale = a.g_scale;
     a_l.d_table_fix = a.d_table_fix; a_l.d_o_ld = a.d_o_ld; a_l.tab_window = 0; a_l.tab_window_kv = 0;
-    static const int no_pre = grl_env_int("GRL_ATTN_BWD_PREFETCH", 1) == 0;
-    a_l.no_prefetch = no_pre;
     const int Dw = p.q.ww + p.k.ww - 1;
     // Split launches (see attn_dq_kernel): when a launch has fewer workgroups than the chip has CUs and a long streamed dimension,
     // cut that dimension over several workgroups that accumulate with atomics.  Needs a destination this function can zero: dense
@@ -712,13 +709,8 @@ extern "C" int grl_attention_bwd(void* stream, const GrlAttnBwdArgs* args) {
         }
         return s < nchunks ? (s < 1 ? 1 : s) : (nchunks > 0 ? nchunks : 1);
     };
-    // (GRL_ZERO_MEMSET=1 restores round 5's hipMemsetAsync -- only so that tools/probes/attn_bwd_graph_memset.py can show the failure
-    // this replaced on the installed runtime; nothing else sets it)
-    const char* zm = getenv("GRL_ZERO_MEMSET");
-    const bool zero_by_memset = zm && zm[0] == '1';
     auto zero = [&](float* ptr, const GrlTokenGrid& g) {          // (dense planes: 32 floats per token, 16-byte aligned rows)
         const int64_t n4 = (int64_t)p.nh * p.B * g.Himg * g.Wimg * 8;
-        if (zero_by_memset) return hipMemsetAsync(ptr, 0, (size_t)n4 * 16, st);
         if (((uintptr_t)ptr & 15) != 0) return hipErrorInvalidValue;
         hipLaunchKernelGGL(zero_f32x4_kernel, dim3((unsigned)((n4 + 255) / 256 < 2048 ? (n4 + 255) / 256 : 2048)), dim3(256), 0, st, (float4*)ptr, n4);
         return hipGetLastError();

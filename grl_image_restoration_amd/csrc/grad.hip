@@ -54,14 +54,11 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(GrlGemmTnArgs p) {
     // Work item = (slab of M, tap; output tile).  The tiles of one slab read the same rows of a and b -- a is re-read by every k tile,
     // b by every n tile -- so they are kept on ONE XCD, next to each other in time: its L2 then serves the re-reads (the dispatcher
     // places workgroup i on XCD i % 8; with the plain blockIdx order the 27 tiles of a QKV slab were spread over all eight L2s and
-    // every one of them fetched its own copy).  GRL_GEMM_TN_XCD=0 at launch time restores the plain order (A/B timing).
-    int bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
-    if (p.reserved0 == 0) {
-        const int T = gridDim.x * gridDim.y;
-        const int w = xcd_remap_tn(bx + gridDim.x * (by + gridDim.y * bz), T * gridDim.z);
-        const int tile = w % T;
-        bz = w / T; by = tile / gridDim.x; bx = tile - by * gridDim.x;
-    }
+    // every one of them fetched its own copy).
+    const int T = gridDim.x * gridDim.y;
+    const int w = xcd_remap_tn(blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z), T * gridDim.z);
+    const int tile = w % T;
+    const int bz = w / T, by = tile / gridDim.x, bx = tile - by * gridDim.x;
     const int n0 = bx * GT, k0 = by * GT;
     const int tap = bz / p.splits, slab = bz - tap * p.splits;
     const int dy = p.taps == 9 ? tap / 3 - 1 : 0, dx = p.taps == 9 ? tap % 3 - 1 : 0;
@@ -204,10 +201,7 @@ extern "C" int grl_gemm_tn(void* stream, const GrlGemmTnArgs* args) {
     if (p.taps == 9 && (p.H <= 0 || p.W <= 0 || p.M % (p.H * p.W) != 0)) return GRL_ERR_BAD_ARG;
     if (p.splits <= 0 || p.splits * p.taps > 65535 || (p.c == nullptr && p.c_fix == nullptr)) return GRL_ERR_BAD_ARG;
     const dim3 grid((p.N + GT - 1) / GT, (p.K + (p.b_ones ? 1 : 0) + GT - 1) / GT, p.splits * p.taps);
-    GrlGemmTnArgs q = p;
-    static const int plain_order = grl_env_int("GRL_GEMM_TN_XCD", 1) == 0;
-    q.reserved0 = plain_order;         // (kernel-internal use of the reserved field: 1 = blockIdx order)
-    hipLaunchKernelGGL(gemm_tn_kernel, grid, dim3(256), 0, (hipStream_t)stream, q);
+    hipLaunchKernelGGL(gemm_tn_kernel, grid, dim3(256), 0, (hipStream_t)stream, p);
     GRL_CHECK_LAUNCH();
     return 0;
 }

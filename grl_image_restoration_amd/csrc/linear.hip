@@ -52,7 +52,7 @@ extern "C" int grl_linear_fwd(void* stream, const GrlLinearArgs* args) {
     if (p.a_split != 0 && p.a_split != 1 && p.a_split != 3) return GRL_ERR_BAD_ARG;
     if (p.out_lo != nullptr && p.out_dtype != GRL_DT_F16) return GRL_ERR_BAD_ARG;
     if (p.add2 != nullptr && (p.add2_scale == nullptr || p.rows_per_image <= 0)) return GRL_ERR_BAD_ARG;
-    if (p.a_split == 3 && p.w_regs != nullptr && !getenv("GRL_LINEAR_SPLIT_GENERIC")) {   // weights-stationary split kernel (csrc/linear_split.hip)
+    if (p.a_split == 3 && p.w_regs != nullptr) {   // weights-stationary split kernel (csrc/linear_split.hip)
         const int rc = grl_linear_split_launch(p, st);
         if (rc != GRL_ERR_UNSUPPORTED) return rc;
     }

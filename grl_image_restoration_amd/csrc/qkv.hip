@@ -192,9 +192,7 @@ int launch_qkv(const GrlQkvArgs& p, hipStream_t st) {
 
 template <int KSTEPS>
 int launch_qkv_k(const GrlQkvArgs& p, hipStream_t st) {
-    static const int w16 = grl_env_int("GRL_QKV_W16", 1);   // 16 waves, slot-split (-5 % vs 8 waves); 0: the 8-wave kernel (A/B)
-    if (p.nslots % 2 == 0 && w16) return launch_qkv<KSTEPS, 2, 16, 8>(p, st);
-    if (p.nslots % 2 == 0) return launch_qkv<KSTEPS, 2, 8>(p, st);
+    if (p.nslots % 2 == 0) return launch_qkv<KSTEPS, 2, 16, 8>(p, st);   // even slot count: 16 waves, slot-split (-5 % vs 8 waves)
     return launch_qkv<KSTEPS, 1, 8>(p, st);
 }
 

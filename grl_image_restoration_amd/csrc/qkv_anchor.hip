@@ -883,8 +883,7 @@ extern "C" int grl_qkv_anchor_fwd(void* stream, const GrlQkvAnchorArgs* args) {
         if (p.Cpad != 192 || p.nslots != 18 || p.nanc != 3 || ((uintptr_t)p.lo_blob & 15) != 0) return GRL_ERR_UNSUPPORTED;
         return launch_qs(p, st);
     }
-    static const bool regs_off = grl_env_int("GRL_QKV_REGS", 1) == 0;
-    if (p.Cpad == 192 && p.nslots + p.nanc == QR_SLOTS && !regs_off) return launch_qr(p, st);
+    if (p.Cpad == 192 && p.nslots + p.nanc == QR_SLOTS) return launch_qr(p, st);
     switch (p.Cpad / 16) {
         case 4: return launch_qa<4>(p, st);
         case 8: return launch_qa<8>(p, st);

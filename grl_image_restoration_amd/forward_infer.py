@@ -1,7 +1,7 @@
 """The inference launch sequence of ``GRL`` (grl.py:506-551) over a packed plan (plan.py): which HIP kernel runs where.
 
 Every function takes the model as its first argument.  Which route a block takes is read off its ``BlockPlan``: an optional field
-that is packed (``is not None``) selects the kernel that consumes it; the ``SW.on`` reads here are per call.
+that is packed (``is not None``) selects the kernel that consumes it, and the rest is decided from the shape.  No environment switch chooses a kernel here.
 """
 import torch
 
@@ -19,13 +19,10 @@ def cab(model, r, pk: BlockPlan, B, H, W, CP):
     sp, dt = (3, torch.float32) if hi else (1, ops.GEMM_DTYPE)
     mid = ops.empty(B * H * W, pk.cab_mid, dtype=dt, device=r.device)  # fast: pad channels zero-filled by the conv store
     ops.conv3x3(r, pk.cab0_w, pk.cab0_b, B, H, W, act=1, out=mid, x_split=pk.cab0_split)
-    # (GRL_SE_FOLD=1: conv2 + pool + squeeze-excite gate in one launch, the gate by the last workgroup of each image.  Measured
-    # SLOWER in the two-stream bench, 88.1 against 82.6 ms/step: the serial tail of one workgroup per image holds the whole
-    # launch, while the separate 10-us se_kernel hides behind the other tile group's kernels.  Kept as an option, off.)
-    if pk.cab2_blob is not None and SW.on("GRL_SE_FOLD"):
-        return ops.cab_conv2(mid, pk.cab2_blob, pk.cab2_bias, B, H, W,
-                             se=(pk.se1_w, pk.se1_b, pk.se3_w, pk.se3_b, model.embed_dim))
-    elif pk.cab2_blob is not None:
+    # (The squeeze-excite gate stays a launch of its own.  Folding it into the conv2 launch, the gate by the last workgroup of each
+    # image, measured SLOWER in the two-stream bench, 88.1 against 82.6 ms/step: the serial tail of one workgroup per image holds the
+    # whole launch, while the separate 10-us se_kernel hides behind the other tile group's kernels.)
+    if pk.cab2_blob is not None:
         raw, pool = ops.cab_conv2(mid, pk.cab2_blob, pk.cab2_bias, B, H, W)
     else:
         raw, pool = ops.conv3x3(mid, pk.cab2_w, pk.cab2_b, B, H, W, want_pool=True, out_dtype=dt, x_split=sp)
@@ -79,8 +76,8 @@ def block(model, r, pk: BlockPlan, geo: BlockGeo, B, H, W):
         return block_high(model, r, pk, geo, B, H, W)
     # q/k/v, anchors and the anchor-side values live as head planes [slot][token][32]: a key tile of 32
     # consecutive tokens is 2 KB contiguous for the attention kernel's staging loads
-    one_pass = pk.qa_blob is not None and df == 2 and H % 2 == 0 and W % 64 == 0 and SW.on("GRL_QKV_ANCHOR")
-    if pk.hiq and one_pass and pk.qa_lo is not None and SW.on("GRL_QKV_SPLIT"):
+    one_pass = pk.qa_blob is not None and df == 2 and H % 2 == 0 and W % 64 == 0
+    if pk.hiq and one_pass and pk.qa_lo is not None:
         qkv, anc = ops.qkv_anchor(r, pk.qa_blob, pk.qa_slots[0], pk.qa_slots[1], B, H, W, lo_blob=pk.qa_lo)
     elif pk.hiq:
         qkv = ops.linear(r, pk.qkv_w3, pk.qkv_b, epi=L.EPI_GROUPNORM, gscale=pk.qkv_gs, planes=True, a_split=3, w_regs=pk.qkv_w3r)
@@ -88,7 +85,7 @@ def block(model, r, pk: BlockPlan, geo: BlockGeo, B, H, W):
     elif one_pass:
         qkv, anc = ops.qkv_anchor(r, pk.qa_blob, pk.qa_slots[0], pk.qa_slots[1], B, H, W)
     else:
-        if pk.qkv_blob is not None and SW.on("GRL_STREAM_QKV"):
+        if pk.qkv_blob is not None:
             qkv = ops.qkv(r, pk.qkv_blob, pk.qkv_slots)
         else:
             qkv = ops.linear(r, pk.qkv_w, pk.qkv_b, epi=L.EPI_GROUPNORM, gscale=pk.qkv_gs, planes=True)
@@ -96,7 +93,7 @@ def block(model, r, pk: BlockPlan, geo: BlockGeo, B, H, W):
     att = ops.empty(M, (nh_w + nh_s) * 32, dtype=ops.GEMM_DTYPE, device=dev)  # operand of the proj GEMM
     attention(model, qkv, anc, att, pk, geo, B, H, W)
     cab_, gate = cab(model, r, pk, B, H, W, CP) if model.local_connection else (None, None)
-    if pk.proj_blob is not None and pk.mlp_blob is not None and H * W >= 128 and SW.on("GRL_FUSED_TAIL"):
+    if pk.proj_blob is not None and pk.mlp_blob is not None and H * W >= 128:
         return ops.block_tail(att, r, cab_, gate, H * W, pk.proj_blob, pk.proj_b, pk.n1_g, pk.n1_b, pk.mlp_blob,
                               pk.fc2_b, pk.n2_g, pk.n2_b, Hpad=pk.mlp_hp, n_real=C, res_scale=model.res_scale,
                               rblob=pk.tail_rblob)
@@ -105,7 +102,7 @@ def block(model, r, pk: BlockPlan, geo: BlockGeo, B, H, W):
                     ln_b=pk.n1_b, n_real=C, res_scale=model.res_scale, resid=r, add2=cab_, add2_scale=gate,
                     rows_per_image=H * W)
     # x = x + res_scale * norm2(mlp(x))                 (efficient.py:554)
-    if pk.mlp_blob is not None and SW.on("GRL_FUSED_MLP"):
+    if pk.mlp_blob is not None:
         return ops.mlp(r1, pk.mlp_blob, pk.fc2_b, pk.n2_g, pk.n2_b, Hpad=pk.mlp_hp, n_real=C,
                        res_scale=model.res_scale)
     h = ops.linear(r1, pk.fc1_w, pk.fc1_b, epi=L.EPI_GELU)
@@ -140,8 +137,7 @@ def block_high(model, r, pk: BlockPlan, geo: BlockGeo, B, H, W):
     cab_, gate = cab(model, r, pk, B, H, W, CP) if model.local_connection else (None, None)
     # norm + residual (+ gated CAB branch) in the epilogue of the weights-stationary kernel where it takes the shape (a row of
     # <= 192 channels is one slab): the fp32 products p1 / p2 never reach memory
-    fuse = (CP <= 192 and M % 32 == 0 and (H * W) % 32 == 0 and pk.proj_wr is not None and pk.fc2_wr is not None
-            and SW.on("GRL_HIGH_FUSE_LN"))
+    fuse = CP <= 192 and M % 32 == 0 and (H * W) % 32 == 0 and pk.proj_wr is not None and pk.fc2_wr is not None
     if fuse:
         r1 = ops.linear(att, pk.proj_w, pk.proj_b, epi=L.EPI_LN_RES, out_dtype=f32, a_split=3, w_regs=pk.proj_wr,
                         ln_g=pk.n1_g, ln_b=pk.n1_b, n_real=C, res_scale=model.res_scale, resid=r, add2=cab_, add2_scale=gate,

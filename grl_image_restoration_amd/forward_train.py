@@ -247,10 +247,9 @@ def attention_train_batched(model, qkv, anc, a, geo: BlockGeo, B, H, W, pre=None
     # (round 6: the two branch outputs as token matrices [M, nh * 32]: one cat along the channels gives the projection's input --
     # block_train_tail places the weight columns accordingly -- and the cat's backward hands each attention backward its column
     # block of the gradient in place; before: cat of the planes, permute, slice, copy, and zeros + copy + two copies back)
-    tm = SW.on("GRL_TRAIN_TOKEN_MAJOR")
     ow = AG.AttentionFn.apply(qw, kw, vw, tabs[0],
                               dict(q=g_tok_w, k=g_tok_w, B=B, nh=nh, d=d, masked=geo.window_shift > 0, floor=fw, prepared=True,
-                                   f16=(qw16, kw16, vw16), token_major=tm))
+                                   f16=(qw16, kw16, vw16), token_major=True))
     y = AG.AttentionFn.apply(aq, ks, vs, tabs[1],
                              dict(q=g_anc, k=g_tok_s, B=B, nh=nh, d=d, masked=geo.stripe_shift, floor=f1, prepared=True,
                                   f16=(aq16, ks16, vs16)))
@@ -264,10 +263,8 @@ def attention_train_batched(model, qkv, anc, a, geo: BlockGeo, B, H, W, pre=None
         yv = torch.addcmul(onev, y, dmask)                          # real head dims only, and the constant 1.0 in column d again
     os_ = AG.AttentionFn.apply(qs, ak, yv, tabs[2],
                                dict(q=g_tok_s, k=g_anc, B=B, nh=nh, d=d, masked=geo.stripe_shift, floor=f2, prepared=True,
-                                    f16=(qs16, ak16, None), token_major=tm))
-    if tm:
-        return torch.cat([ow, os_], dim=1)                          # [M, 2 * nh * 32]
-    return torch.cat([ow, os_], dim=0).permute(1, 0, 2)[..., :d].reshape(M, C)
+                                    f16=(qs16, ak16, None), token_major=True))
+    return torch.cat([ow, os_], dim=1)                              # [M, 2 * nh * 32]
 
 
 def block_train_tail(model, r, att, blk, B, H, W, dp: float, r_conv=None):
@@ -293,12 +290,9 @@ def block_train_tail(model, r, att, blk, B, H, W, dp: float, r_conv=None):
         # x1 + u * gate(u): pool, squeeze-excite MLP and the gated residual as three launches each way (autograd.se_residual)
         x1 = AG.se_residual(x1, u, se[1].weight.flatten(1), se[1].bias, se[3].weight.flatten(1), se[3].bias, H * W)
     # Mlp (swin_v1_block.py:37-43): the GELU between fc1 and fc2 is taken by fc2's loader, its adjoint by the epilogue of fc2's
-    # data-gradient launch (autograd.linear gelu_in; GRL_GELU_FUSED=0: the torch activation)
+    # data-gradient launch (autograd.linear gelu_in)
     h1 = AG.linear(x1, blk.mlp.fc1.weight, blk.mlp.fc1.bias)
-    if SW.on("GRL_GELU_FUSED"):
-        m = AG.linear(h1, blk.mlp.fc2.weight, blk.mlp.fc2.bias, gelu_in=True)
-    else:
-        m = AG.linear(F.gelu(h1), blk.mlp.fc2.weight, blk.mlp.fc2.bias)
+    m = AG.linear(h1, blk.mlp.fc2.weight, blk.mlp.fc2.bias, gelu_in=True)
     return norm_residual(model, x1, m, blk.norm2, H * W, dp)
 
 

@@ -58,10 +58,8 @@ def deterministic() -> bool:
 # are cut from ONE arena that is zeroed by one launch when the backward pass starts (autograd.GradScaleTop.backward calls
 # zero_arena_begin): sized by what the previous pass used; a pass that needs more falls back to torch.zeros for the rest and the next
 # arena is larger.  The slices become gradients (``.grad`` of the parameters): the arena lives as long as any of them.
-# GRL_ZERO_ARENA=0: torch.zeros per buffer.
 _ARENA: dict = {}            # device index -> [buffer, next free element, elements requested in this pass, autograd graph-task id]
 _ARENA_SIZE: dict = {}       # device index -> elements the last complete pass requested
-_ARENA_ON = SW.on("GRL_ZERO_ARENA")
 
 
 def _graph_task() -> int:
@@ -74,7 +72,7 @@ def zero_arena_begin(device) -> None:
     """Start of a backward pass on ``device``: one zeroed arena for its small accumulation buffers (scoped to THIS pass by the
     autograd graph-task id: a request from anywhere else -- a forward pass, a direct call, another backward -- gets torch.zeros)."""
     task = _graph_task()
-    if not _ARENA_ON or device.type != "cuda" or task < 0:
+    if device.type != "cuda" or task < 0:
         return
     idx = device.index if device.index is not None else torch.cuda.current_device()
     prev = _ARENA.get(idx)
@@ -88,7 +86,7 @@ def zero_arena_begin(device) -> None:
 def zeros_f32(n: int, device) -> torch.Tensor:
     """A zeroed fp32 vector of n elements (16-byte aligned): a slice of the running backward pass's arena when there is room, else
     torch.zeros."""
-    if _ARENA_ON and device.type == "cuda":
+    if device.type == "cuda":
         a = _ARENA.get(device.index if device.index is not None else torch.cuda.current_device())
         if a is not None and a[3] == _graph_task():
             n4 = (n + 3) // 4 * 4
@@ -781,13 +779,9 @@ def pack_cab_conv2(w: torch.Tensor, bias: torch.Tensor):
     return blob, b
 
 
-_SE_COUNTERS = {}   # (device, stream) -> zeroed int32 counters the kernel returns to zero (one launch at a time per stream)
-
-
-def cab_conv2(x: torch.Tensor, blob: torch.Tensor, bias: torch.Tensor, B: int, H: int, W: int, se=None):
+def cab_conv2(x: torch.Tensor, blob: torch.Tensor, bias: torch.Tensor, B: int, H: int, W: int):
     """(out [B*H*W, 192] fp16, pool partial sums [B * wgs_per_image, 192]) = conv3x3(x) + bias of the CAB's second convolution
-    (grl_cab_conv2_fwd: filter bank in registers); x [B*H*W, >= 56] fp16 with zero pad channels.  ``se=(w1, b1, w2, b2, C)``:
-    the squeeze-excite gate [B, 192] is computed by the kernel's last workgroup per image and returned instead of the sums."""
+    (grl_cab_conv2_fwd: filter bank in registers); x [B*H*W, >= 56] fp16 with zero pad channels."""
     _dev_check(x, blob, bias)
     assert x.dim() == 2 and x.stride(1) == 1 and x.dtype == GEMM_DTYPE and x.shape[0] == B * H * W and x.shape[1] >= 56
     out = empty(B * H * W, 192, dtype=GEMM_DTYPE, device=x.device)
@@ -796,24 +790,9 @@ def cab_conv2(x: torch.Tensor, blob: torch.Tensor, bias: torch.Tensor, B: int, H
     pool = empty(B * wgs, 192, dtype=torch.float32, device=x.device)
     args = L.GrlCabConv2Args(x=_ptr(x), ldx=x.stride(0), blob=_ptr(blob), bias=_ptr(bias), B=B, H=H, W=W, wgs_per_image=wgs,
                              out=_ptr(out), ldo=192, pool_partial=_ptr(pool), pool_stride=192)
-    gate = None
-    if se is not None:
-        w1, b1, w2, b2, C_ = se
-        _dev_check(w1, b1, w2, b2)
-        key = (x.device, torch.cuda.current_stream(x.device).cuda_stream)
-        cnt = _SE_COUNTERS.get(key)
-        if cnt is None or cnt.numel() < B:
-            if torch.cuda.is_current_stream_capturing():   # (the buffer would live in the capturing graph's private pool)
-                raise RuntimeError("cab_conv2(se=...): run one eager forward on this stream before capturing it in a graph")
-            cnt = _SE_COUNTERS[key] = torch.zeros(max(B, 64), dtype=torch.int32, device=x.device)
-        cnt[:B].zero_()   # explicit: an aborted launch must not leave arrivals behind (the kernel also returns them to zero)
-        gate = empty(B, 192, dtype=torch.float32, device=x.device)
-        args.gate, args.se_counter = _ptr(gate), _ptr(cnt)
-        args.se_w1, args.se_b1, args.se_w2, args.se_b2 = _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2)
-        args.se_c, args.se_mid, args.inv_hw = C_, w1.shape[0], 1.0 / (H * W)
     with _timed("cab_conv2"):
         L.launch("grl_cab_conv2_fwd", args)
-    return out, (gate if se is not None else pool)
+    return out, pool
 
 
 def se_scale(pool: torch.Tensor, B: int, CP: int, C_: int, HW: int, w1, b1, w2, b2) -> torch.Tensor:

@@ -256,8 +256,9 @@ def pack_block(model, blk, geo: BlockGeo, dev, hi: Optional[bool] = None, cab_sp
                    fc1_wr=ops.pack_linear_split(fc1_w), fc2_wr=ops.pack_linear_split(fc2_w))
     if fast_cp and KA == CP and model.local_connection:   # + proj/norm1/CAB in front: one kernel per block tail
         opt.update(proj_blob=ops.pack_proj(Wop))
-        # weights stationary in registers (csrc/tail_regs.hip, round 4): 255 against 290 us per 4 tiles; GRL_TAIL_REGS=0: streaming kernel
-        if CP == 192 and HP == 384 and C > 160 and SW.on("GRL_TAIL_REGS"):
+        # weights stationary in registers (csrc/tail_regs.hip, round 4): 255 against 290 us per 4 tiles.  Its register image is built for
+        # the Base widths only (192 padded channels, 384 hidden, more than 160 real channels); every other width streams its weights
+        if CP == 192 and HP == 384 and C > 160:
             opt.update(tail_rblob=ops.pack_tail_regs(Wop, blk.mlp.fc1.weight.to(dev), blk.mlp.fc1.bias.to(dev), blk.mlp.fc2.weight.to(dev)))
     if fast_cp:  # fused fc1 -> GELU -> fc2 -> norm2 -> residual kernel (csrc/mlp.hip)
         opt.update(mlp_blob=ops.pack_mlp(blk.mlp.fc1.weight.to(dev), blk.mlp.fc1.bias.to(dev), blk.mlp.fc2.weight.to(dev), CP, HP),
@@ -271,7 +272,7 @@ def pack_block(model, blk, geo: BlockGeo, dev, hi: Optional[bool] = None, cab_sp
         coords = tables.coords_table(win, df, device=dev)
         bias = tables.bias_rows(m.cpb_mlp[0].weight.to(dev), m.cpb_mlp[0].bias.to(dev), m.cpb_mlp[2].weight.to(dev), coords)
         sw = lambda t: (t[1], t[0])
-        tr = (not hi and SW.on("GRL_ATTN_TRANSPOSE")
+        tr = (not hi
               and not ops.attention_rows_ok(q_win, k_win, q_sh, k_sh, masked, d)
               and ops.attention_rows_ok(sw(q_win), sw(k_win), sw(q_sh), sw(k_sh), masked, d))
         if tr:
@@ -312,7 +313,7 @@ def pack_block(model, blk, geo: BlockGeo, dev, hi: Optional[bool] = None, cab_sp
             se3_w=se[3].weight.detach().float().reshape(C, -1).to(dev).clone(),
             se3_b=se[3].bias.detach().float().to(dev).clone(),
         )
-        if not hi_c and CP == 192 and Cm <= 48 and CmI >= 56 and SW.on("GRL_CAB_CONV2"):
+        if not hi_c and CP == 192 and Cm <= 48 and CmI >= 56:
             opt["cab2_blob"], opt["cab2_bias"] = ops.pack_cab_conv2(c2.weight.to(dev), c2.bias.to(dev))   # csrc/cab_conv2.hip
     return BlockPlan(
         hi=hi, hiq=hiq, one_w=one_w, one_s=one_s, qkv_w=qkv_w, qkv_b=bp, qkv_gs=gs, anc_w=anc_w, anc_b=bap, anc_gs=anc_gs,

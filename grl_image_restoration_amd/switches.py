@@ -2,7 +2,8 @@
 
 This module is the only place in the package that touches ``os.environ`` for a ``GRL_*`` name.  A new switch is one row here, one
 accessor call where it is read (``grl_env_int`` in csrc/common.h on the C side) and one row in DESIGN.md's "Knobs" table;
-tests/test_switches.py fails when the three disagree.
+tests/test_switches.py fails when the three disagree.  No switch selects a kernel: a path is chosen from what the code can observe
+(shape, precision, device), and an A/B toggle lives on a development branch and is removed before merge.
 
 kind   on     default-on:  off only for the exact string "0"
        off    default-off: on only for the exact string "1"
@@ -38,49 +39,23 @@ TABLE = {row[0]: Switch(*row) for row in (
     ("GRL_GRAPH", "off", False, "plan", "1: replay the inference forward as a captured HIP graph (read at the first forward)"),
     ("GRL_CONV_SPLIT", "int", SITE, "call", "output channels per launch of a 3x3 convolution (0: one launch); default 96 for short-K layers, else 0"),
     ("GRL_PERSIST_GRID", "int", 256, "import", "cap on the grid of the persistent kernels (one workgroup per CU)", "csrc"),
-    ("GRL_CONV_KC", "int", 0, "import", "32: 32-channel chunks in the generic conv kernel", "csrc"),
     ("GRL_NO_CPU_COMPOSITE", "off", False, "call", "1: CPU tensors raise instead of taking the composite torch path"),
     ("GRL_NIQE_PARAMS", "str", "", "call", "path of the pristine NIQE model (niqe_pris_params.npz) when none is passed"),
-    # ---- A/B switches back to the previous kernels ----
-    ("GRL_ATTN_ROWS", "on", True, "import", "0: the tile kernels instead of the row-streaming attention kernel", "csrc"),
-    ("GRL_ATTN_GENERIC", "off", False, "call", "set (to anything): the generic attention kernel only", "csrc"),
-    ("GRL_ATTN_TRANSPOSE", "on", True, "plan", "0: no transposed grid views for the row-streaming attention kernel"),
-    ("GRL_QKV_ANCHOR", "on", True, "call", "0: QKV and anchor projections as separate launches"),
-    ("GRL_QKV_REGS", "on", True, "import", "0: the streaming QKV + anchor kernel instead of the weights-in-registers one", "csrc"),
-    ("GRL_QKV_SPLIT", "on", True, "call", "0: generic split-operand linears for the q / k / anchor planes of high-scale blocks"),
-    ("GRL_QKV_W16", "int", 1, "import", "0: the 8-wave QKV kernel instead of the 16-wave slot-split one", "csrc"),
-    ("GRL_STREAM_QKV", "on", True, "call", "0: the generic linear kernel for the QKV projection"),
-    ("GRL_FUSED_TAIL", "on", True, "call", "0: proj + norm1 and the MLP as separate launches"),
-    ("GRL_FUSED_MLP", "on", True, "call", "0: fc1 and fc2 as separate linear launches"),
-    ("GRL_TAIL_REGS", "on", True, "plan", "0: the streaming block-tail kernel instead of the weights-in-registers one"),
-    ("GRL_CAB_CONV2", "on", True, "plan", "0: the generic conv kernel for the CAB's second convolution"),
-    ("GRL_SE_FOLD", "off", False, "call", "1: conv2 + pool + squeeze-excite gate in one launch (measured slower)"),
-    ("GRL_CONV192", "on", True, "import", "0: the generic kernel for the 192 -> 192 convolutions", "csrc"),
-    ("GRL_HIGH_FUSE_LN", "on", True, "call", "0: the norms of precision `high` as launches of their own"),
-    ("GRL_LINEAR_SPLIT_GENERIC", "off", False, "call", "set (to anything): the generic split linear instead of the weights-stationary one", "csrc"),
     # ---- training ----
     ("GRL_DETERMINISTIC", "off", False, "call", "1: bit-identical training gradients (fixed-point accumulation; slower)"),
     ("GRL_TRAIN_BATCHED_PLANES", "on", True, "call", "0: per-slot plane and per-block table chains"),
     ("GRL_PLANES_KERNEL", "on", True, "call", "0: the torch chain instead of the head-plane kernel"),
     ("GRL_PLANES_WRITE32", "off", False, "call", "1: the head-plane kernel also writes the fp32 planes"),
-    ("GRL_TRAIN_TOKEN_MAJOR", "on", True, "call", "0: attention outputs as head planes instead of token matrices"),
-    ("GRL_GELU_FUSED", "on", True, "call", "0: the torch activation between fc1 and fc2"),
-    ("GRL_FAN_OUT", "on", True, "call", "0: autograd's own accumulation for a tensor with several consumers"),
     ("GRL_SE_KERNEL", "on", True, "call", "0: the torch expression of the squeeze-excite gate and gated residual"),
     ("GRL_REAL_WIDTHS", "on", True, "import", "0: padded operand copies everywhere"),
-    ("GRL_F16_HANDOVER", "on", True, "import", "0: no fp16 operand copies for the weight gradient of the linear layers"),
     ("GRL_STAT_REPLICAS", "int", 32, "import", "copies of the small cross-workgroup sums (LayerNorm dgamma / dbeta, plane scale gradients)"),
-    ("GRL_ZERO_ARENA", "on", True, "import", "0: torch.zeros per zero-initialised gradient buffer instead of one arena"),
     ("GRL_GEMM_TN_WGS", "int", 0, "call", "workgroups the weight-gradient GEMM aims for (0: chosen by tile count)"),
-    ("GRL_GEMM_TN_XCD", "on", True, "import", "0: blockIdx order in the weight-gradient GEMM", "csrc"),
-    ("GRL_ATTN_BWD_PREFETCH", "on", True, "import", "0: the attention backward stages every chunk behind its loads (no prefetch)", "csrc"),
     ("GRL_ATTN_BWD_SPLITS", "int", 0, "call", "1: no split attention-backward launches, n: n parts on every launch, -n: cap of the automatic choice",
      "csrc"),
     # ---- debug ----
     ("GRL_POISON", "off", False, "import", "1: every workspace tensor is NaN-filled before use"),
     ("GRL_DIRTY_LDS", "off", False, "import", "1: fill the LDS of every CU with NaN bytes before every launch"),
     ("GRL_CHECK_RANGE", "off", False, "call", "1: print the largest residual-stream magnitude per block (one stream)"),
-    ("GRL_ZERO_MEMSET", "off", False, "call", "1: hipMemsetAsync instead of the zero-fill kernel (tools/probes/attn_bwd_graph_memset.py only)", "csrc"),
 )}
 
 

@@ -23,7 +23,7 @@ extern "C" {
 
 #define GRL_ERR_BAD_ARG (-1)
 #define GRL_ERR_UNSUPPORTED (-2)
-#define GRL_ABI_VERSION 32
+#define GRL_ABI_VERSION 33
 
 /* element kinds of activation / weight buffers */
 enum { GRL_DT_F32 = 0, GRL_DT_BF16 = 1, GRL_DT_F16 = 2 };
@@ -385,16 +385,6 @@ typedef struct GrlCabConv2Args {
     int64_t ldo;
     float* pool_partial;
     int64_t pool_stride;    /* >= 192 */
-    /* optional squeeze-excite gate (ChannelAttention.attention, mixed_attn_block.py:956-963) computed by the last workgroup   */
-    /* of every image from the partial sums: gate[b][c] = sigmoid(W2 . relu(W1 . mean_b + b1) + b2), 0 for c >= se_c           */
-    float* gate;            /* [B, 192] or NULL (then the fields below are ignored)                           */
-    int32_t* se_counter;    /* [B] zero-initialised once; the kernel leaves it zero (one launch at a time per buffer) */
-    const float* se_w1;     /* [se_mid, se_c] */
-    const float* se_b1;     /* [se_mid]       */
-    const float* se_w2;     /* [se_c, se_mid] */
-    const float* se_b2;     /* [se_c]         */
-    int32_t se_c, se_mid;   /* <= 192, <= 64  */
-    float inv_hw;           /* 1 / (H * W)    */
 } GrlCabConv2Args;
 
 int grl_cab_conv2_fwd(void* stream, const GrlCabConv2Args* args);
@@ -467,7 +457,7 @@ typedef struct GrlGemmTnArgs {
     /* column N / K of a row -- and the bias gradient without a ones column in memory:                                          */
     int32_t b_ones;         /* != 0: b has a VIRTUAL column K that holds 1.0 (taps = 9: inside the image); its products, the   */
     int32_t reserved0;      /* column sums of a, go to c_bias[n] (taps = 9: of the centre tap) instead of a column of c         */
-                            /* (reserved0: ignored -- the entry point uses the slot to tell the kernel its tile order)          */
+                            /* (reserved0: ignored)                                                                          */
     float* c_bias;          /* [N] fp32, zeroed by the caller (required with b_ones unless c_bias_fix)                          */
     int64_t* c_bias_fix;    /* [N], the deterministic counterpart (with c_fix)                                                  */
     int32_t a_dtype;        /* 0 / GRL_DT_F32: a is fp32 (the field `a`); GRL_DT_F16: a points at fp16 values that are ALREADY     */
