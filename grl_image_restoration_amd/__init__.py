@@ -8,6 +8,8 @@ from .data import PatchSampler, PatchStore  # noqa: F401
 from .train import charbonnier, multistep_warmup_lr  # noqa: F401
 from .image8 import ImageWriter, pack8  # noqa: F401
 from .restore import restore_folder  # noqa: F401
+from .discriminator import UNetDiscriminatorSN  # noqa: F401
+from .gan import GanStep, gan_loss  # noqa: F401
 
 __all__ = ["GRL", "FusedAdamW", "GraphedTrainStep", "make_config", "baseline_config", "PatchStore", "PatchSampler",
-           "charbonnier", "multistep_warmup_lr", "pack8", "ImageWriter", "restore_folder"]
+           "charbonnier", "multistep_warmup_lr", "pack8", "ImageWriter", "restore_folder", "UNetDiscriminatorSN", "GanStep", "gan_loss"]

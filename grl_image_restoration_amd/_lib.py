@@ -11,7 +11,7 @@ from . import switches as SW
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgrl_hip.so")
-ABI_VERSION = 33
+ABI_VERSION = 34
 DT_F32, DT_BF16, DT_F16 = 0, 1, 2
 
 EPI_PLAIN, EPI_GELU, EPI_GROUPNORM, EPI_LN_RES, EPI_GELU_GRAD = 0, 1, 2, 3, 4
@@ -648,6 +648,11 @@ SIGNATURES = {
     "grl_usm_sharp": _launch(GrlUsmArgs),
     "grl_cv_resize": _launch(GrlCvResizeArgs),
     "grl_blur_items": _launch(GrlBlurItemsArgs),
+    "grl_conv4x4s2_fwd": _launch(GrlConvArgs),
+    "grl_conv4x4s2_bwd_data": _launch(GrlConvArgs),
+    "grl_pack_conv4x4": (C.c_int, [_PTR] * 3 + [_I32] * 5),
+    "grl_upsample2x_bilinear_fwd": (C.c_int, [_PTR, _PTR, _I64, _PTR, _I64] + [_I32] * 4),
+    "grl_upsample2x_bilinear_bwd": (C.c_int, [_PTR, _PTR, _I64, _PTR, _I64] + [_I32] * 4),
     "grl_debug_dirty_lds": (C.c_int, [_PTR]),
     "grl_abi_version": (C.c_int, []),
     "grl_build_info": (C.c_char_p, []),

@@ -6,6 +6,9 @@ the forward AND the backward pass runs in libgrl_hip.so:
   torch.ops.grl.linear     y = x W^T + b      fwd grl_linear_fwd | dx = grl_linear_fwd on (dy, W) | dW = grl_gemm_tn(dy, x)
   torch.ops.grl.conv3x3    3x3 conv (pad 1)   fwd grl_conv3x3_fwd | dx = grl_conv3x3_fwd on (dy, flipped W^T) | dW = grl_gemm_tn (9 taps)
   torch.ops.grl.attention  cosine attention   fwd grl_attention_fwd (+ log-sum-exp) | grl_attention_bwd (dq, dk, dv, dtable)
+  torch.ops.grl.conv3x3_lrelu   conv3x3 + LeakyReLU in the epilogue (the U-Net discriminator, discriminator.py) | as conv3x3 on the masked dy
+  torch.ops.grl.conv4x4s2  4x4 conv, stride 2 (pad 1, + LeakyReLU)   fwd grl_conv4x4s2_fwd | dx = grl_conv4x4s2_bwd_data | dW = grl_gemm_tn (16 taps)
+  torch.ops.grl.upsample2x bilinear x2        fwd grl_upsample2x_bilinear_fwd | grl_upsample2x_bilinear_bwd (a gather)
 
 (torch.library custom ops with registered autograd and fake kernels)
 
@@ -395,9 +398,7 @@ def _conv_pads(Cin: int, Cout: int):
     return CinP, CoutP, keep192
 
 
-@torch.library.custom_op("grl::conv3x3", mutates_args=())
-def conv3x3_op(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, B: int, H: int, W: int) -> torch.Tensor:
-    """3x3 convolution, stride 1, zero pad 1, on channels-last token matrices x[B*H*W, Cin] -> [B*H*W, Cout] (grl_conv3x3_fwd)."""
+def _conv3x3_forward(x, w, b, B, H, W, **epi):
     Cout, Cin = w.shape[:2]
     CinP, CoutP, keep192 = _conv_pads(Cin, Cout)
     wp, bp = ops.pack_conv_train(w, b, CoutP, CinP)           # one launch (round 6; torch chain: pack_conv_weight + pack_conv_bias)
@@ -406,10 +407,17 @@ def conv3x3_op(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, B: int, H: int
     else:
         xa, kw = _padded(x.detach().float(), CinP, ones=True), {}   # (the ones column meets zero weight columns; see _padded)
     _leave_operand(x, xa)
+    kw.update(epi)
     if _real(Cout, CoutP) and not keep192:
         return ops.conv3x3(xa, wp, bp, B, H, W, n_store=Cout, **kw)
     y = ops.conv3x3(xa, wp, bp, B, H, W, **kw)
     return y if Cout == CoutP else y[:, :Cout].contiguous()
+
+
+@torch.library.custom_op("grl::conv3x3", mutates_args=())
+def conv3x3_op(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, B: int, H: int, W: int) -> torch.Tensor:
+    """3x3 convolution, stride 1, zero pad 1, on channels-last token matrices x[B*H*W, Cin] -> [B*H*W, Cout] (grl_conv3x3_fwd)."""
+    return _conv3x3_forward(x, w, b, B, H, W)
 
 
 @conv3x3_op.register_fake
@@ -426,7 +434,7 @@ def _conv_setup(ctx, inputs, output):
 
 
 def _conv_backward(ctx, dy):
-    xs, w = ctx.saved_tensors
+    xs, w = ctx.saved_tensors[:2]
     B, H, W = ctx.bhw
     Cout, Cin = w.shape[:2]
     CinP, CoutP, keep192 = _conv_pads(Cin, Cout)
@@ -474,6 +482,124 @@ def _conv_backward(ctx, dy):
 
 
 conv3x3_op.register_autograd(_conv_backward, setup_context=_conv_setup)
+
+
+# ---- U-Net discriminator of the GAN stage (discriminator.py; models/aux_archs/discriminator.py:92-144) -----------------------
+# LeakyReLU rides in the forward launches' epilogues (GrlConvArgs.act = 2).  Its backward mask is read off the saved ACTIVATED
+# output: the slope is positive, so y > 0 exactly where the pre-activation was.  One torch.where per layer -- glue, no contraction --
+# and the U-Net's skip additions stay torch adds, so the saved tensor is the activation itself, not activation + skip.
+def _lrelu_grad(y: torch.Tensor, dy: torch.Tensor, slope: float) -> torch.Tensor:
+    return torch.where(y > 0, dy, dy * slope)
+
+
+@torch.library.custom_op("grl::conv3x3_lrelu", mutates_args=())
+def conv3x3_lrelu_op(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor], B: int, H: int, W: int, slope: float) -> torch.Tensor:
+    """leaky_relu(conv3x3(x) (+ b), slope) in one launch (grl_conv3x3_fwd, act = 2); slope = 1: the plain convolution, b optional."""
+    return _conv3x3_forward(x, w, b, B, H, W, act=2, slope=float(slope)) if slope != 1.0 else _conv3x3_forward(x, w, b, B, H, W)
+
+
+@conv3x3_lrelu_op.register_fake
+def _(x, w, b, B, H, W, slope):
+    return x.new_empty(x.shape[0], w.shape[0], dtype=torch.float32)
+
+
+def _conv_lrelu_setup(ctx, inputs, output):
+    x, w, b, B, H, W, slope = inputs
+    xp = _take_operand(x)
+    ctx.slope = float(slope)
+    if ctx.slope != 1.0:
+        ctx.save_for_backward(xp if xp is not None else x, w, output)
+    else:
+        ctx.save_for_backward(xp if xp is not None else x, w)
+    ctx.padded = xp is not None and xp.shape[1] != x.shape[1]
+    ctx.bhw = (B, H, W)
+
+
+def _conv_lrelu_backward(ctx, dy):
+    if ctx.slope != 1.0:
+        dy = _lrelu_grad(ctx.saved_tensors[2], dy, ctx.slope)
+    return _conv_backward(ctx, dy) + (None,)
+
+
+conv3x3_lrelu_op.register_autograd(_conv_lrelu_backward, setup_context=_conv_lrelu_setup)
+
+
+def _conv4_pads(Cin: int, Cout: int):
+    if Cin % 4 or Cout % 4:
+        raise ValueError(f"grl::conv4x4s2 takes channel counts that are multiples of 4 (got {Cin} -> {Cout})")
+    return (Cin + 31) // 32 * 32, (Cout + 15) // 16 * 16
+
+
+@torch.library.custom_op("grl::conv4x4s2", mutates_args=())
+def conv4x4s2_op(x: torch.Tensor, w: torch.Tensor, B: int, H: int, W: int, slope: float = 1.0) -> torch.Tensor:
+    """Conv2d(Cin, Cout, 4, 2, 1, bias=False) on channels-last token matrices x[B*H*W, Cin] -> [B*(H/2)*(W/2), Cout]
+    (grl_conv4x4s2_fwd); slope != 1: LeakyReLU(slope) in the epilogue."""
+    Cout, Cin = w.shape[:2]
+    CinP, CoutP = _conv4_pads(Cin, Cout)
+    wp = ops.pack_conv4x4(w, CoutP, CinP)
+    xa = _rows16(x.detach())
+    _leave_operand(x, xa)
+    act = dict(act=2, slope=float(slope)) if slope != 1.0 else {}
+    return ops.conv4x4s2(xa, wp, B, H, W, x_cols=Cin, n_store=Cout, **act)
+
+
+@conv4x4s2_op.register_fake
+def _(x, w, B, H, W, slope=1.0):
+    return x.new_empty(B * (H // 2) * (W // 2), w.shape[0], dtype=torch.float32)
+
+
+def _conv4_setup(ctx, inputs, output):
+    x, w, B, H, W, slope = inputs
+    xp = _take_operand(x)
+    ctx.slope = float(slope)
+    saved = (xp if xp is not None else x, w) + ((output,) if ctx.slope != 1.0 else ())
+    ctx.save_for_backward(*saved)
+    ctx.bhw = (B, H, W)
+
+
+def _conv4_backward(ctx, dy):
+    xs, w = ctx.saved_tensors[:2]
+    B, H, W = ctx.bhw
+    Cout, Cin = w.shape[:2]
+    if ctx.slope != 1.0:
+        dy = _lrelu_grad(ctx.saved_tensors[2], dy, ctx.slope)
+    dya = _rows16(dy)
+    s = grad_scale(dy.device)
+    dx = dw = None
+    if ctx.needs_input_grad[0]:
+        # the transposed convolution: per parity class of the input pixel a 2x2-tap convolution of dy (grl_conv4x4s2_bwd_data)
+        wt = ops.pack_conv4x4(w, (Cin + 15) // 16 * 16, (Cout + 31) // 32 * 32, transpose=True)
+        dx = ops.conv4x4s2(dya, wt, B, H, W, x_cols=Cout, n_store=Cin, transposed=True, x_scale=s, out_scale=1.0 / s)
+    if ctx.needs_input_grad[1]:
+        c = ops.gemm_tn(dya, _rows16(xs.detach()), Cout, Cin, taps=16, hw=(H // 2, W // 2), a_scale=s, out_scale=1.0 / s)   # [16, Cout, Cin]
+        dw = c.reshape(4, 4, Cout, Cin).permute(2, 3, 0, 1).contiguous()
+    return dx, dw, None, None, None, None
+
+
+conv4x4s2_op.register_autograd(_conv4_backward, setup_context=_conv4_setup)
+
+
+@torch.library.custom_op("grl::upsample2x", mutates_args=())
+def upsample2x_op(x: torch.Tensor, B: int, H: int, W: int) -> torch.Tensor:
+    """F.interpolate(scale_factor=2, mode="bilinear", align_corners=False) on a channels-last token matrix x[B*H*W, C] ->
+    [B*2H*2W, C] (grl_upsample2x_bilinear_fwd)."""
+    return ops.upsample2x(_rows16(x.detach()), B, H, W)
+
+
+@upsample2x_op.register_fake
+def _(x, B, H, W):
+    return x.new_empty(4 * x.shape[0], x.shape[1], dtype=torch.float32)
+
+
+def _up_setup(ctx, inputs, output):
+    ctx.bhw = inputs[1:]
+
+
+def _up_backward(ctx, dy):
+    return ops.upsample2x(_rows16(dy), *ctx.bhw, backward=True), None, None, None
+
+
+upsample2x_op.register_autograd(_up_backward, setup_context=_up_setup)
 
 
 def _attn_operands(q, k, v, d, prepared, have=(None, None, None)):

@@ -5,7 +5,9 @@
 //       (engines/base.py:221-236 backward through models/common/mixed_attn_block_efficient.py, mixed_attn_block.py,
 //       swin_v1_block.py, networks/grl.py): dW = dY^T X for the token-wise linears (QKV, anchor, proj, fc1, fc2) and,
 //       with the image-shift mode, the nine taps of a 3x3 convolution's weight gradient
-//       dW[tap][co][ci] = sum_pixels dY[p, co] * X[p + (dy, dx), ci]   (zero outside the image).
+//       dW[tap][co][ci] = sum_pixels dY[p, co] * X[p + (dy, dx), ci]   (zero outside the image);
+//       with taps = 16 the sixteen taps of a 4x4 stride-2 convolution (models/aux_archs/discriminator.py:102-104):
+//       dW[ky*4+kx][co][ci] = sum_{oy,ox} dY[oy, ox, co] * X[2 oy + ky - 1, 2 ox + kx - 1, ci].
 //   grl_adamw_step : torch.optim.AdamW (config/optimizer/adamw.yaml) over a list of tensors in ONE launch
 //       (1390 parameter tensors for GRL-Base: a per-tensor launch would be host-bound).
 //
@@ -86,6 +88,11 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(GrlGemmTnArgs p) {
                 const int x = m % p.W, y = (m / p.W) % p.H;
                 inside = (unsigned)(y + dy) < (unsigned)p.H && (unsigned)(x + dx) < (unsigned)p.W;
                 brow = (int64_t)m + dy * p.W + dx;
+            } else if (p.taps == 16) {   // 4x4 stride-2 convolution: a lives on the H x W output grid, b on the 2H x 2W input grid
+                const int x = m % p.W, y = (m / p.W) % p.H, img = m / (p.W * p.H);
+                const int sy = 2 * y + (tap >> 2) - 1, sx = 2 * x + (tap & 3) - 1;
+                inside = (unsigned)sy < (unsigned)(2 * p.H) && (unsigned)sx < (unsigned)(2 * p.W);
+                brow = ((int64_t)img * 2 * p.H + sy) * (2 * p.W) + sx;
             }
             const int kc = k0 + sseg * 8;
             if (inside) {
@@ -197,8 +204,9 @@ extern "C" int grl_gemm_tn(void* stream, const GrlGemmTnArgs* args) {
     if (p.lda < (p.N + aq - 1) / aq * aq || p.ldb < (p.K + bq - 1) / bq * bq) return GRL_ERR_BAD_ARG;   // (whole pieces are read)
     if (p.b_ones && p.c_bias == nullptr && p.c_bias_fix == nullptr) return GRL_ERR_BAD_ARG;
     if ((p.c_fix != nullptr) != (p.c_bias_fix != nullptr) && p.b_ones) return GRL_ERR_BAD_ARG;
-    if (p.taps != 1 && p.taps != 9) return GRL_ERR_BAD_ARG;
-    if (p.taps == 9 && (p.H <= 0 || p.W <= 0 || p.M % (p.H * p.W) != 0)) return GRL_ERR_BAD_ARG;
+    if (p.taps != 1 && p.taps != 9 && p.taps != 16) return GRL_ERR_BAD_ARG;
+    if (p.taps != 1 && (p.H <= 0 || p.W <= 0 || p.M % (p.H * p.W) != 0)) return GRL_ERR_BAD_ARG;
+    if (p.taps == 16 && p.b_ones) return GRL_ERR_BAD_ARG;
     if (p.splits <= 0 || p.splits * p.taps > 65535 || (p.c == nullptr && p.c_fix == nullptr)) return GRL_ERR_BAD_ARG;
     const dim3 grid((p.N + GT - 1) / GT, (p.K + (p.b_ones ? 1 : 0) + GT - 1) / GT, p.splits * p.taps);
     hipLaunchKernelGGL(gemm_tn_kernel, grid, dim3(256), 0, (hipStream_t)stream, p);

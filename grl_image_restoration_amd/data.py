@@ -159,6 +159,10 @@ class PatchSampler:
                   crop / scale LQ and the aligned (lq, gt) patches are cut.  Images smaller than the crop are refused at
                   construction: the store would pad them with zeros where the reference reflects them.  What is not built
                   (camera noise, colour jitter): bsr_degrade's docstring
+      sr with ``usm`` and ``plain_gt``
+                  ``next`` returns (lq, gt, gt_plain): the sharpened target as above and the unsharpened crop of the same place --
+                  the GAN stage's pixel target and the discriminator's real input (use_usm_pixel: True, use_usm_gan: False of
+                  config/experiment/bsr/grl.yaml).  Draws and generator are untouched
       sr_bicubic, jpeg at a fixed ``quality``
                   GT store only.  The LQ store is made once per image at construction (``tasks.TRAIN_STORE_LQ`` on the store's
                   device; sr_bicubic also replaces the GT store by the images cropped to the scale); then sampled as ``sr``
@@ -178,7 +182,7 @@ class PatchSampler:
                  scale: int = 1, sigma: Optional[float] = None, sigma_range: Optional[Sequence[float]] = None, seed: int = 0,
                  taps: Optional[torch.Tensor] = None, quality: Optional[int] = None,
                  quality_range: Optional[Sequence[int]] = None, patchwise: bool = True, usm: bool = False, degrade: bool = False,
-                 degrade_crop: int = 400):
+                 degrade_crop: int = 400, plain_gt: bool = False):
         from . import tasks
 
         patch, batch, scale = int(patch), int(batch), int(scale)
@@ -198,6 +202,7 @@ class PatchSampler:
                 raise ValueError(f"degrade: image {small[0]} ({gt_store.dims[small[0]][0]} x {gt_store.dims[small[0]][1]}) is smaller than "
                                  f"the crop {o.degrade_crop}; the store pads with zeros where the reference reflects")
         elif usm:
+            self.plain_store = gt_store if plain_gt else None
             gt_store = _usm_store(gt_store)
         if lq_store is not None:
             if len(lq_store) != len(gt_store) or lq_store.channels != gt_store.channels or lq_store.device != gt_store.device:
@@ -213,6 +218,9 @@ class PatchSampler:
         self.device = gt_store.device
         self.gen = torch.Generator(device=self.device).manual_seed(int(seed)) if o.rule.noise or degrade else None
         self.degrade, self.degrade_crop, self.usm = bool(degrade), o.degrade_crop, bool(usm)
+        if plain_gt and not usm:
+            raise ValueError("plain_gt hands out the unsharpened target next to the sharpened one: it belongs to usm")
+        self.plain_gt = bool(plain_gt)
         self.taps = taps.to(device=self.device, dtype=torch.float32).contiguous() if taps is not None else None
         self.draw_patch = patch + (self.taps.shape[0] - 1 if taps is not None else 0)   # the side the draws and the crop use
         if degrade:
@@ -258,7 +266,7 @@ class PatchSampler:
 
     # ---- batches -------------------------------------------------------------------------------------------------------------
     def next(self, work=None, sigmas: Optional[Sequence[float]] = None, noise: Optional[torch.Tensor] = None):
-        """(lq, gt) on the store's device.  ``work``: an explicit work list (a sequence of (image, x, y, flags) or an int32 (B, 4)
+        """(lq, gt) -- with ``plain_gt`` (lq, gt, gt_plain) -- on the store's device.  ``work``: an explicit work list (a sequence of (image, x, y, flags) or an int32 (B, 4)
         tensor) instead of fresh draws; ``sigmas`` with it for dn with a sigma range and for jpeg with a quality range (the
         qualities) and for ``degrade`` (the (plan, row, column) per sample).  ``noise`` (db): a unit-variance
         (B, 3, patch, patch) fp32 tensor used instead of the generator's draw (it is scaled by ``sigma / 255``)."""
@@ -273,6 +281,8 @@ class PatchSampler:
         if self.lq_store is not None:                # paired stores, given or made at construction
             lq = self.lq_store.sample(wt, self.patch, 1)
             gt = self.gt_store.sample(wt, self.patch, self.scale)
+            if self.plain_gt:
+                return lq, gt, self.plain_store.sample(wt, self.patch, self.scale)
             return lq, gt
         return self._pair(self, self.gt_store.sample(wt, self.draw_patch, 1), sigmas, noise)
 
@@ -283,13 +293,15 @@ class PatchSampler:
 
         if extras is None or len(extras) != wt.shape[0]:
             raise ValueError("degrade: one (plan, row, column) per sample next to an explicit work list")
-        crops = self.gt_store.sample(wt, self.degrade_crop, 1)
+        crops = plain = self.gt_store.sample(wt, self.degrade_crop, 1)
         if self.usm:
             crops = tasks.usm_sharp(crops)
         full = apply_plans(crops, [e[0] for e in extras], self.gen)
         P, s = self.patch, self.scale
         lq = torch.stack([full[b, :, r : r + P, c : c + P] for b, (_, r, c) in enumerate(extras)])
         gt = torch.stack([crops[b, :, r * s : (r + P) * s, c * s : (c + P) * s] for b, (_, r, c) in enumerate(extras)])
+        if self.plain_gt:
+            return lq, gt, torch.stack([plain[b, :, r * s : (r + P) * s, c * s : (c + P) * s] for b, (_, r, c) in enumerate(extras)])
         return lq, gt
 
     @staticmethod

@@ -69,12 +69,32 @@ def load_checkpoint(model, path_or_obj, strict: bool = True):
     (The other direction: ``GRL.state_dict()`` has no ``table_/index_/mask_`` buffers, so loading it into the reference module
     needs ``strict=False`` or the reference's own buffers merged in the same way.)"""
     obj = torch.load(path_or_obj, map_location="cpu") if isinstance(path_or_obj, (str, os.PathLike)) else path_or_obj
-    sd = extract_state_dict(obj)
+    sd = _gan_part(extract_state_dict(obj), "model_g.", "model.")
     sd = model.convert_checkpoint(dict(sd))           # needs the un-stripped "model.table_*" names (grl.py:556-569)
     sd = {(k[len("model."):] if k.startswith("model.") else k): v for k, v in sd.items()}
     cur = dict(model.state_dict())
     cur.update(sd)
     return model.load_state_dict(cur, strict=strict)
+
+
+def _gan_part(sd, part: str, prefix: str):
+    """A GAN-stage checkpoint (engines/base_gan.py: ``model.model_g.<k>`` / ``model.model_d.<k>``, or bare ``model_g.`` / ``model_d.``)
+    -> its ``part`` ("model_g." / "model_d.") keys as ``prefix + <k>``; any other state dict is returned as it is."""
+    if not any(k.startswith(("model.model_g.", "model_g.", "model.model_d.", "model_d.")) for k in sd):
+        return sd
+    out = {}
+    for k, v in sd.items():
+        bare = k[len("model."):] if k.startswith("model.model_") else k
+        if bare.startswith(part):
+            out[prefix + bare[len(part):]] = v
+    return out
+
+
+def load_discriminator_checkpoint(model_d, path_or_obj, strict: bool = True):
+    """The ``model_d.`` keys of a GAN-stage checkpoint (the reference's ``bsr_discriminator_checkpoint``, engines/base_gan.py:71-84, or
+    one written by ``train --gan``) into a ``discriminator.UNetDiscriminatorSN``; a bare discriminator state dict loads as it is."""
+    obj = torch.load(path_or_obj, map_location="cpu") if isinstance(path_or_obj, (str, os.PathLike)) else path_or_obj
+    return model_d.load_state_dict(_gan_part(extract_state_dict(obj), "model_d.", ""), strict=strict)
 
 
 # ---- metric (restated here: the product does not depend on the test infrastructure) -------------------------------

@@ -313,7 +313,8 @@ def forward(model, x):
     if x.is_cuda and getattr(model, "_ag_registered", None) != (first.data_ptr(), first.device):   # (re)register after .to() / load
         AG.register_parameters(model)
         model._ag_registered = (first.data_ptr(), first.device)
-    x = model.check_image_size(x.float())
+    # (a float64 model on the composite path computes in float64; every other input is cast to float32, whatever it came as)
+    x = model.check_image_size(x.to(first.dtype) if (first.dtype == torch.float64 and not x.is_cuda) else x.float())
     mean = model._mean.to(x.device, x.dtype)
     x = (x - mean) * model.img_range
     B, Cin, H, W = x.shape

@@ -1,0 +1,81 @@
+"""The GAN stage of real-world SR (config/experiment/bsr/grl.yaml): the vanilla GAN loss and one iteration of the alternation.
+
+  gan_loss   losses/losses.py:190-293, gan_type "vanilla": BCEWithLogitsLoss against constant labels 1 / 0; the loss weight applies
+             to the generator's term only
+  GanStep    engines/base_gan.py:86-147 as Lightning runs it with two optimizers: optimizer 0 (generator) with the discriminator's
+             parameters toggled off, then optimizer 1 (discriminator) on a fresh forward of the updated generator
+
+The perceptual (VGG19) and style losses of the reference's criterion are not built (``perceptual=None`` is the seam they go in).
+"""
+from typing import Callable, Dict, Optional
+
+import torch
+import torch.nn.functional as F
+
+
+def gan_loss(logits: torch.Tensor, target_is_real: bool, is_disc: bool, weight: float = 0.1) -> torch.Tensor:
+    """losses/losses.py:212, 267-268, 290-293 (vanilla)."""
+    label = logits.new_ones(logits.size()) * (1.0 if target_is_real else 0.0)
+    loss = F.binary_cross_entropy_with_logits(logits, label)
+    return loss if is_disc else loss * weight
+
+
+def _forward_in_training(G, lq: torch.Tensor) -> torch.Tensor:
+    """The generator's second forward of an iteration, under ``no_grad``.  A GRL on the GPU takes the training launch sequence for it,
+    as in the first forward: without gradients ``GRL.forward`` would go the inference way, which packs a plan of every weight (and
+    opens the tile-group streams) for weights that the optimizer has just changed and changes again one step later."""
+    from . import forward_train
+    from .model import GRL
+
+    if isinstance(G, GRL) and G.training and lq.is_cuda:
+        return forward_train.forward(G, lq)
+    return G(lq)
+
+
+class GanStep:
+    """One call = one Lightning iteration of the reference's GAN engine.  ``pixel_loss(restored, target)``; both optimizers step
+    once; returns the reference's logged scalars (detached tensors)."""
+
+    def __init__(self, model_g, model_d, opt_g, opt_d, pixel_loss: Callable, pixel_weight: float = 1.0, gan_weight: float = 1.0,
+                 gan_loss_weight: float = 0.1, usm_pixel: bool = False, usm_gan: bool = False, perceptual=None):
+        if perceptual is not None:
+            raise NotImplementedError("the perceptual (VGG19) loss is not part of this package yet")
+        self.model_g, self.model_d, self.opt_g, self.opt_d = model_g, model_d, opt_g, opt_d
+        self.pixel_loss, self.pixel_weight, self.gan_weight, self.gan_loss_weight = pixel_loss, pixel_weight, gan_weight, gan_loss_weight
+        self.usm_pixel, self.usm_gan = usm_pixel, usm_gan
+
+    def __call__(self, lq: torch.Tensor, gt: torch.Tensor, gt_usm: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+        if (self.usm_pixel or self.usm_gan) and gt_usm is None:
+            raise ValueError("usm_pixel / usm_gan need the sharpened target")
+        G, D_ = self.model_g, self.model_d
+        out = {}
+        # ---- optimizer 0: the generator (base_gan.py:96-126); toggle_optimizer: the discriminator's parameters are off ----
+        d_params = [p for p in D_.parameters() if p.requires_grad]
+        for p in d_params:
+            p.requires_grad_(False)
+        try:
+            restored = G(lq)
+            loss_g_pix = self.pixel_loss(restored, gt_usm if self.usm_pixel else gt) * self.pixel_weight
+            loss_g_gan = gan_loss(D_(restored), True, is_disc=False, weight=self.gan_loss_weight) * self.gan_weight
+            self.opt_g.zero_grad(set_to_none=True)
+            (loss_g_pix + loss_g_gan).backward()
+            self.opt_g.step()
+            self.opt_g.zero_grad(set_to_none=True)      # (gradients do not outlive their step: nothing of one optimizer's pass is
+        finally:                                        # visible to the other's)
+            for p in d_params:
+                p.requires_grad_(True)
+        out["loss_g_pix"], out["loss_g_gan"] = loss_g_pix.detach(), loss_g_gan.detach()
+        # ---- optimizer 1: the discriminator (base_gan.py:129-145); training_step calls self(batch) again ----
+        with torch.no_grad():
+            restored = _forward_in_training(G, lq)
+        real_d_pred = D_(gt_usm if self.usm_gan else gt)
+        loss_d_real = gan_loss(real_d_pred, True, is_disc=True)
+        fake_d_pred = D_(restored.detach())
+        loss_d_fake = gan_loss(fake_d_pred, False, is_disc=True)
+        self.opt_d.zero_grad(set_to_none=True)
+        (loss_d_real + loss_d_fake).backward()
+        self.opt_d.step()
+        self.opt_d.zero_grad(set_to_none=True)
+        out.update(loss_d_real=loss_d_real.detach(), loss_d_fake=loss_d_fake.detach(), out_d_real=real_d_pred.detach().mean(),
+                   out_d_fake=fake_d_pred.detach().mean())
+        return out

@@ -811,12 +811,15 @@ def se_scale(pool: torch.Tensor, B: int, CP: int, C_: int, HW: int, w1, b1, w2, 
 def gemm_tn(a: torch.Tensor, b: torch.Tensor, N: int, K: int, *, taps: int = 1, hw: Optional[Tuple[int, int]] = None,
             a_scale: float = 1.0, out_scale: float = 1.0, b_ones: bool = False):
     """c[taps, N, K] = out_scale * sum_m (a_scale * a[m, :N])^T b[row(m, tap), :K]  (grl_gemm_tn): the weight gradient of a
-    token-wise linear (taps=1) or of a 3x3 convolution on channels-last pixel matrices (taps=9, hw=(H, W)).  N, K multiples of 4;
+    token-wise linear (taps=1), of a 3x3 convolution on channels-last pixel matrices (taps=9, hw=(H, W)) or of a 4x4 stride-2
+    convolution (taps=16, hw = the OUTPUT grid, row(m, tap) = input pixel (2y + ky - 1, 2x + kx - 1)).  N, K multiples of 4;
     nothing is read beyond column N / K of a row, so a and b may be the layer's tensors at their real widths.  ``b_ones``: returns
     (c, bias) with bias[n] = out_scale * sum_m a_scale * a[m, n] -- the bias gradient, as if b had a column of ones (ABI 22)."""
     _dev_check(a, b)
     assert a.dim() == 2 and b.dim() == 2 and a.dtype in (torch.float32, torch.float16) and b.dtype in (torch.float32, torch.float16)
-    assert a.stride(1) == 1 and b.stride(1) == 1 and a.shape[0] == b.shape[0] and a.shape[1] >= N and b.shape[1] >= K
+    # (taps=16, the 4x4 stride-2 convolution: hw is a's grid, b lives on the 2H x 2W input grid)
+    assert a.stride(1) == 1 and b.stride(1) == 1 and b.shape[0] == (4 if taps == 16 else 1) * a.shape[0] and a.shape[1] >= N and b.shape[1] >= K
+    assert taps in (1, 9, 16) and not (taps == 16 and b_ones)
     # (an fp16 ``a`` is taken as already multiplied by a_scale: the operand copy of the data-gradient launch, linear(a16_out=...))
     M = a.shape[0]
     H, W = hw if hw is not None else (0, 0)
@@ -1123,4 +1126,50 @@ def sum_tensors(ts) -> torch.Tensor:
     out = empty(ts[0].shape, dtype=torch.float32, device=ts[0].device)
     p = [_ptr(t) for t in ts] + [None] * (4 - len(ts))
     L.check(L.lib().grl_sum4(L.stream_ptr(), p[0], p[1], p[2], p[3], _ptr(out), n), "grl_sum4")
+    return out
+
+
+# ---- U-Net discriminator (csrc/disc.hip): 4x4 stride-2 convolution and x2 bilinear upsampling ---------------------------------
+def pack_conv4x4(w: torch.Tensor, rows_pad: int, cols_pad: int, transpose: bool = False) -> torch.Tensor:
+    """grl_pack_conv4x4: conv weight [Cout, Cin, 4, 4] -> fp16 [16, rows_pad, cols_pad] (tap = ky*4+kx), rows = output channels;
+    ``transpose``: rows = input channels (the operand of the data gradient)."""
+    _dev_check(w)
+    Cout, Cin = w.shape[:2]
+    assert tuple(w.shape[2:]) == (4, 4)
+    wc = w.detach().float().contiguous()
+    ow = empty(16, rows_pad, cols_pad, dtype=GEMM_DTYPE, device=w.device)
+    L.check(L.lib().grl_pack_conv4x4(L.stream_ptr(), _ptr(wc), _ptr(ow), Cout, Cin, rows_pad, cols_pad, int(transpose)), "grl_pack_conv4x4")
+    return ow
+
+
+def conv4x4s2(x: torch.Tensor, w: torch.Tensor, B: int, H: int, W: int, *, x_cols: int, n_store: int, act: int = 0, slope: float = 0.0,
+              transposed: bool = False, x_scale: float = 1.0, out_scale: float = 1.0) -> torch.Tensor:
+    """Conv2d(k=4, s=2, p=1, bias=False) on a channels-last token matrix (grl_conv4x4s2_fwd): x [B*H*W, x_cols] -> [B*(H/2)*(W/2),
+    n_store], w from pack_conv4x4.  ``transposed``: the data gradient (grl_conv4x4s2_bwd_data) -- x is dy [B*(H/2)*(W/2), x_cols], the
+    result dx [B*H*W, n_store], w the transposed pack; H, W are the full-resolution size either way."""
+    _dev_check(x, w)
+    assert x.dim() == 2 and x.stride(1) == 1 and x.dtype == torch.float32 and w.dtype == GEMM_DTYPE and w.is_contiguous() and w.shape[0] == 16
+    rows_in, rows_out = (B * (H // 2) * (W // 2), B * H * W) if transposed else (B * H * W, B * (H // 2) * (W // 2))
+    assert x.shape[0] == rows_in and x.shape[1] >= x_cols
+    RowsP, ColsP = w.shape[1], w.shape[2]
+    out = empty(rows_out, n_store, dtype=torch.float32, device=x.device)
+    args = L.GrlConvArgs(x=_ptr(x), x_dtype=L.DT_F32, ldx=x.stride(0), w=_ptr(w), w_tap_stride=RowsP * ColsP, B=B, H=H, W=W, CinP=ColsP,
+                         CoutP=RowsP, x_scale=x_scale, out_scale=out_scale, act=act, slope=slope, out=_ptr(out), out_dtype=L.DT_F32,
+                         ldo=out.stride(0), x_cols=x_cols, n_store=n_store)
+    name = "conv4x4s2_bwd_data" if transposed else "conv4x4s2"
+    with _timed(f"{name} {ColsP}->{RowsP} {H}x{W}" if _PROFILE is not None else name):
+        L.launch("grl_conv4x4s2_bwd_data" if transposed else "grl_conv4x4s2_fwd", args)
+    return out
+
+
+def upsample2x(x: torch.Tensor, B: int, H: int, W: int, *, backward: bool = False) -> torch.Tensor:
+    """x2 bilinear upsampling (align_corners=False) of a token matrix x [B*H*W, C] -> [B*2H*2W, C] (grl_upsample2x_bilinear_fwd), or
+    with ``backward`` its adjoint dy [B*2H*2W, C] -> [B*H*W, C] (grl_upsample2x_bilinear_bwd).  H, W: the LOW-resolution size."""
+    _dev_check(x)
+    assert x.dim() == 2 and x.stride(1) == 1 and x.dtype == torch.float32 and x.shape[0] == B * H * W * (4 if backward else 1)
+    C_ = x.shape[1]
+    out = empty(B * H * W * (1 if backward else 4), C_, dtype=torch.float32, device=x.device)
+    name = "grl_upsample2x_bilinear_bwd" if backward else "grl_upsample2x_bilinear_fwd"
+    with _timed(name[4:]):
+        L.check(getattr(L.lib(), name)(L.stream_ptr(), _ptr(x), x.stride(0), _ptr(out), out.stride(0), B, H, W, C_), name)
     return out

@@ -27,6 +27,7 @@ class TaskRule:
     quality: bool = False               # takes a JPEG quality, or for training a quality range
     usm: bool = False                   # the GT may be USM-sharpened (use_usm / use_usm_pixel: restoration_sr.py:94,105-109)
     degrade: bool = False               # training may make its LQ on the fly by the blind-SR degradation (restoration_bsr.py:83-110)
+    gan: bool = False                   # training may run the GAN stage against the U-Net discriminator (engines/base_gan.py, bsr/grl.yaml)
     save_tag: Optional[str] = None      # saved images go under X<scale> ("scale"), Sigma<sigma> ("sigma"), QF<quality> ("quality") or
                                         # straight under the data set's name (None): engines/base.py:504-524
 
@@ -34,7 +35,7 @@ class TaskRule:
 RULES = {
     "sr": TaskRule("classical SR from an LQ / GT folder pair (also deblurring and JPEG from folders): config/experiment/sr, "
                    "data/datasets/restoration_sr.py:97-123 with load_lr; USM-sharpened GT: config/experiment/bsr/grl_psnr.yaml:26-33",
-                   lq_from="folder", default_scale=4, max_scale=None, usm=True, degrade=True, save_tag="scale"),
+                   lq_from="folder", default_scale=4, max_scale=None, usm=True, degrade=True, gan=True, save_tag="scale"),
     "dn": TaskRule("denoising: config/data_module/dn.yaml; training noise restoration_dn.py:126-143, seeded validation noise :133-143",
                    crop=8, noise=True, sigma_range=True, save_tag="sigma"),
     "dm": TaskRule("demosaicking: restoration_dm.py:25-35 (mosaic), engines/base.py:126-128 (dm_matlab before the model)",
@@ -57,7 +58,7 @@ SYNTHESISED = tuple(t for t in RULES if RULES[t].lq_from == "gt")
 
 def resolve(task, where, *, scale=None, channels=3, lq=False, sigma=None, sigma_range=None, taps=False, quality=None,
             quality_range=None, patch=None, patchwise=True, val=False, val_lq=False, usm=False, val_usm=False, degrade=False,
-            degrade_crop=None):
+            degrade_crop=None, gan=False):
     """Checks the options of one call against ``RULES[task]``, fills the defaults and returns them as a namespace (``rule``,
     ``scale``, ``sigma``, ``sigma_range``, ``quality``, ``quality_range``).  Raises ValueError.  ``where`` is the caller: "evaluate" /
     "train" (the command lines), "evaluate_folder", "task_inputs", "sampler".  ``lq`` / ``taps``: whether an LQ folder or store / a blur
@@ -66,7 +67,7 @@ def resolve(task, where, *, scale=None, channels=3, lq=False, sigma=None, sigma_
     have always differed, the difference is a branch on ``where`` below, marked "kept".  ``degrade`` (training): the LQ is made per
     sample from a ``degrade_crop`` x ``degrade_crop`` GT crop (default 400) by ``bsr_degrade``; then no LQ folder or store is given,
     the scale is 2 or 4, the images have three channels, the crop is a multiple of 4 and at least 4 * scale, and ``patch`` is at
-    most crop / scale.  The namespace also carries ``degrade_crop`` (None without ``degrade``).
+    most crop / scale.  The namespace also carries ``degrade_crop`` (None without ``degrade``).  ``gan`` (train): the GAN stage.
     """
     training, library_eval = where in ("train", "sampler"), where in ("evaluate_folder", "task_inputs")
     r = RULES.get(task)
@@ -74,6 +75,9 @@ def resolve(task, where, *, scale=None, channels=3, lq=False, sigma=None, sigma_
         raise ValueError(f"unknown task {task!r}: one of {TRAIN_TASKS if training else TASKS}")
     if where == "task_inputs" and r.lq_from != "gt":
         raise ValueError(f"task {task!r} reads its LQ from a folder; synthesised tasks: {', '.join(SYNTHESISED)}")
+    if gan and (not training or not r.gan):
+        raise ValueError(f"task {task} has no GAN stage (--gan): only training of {', '.join(t for t in RULES if RULES[t].gan)} runs "
+                         "against the discriminator")
     if degrade:
         if not training or not r.degrade:
             raise ValueError(f"task {task} has no on-the-fly degradation (--degrade, degrade): only training of "

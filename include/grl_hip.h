@@ -23,7 +23,7 @@ extern "C" {
 
 #define GRL_ERR_BAD_ARG (-1)
 #define GRL_ERR_UNSUPPORTED (-2)
-#define GRL_ABI_VERSION 33
+#define GRL_ABI_VERSION 34
 
 /* element kinds of activation / weight buffers */
 enum { GRL_DT_F32 = 0, GRL_DT_BF16 = 1, GRL_DT_F16 = 2 };
@@ -436,7 +436,10 @@ int grl_layernorm_res_fwd(void* stream, const GrlLnResArgs* args);
 /* Weight gradient: c[tap][n][k] += out_scale * sum_m (a_scale * a[m][n]) * b[row(m, tap)][k]   (fp32 atomics; zero c first)
  *   taps = 1: row = m (token-wise linear: dW = dY^T X)
  *   taps = 9: 3x3 convolution, a / b are [images*H*W, ld] channels-last pixel matrices, tap = (dy+1)*3 + (dx+1),
- *             row = pixel (y + dy, x + dx) of the same image, zero outside: dW[tap][co][ci]                          */
+ *             row = pixel (y + dy, x + dx) of the same image, zero outside: dW[tap][co][ci]
+ *   taps = 16 (ABI 34): 4x4 stride-2 pad-1 convolution (models/aux_archs/discriminator.py:102-104).  a is [images*H*W, lda] on the
+ *             OUTPUT grid, b [images*2H*2W, ldb] on the input grid, tap = ky*4 + kx, row = pixel (2y + ky - 1, 2x + kx - 1) of
+ *             the same image, zero outside; M = images*H*W; b_ones is not available                                    */
 typedef struct GrlGemmTnArgs {
     const float* a;         /* [M, lda] fp32 (output gradient)                                      */
     int64_t lda;
@@ -444,7 +447,7 @@ typedef struct GrlGemmTnArgs {
     int32_t b_dtype;
     int64_t ldb;
     int32_t M, N, K;        /* N, K multiples of 4 (of 8 for fp16 b)                                */
-    int32_t taps, H, W;     /* 1, or 9 with the image size                                          */
+    int32_t taps, H, W;     /* 1, or 9 / 16 with the image size (of a)                              */
     int32_t splits;         /* M is cut into this many slabs (one workgroup column each)            */
     float a_scale, out_scale;
     float* c;               /* [taps][N][ldc] fp32                                                  */
@@ -1008,6 +1011,41 @@ typedef struct GrlBlurItemsArgs {
 } GrlBlurItemsArgs;
 
 int grl_blur_items(void* stream, const GrlBlurItemsArgs* args);
+
+/* ---------------------------------------------------------------------------------------------
+ * U-Net discriminator of the GAN stage (ABI 34, csrc/disc.hip): the contractions the 3x3 kernels do not cover.
+ *   replaces  UNetDiscriminatorSN.conv1 / conv2 / conv3 (+ leaky_relu)      models/aux_archs/discriminator.py:102-104,118-120
+ *             F.interpolate(scale_factor=2, mode="bilinear", align_corners=False)   models/aux_archs/discriminator.py:123,128,133
+ *             and autograd through both in the two optimizer steps            engines/base_gan.py:86-147
+ *
+ * grl_conv4x4s2_fwd: Conv2d(Cin, Cout, 4, 2, 1, bias=False) on a channels-last token matrix, out[b, oy, ox, co] =
+ *   act(out_scale * sum_{ky,kx,ci} w[ky*4+kx][co][ci] * x_scale * x[b, 2 oy + ky - 1, 2 ox + kx - 1, ci]), zero outside the image.
+ *   GrlConvArgs: H, W = the size of x (even; odd: GRL_ERR_UNSUPPORTED), out is [B*(H/2)*(W/2), ldo]; w = grl_pack_conv4x4(transpose
+ *   = 0): fp16 [16][CoutP][CinP], w_tap_stride >= CoutP * CinP; CinP % 32 == 0, CoutP % 16 == 0; x / out GRL_DT_F32, 16-byte aligned,
+ *   ldx / ldo multiples of 4 and at least the real widths (GRL_ERR_BAD_ARG otherwise); x_cols / n_store as grl_conv3x3_fwd;
+ *   act 0 or 2 (LeakyReLU(slope)); bias, resid, pool_partial must be NULL, x_split <= 1, shuffle_r <= 1 (GRL_ERR_UNSUPPORTED).
+ * grl_conv4x4s2_bwd_data: the transposed convolution, dx[b, iy, ix, ci] = out_scale * sum w[ky*4+kx][co][ci] * x_scale * dy[b, oy, ox, co]
+ *   over 2 oy + ky - 1 = iy, 2 ox + kx - 1 = ix -- per parity class of (iy, ix) a 2 x 2-tap convolution of dy.
+ *   GrlConvArgs: x = dy [B*(H/2)*(W/2), ldx] with x_cols = Cout, out = dx [B*H*W, ldo] with n_store = Cin, H, W = the size of dx;
+ *   w = grl_pack_conv4x4(transpose = 1): fp16 [16][CoutP = pad16(Cin)][CinP = pad32(Cout)]; act must be 0; x_scale / out_scale as in
+ *   the 3x3 data gradient.  Same checks as the forward; nothing is launched when one fails.
+ * grl_pack_conv4x4: w [Cout][Cin][4][4] fp32 -> fp16 [16][rows_pad][cols_pad] zero padded, tap = ky*4 + kx; transpose = 0: rows =
+ *   output channels, columns = input channels; transpose = 1: rows = input channels, columns = output channels. */
+int grl_conv4x4s2_fwd(void* stream, const GrlConvArgs* args);
+int grl_conv4x4s2_bwd_data(void* stream, const GrlConvArgs* args);
+int grl_pack_conv4x4(void* stream, const float* w, void* out_w, int32_t Cout, int32_t Cin, int32_t rows_pad, int32_t cols_pad,
+                     int32_t transpose);
+
+/* x2 bilinear upsampling (align_corners=False) of a channels-last token matrix and its adjoint:
+ *   forward  x [B*H*W, ldx] -> out [B*2H*2W, ldo]: per axis weights 0.75 / 0.25 on the two nearest inputs, the index clamped at the
+ *            edges (output 0 reads input 0 alone), combined in torch's order h0 (w0 v00 + w1 v01) + h1 (w0 v10 + w1 v11);
+ *   backward dy [B*2H*2W, lddy] -> dx [B*H*W, lddx]: each input gathers its <= 16 outputs in a fixed order (no atomics).
+ * C real channels, a multiple of 4 (16-byte accesses); leading dimensions multiples of 4 and >= C; 16-byte aligned bases
+ * (GRL_ERR_BAD_ARG otherwise, nothing is launched). */
+int grl_upsample2x_bilinear_fwd(void* stream, const float* x, int64_t ldx, float* out, int64_t ldo, int32_t B, int32_t H, int32_t W,
+                                int32_t C);
+int grl_upsample2x_bilinear_bwd(void* stream, const float* dy, int64_t lddy, float* dx, int64_t lddx, int32_t B, int32_t H, int32_t W,
+                                int32_t C);
 
 /* Debug aid (ABI 21; no reference counterpart): fills the LDS of every CU with 0xFF bytes (fp32 / fp16 NaN) by a launch on
  * `stream`.  LDS keeps what the previous workgroup left in it; a kernel that reads LDS it has not written is otherwise right or
