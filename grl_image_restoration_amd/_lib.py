@@ -11,7 +11,7 @@ from . import switches as SW
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgrl_hip.so")
-ABI_VERSION = 34
+ABI_VERSION = 35
 DT_F32, DT_BF16, DT_F16 = 0, 1, 2
 
 EPI_PLAIN, EPI_GELU, EPI_GROUPNORM, EPI_LN_RES, EPI_GELU_GRAD = 0, 1, 2, 3, 4
@@ -585,6 +585,41 @@ class GrlBlurItemsArgs(_Strict):
     ]
 
 
+class GrlVggPrepArgs(_Strict):
+    _fields_ = [
+        ("image", C.c_void_p),
+        ("stride", C.c_int64 * 4),
+        ("tok", C.c_void_p),
+        ("ldt", C.c_int64),
+        ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+        ("use_input_norm", C.c_int32), ("range_norm", C.c_int32),
+        ("scale", C.c_float),
+    ]
+
+
+class GrlVggTapArgs(_Strict):
+    _fields_ = [
+        ("fx", C.c_void_p),
+        ("fg", C.c_void_p),
+        ("ldf", C.c_int64),
+        ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("C", C.c_int32),
+        ("pool", C.c_int32), ("pool_dtype", C.c_int32),
+        ("px", C.c_void_p),
+        ("pg", C.c_void_p),
+        ("ldp", C.c_int64),
+        ("partial", C.c_void_p),
+        ("n_partial", C.c_int32), ("accumulate", C.c_int32),
+        ("loss", C.c_void_p),
+        ("layer_sum", C.c_void_p),
+        ("coef", C.c_float),
+        ("k", C.c_float),
+        ("dpool", C.c_void_p),
+        ("lddp", C.c_int64),
+        ("dfx", C.c_void_p),
+        ("lddf", C.c_int64),
+    ]
+
+
 _I32, _I64, _PTR = C.c_int32, C.c_int64, C.c_void_p
 
 
@@ -653,6 +688,11 @@ SIGNATURES = {
     "grl_pack_conv4x4": (C.c_int, [_PTR] * 3 + [_I32] * 5),
     "grl_upsample2x_bilinear_fwd": (C.c_int, [_PTR, _PTR, _I64, _PTR, _I64] + [_I32] * 4),
     "grl_upsample2x_bilinear_bwd": (C.c_int, [_PTR, _PTR, _I64, _PTR, _I64] + [_I32] * 4),
+    "grl_vgg_prep_fwd": _launch(GrlVggPrepArgs),
+    "grl_vgg_prep_bwd": _launch(GrlVggPrepArgs),
+    "grl_vgg_tap_num_workgroups": (C.c_int, [_I32] * 4),
+    "grl_vgg_tap_fwd": _launch(GrlVggTapArgs),
+    "grl_vgg_tap_bwd": _launch(GrlVggTapArgs),
     "grl_debug_dirty_lds": (C.c_int, [_PTR]),
     "grl_abi_version": (C.c_int, []),
     "grl_build_info": (C.c_char_p, []),

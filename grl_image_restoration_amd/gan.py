@@ -5,7 +5,8 @@
   GanStep    engines/base_gan.py:86-147 as Lightning runs it with two optimizers: optimizer 0 (generator) with the discriminator's
              parameters toggled off, then optimizer 1 (discriminator) on a fresh forward of the updated generator
 
-The perceptual (VGG19) and style losses of the reference's criterion are not built (``perceptual=None`` is the seam they go in).
+The perceptual (VGG19) loss of the reference's criterion is ``perceptual.PerceptualLoss``, handed in as ``perceptual=``; the style
+loss is not built.
 """
 from typing import Callable, Dict, Optional
 
@@ -34,19 +35,22 @@ def _forward_in_training(G, lq: torch.Tensor) -> torch.Tensor:
 
 class GanStep:
     """One call = one Lightning iteration of the reference's GAN engine.  ``pixel_loss(restored, target)``; both optimizers step
-    once; returns the reference's logged scalars (detached tensors)."""
+    once; returns the reference's logged scalars (detached tensors).  ``perceptual``: a ``perceptual.PerceptualLoss`` (or any callable
+    returning ``(percep_loss, style_loss)``); its term, times ``perceptual_weight``, joins the generator's loss between the pixel and
+    the GAN term (base_gan.py:105-112) against ``gt_usm`` under ``usm_percep``, and ``loss_g_percep`` joins the scalars.  With
+    ``perceptual=None`` nothing of it exists."""
 
     def __init__(self, model_g, model_d, opt_g, opt_d, pixel_loss: Callable, pixel_weight: float = 1.0, gan_weight: float = 1.0,
-                 gan_loss_weight: float = 0.1, usm_pixel: bool = False, usm_gan: bool = False, perceptual=None):
-        if perceptual is not None:
-            raise NotImplementedError("the perceptual (VGG19) loss is not part of this package yet")
+                 gan_loss_weight: float = 0.1, usm_pixel: bool = False, usm_gan: bool = False, perceptual=None,
+                 perceptual_weight: float = 1.0, usm_percep: bool = False):
         self.model_g, self.model_d, self.opt_g, self.opt_d = model_g, model_d, opt_g, opt_d
         self.pixel_loss, self.pixel_weight, self.gan_weight, self.gan_loss_weight = pixel_loss, pixel_weight, gan_weight, gan_loss_weight
         self.usm_pixel, self.usm_gan = usm_pixel, usm_gan
+        self.perceptual, self.perceptual_weight, self.usm_percep = perceptual, perceptual_weight, usm_percep and perceptual is not None
 
     def __call__(self, lq: torch.Tensor, gt: torch.Tensor, gt_usm: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
-        if (self.usm_pixel or self.usm_gan) and gt_usm is None:
-            raise ValueError("usm_pixel / usm_gan need the sharpened target")
+        if (self.usm_pixel or self.usm_gan or self.usm_percep) and gt_usm is None:
+            raise ValueError("usm_pixel / usm_gan / usm_percep need the sharpened target")
         G, D_ = self.model_g, self.model_d
         out = {}
         # ---- optimizer 0: the generator (base_gan.py:96-126); toggle_optimizer: the discriminator's parameters are off ----
@@ -56,15 +60,26 @@ class GanStep:
         try:
             restored = G(lq)
             loss_g_pix = self.pixel_loss(restored, gt_usm if self.usm_pixel else gt) * self.pixel_weight
+            loss_g_percep = None
+            if self.perceptual is not None:
+                loss_g_percep, style = self.perceptual(restored, gt_usm if self.usm_percep else gt)
+                if style is not None:
+                    raise NotImplementedError("the style loss is not part of this package")
+                if loss_g_percep is not None:
+                    loss_g_percep = loss_g_percep * self.perceptual_weight
             loss_g_gan = gan_loss(D_(restored), True, is_disc=False, weight=self.gan_loss_weight) * self.gan_weight
             self.opt_g.zero_grad(set_to_none=True)
-            (loss_g_pix + loss_g_gan).backward()
+            total = loss_g_pix + loss_g_gan if loss_g_percep is None else loss_g_pix + loss_g_percep + loss_g_gan
+            total.backward()
             self.opt_g.step()
             self.opt_g.zero_grad(set_to_none=True)      # (gradients do not outlive their step: nothing of one optimizer's pass is
         finally:                                        # visible to the other's)
             for p in d_params:
                 p.requires_grad_(True)
-        out["loss_g_pix"], out["loss_g_gan"] = loss_g_pix.detach(), loss_g_gan.detach()
+        out["loss_g_pix"] = loss_g_pix.detach()
+        if loss_g_percep is not None:
+            out["loss_g_percep"] = loss_g_percep.detach()
+        out["loss_g_gan"] = loss_g_gan.detach()
         # ---- optimizer 1: the discriminator (base_gan.py:129-145); training_step calls self(batch) again ----
         with torch.no_grad():
             restored = _forward_in_training(G, lq)

@@ -1173,3 +1173,81 @@ def upsample2x(x: torch.Tensor, B: int, H: int, W: int, *, backward: bool = Fals
     with _timed(name[4:]):
         L.check(getattr(L.lib(), name)(L.stream_ptr(), _ptr(x), x.stride(0), _ptr(out), out.stride(0), B, H, W, C_), name)
     return out
+
+
+# ---- VGG19 perceptual loss (csrc/vgg.hip): input normalisation, feature taps with ReLU + max pool, and their backward ------------------
+def vgg_prep(x: torch.Tensor, out: Optional[torch.Tensor] = None, *, use_input_norm: bool = True, range_norm: bool = False) -> torch.Tensor:
+    """grl_vgg_prep_fwd: an fp32 image [B, 3, H, W] (any strides) -> the normalised token matrix [B*H*W, 4] (column 3 = 0); ``out``: a
+    [B*H*W, 4] slice of a larger matrix to write into."""
+    _dev_check(x, out)
+    assert x.dim() == 4 and x.shape[1] == 3 and x.dtype == torch.float32
+    B, _, H, W = x.shape
+    if out is None:
+        out = empty(B * H * W, 4, dtype=torch.float32, device=x.device)
+    assert out.shape == (B * H * W, 4) and out.dtype == torch.float32 and out.stride(1) == 1
+    args = L.GrlVggPrepArgs(image=_ptr(x), stride=(C.c_int64 * 4)(*x.stride()), tok=_ptr(out), ldt=out.stride(0), B=B, H=H, W=W,
+                            use_input_norm=int(use_input_norm), range_norm=int(range_norm), scale=1.0)
+    with _timed("vgg_prep"):
+        L.launch("grl_vgg_prep_fwd", args)
+    return out
+
+
+def vgg_prep_bwd(dtok: torch.Tensor, B: int, H: int, W: int, *, scale: float = 1.0, use_input_norm: bool = True,
+                 range_norm: bool = False) -> torch.Tensor:
+    """grl_vgg_prep_bwd: the gradient token matrix [B*H*W, >= 4] -> the image gradient [B, 3, H, W] fp32, times ``scale`` (the removal
+    of the chain's operand scale) and the 1/2 of ``range_norm``."""
+    _dev_check(dtok)
+    assert dtok.dim() == 2 and dtok.shape[0] == B * H * W and dtok.shape[1] >= 4 and dtok.dtype == torch.float32 and dtok.stride(1) == 1
+    dx = empty(B, 3, H, W, dtype=torch.float32, device=dtok.device)
+    args = L.GrlVggPrepArgs(image=_ptr(dx), stride=(C.c_int64 * 4)(*dx.stride()), tok=_ptr(dtok), ldt=dtok.stride(0), B=B, H=H, W=W,
+                            use_input_norm=int(use_input_norm), range_norm=int(range_norm), scale=scale * (0.5 if range_norm else 1.0))
+    with _timed("vgg_prep_bwd"):
+        L.launch("grl_vgg_prep_bwd", args)
+    return dx
+
+
+def _tap_check(fx, fg, B, H, W):
+    _dev_check(fx, fg)
+    assert fx.dim() == 2 and fx.shape == fg.shape == (B * H * W, fx.shape[1]) and fx.dtype == fg.dtype == torch.float32
+    assert fx.stride(1) == fg.stride(1) == 1 and fx.stride(0) == fg.stride(0) and fx.shape[1] % 4 == 0
+
+
+def vgg_tap(fx: torch.Tensor, fg: torch.Tensor, B: int, H: int, W: int, loss: torch.Tensor, coef: float, *, accumulate: bool = True,
+            pool: bool = True, pool_out: Optional[torch.Tensor] = None, pool_dtype=GEMM_DTYPE, layer_sum: Optional[torch.Tensor] = None):
+    """grl_vgg_tap_fwd on one tapped layer: loss[0] (+)= coef * sum |fx - fg| (fixed order, no atomics) and, with ``pool``,
+    maxpool2x2(relu(.)) of both halves: returns the pooled matrix [2 * B*(H/2)*(W/2), C] (restored rows first, then the target's) or
+    None.  fx / fg [B*H*W, C] fp32: two matrices or the two halves of one."""
+    _tap_check(fx, fg, B, H, W)
+    C_ = fx.shape[1]
+    nwg = L.lib().grl_vgg_tap_num_workgroups(B, H, W, C_)
+    assert nwg > 0 and loss.dtype == torch.float32 and loss.numel() >= 1
+    partial = empty(nwg, dtype=torch.float64, device=fx.device)
+    rows = B * (H // 2) * (W // 2)
+    if pool:
+        assert H >= 2 and W >= 2
+        if pool_out is None:
+            pool_out = empty(2 * rows, C_, dtype=pool_dtype, device=fx.device)
+        assert pool_out.shape == (2 * rows, C_) and pool_out.is_contiguous()
+    args = L.GrlVggTapArgs(fx=_ptr(fx), fg=_ptr(fg), ldf=fx.stride(0), B=B, H=H, W=W, C=C_, pool=int(pool),
+                           pool_dtype=_KIND[pool_out.dtype] if pool else 0, px=_ptr(pool_out[:rows]) if pool else None,
+                           pg=_ptr(pool_out[rows:]) if pool else None, ldp=C_ if pool else 0, partial=_ptr(partial), n_partial=nwg,
+                           accumulate=int(accumulate), loss=_ptr(loss), layer_sum=_ptr(layer_sum), coef=coef)
+    with _timed("vgg_tap"):
+        L.launch("grl_vgg_tap_fwd", args)
+    return pool_out if pool else None
+
+
+def vgg_tap_bwd(fx: torch.Tensor, fg: torch.Tensor, B: int, H: int, W: int, k: float, dpool: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """grl_vgg_tap_bwd: dfx [B*H*W, C] = k * sign(fx - fg) + the gradient ``dpool`` [B*(H/2)*(W/2), C] routed through ReLU and the 2 x 2
+    max pool (first maximum of a window); ``dpool`` None: the last tap."""
+    _tap_check(fx, fg, B, H, W)
+    _dev_check(dpool)
+    C_ = fx.shape[1]
+    if dpool is not None:
+        assert dpool.shape == (B * (H // 2) * (W // 2), C_) and dpool.dtype == torch.float32 and dpool.stride(1) == 1
+    dfx = empty(B * H * W, C_, dtype=torch.float32, device=fx.device)
+    args = L.GrlVggTapArgs(fx=_ptr(fx), fg=_ptr(fg), ldf=fx.stride(0), B=B, H=H, W=W, C=C_, k=k, dpool=_ptr(dpool),
+                           lddp=dpool.stride(0) if dpool is not None else 0, dfx=_ptr(dfx), lddf=C_)
+    with _timed("vgg_tap_bwd"):
+        L.launch("grl_vgg_tap_bwd", args)
+    return dfx

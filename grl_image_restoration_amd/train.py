@@ -43,10 +43,11 @@ eval forward -- so it is neither finished nor re-captured.  ``step.finish()`` ru
 GAN stage.  ``--gan`` (``--task sr``) runs ``gan.GanStep`` per step: the generator's step on pixel loss + GAN loss, then the
 discriminator's (``discriminator.UNetDiscriminatorSN``), eagerly and single-process.  The printed loss is the generator's total.
 Checkpoints carry both networks (``model.model_g.`` / ``model.model_d.``, u / v included) and both optimizers; ``evaluate`` reads
-the generator out of them.
+the generator out of them.  ``--vgg vgg19-dcbb9e9d.pth`` adds the third term of config/loss/gan_training_loss.yaml, the VGG19
+perceptual loss (``perceptual.PerceptualLoss``); the frozen VGG is not written into checkpoints, so ``--resume`` takes ``--vgg`` again.
 
     python -m grl_image_restoration_amd.train --task sr --scale 4 --model base --geometry bsr --upsampler nearest+conv --gan \\
-        --degrade --usm --ckpt runs/psnr/step_N.ckpt --lr 1e-4 --gt DF2K/HR --out runs/gan ...
+        --vgg vgg19-dcbb9e9d.pth --usm-percep --degrade --usm --ckpt runs/psnr/step_N.ckpt --lr 1e-4 --gt DF2K/HR --out runs/gan ...
 
 Data-parallel.  Under ``torchrun`` (torch.distributed initialised from the environment) the bare module goes to
 ``GraphedTrainStep``, which owns the gradient all-reduce; each rank's sampler is seeded ``seed + rank``; rank 0 validates and
@@ -163,6 +164,12 @@ def _parser():
     ap.add_argument("--gan-loss-weight", type=float, default=0.1, help="--gan: loss_weight of the GAN loss itself (losses.py:293)")
     ap.add_argument("--pixel-weight", type=float, default=1.0, help="--gan: weight of the pixel loss (base_gan.py:101)")
     ap.add_argument("--usm-gan", action="store_true", help="--gan: the discriminator's real input is the USM-sharpened GT (use_usm_gan)")
+    ap.add_argument("--vgg", default=None, metavar="PATH",
+                    help="--gan: turns the VGG19 perceptual loss on (config/loss/gan_training_loss.yaml: conv1_2 .. conv5_4 before ReLU, "
+                         "layer weights 0.1 / 0.1 / 1 / 1 / 1, L1).  PATH is torchvision's vgg19-dcbb9e9d.pth, read with torch.load; nothing "
+                         "is downloaded.  The frozen VGG is not written into checkpoints: --resume takes --vgg again")
+    ap.add_argument("--perceptual-weight", type=float, default=1.0, help="--gan --vgg: weight of the perceptual loss (base_gan.py:110)")
+    ap.add_argument("--usm-percep", action="store_true", help="--gan --vgg: the perceptual target is the USM-sharpened GT (use_usm_percep)")
     ap.add_argument("--device", default="cuda:0")
     return ap
 
@@ -171,11 +178,17 @@ def _check(ap, a):
     if a.val_every and a.val_gt is None:
         ap.error("--val-every needs --val-gt")
     o = resolve_arguments(ap, a, "train", sigma_range=a.sigma_range, quality_range=a.quality_range, patch=a.patch,
-                          val=bool(a.val_every), val_lq=a.val_lq is not None, usm=a.usm or a.usm_gan, val_usm=a.val_usm,
+                          val=bool(a.val_every), val_lq=a.val_lq is not None, usm=a.usm or a.usm_gan or a.usm_percep, val_usm=a.val_usm,
                           degrade=a.degrade, degrade_crop=a.degrade_crop, gan=a.gan)
     a.scale, a.sigma, a.degrade_crop = o.scale, o.sigma, o.degrade_crop
     if not a.gan and (a.disc_ckpt is not None or a.usm_gan):
         ap.error("--disc-ckpt and --usm-gan belong to --gan")
+    if not a.gan and (a.vgg is not None or a.usm_percep or a.perceptual_weight != 1.0):
+        ap.error("--vgg, --perceptual-weight and --usm-percep belong to --gan")
+    if a.vgg is None and (a.usm_percep or a.perceptual_weight != 1.0):
+        ap.error("--perceptual-weight and --usm-percep need --vgg")
+    if a.vgg is not None and a.patch * a.scale < 16:
+        ap.error("--vgg: the GT patch side (--patch times --scale) must be at least 16 (VGG19 pools four times)")
     if a.gan and int(os.environ.get("WORLD_SIZE", "1")) > 1:
         ap.error("--gan runs eagerly: --eager is single-process; the captured step owns the gradient all-reduce")
     if a.gan and (a.patch * a.scale) % 8:
@@ -244,13 +257,19 @@ def main(argv: Optional[List[str]] = None):
         elif a.disc_ckpt:
             load_discriminator_checkpoint(model_d, a.disc_ckpt)
         model_d = model_d.to(device).train()
+        percep = None
+        if a.vgg is not None:
+            from .perceptual import GAN_LAYER_WEIGHTS, PerceptualLoss, load_vgg19
 
+            percep = PerceptualLoss(GAN_LAYER_WEIGHTS, load_vgg19(a.vgg)).to(device)
+
+    usm_flags = [a.usm, a.usm_gan] + ([a.usm_percep] if a.vgg is not None else [])      # the targets that are the sharpened GT
     gt_store = D.PatchStore.from_folder(a.gt, a.channels, device)
     lq_store = D.PatchStore.from_folder(a.lq, a.channels, device) if a.lq is not None else None
     sampler = D.PatchSampler(a.task, gt_store, lq_store, patch=a.patch, batch=a.batch, scale=a.scale, sigma=a.sigma,
                              sigma_range=a.sigma_range, seed=a.seed + rank, taps=taps,
                              quality=a.quality if a.quality_range is None else None, quality_range=a.quality_range,
-                             usm=a.usm or a.usm_gan, **(dict(plain_gt=True) if a.usm != a.usm_gan else {}),
+                             usm=any(usm_flags), **(dict(plain_gt=True) if any(usm_flags) and not all(usm_flags) else {}),
                              **(dict(degrade=True, degrade_crop=a.degrade_crop) if a.degrade else {}))
 
     opt = FusedAdamW(model.parameters(), lr=a.lr, weight_decay=0.0 if a.gan else a.weight_decay)
@@ -279,7 +298,8 @@ def main(argv: Optional[List[str]] = None):
     if a.gan:
         out["gan"] = []                                 # per step the reference's logged scalars (base_gan.py:103-140)
         gan_step = GanStep(model, model_d, opt, opt_d, loss_fn, pixel_weight=a.pixel_weight, gan_weight=a.gan_weight,
-                           gan_loss_weight=a.gan_loss_weight, usm_pixel=a.usm, usm_gan=a.usm_gan)
+                           gan_loss_weight=a.gan_loss_weight, usm_pixel=a.usm, usm_gan=a.usm_gan, perceptual=percep,
+                           perceptual_weight=a.perceptual_weight, usm_percep=a.usm_percep)
 
     def checkpoint(n):
         if step_fn is not None:
@@ -296,10 +316,10 @@ def main(argv: Optional[List[str]] = None):
         lq, gt = batch[:2]
         if gan_step is not None:
             # (lq, sharpened, plain) when the two targets differ; else one target serves both roles
-            plain, sharp = (batch[2], gt) if len(batch) == 3 else (gt, gt if (a.usm or a.usm_gan) else None)
+            plain, sharp = (batch[2], gt) if len(batch) == 3 else (gt, gt if any(usm_flags) else None)
             logged = gan_step(lq, plain, sharp)
             out["gan"].append({k: float(v) for k, v in logged.items()})
-            loss = logged["loss_g_pix"] + logged["loss_g_gan"]
+            loss = sum(logged[k] for k in ("loss_g_pix", "loss_g_percep", "loss_g_gan") if k in logged)
         elif a.eager:
             opt.zero_grad(set_to_none=True)
             loss = loss_fn(model(lq), gt)

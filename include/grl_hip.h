@@ -23,7 +23,7 @@ extern "C" {
 
 #define GRL_ERR_BAD_ARG (-1)
 #define GRL_ERR_UNSUPPORTED (-2)
-#define GRL_ABI_VERSION 34
+#define GRL_ABI_VERSION 35
 
 /* element kinds of activation / weight buffers */
 enum { GRL_DT_F32 = 0, GRL_DT_BF16 = 1, GRL_DT_F16 = 2 };
@@ -1046,6 +1046,70 @@ int grl_upsample2x_bilinear_fwd(void* stream, const float* x, int64_t ldx, float
                                 int32_t C);
 int grl_upsample2x_bilinear_bwd(void* stream, const float* dy, int64_t lddy, float* dx, int64_t lddx, int32_t B, int32_t H, int32_t W,
                                 int32_t C);
+
+/* ---------------------------------------------------------------------------------------------
+ * VGG19 perceptual loss of the GAN stage (ABI 35, csrc/vgg.hip): everything between the 3x3 convolutions.
+ *   replaces  VGGFeatureExtractor.forward: range_norm, input norm, ReLU, MaxPool2d(2, 2), the feature taps
+ *                                                                            models/aux_archs/vgg.py:223,240-246,257-266
+ *             PerceptualLoss.forward: L1Loss per tapped layer * layer weight * perceptual_weight   losses/losses.py:126-143
+ *             and autograd through them for the restored image (the VGG is frozen, gt is detached: losses.py:127, vgg.py:229-232)
+ * The convolutions themselves are grl_conv3x3_fwd launches (act = 2, slope = 0: ReLU in the epilogue of the untapped layers).
+ *
+ * grl_vgg_prep_fwd: image (fp32, any element strides stride[0..3] over (b, c, y, x), 3 channels) -> tok [B*H*W, ldt] fp32, columns
+ *   0..2 = the channels, column 3 = 0: t = range_norm ? (x + 1) / 2 : x;  t = use_input_norm ? (t - mean[c]) / std[c] : t with the
+ *   float32 values of mean = (0.485, 0.456, 0.406), std = (0.229, 0.224, 0.225).  `scale` is not read.
+ * grl_vgg_prep_bwd: the adjoint, tok = the gradient [B*H*W, ldt] (columns 0..2 read) -> image[b, c, y, x] = (use_input_norm ?
+ *   g / std[c] : g) * scale; the caller folds 1 / S of the operand scale and the 1/2 of range_norm into `scale`.
+ *   ldt >= 4, a multiple of 4; tok 16-byte aligned (GRL_ERR_BAD_ARG otherwise; nothing is launched). */
+typedef struct GrlVggPrepArgs {
+    float* image;               /* forward: read; backward: written                               */
+    int64_t stride[4];          /* element strides of image over (b, c, y, x)                     */
+    float* tok;                 /* forward: written; backward: read                               */
+    int64_t ldt;
+    int32_t B, H, W;
+    int32_t use_input_norm, range_norm;
+    float scale;                /* backward only                                                  */
+} GrlVggPrepArgs;
+
+int grl_vgg_prep_fwd(void* stream, const GrlVggPrepArgs* args);
+int grl_vgg_prep_bwd(void* stream, const GrlVggPrepArgs* args);
+
+/* One tapped layer.  fx / fg: the pre-ReLU features [B*H*W, ldf] fp32 of the restored image and of the target (two halves of one
+ * matrix or two matrices), C real channels (C % 4 == 0), 16-byte aligned, ldf % 4 == 0.
+ * grl_vgg_tap_fwd:
+ *   (a) partial[w] (fp64, one per workgroup; n_partial >= grl_vgg_tap_num_workgroups(B, H, W, C)) = that workgroup's share of
+ *       sum |fx - fg|; a finishing launch adds them in a fixed order: loss[0] = (accumulate ? loss[0] : 0) + (float)(coef * sum), and
+ *       layer_sum[0] = (float)sum when layer_sum is not NULL.  No atomics: bit-identical from run to run.
+ *   (b) pool != 0: px / pg [B*(H/2)*(W/2), ldp] = maxpool2x2(relu(fx)) / (fg), floor sizes as nn.MaxPool2d(2, 2) (an odd last row /
+ *       column is not pooled); pool_dtype GRL_DT_F32 or GRL_DT_F16 (what the next convolution's loader rounds to anyway).
+ * grl_vgg_tap_bwd: dfx [B*H*W, lddf] = k * sign(fx - fg) + (fx > 0 and fx is the first maximum of its window in (dy, dx) row-major
+ *   order ? dpool : 0); sign(0) = 0; dpool [B*(H/2)*(W/2), lddp] fp32 or NULL (the last tap); pixels outside the floor-pooled region
+ *   get the first term alone.  k = S * layer_weight * perceptual_weight * upstream / (B*C*H*W) with S the chain's operand scale.
+ * Bad pointers / leading dimensions: GRL_ERR_BAD_ARG, nothing is launched. */
+typedef struct GrlVggTapArgs {
+    const float* fx;
+    const float* fg;
+    int64_t ldf;
+    int32_t B, H, W, C;
+    int32_t pool, pool_dtype;
+    void* px;
+    void* pg;
+    int64_t ldp;
+    double* partial;
+    int32_t n_partial, accumulate;
+    float* loss;
+    float* layer_sum;
+    float coef;                 /* forward: layer_weight * perceptual_weight / (B*C*H*W)          */
+    float k;                    /* backward: S * coef * upstream gradient                         */
+    const float* dpool;
+    int64_t lddp;
+    float* dfx;
+    int64_t lddf;
+} GrlVggTapArgs;
+
+int grl_vgg_tap_num_workgroups(int32_t B, int32_t H, int32_t W, int32_t C);
+int grl_vgg_tap_fwd(void* stream, const GrlVggTapArgs* args);
+int grl_vgg_tap_bwd(void* stream, const GrlVggTapArgs* args);
 
 /* Debug aid (ABI 21; no reference counterpart): fills the LDS of every CU with 0xFF bytes (fp32 / fp16 NaN) by a launch on
  * `stream`.  LDS keeps what the previous workgroup left in it; a kernel that reads LDS it has not written is otherwise right or
