@@ -11,7 +11,7 @@ from . import switches as SW
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgrl_hip.so")
-ABI_VERSION = 35
+ABI_VERSION = 36
 DT_F32, DT_BF16, DT_F16 = 0, 1, 2
 
 EPI_PLAIN, EPI_GELU, EPI_GROUPNORM, EPI_LN_RES, EPI_GELU_GRAD = 0, 1, 2, 3, 4
@@ -620,6 +620,32 @@ class GrlVggTapArgs(_Strict):
     ]
 
 
+class GrlLpipsPrepArgs(_Strict):
+    _fields_ = [
+        ("image", C.c_void_p),
+        ("stride", C.c_int64 * 4),
+        ("tok", C.c_void_p),
+        ("ldt", C.c_int64),
+        ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+        ("reserved0", C.c_int32),
+    ]
+
+
+class GrlLpipsTapArgs(_Strict):
+    _fields_ = [
+        ("f", C.c_void_p),
+        ("ldf", C.c_int64),
+        ("w", C.c_void_p),
+        ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("C", C.c_int32),
+        ("pool", C.c_int32), ("accumulate", C.c_int32),
+        ("pool_out", C.c_void_p),
+        ("ldp", C.c_int64),
+        ("partial", C.c_void_p),
+        ("out", C.c_void_p),
+        ("n_partial", C.c_int32), ("reserved0", C.c_int32),
+    ]
+
+
 _I32, _I64, _PTR = C.c_int32, C.c_int64, C.c_void_p
 
 
@@ -693,6 +719,9 @@ SIGNATURES = {
     "grl_vgg_tap_num_workgroups": (C.c_int, [_I32] * 4),
     "grl_vgg_tap_fwd": _launch(GrlVggTapArgs),
     "grl_vgg_tap_bwd": _launch(GrlVggTapArgs),
+    "grl_lpips_prep": _launch(GrlLpipsPrepArgs),
+    "grl_lpips_tap_num_workgroups": (C.c_int, [_I32] * 4),
+    "grl_lpips_tap": _launch(GrlLpipsTapArgs),
     "grl_debug_dirty_lds": (C.c_int, [_PTR]),
     "grl_abi_version": (C.c_int, []),
     "grl_build_info": (C.c_char_p, []),

@@ -29,6 +29,9 @@ Restates, for the MI355X module, the three pieces of the reference's evaluation 
         --gt LIVE1 --metric restorer_jpeg
     python -m grl_image_restoration_amd.evaluate --task bsr --model base --geometry bsr --upsampler nearest+conv \\
         --ckpt bsr_grl_base.ckpt --lq RealSRSet --niqe-params niqe_pris_params.npz
+    python -m grl_image_restoration_amd.evaluate --model base --geometry bsr --upsampler nearest+conv --scale 4 --ckpt bsr_grl_base.ckpt \\
+        --lq DIV2K_val/LRbicx4 --gt DIV2K_val/HR --metric restorer_perceptual --lpips-vgg vgg16-397923af.pth --lpips-lin vgg.pth \\
+        --niqe-params niqe_pris_params.npz
     python -m grl_image_restoration_amd.evaluate --model base --geometry bsr_psnr --upsampler nearest+conv --scale 4 \\
         --ckpt bsr_psnr.ckpt --lq Set5/LRbicx4 --gt Set5/GTmod12 --usm-gt      scores against the USM-sharpened GT (val.use_usm: True)
     ... --save-dir results [--save-gt]    also writes results/X4/<data set>/<stem>_{LQ,HQ,GT}.png (image8.py), as the reference does
@@ -155,11 +158,12 @@ def image_pairs(lq_dir: str, gt_dir: str) -> List[Tuple[str, str]]:
 
 @torch.no_grad()
 def evaluate_pairs(model, pairs: Iterable[Tuple[torch.Tensor, torch.Tensor]], scale: int, tile: int = 0, overlap: int = 32,
-                   device: str = "cuda:0", metric_group: Optional[str] = None, niqe_params=None, on_result=None):
+                   device: str = "cuda:0", metric_group: Optional[str] = None, niqe_params=None, on_result=None, lpips_model=None):
     """PSNR-Y of ``model`` on (lq, gt) tensors in [0, 1], (1,3,h,w) / (1,3,h*scale,w*scale): a list, one value per pair.
     ``tile > 0`` uses the reference's tiled inference (engines/base.py:90-116) through ``tiling.forward_tiled``.
-    With ``metric_group`` (a key of ``metrics.ALL_GROUPS``): {metric name: mean over the pairs} of that group instead.  ``gt`` may be
-    None for the group "restorer_niqe", which scores the output alone against ``niqe_params``.  ``on_result(index, lq, sr, gt)`` is
+    With ``metric_group`` (a key of ``metrics.ALL_GROUPS`` or ``metrics.PERCEPTUAL_GROUPS``): {metric name: mean over the pairs} of
+    that group instead.  ``gt`` may be None for the group "restorer_niqe", which scores the output alone against ``niqe_params``;
+    "restorer_perceptual" takes ``lpips_model`` (an ``lpips.LPIPS`` on ``device``) alongside ``niqe_params``.  ``on_result(index, lq, sr, gt)`` is
     called for every pair with the tensors on ``device``, after ``sr`` and ``gt`` were cropped to each other and before the metrics:
     the images the reference saves (engines/base.py:259-264, before ``shave``)."""
     from . import tiling
@@ -183,7 +187,7 @@ def evaluate_pairs(model, pairs: Iterable[Tuple[torch.Tensor, torch.Tensor]], sc
         if metric_group is None:
             out.append(float(psnr_y(sr, gt, scale)))
         else:
-            out.append({k: float(v.mean()) for k, v in image_metrics(sr, gt, metric_group, scale, niqe_params).items()})
+            out.append({k: float(v.mean()) for k, v in image_metrics(sr, gt, metric_group, scale, niqe_params, lpips_model).items()})
     if metric_group is None:
         return out
     return {k: sum(o[k] for o in out) / len(out) for k in out[0]}
@@ -225,12 +229,13 @@ def evaluate_folder(model, lq_dir: Optional[str], gt_dir: Optional[str], scale: 
                     device: str = "cuda:0", verbose: bool = True, metric_group: Optional[str] = None, channels: int = 3,
                     task: str = "sr", sigma: Optional[float] = None, noise_prefix: Optional[str] = None, niqe_params=None,
                     taps: Optional[torch.Tensor] = None, quality: Optional[int] = None, save_dir: Optional[str] = None,
-                    save_gt: bool = False, save_workers: int = 4, usm_gt: bool = False):
+                    save_gt: bool = False, save_workers: int = 4, usm_gt: bool = False, lpips_model=None):
     """Mean PSNR-Y over the image pairs of two folders; with ``metric_group``, {metric name: mean} of that group.  ``channels`` 1
     reads the images as grayscale.  A ``task`` that synthesises its input ignores ``lq_dir`` and builds the LQ from the GT
     (``task_inputs``, with ``sigma``, ``taps``, ``quality`` and ``scale`` as the task's rule takes them).  A task without a ground
     truth ("bsr") reads ``lq_dir`` alone (``gt_dir`` is not used) and returns {"val_niqe": mean}; ``niqe_params`` is the pristine
-    model of ``metrics.niqe`` (also for "restorer_niqe" elsewhere).  With ``save_dir`` every image is also written as 8-bit PNG under
+    model of ``metrics.niqe`` (also for "restorer_niqe" elsewhere, and for "restorer_perceptual", which takes ``lpips_model`` -- an
+    ``lpips.LPIPS``, moved to ``device`` here -- as well).  With ``save_dir`` every image is also written as 8-bit PNG under
     the reference's layout (``image8.save_paths``): ``<stem>_HQ.png`` the restored image, ``<stem>_LQ.png`` the model's input
     (enlarged ``scale`` times by replication, as the reference saves it), and with ``save_gt`` ``<stem>_GT.png``; the files are complete
     when the call returns.  The metrics do not depend on it.  ``usm_gt`` (task "sr" only; ValueError elsewhere): every GT is cropped
@@ -254,6 +259,8 @@ def evaluate_folder(model, lq_dir: Optional[str], gt_dir: Optional[str], scale: 
             raise ValueError(f"task {task} has no ground truth: its metric group is restorer_niqe, not {metric_group!r}")
         metric_group = "restorer_niqe"
         items = ((os.path.relpath(p, lq_dir), _read_image(p, mode), None) for p in gt_images(lq_dir))
+    if lpips_model is not None:
+        lpips_model = lpips_model.to(device)
     vals, writer, save = [], contextlib.nullcontext(), None
     if save_dir is not None:
         from .image8 import ImageWriter, save_paths
@@ -271,7 +278,7 @@ def evaluate_folder(model, lq_dir: Optional[str], gt_dir: Optional[str], scale: 
     with writer:                                          # closed, every file in place, before the mean is returned
         for name, lq, gt in items:
             on_result = None if save is None else (lambda i, lq_, sr_, gt_, name=name: save(name, lq_, sr_, gt_))
-            v = evaluate_pairs(model, [(lq, gt)], scale, tile, overlap, device, metric_group, niqe_params, on_result)
+            v = evaluate_pairs(model, [(lq, gt)], scale, tile, overlap, device, metric_group, niqe_params, on_result, lpips_model)
             v = v[0] if metric_group is None else v
             vals.append(v)
             if verbose:
@@ -292,7 +299,7 @@ def _columns(v) -> str:
 
 
 def _parser():
-    from .metrics import ALL_GROUPS
+    from .metrics import ALL_GROUPS, PERCEPTUAL_GROUPS
 
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     add_task_arguments(ap, TASKS)
@@ -302,10 +309,14 @@ def _parser():
     ap.add_argument("--niqe-params", default=None,
                     help="restorer_niqe: the reference's utils/metrics/niqe_pris_params.npz (default: the environment variable "
                          "GRL_NIQE_PARAMS)")
+    ap.add_argument("--lpips-vgg", default=None, metavar="PATH",
+                    help="restorer_perceptual: torchvision's vgg16-397923af.pth, read with torch.load; nothing is downloaded")
+    ap.add_argument("--lpips-lin", default=None, metavar="PATH",
+                    help="restorer_perceptual: the lpips package's weights/v0.1/vgg.pth (the five 1x1 layers)")
     ap.add_argument("--tile", type=int, default=0)
     ap.add_argument("--overlap", type=int, default=32)
     ap.add_argument("--device", default="cuda:0")
-    ap.add_argument("--metric", default=None, choices=sorted(ALL_GROUPS),
+    ap.add_argument("--metric", default=None, choices=sorted(ALL_GROUPS) + sorted(PERCEPTUAL_GROUPS),
                     help="report this metric group of the reference (config/metric/*.yaml) instead of PSNR-Y alone")
     ap.add_argument("--save-dir", default=None,
                     help="also write every restored image (<stem>_HQ.png) and the model's input (<stem>_LQ.png) as 8-bit PNG under "
@@ -337,6 +348,26 @@ def _check(ap, a):
     a.scale, a.sigma = o.scale, o.sigma
 
 
+def load_lpips_arguments(ap, a):
+    """The ``lpips.LPIPS`` that ``--metric restorer_perceptual`` needs, from ``--lpips-vgg`` and ``--lpips-lin`` (evaluate and train);
+    None for every other group.  A missing option, file or key ends through ``ap.error``."""
+    if a.metric != "restorer_perceptual":
+        if a.lpips_vgg is not None or a.lpips_lin is not None:
+            ap.error("--lpips-vgg and --lpips-lin belong to --metric restorer_perceptual")
+        return None
+    for opt, path in (("--lpips-vgg", a.lpips_vgg), ("--lpips-lin", a.lpips_lin)):
+        if path is None:
+            ap.error(f"--metric restorer_perceptual needs {opt} (torchvision's vgg16-397923af.pth / the lpips package's vgg.pth)")
+        if not os.path.isfile(path):
+            ap.error(f"{opt}: file {path!r} not found")
+    from .lpips import load_lpips
+
+    try:
+        return load_lpips(a.lpips_vgg, a.lpips_lin)
+    except (KeyError, ValueError) as e:
+        ap.error(f"--lpips-vgg / --lpips-lin: {e}")
+
+
 def main(argv: Optional[List[str]] = None):
     from . import GRL, make_config
 
@@ -344,8 +375,8 @@ def main(argv: Optional[List[str]] = None):
     a = ap.parse_args(argv)
     _check(ap, a)
     taps = load_taps(ap, a)
-    niqe_params = None
-    if a.metric == "restorer_niqe":
+    niqe_params, lpips_model = None, load_lpips_arguments(ap, a)
+    if a.metric in ("restorer_niqe", "restorer_perceptual"):
         from .metrics import load_niqe_params
 
         try:
@@ -359,7 +390,7 @@ def main(argv: Optional[List[str]] = None):
     model = model.to(a.device)
     return evaluate_folder(model, a.lq, a.gt, a.scale, a.tile, a.overlap, a.device, metric_group=a.metric, channels=a.channels,
                            task=a.task, sigma=a.sigma, noise_prefix=a.noise_prefix, niqe_params=niqe_params, taps=taps,
-                           quality=a.quality, save_dir=a.save_dir, save_gt=a.save_gt, usm_gt=a.usm_gt)
+                           quality=a.quality, save_dir=a.save_dir, save_gt=a.save_gt, usm_gt=a.usm_gt, lpips_model=lpips_model)
 
 
 if __name__ == "__main__":

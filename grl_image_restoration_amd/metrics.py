@@ -9,6 +9,8 @@ steps engines/base.py:256-271 takes first: ``tensor_round`` of both images and, 
   restorer_jpeg         restorer + val_psnrb, val_psnrb_y                           colour JPEG artifact removal
   restorer_jpeg_gray    val_psnr, val_ssim, val_psnrb                               grayscale JPEG artifact removal
   restorer_niqe         val_niqe (no reference: ``target`` is ignored, no shave)    blind / real-world SR (``niqe`` below)
+  restorer_perceptual   restorer + val_lpips, val_niqe (RGB only; needs the LPIPS   real-world SR, GAN stage (``lpips`` below,
+                        model and the NIQE model: PERCEPTUAL_GROUPS)                lpips.py)
 
 CUDA tensors go through ``grl_image_metrics`` of libgrl_hip.so (csrc/metrics.hip: one tile pass, one per-image reduction); there
 is no torch fallback for them.  CPU tensors take the plain-torch restatement below (the same definitions, evaluated in float64 on
@@ -41,6 +43,9 @@ GROUPS = {
 # groups that score the restored image alone (no ground truth): kept apart from GROUPS, whose every entry compares a pair
 NO_REFERENCE_GROUPS = {"restorer_niqe": ("val_niqe",)}
 ALL_GROUPS = {**GROUPS, **NO_REFERENCE_GROUPS}
+# groups that need user-supplied models on top of a pair (an ``lpips.LPIPS`` and the NIQE pristine model): kept apart from ALL_GROUPS,
+# whose every entry is computable from the images alone or with the NIQE model alone.  The command lines offer both tables
+PERCEPTUAL_GROUPS = {"restorer_perceptual": ("val_psnr", "val_psnr_y", "val_ssim", "val_ssim_y", "val_lpips", "val_niqe")}
 # GRL_METRIC_* bit of each metric; bit i is column i of grl_image_metrics' output
 BITS = {"val_psnr": 1, "val_psnr_y": 2, "val_ssim": 4, "val_ssim_y": 8, "val_psnrb": 16, "val_psnrb_y": 32}
 Y_COEF = (65.481, 128.553, 24.966)
@@ -79,14 +84,29 @@ def _check(restored: torch.Tensor, target: torch.Tensor, group: str, scale: int)
 
 
 def image_metrics(restored: torch.Tensor, target: Optional[torch.Tensor], group: str = "restorer", scale: int = 1,
-                  niqe_params=None) -> Dict[str, torch.Tensor]:
+                  niqe_params=None, lpips_model=None) -> Dict[str, torch.Tensor]:
     """Per-image metrics of ``group`` as the reference's validation step reports them: {name: float64 tensor of shape (B,)}.
     ``restored`` and ``target`` are (B, C, H, W) images in [0, 1] (values outside are clamped by the rounding), C = 3 or, for the
     *_gray groups, 1; ``scale > 1`` shaves ``scale`` pixels off every side first (SR).  PSNR is +inf for identical images;
     PSNR-B is finite there and -inf for sides below 16 (the reference's counts are 0).  Group "restorer_niqe" scores ``restored``
-    alone (``target`` may be None; no shave: the reference's border is 0) against the pristine model ``niqe_params`` (see ``niqe``)."""
+    alone (``target`` may be None; no shave: the reference's border is 0) against the pristine model ``niqe_params`` (see ``niqe``).
+    Group "restorer_perceptual" (RGB only): the four ``restorer`` values, then ``val_lpips`` from ``lpips_model`` (an ``lpips.LPIPS``)
+    and ``val_niqe`` against ``niqe_params``, both on the rounded, shaved images every metric of the validation step is handed."""
     if group in NO_REFERENCE_GROUPS:
         return {"val_niqe": niqe(restored, niqe_params)}
+    if group in PERCEPTUAL_GROUPS:
+        if lpips_model is None:
+            raise ValueError(f"metric group {group!r} needs the LPIPS model: pass lpips_model (lpips.load_lpips(vgg16 file, lin file); "
+                             "--lpips-vgg / --lpips-lin)")
+        if niqe_params is None and not SW.text(NIQE_ENV):
+            raise ValueError(f"metric group {group!r} needs the NIQE pristine model: pass niqe_params (--niqe-params), or set the "
+                             f"environment variable {NIQE_ENV}")
+        if restored.dim() != 4 or restored.shape[1] != 3:
+            raise ValueError(f"group {group!r} is for RGB images (B, 3, H, W), got {tuple(restored.shape)}")
+        out = image_metrics(restored, target, "restorer", scale)
+        out["val_lpips"] = lpips(restored, target, lpips_model, scale)
+        out["val_niqe"] = niqe(shave(tensor_round(restored.float()), scale if scale > 1 else 0), niqe_params)
+        return out
     keys, border = _check(restored, target, group, scale)
     if restored.is_cuda:
         bits = 0
@@ -118,6 +138,16 @@ def hip_image_metrics(restored: torch.Tensor, target: torch.Tensor, border: int,
         workspace=ws.data_ptr(), workspace_bytes=ws_bytes, out=out.data_ptr())
     _lib.launch("grl_image_metrics", args)
     return out
+
+
+def lpips(restored: torch.Tensor, target: torch.Tensor, lpips_model, scale: int = 1) -> torch.Tensor:
+    """``val_lpips`` alone, as the reference's validation step reports it: ``lpips_model`` (an ``lpips.LPIPS``) on ``tensor_round`` of
+    both images, shaved by ``scale`` pixels for SR: (B,) float64, lower is better."""
+    border = scale if scale > 1 else 0
+    if restored.dim() != 4 or restored.shape != target.shape or 2 * border >= min(restored.shape[-2:]):
+        raise ValueError(f"restored {tuple(restored.shape)} and target {tuple(target.shape)}: need two equal (B, 3, H, W) shapes larger "
+                         f"than the shave of {border}")
+    return lpips_model(shave(tensor_round(restored.float()), border), shave(tensor_round(target.float()), border))
 
 
 # ---- CPU restatement -------------------------------------------------------------------------------------------------------

@@ -1251,3 +1251,46 @@ def vgg_tap_bwd(fx: torch.Tensor, fg: torch.Tensor, B: int, H: int, W: int, k: f
     with _timed("vgg_tap_bwd"):
         L.launch("grl_vgg_tap_bwd", args)
     return dfx
+
+
+# ---- LPIPS (csrc/lpips.hip): input scaling, and the tapped layers' normalise / weight / mean with ReLU + max pool -----------------------
+def lpips_prep(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """grl_lpips_prep: an fp32 image [B, 3, H, W] in [0, 1] (any strides) -> the token matrix [B*H*W, 4] of ((2x - 1) - shift) / scale
+    (column 3 = 0); ``out``: a [B*H*W, 4] slice of a larger matrix to write into."""
+    _dev_check(x, out)
+    assert x.dim() == 4 and x.shape[1] == 3 and x.dtype == torch.float32
+    B, _, H, W = x.shape
+    if out is None:
+        out = empty(B * H * W, 4, dtype=torch.float32, device=x.device)
+    assert out.shape == (B * H * W, 4) and out.dtype == torch.float32 and out.stride(1) == 1
+    args = L.GrlLpipsPrepArgs(image=_ptr(x), stride=(C.c_int64 * 4)(*x.stride()), tok=_ptr(out), ldt=out.stride(0), B=B, H=H, W=W)
+    with _timed("lpips_prep"):
+        L.launch("grl_lpips_prep", args)
+    return out
+
+
+def lpips_tap(f: torch.Tensor, w: torch.Tensor, B: int, H: int, W: int, out: torch.Tensor, *, accumulate: bool = True, pool: bool = True,
+              pool_out: Optional[torch.Tensor] = None):
+    """grl_lpips_tap on one tapped layer.  f [2*B*H*W, C] fp32: the pre-activation, restored rows first, then the target's; w [C]
+    fp32.  out [B] float64 (+)= the layer's distance per image (fixed order, no atomics).  With ``pool`` returns
+    maxpool2x2(relu(f)) [2 * B*(H/2)*(W/2), C] as the 16-bit operand of the next block, else None."""
+    _dev_check(f, w, out, pool_out)
+    assert f.dim() == 2 and f.shape[0] == 2 * B * H * W and f.dtype == torch.float32 and f.stride(1) == 1
+    C_ = f.shape[1]
+    assert w.shape == (C_,) and w.dtype == torch.float32 and w.is_contiguous()
+    assert out.shape == (B,) and out.dtype == torch.float64 and out.is_contiguous()
+    nwg = L.lib().grl_lpips_tap_num_workgroups(B, H, W, C_)
+    L.check(min(nwg, 0), "grl_lpips_tap_num_workgroups")
+    partial = empty(nwg, dtype=torch.float64, device=f.device)
+    rows = B * (H // 2) * (W // 2)
+    if pool:
+        assert H >= 2 and W >= 2
+        if pool_out is None:
+            pool_out = empty(2 * rows, C_, dtype=GEMM_DTYPE, device=f.device)
+        assert pool_out.shape == (2 * rows, C_) and pool_out.dtype == GEMM_DTYPE and pool_out.is_contiguous()
+    args = L.GrlLpipsTapArgs(f=_ptr(f), ldf=f.stride(0), w=_ptr(w), B=B, H=H, W=W, C=C_, pool=int(pool), accumulate=int(accumulate),
+                             pool_out=_ptr(pool_out) if pool else None, ldp=C_ if pool else 0, partial=_ptr(partial), out=_ptr(out),
+                             n_partial=nwg)
+    with _timed("lpips_tap"):
+        L.launch("grl_lpips_tap", args)
+    return pool_out if pool else None

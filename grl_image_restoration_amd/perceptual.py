@@ -46,6 +46,17 @@ GAN_LAYER_WEIGHTS = {"conv1_2": 0.1, "conv2_2": 0.1, "conv3_4": 1.0, "conv4_4": 
 MIN_SIDE = 16                                    # four pools: below 16 nothing is left for block 5
 
 
+def layer_names(blocks: Sequence[int]) -> List[str]:
+    """The NAMES list of a VGG with ``blocks`` convolutions per block, positions as in torchvision's ``features`` without batch norm:
+    ``layer_names(_BLOCKS) == NAMES``; (2, 2, 3, 3, 3) is vgg16 (lpips.py)."""
+    names: List[str] = []
+    for b, n in enumerate(blocks, 1):
+        for j in range(1, n + 1):
+            names += [f"conv{b}_{j}", f"relu{b}_{j}"]
+        names.append(f"pool{b}")
+    return names
+
+
 def _conv_shapes(last_idx: int):
     """(name, features index, cin, cout) of the convolutions up to position ``last_idx`` of NAMES."""
     out, cin = [], 3

@@ -148,7 +148,14 @@ def _parser():
     ap.add_argument("--val-gt", default=None)
     ap.add_argument("--val-lq", default=None)
     ap.add_argument("--val-every", type=int, default=0)
-    ap.add_argument("--metric", default=None, help="a metric group of metrics.ALL_GROUPS instead of PSNR-Y")
+    ap.add_argument("--metric", default=None, help="a metric group of metrics.ALL_GROUPS or metrics.PERCEPTUAL_GROUPS instead of PSNR-Y")
+    ap.add_argument("--lpips-vgg", default=None, metavar="PATH",
+                    help="--metric restorer_perceptual: torchvision's vgg16-397923af.pth, read with torch.load; nothing is downloaded")
+    ap.add_argument("--lpips-lin", default=None, metavar="PATH",
+                    help="--metric restorer_perceptual: the lpips package's weights/v0.1/vgg.pth (the five 1x1 layers)")
+    ap.add_argument("--niqe-params", default=None,
+                    help="--metric restorer_perceptual: the reference's utils/metrics/niqe_pris_params.npz (default: the environment "
+                         "variable GRL_NIQE_PARAMS)")
     ap.add_argument("--out", default=None, help="checkpoint folder")
     ap.add_argument("--save-every", type=int, default=0)
     ap.add_argument("--resume", default=None, help="a checkpoint of this command: weights, optimizer, step and sampler state")
@@ -203,10 +210,10 @@ def _check(ap, a):
     except ValueError:
         ap.error("--milestones and --depths are integers joined by +")
     if a.metric is not None:
-        from .metrics import ALL_GROUPS
+        from .metrics import ALL_GROUPS, PERCEPTUAL_GROUPS
 
-        if a.metric not in ALL_GROUPS:
-            ap.error(f"--metric: one of {sorted(ALL_GROUPS)}")
+        if a.metric not in ALL_GROUPS and a.metric not in PERCEPTUAL_GROUPS:
+            ap.error(f"--metric: one of {sorted(ALL_GROUPS) + sorted(PERCEPTUAL_GROUPS)}")
 
 
 def main(argv: Optional[List[str]] = None):
@@ -215,12 +222,22 @@ def main(argv: Optional[List[str]] = None):
     import torch.distributed as dist
 
     from . import GRL, FusedAdamW, GraphedTrainStep, make_config
-    from .evaluate import evaluate_folder, load_checkpoint, load_discriminator_checkpoint
+    from .evaluate import evaluate_folder, load_checkpoint, load_discriminator_checkpoint, load_lpips_arguments
 
     ap = _parser()
     a = ap.parse_args(argv)
     _check(ap, a)
     taps = load_taps(ap, a)
+    lpips_model, niqe_params = load_lpips_arguments(ap, a), None
+    if a.metric == "restorer_perceptual":
+        from .metrics import load_niqe_params
+
+        try:
+            niqe_params = load_niqe_params(a.niqe_params)
+        except ValueError as e:
+            ap.error(str(e))
+    elif a.niqe_params is not None:
+        ap.error("--niqe-params belongs to --metric restorer_perceptual")
 
     rank, world = 0, 1
     if int(os.environ.get("WORLD_SIZE", "1")) > 1 and not dist.is_initialized():
@@ -340,7 +357,8 @@ def main(argv: Optional[List[str]] = None):
             model.eval()
             with torch.no_grad():
                 v = evaluate_folder(model, a.val_lq, a.val_gt, a.scale, device=a.device, verbose=False, metric_group=a.metric,
-                                    channels=a.channels, task=a.task, sigma=a.sigma, taps=taps, quality=a.quality, usm_gt=a.val_usm)
+                                    channels=a.channels, task=a.task, sigma=a.sigma, taps=taps, quality=a.quality, usm_gt=a.val_usm,
+                                    niqe_params=niqe_params, lpips_model=lpips_model)
             model.train()
             out["val"].append((done, v))
             print(f"step {n:8d}  validation {v}", flush=True)

@@ -23,7 +23,7 @@ extern "C" {
 
 #define GRL_ERR_BAD_ARG (-1)
 #define GRL_ERR_UNSUPPORTED (-2)
-#define GRL_ABI_VERSION 35
+#define GRL_ABI_VERSION 36
 
 /* element kinds of activation / weight buffers */
 enum { GRL_DT_F32 = 0, GRL_DT_BF16 = 1, GRL_DT_F16 = 2 };
@@ -1110,6 +1110,53 @@ typedef struct GrlVggTapArgs {
 int grl_vgg_tap_num_workgroups(int32_t B, int32_t H, int32_t W, int32_t C);
 int grl_vgg_tap_fwd(void* stream, const GrlVggTapArgs* args);
 int grl_vgg_tap_bwd(void* stream, const GrlVggTapArgs* args);
+
+/* ---------------------------------------------------------------------------------------------
+ * LPIPS, net = "vgg" (ABI 36, csrc/lpips.hip): everything between the 3x3 convolutions of the metric's VGG16 trunk.
+ *   replaces  lpips.LPIPS(net="vgg").forward(img1, img2, normalize=True) of package version 0.1, as
+ *             LearnedPerceptualImagePatchSimilarity calls it                              utils/metrics/lpips.py:20,40
+ *             (config/metric/restorer_perceptual.yaml: val_lpips)
+ * The convolutions themselves are grl_conv3x3_fwd launches (act = 2, slope = 0: ReLU in the epilogue of the untapped layers).
+ *
+ * grl_lpips_prep: image (fp32 in [0, 1], any element strides stride[0..3] over (b, c, y, x), 3 channels) -> tok [B*H*W, ldt] fp32,
+ *   columns 0..2 = ((2x - 1) - shift[c]) / scale[c] with the float32 values of shift = (-0.030, -0.088, -0.188), scale = (0.458,
+ *   0.448, 0.450), column 3 = 0: the layout of grl_vgg_prep_fwd.  ldt >= 4, a multiple of 4; tok 16-byte aligned. */
+typedef struct GrlLpipsPrepArgs {
+    const float* image;
+    int64_t stride[4];          /* element strides of image over (b, c, y, x)                     */
+    float* tok;
+    int64_t ldt;
+    int32_t B, H, W;
+    int32_t reserved0;
+} GrlLpipsPrepArgs;
+
+int grl_lpips_prep(void* stream, const GrlLpipsPrepArgs* args);
+
+/* One tapped layer.  f: the fp32 pre-activation [2*B*H*W, ldf] of a block-closing convolution, the B restored images' rows first,
+ * then the B targets'; C = 64, 128, 256 or 512 real channels (GRL_ERR_UNSUPPORTED otherwise, and for B > 65535), 16-byte aligned,
+ * ldf % 4 == 0.  w [C] fp32, 16-byte aligned: the layer's 1x1 weights, any sign.
+ *   (a) out[b] (fp64, b < B) = (accumulate ? out[b] : 0) + mean over the H*W pixels of sum_c w[c] * (u0_c - u1_c)^2 with
+ *       u = relu(f) / (sqrt(sum_c relu(f)_c^2) + 1e-10) per pixel and image (an all-zero pixel gives zeros).  fp32 inside a pixel,
+ *       fp64 from the pixel on; partial [n_partial >= grl_lpips_tap_num_workgroups(B, H, W, C)] fp64 holds one sum per (workgroup,
+ *       image), a finishing launch adds them in a fixed order.  No atomics: bit-identical from run to run; equal halves give 0.
+ *   (b) pool != 0: pool_out [2*B*(H/2)*(W/2), ldp] 16-bit (GRL_DT_F16) = maxpool2x2(relu(f)) of both halves in f's order, floor
+ *       sizes as nn.MaxPool2d(2, 2) (an odd last row / column is not pooled, and still counts in (a)); NaN is kept.
+ * Bad pointers / leading dimensions: GRL_ERR_BAD_ARG, nothing is launched. */
+typedef struct GrlLpipsTapArgs {
+    const float* f;
+    int64_t ldf;
+    const float* w;
+    int32_t B, H, W, C;
+    int32_t pool, accumulate;
+    void* pool_out;
+    int64_t ldp;
+    double* partial;
+    double* out;
+    int32_t n_partial, reserved0;
+} GrlLpipsTapArgs;
+
+int grl_lpips_tap_num_workgroups(int32_t B, int32_t H, int32_t W, int32_t C);
+int grl_lpips_tap(void* stream, const GrlLpipsTapArgs* args);
 
 /* Debug aid (ABI 21; no reference counterpart): fills the LDS of every CU with 0xFF bytes (fp32 / fp16 NaN) by a launch on
  * `stream`.  LDS keeps what the previous workgroup left in it; a kernel that reads LDS it has not written is otherwise right or
