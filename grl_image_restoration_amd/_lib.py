@@ -11,7 +11,7 @@ from . import switches as SW
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgrl_hip.so")
-ABI_VERSION = 36
+ABI_VERSION = 37
 DT_F32, DT_BF16, DT_F16 = 0, 1, 2
 
 EPI_PLAIN, EPI_GELU, EPI_GROUPNORM, EPI_LN_RES, EPI_GELU_GRAD = 0, 1, 2, 3, 4
@@ -646,6 +646,22 @@ class GrlLpipsTapArgs(_Strict):
     ]
 
 
+class GrlIspArgs(_Strict):
+    _fields_ = [
+        ("src", C.c_void_p),
+        ("dst", C.c_void_p),
+        ("src_elems", C.c_int64), ("dst_elems", C.c_int64),
+        ("items", C.c_void_p),
+        ("params", C.c_void_p),
+        ("tables", C.c_void_p),
+        ("tables_elems", C.c_int64),
+        ("normals", C.c_void_p),
+        ("normals_elems", C.c_int64),
+        ("n_items", C.c_int32), ("C", C.c_int32),
+        ("max_h", C.c_int32), ("max_w", C.c_int32),
+    ]
+
+
 _I32, _I64, _PTR = C.c_int32, C.c_int64, C.c_void_p
 
 
@@ -722,6 +738,9 @@ SIGNATURES = {
     "grl_lpips_prep": _launch(GrlLpipsPrepArgs),
     "grl_lpips_tap_num_workgroups": (C.c_int, [_I32] * 4),
     "grl_lpips_tap": _launch(GrlLpipsTapArgs),
+    "grl_isp_unprocess": _launch(GrlIspArgs),
+    "grl_isp_process": _launch(GrlIspArgs),
+    "grl_isp_roundtrip": _launch(GrlIspArgs),
     "grl_debug_dirty_lds": (C.c_int, [_PTR]),
     "grl_abi_version": (C.c_int, []),
     "grl_build_info": (C.c_char_p, []),

@@ -15,16 +15,18 @@ BSRGAN-style random degradation that ``BSRDataset`` runs per sample on a 400 x 4
 coordinates.  OpenCV rounds the coordinate to fp32 first, which moves a weight by up to n * 2^-24; equality with OpenCV's bytes is
 not claimed (OpenCV is not a dependency).
 
-Not built, on purpose: stage 2 of the reference, the ISP camera-noise model (utils_sisr.py:365-370), which needs the camera profiles
--- the stage is a no-op here and its draw is not made -- and the ``ColorJitter`` of restoration_bsr.py:66-68,100.  Scales 2 and 4
-only (``int(1 / sf * n)`` is then exact), three channels (the correlated noise has a 3 x 3 covariance), ``crop`` a multiple of 4 and
-at least ``4 * scale``.
+Stage 2 of the reference, the ISP camera-noise model (utils_sisr.py:365-370), is opt-in: it needs the camera profiles, which are the
+user's data (``isp.CameraBank.load``).  With ``camera=None`` the stage is a no-op and its draw is not made: every draw stream, plan
+and output is then what it was before the stage existed.  With a bank, ``draw_plan`` makes the stage's draws and ``apply_plans``
+runs it through ``isp`` (csrc/isp.hip on CUDA).  Not built, on purpose: the ``ColorJitter`` of restoration_bsr.py:66-68,100.
+Scales 2 and 4 only (``int(1 / sf * n)`` is then exact), three channels (the correlated noise has a 3 x 3 covariance), ``crop`` a
+multiple of 4 and at least ``4 * scale``.
 
-    python -m grl_image_restoration_amd.bsr_degrade --gt DIR --out DIR --scale 4 --seed S [--crop 400]
+    python -m grl_image_restoration_amd.bsr_degrade --gt DIR --out DIR --scale 4 --seed S [--crop 400] [--camera-profiles DIR]
 
 writes a frozen validation set: every image centre-cropped and degraded once, ``<out>/LQ/<stem>.png`` and ``<out>/GT/<stem>.png``
-(the reference's ``with_gt: True`` validation, restoration_bsr.py:113-114).  ``train --val-lq / --val-gt`` and ``evaluate`` read the
-two folders as they are.
+(the reference's ``with_gt: True`` validation, restoration_bsr.py:113-114; with ``--camera-profiles`` the GT written is the one
+the camera stage's HR pass returns, as there).  ``train --val-lq / --val-gt`` and ``evaluate`` read the two folders as they are.
 """
 import argparse
 import functools
@@ -296,7 +298,7 @@ def _corr_noise(rng) -> dict:
     return {"cov": cov.tolist(), "transform": (np.sqrt(sv)[:, None] * v).tolist()}
 
 
-def draw_plan(rng: random.Random, scale: int, crop: int, stages: Optional[Sequence[int]] = None) -> List[dict]:
+def draw_plan(rng: random.Random, scale: int, crop: int, stages: Optional[Sequence[int]] = None, camera=None) -> List[dict]:
     """The degradation of ONE sample: every scalar draw of ``degradation_sr2`` from ``rng`` (the reference mixes ``random`` and
     ``np.random``; here all come from the one ``random.Random``), in the reference's order of decisions.  A pure function of the
     generator's state.  Returns a list of ops in execution order, each a dict with ``pos`` (0: the initial halving, 1 .. 9: the
@@ -313,7 +315,15 @@ def draw_plan(rng: random.Random, scale: int, crop: int, stages: Optional[Sequen
         1 downsample  a = n; random() < 0.5 ? sf1 = uniform(1, 2 sf), resize to int(n / sf1) with choice([1, 2, 3])
                                             : sigma = uniform(0.1, 0.4 sf), the 25 x 25 Gaussian shifted by (sf - 1) / 2 and
                                               renormalised, blur with stride sf;  clip
-        2 camera noise  not built: no draw, no op
+        2 camera noise  ``camera`` (an ``isp.CameraBank``) is None: no draw, no op.  Else random() > 0.75: choice of the 11 cameras,
+                      choice of the 11 tone curves, FW = random(), d_r = 1.2 + 1.2 random(), d_b = 1.2 + 1.2 random(),
+                      e = 0.2 random() - 0.1 (utils_isp.py:484-529), log_shot = uniform(log10(1e-4), log10(0.006)),
+                      log_read = 2.275 log_shot + 1.47 + gauss(0, 0.25) clamped to +-1.5 (utils_noise.py:60-74); the op carries the
+                      draws, shot = 10 ** log_shot, read = 10 ** log_read and ``params``, the record ``camera.params`` makes of
+                      them.  No clip follows: the stage clamps.  A side below 3 raises (the demosaic reflects by 2).  One
+                      deliberate difference: the reference keeps one camera, curve and exposure for 64 consecutive calls of a
+                      data-loader worker (``self.count % 64``, an artefact of worker state) and redraws only the noise levels;
+                      here every acting sample draws its own, so that a plan stays a pure function of the generator's state
         3 Gaussian noise  level = randint(2, 25); r = random(): r > 0.5 per pixel, r < 0.4 one value per pixel for all channels,
                       else channel-correlated (twelve random(): ``_corr_noise``); clip
         4 JPEG        random() < 0.9: quality = randint(20, 95)
@@ -378,6 +388,16 @@ def draw_plan(rng: random.Random, scale: int, crop: int, stages: Optional[Sequen
             emit(pos, ii, "clip", m)
             if ii in allowed:
                 n = m
+        elif ii == 2 and camera is not None:
+            if rng.random() > 0.75:
+                d = dict(camera=rng.choice(range(11)), curve=rng.choice(range(11)), fw=rng.random(), d_r=1.2 + 1.2 * rng.random(),
+                         d_b=1.2 + 1.2 * rng.random(), e=0.2 * rng.random() - 0.1)
+                log_shot = rng.uniform(math.log10(1e-4), math.log10(0.006))
+                log_read = 2.275 * log_shot + 1.47 + min(max(rng.gauss(0.0, 0.25), -1.5), 1.5)
+                d.update(shot=10 ** log_shot, read=10 ** log_read)
+                if ii in allowed and n < 3:
+                    raise ValueError(f"plan: the camera stage meets a side of {n}; its demosaic reflects by 2 and needs at least 3")
+                emit(pos, ii, "camera", n, params=camera.params(d), **d)
         elif ii == 3:
             level = rng.randint(2, 25)
             r = rng.random()
@@ -498,30 +518,76 @@ def _run_blur(ar: _Arenas, group):
         ar.moved(b, op["size"])
 
 
-def apply_plans(x: torch.Tensor, plans: Sequence[List[dict]], gen: Optional[torch.Generator] = None, parts: bool = False):
+def _camera_normals(gen, side: int, device) -> torch.Tensor:
+    """The unit normals of one item of the camera stage: one ``randn`` of (side, side) from ``gen``."""
+    return torch.randn(side, side, generator=gen, device=device, dtype=torch.float32)
+
+
+def _run_camera(ar: _Arenas, group, gen, hr):
+    """Stage 2 for the samples of ``group``: normals from ``gen``, one draw per item in batch order, then one ``isp.camera_noise``
+    over the arenas -- on CUDA the raw plane goes into the item's slot of the other arena and the result back into its own, and the
+    HR pass rewrites the items' images of ``hr`` in place."""
+    from . import isp
+
+    params = [op["params"] for _, op in group]
+    if any(ar.size[b] < isp.MIN_SIDE for b, _ in group):
+        raise ValueError(f"plan: the camera stage needs sides of at least {isp.MIN_SIDE}")
+    z = [_camera_normals(gen, ar.size[b], ar.buf.device) for b, _ in group]
+    if ar.buf.is_cuda:
+        fwd, back, zo = [], [], 0
+        for b, _ in group:
+            n, here, there = ar.size[b], ar.offset(b, ar.side[b]), ar.offset(b, 1 - ar.side[b])
+            fwd.append((here, there, n, n, zo))
+            back.append((there, here, n, n, 0))
+            zo += n * n
+        isp.hip_isp("grl_isp_unprocess", ar.flat, ar.flat, fwd, params, torch.cat([n.reshape(-1) for n in z]))
+        isp.hip_isp("grl_isp_process", ar.flat, ar.flat, back, params)
+        if hr is not None:
+            S, flat = hr.shape[2], hr.view(-1)
+            isp.hip_isp("grl_isp_roundtrip", flat, flat, [(b * 3 * S * S, b * 3 * S * S, S, S, 0) for b, _ in group], params)
+    else:
+        lq, sharp = isp.camera_noise([ar.view(b) for b, _ in group], None if hr is None else [hr[b] for b, _ in group], params, z)
+        for i, (b, _) in enumerate(group):
+            ar.view(b).copy_(lq[i])
+            if hr is not None:
+                hr[b].copy_(sharp[i])
+
+
+def apply_plans(x: torch.Tensor, plans: Sequence[List[dict]], gen: Optional[torch.Generator] = None, parts: bool = False,
+                hr: Optional[torch.Tensor] = None):
     """A batch ``x`` (N, C, crop, crop) fp32 in [0, 1] through the plans of ``draw_plan`` (one per sample): walks the positions of the
     shuffles; at each position the samples are grouped by op, and each kind of image op is ONE call with an item list over two
     ping-pong arenas (``grl_cv_resize``, ``grl_blur_items`` on CUDA; the float64 restatements, rounded to fp32 per op, on the CPU).
     The mid-pipeline JPEG goes through ``tasks.jpeg_roundtrip`` per group of equal size, the noise stages are torch expressions
     drawing from ``gen`` (a generator on ``x``'s device), the final JPEG is one batch with a quality per sample.  Returns
     (N, C, m, m) with m the plans' common final side (crop / scale) on the k / 255 grid; with ``parts`` also the batch before the
-    final JPEG and the int32 qualities: ``(out, pre, q)`` with ``out == tasks.jpeg_roundtrip(pre, q)``."""
+    final JPEG and the int32 qualities: ``(out, pre, q)`` with ``out == tasks.jpeg_roundtrip(pre, q)``.
+    The samples whose op at a position is ``camera`` (``draw_plan`` with a bank) form one group: ``_run_camera``.  ``hr``: a CLONE of
+    the batch, fp32 contiguous of ``x``'s shape and device -- the reference hands the stage the HR next to the LQ and takes both back
+    (utils_sisr.py:369; restoration_bsr.py:107-108, 114 make it the target).  The stage's HR pass rewrites the images of the acting
+    samples in place, and ``hr`` is returned as the last element: ``(out, hr)`` / ``(out, pre, q, hr)``.  Without ``hr`` the HR
+    pass is not run and the return value is as above."""
     from . import tasks
 
     if x.dim() != 4 or x.shape[2] != x.shape[3] or x.shape[1] not in (1, 3) or x.shape[0] < 1 or x.dtype != torch.float32:
         raise ValueError(f"apply_plans: need an fp32 (N, C, crop, crop) batch with C = 1 or 3, got {x.dtype} {tuple(x.shape)}")
     if len(plans) != x.shape[0]:
         raise ValueError(f"apply_plans: {len(plans)} plans for a batch of {x.shape[0]}")
+    if hr is not None and (hr.shape != x.shape or hr.dtype != x.dtype or hr.device != x.device or not hr.is_contiguous() or x.shape[1] != 3):
+        raise ValueError("apply_plans: hr is a contiguous clone of the batch (three channels)")
     ar = _Arenas(x)
     for pos in range(10):
         per = [[op for op in plan if op["pos"] == pos] for plan in plans]
         for b, ops in enumerate(per):
-            if any(op["op"] in ("resize", "blur", "jpeg") for op in ops[1:]):
-                raise ValueError("plan: an image op or a JPEG is the first op of its position")
+            if any(op["op"] in ("resize", "blur", "jpeg", "camera") for op in ops[1:]):
+                raise ValueError("plan: an image op, a JPEG or the camera stage is the first op of its position")
         for kind, run in (("resize", _run_resize), ("blur", _run_blur)):
             group = [(b, ops[0]) for b, ops in enumerate(per) if ops and ops[0]["op"] == kind]
             if group:
                 run(ar, group)
+        group = [(b, ops[0]) for b, ops in enumerate(per) if ops and ops[0]["op"] == "camera"]
+        if group:
+            _run_camera(ar, group, gen, hr)
         by_size = {}
         for b, ops in enumerate(per):
             if ops and ops[0]["op"] == "jpeg":
@@ -540,7 +606,7 @@ def apply_plans(x: torch.Tensor, plans: Sequence[List[dict]], gen: Optional[torc
                     o = tasks.imresize(ar.view(b), 0.5)
                     ar.view(b, 1 - ar.side[b], op["size"]).copy_(o)
                     ar.moved(b, op["size"])
-                elif op["op"] not in ("resize", "blur", "jpeg"):
+                elif op["op"] not in ("resize", "blur", "jpeg", "camera"):
                     raise ValueError(f"plan: unknown op {op['op']!r}")
     final = [[op for op in plan if op["pos"] == 10] for plan in plans]
     if any(len(f) != 1 or f[0]["op"] != "jpeg_final" for f in final) or len(set(ar.size)) != 1:
@@ -548,7 +614,10 @@ def apply_plans(x: torch.Tensor, plans: Sequence[List[dict]], gen: Optional[torc
     pre = torch.stack([ar.view(b) for b in range(ar.N)])
     q = torch.tensor([f[0]["quality"] for f in final], dtype=torch.int32)
     out = tasks.jpeg_roundtrip(pre, q)
-    return (out, pre, q) if parts else out
+    ret = (out, pre, q) if parts else (out,)
+    if hr is not None:
+        ret += (hr,)
+    return ret if len(ret) > 1 else out
 
 
 # ---- a frozen validation set ------------------------------------------------------------------------------------------------------
@@ -565,11 +634,20 @@ def main(argv: Optional[List[str]] = None):
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--crop", type=int, default=400, help="side of the centre crop (a multiple of 4, at least 4 * scale)")
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--camera-profiles", default=None,
+                    help="the reference's utils/cameraprofile folder: turns on stage 2, the camera-noise model (isp.CameraBank.load)")
     a = ap.parse_args(argv)
     try:
         _check_geometry(a.scale, a.crop)
+        if a.camera_profiles is not None and a.crop < 32:
+            raise ValueError(f"with --camera-profiles the crop is at least 32 (no side of the pipeline may fall below 3), got {a.crop}")
     except ValueError as e:
         ap.error(str(e))
+    camera = None
+    if a.camera_profiles is not None:
+        from .isp import CameraBank
+
+        camera = CameraBank.load(a.camera_profiles)
     device = torch.device(a.device)
     rng = random.Random(a.seed)
     gen = torch.Generator(device=device).manual_seed(a.seed)
@@ -584,7 +662,10 @@ def main(argv: Optional[List[str]] = None):
                 ap.error(f"{path}: {H} x {W} is smaller than the crop {a.crop}")
             y, x = (H - a.crop) // 2, (W - a.crop) // 2
             gt = torch.from_numpy(im[y : y + a.crop, x : x + a.crop].copy()).permute(2, 0, 1)[None].float().div(255).to(device)
-            lq = apply_plans(gt, [draw_plan(rng, a.scale, a.crop)], gen)
+            if camera is None:
+                lq = apply_plans(gt, [draw_plan(rng, a.scale, a.crop)], gen)
+            else:
+                lq, gt = apply_plans(gt, [draw_plan(rng, a.scale, a.crop, camera=camera)], gen, hr=gt.clone())
             stem = os.path.splitext(os.path.basename(path))[0]
             writer.write(os.path.join(a.out, "LQ", stem + ".png"), lq)
             writer.write(os.path.join(a.out, "GT", stem + ".png"), gt)

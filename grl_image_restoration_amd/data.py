@@ -157,8 +157,13 @@ class PatchSampler:
                   and the target (restoration_bsr.py:103-110), not a whole-image store as on the paired path -- and run through a
                   freshly drawn ``bsr_degrade.draw_plan`` by ``bsr_degrade.apply_plans``; then one patch position is drawn in the
                   crop / scale LQ and the aligned (lq, gt) patches are cut.  Images smaller than the crop are refused at
-                  construction: the store would pad them with zeros where the reference reflects them.  What is not built
-                  (camera noise, colour jitter): bsr_degrade's docstring
+                  construction: the store would pad them with zeros where the reference reflects them.  With ``camera`` (an
+                  ``isp.CameraBank``; the crop is then at least 32) the plans are drawn with the bank, so a quarter of them carry
+                  stage 2, the camera-noise model.  The reference hands that stage the degradation's input as HR and makes what
+                  comes back the sharpened target (restoration_bsr.py:104-110): with ``usm`` the target of an acting sample is
+                  the sharpened crop after the stage's HR pass; the ``plain_gt`` output is untouched; without ``usm`` the
+                  engines train on the untouched crop (engines/base_psnr.py:39-41, base_gan.py:99-131), so the HR pass is not
+                  run.  What is not built (colour jitter): bsr_degrade's docstring
       sr with ``usm`` and ``plain_gt``
                   ``next`` returns (lq, gt, gt_plain): the sharpened target as above and the unsharpened crop of the same place --
                   the GAN stage's pixel target and the discriminator's real input (use_usm_pixel: True, use_usm_gan: False of
@@ -182,7 +187,7 @@ class PatchSampler:
                  scale: int = 1, sigma: Optional[float] = None, sigma_range: Optional[Sequence[float]] = None, seed: int = 0,
                  taps: Optional[torch.Tensor] = None, quality: Optional[int] = None,
                  quality_range: Optional[Sequence[int]] = None, patchwise: bool = True, usm: bool = False, degrade: bool = False,
-                 degrade_crop: int = 400, plain_gt: bool = False):
+                 degrade_crop: int = 400, plain_gt: bool = False, camera=None):
         from . import tasks
 
         patch, batch, scale = int(patch), int(batch), int(scale)
@@ -190,7 +195,8 @@ class PatchSampler:
             raise ValueError(f"patch and batch must be positive, got {patch}, {batch}")
         o = resolve(task, "sampler", scale=scale, channels=gt_store.channels, lq=lq_store is not None, sigma=sigma,
                     sigma_range=sigma_range, taps=taps is not None, quality=quality, quality_range=quality_range, patch=patch,
-                    patchwise=patchwise, usm=usm, degrade=degrade, degrade_crop=degrade_crop if degrade else None)
+                    patchwise=patchwise, usm=usm, degrade=degrade, degrade_crop=degrade_crop if degrade else None,
+                    camera=camera is not None)
         if taps is not None and (taps.dim() != 2 or taps.shape[0] != taps.shape[1] or taps.shape[0] % 2 == 0 or taps.shape[0] > 31):
             raise ValueError("taps: the (K, K) fp32 table of tasks.blur_taps, K odd and at most 31")
         store_lq = tasks.TRAIN_STORE_LQ.get(task) if o.quality_range is None else None
@@ -217,7 +223,7 @@ class PatchSampler:
         self.rng = random.Random(seed)
         self.device = gt_store.device
         self.gen = torch.Generator(device=self.device).manual_seed(int(seed)) if o.rule.noise or degrade else None
-        self.degrade, self.degrade_crop, self.usm = bool(degrade), o.degrade_crop, bool(usm)
+        self.degrade, self.degrade_crop, self.usm, self.camera = bool(degrade), o.degrade_crop, bool(usm), camera
         if plain_gt and not usm:
             raise ValueError("plain_gt hands out the unsharpened target next to the sharpened one: it belongs to usm")
         self.plain_gt = bool(plain_gt)
@@ -251,7 +257,8 @@ class PatchSampler:
             if self.degrade:
                 from .bsr_degrade import draw_plan
 
-                plan, room = draw_plan(self.rng, self.scale, self.degrade_crop), self.degrade_crop // self.scale - self.patch + 1
+                plan = draw_plan(self.rng, self.scale, self.degrade_crop, camera=self.camera)
+                room = self.degrade_crop // self.scale - self.patch + 1
                 sigmas.append((plan, self.rng.randrange(room), self.rng.randrange(room)))
         return work, (sigmas if self.sigma_range is not None or self.quality_range is not None or self.degrade else None)
 
@@ -296,10 +303,15 @@ class PatchSampler:
         crops = plain = self.gt_store.sample(wt, self.degrade_crop, 1)
         if self.usm:
             crops = tasks.usm_sharp(crops)
-        full = apply_plans(crops, [e[0] for e in extras], self.gen)
+        plans = [e[0] for e in extras]
+        target = crops
+        if self.usm and any(op["op"] == "camera" for plan in plans for op in plan):
+            full, target = apply_plans(crops, plans, self.gen, hr=crops.clone())
+        else:
+            full = apply_plans(crops, plans, self.gen)
         P, s = self.patch, self.scale
         lq = torch.stack([full[b, :, r : r + P, c : c + P] for b, (_, r, c) in enumerate(extras)])
-        gt = torch.stack([crops[b, :, r * s : (r + P) * s, c * s : (c + P) * s] for b, (_, r, c) in enumerate(extras)])
+        gt = torch.stack([target[b, :, r * s : (r + P) * s, c * s : (c + P) * s] for b, (_, r, c) in enumerate(extras)])
         if self.plain_gt:
             return lq, gt, torch.stack([plain[b, :, r * s : (r + P) * s, c * s : (c + P) * s] for b, (_, r, c) in enumerate(extras)])
         return lq, gt

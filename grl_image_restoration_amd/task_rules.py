@@ -58,7 +58,7 @@ SYNTHESISED = tuple(t for t in RULES if RULES[t].lq_from == "gt")
 
 def resolve(task, where, *, scale=None, channels=3, lq=False, sigma=None, sigma_range=None, taps=False, quality=None,
             quality_range=None, patch=None, patchwise=True, val=False, val_lq=False, usm=False, val_usm=False, degrade=False,
-            degrade_crop=None, gan=False):
+            degrade_crop=None, gan=False, camera=False):
     """Checks the options of one call against ``RULES[task]``, fills the defaults and returns them as a namespace (``rule``,
     ``scale``, ``sigma``, ``sigma_range``, ``quality``, ``quality_range``).  Raises ValueError.  ``where`` is the caller: "evaluate" /
     "train" (the command lines), "evaluate_folder", "task_inputs", "sampler".  ``lq`` / ``taps``: whether an LQ folder or store / a blur
@@ -68,6 +68,8 @@ def resolve(task, where, *, scale=None, channels=3, lq=False, sigma=None, sigma_
     sample from a ``degrade_crop`` x ``degrade_crop`` GT crop (default 400) by ``bsr_degrade``; then no LQ folder or store is given,
     the scale is 2 or 4, the images have three channels, the crop is a multiple of 4 and at least 4 * scale, and ``patch`` is at
     most crop / scale.  The namespace also carries ``degrade_crop`` (None without ``degrade``).  ``gan`` (train): the GAN stage.
+    ``camera`` (training with ``degrade``): stage 2 of the degradation, the camera-noise model, is on (camera profiles were given);
+    the crop is then at least 32.
     """
     training, library_eval = where in ("train", "sampler"), where in ("evaluate_folder", "task_inputs")
     r = RULES.get(task)
@@ -86,6 +88,9 @@ def resolve(task, where, *, scale=None, channels=3, lq=False, sigma=None, sigma_
             raise ValueError(f"task {task} with degrade makes its LQ from the GT crops; an LQ folder (--lq) or store is not used")
     elif degrade_crop is not None:
         raise ValueError("degrade_crop (--degrade-crop) belongs to degrade (--degrade)")
+    if camera and not (training and degrade):
+        raise ValueError("the camera-noise stage (--camera-profiles, camera) is stage 2 of the on-the-fly degradation: it belongs to "
+                         "training with degrade (--degrade)")
     # kept: evaluate_folder ignores an LQ folder that the evaluate command line refuses
     if not library_eval:
         if r.lq_from == "folder" and not lq and not degrade:
@@ -114,6 +119,10 @@ def resolve(task, where, *, scale=None, channels=3, lq=False, sigma=None, sigma_
             raise ValueError(f"task {task} with degrade works on RGB images (the correlated noise has a 3 x 3 covariance)")
         if degrade_crop % 4 or degrade_crop < 4 * scale:
             raise ValueError(f"task {task}: the degradation crop is a multiple of 4 and at least 4 * scale = {4 * scale}, got {degrade_crop}")
+        if camera and degrade_crop < 32:
+            raise ValueError(f"task {task}: with the camera-noise stage the degradation crop is at least 32, got {degrade_crop}: the "
+                             "stage's demosaic reflects by 2 and needs sides of at least 3, and the stage can follow the initial "
+                             "halving and a resize by up to 2 * scale")
         if patch is not None and patch > degrade_crop // scale:
             raise ValueError(f"task {task}: a patch of {patch} does not fit the degraded crop of {degrade_crop // scale}")
     # kept: the evaluate command line checks the channels of db alone; dm on gray images fails later, in task_inputs

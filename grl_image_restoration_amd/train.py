@@ -18,7 +18,8 @@ Restates the pieces of the reference's training run that sit around ``model(x)``
     python -m grl_image_restoration_amd.train --task sr --scale 4 --model base --geometry bsr_psnr --upsampler nearest+conv \\
         --usm --val-usm --weight-decay 0 --gt pairs/GT --lq pairs/LQ --val-gt Set5/GTmod12 --val-lq Set5/LRbicx4 ...
     python -m grl_image_restoration_amd.train --task sr --scale 4 --model base --geometry bsr_psnr --upsampler nearest+conv \\
-        --degrade --usm --weight-decay 0 --gt DF2K/HR --val-gt frozen/GT --val-lq frozen/LQ ...      (no --lq: bsr_degrade makes it)
+        --degrade --usm --weight-decay 0 --gt DF2K/HR --val-gt frozen/GT --val-lq frozen/LQ ...      (no --lq: bsr_degrade makes it;
+        with --camera-profiles DIR, the reference's utils/cameraprofile folder, a quarter of the samples get its camera-noise stage)
     python -m grl_image_restoration_amd.train --task sr_bicubic --scale 2 --model small --geometry sr_ckpt_df4 --gt DIV2K/HR ...
     python -m grl_image_restoration_amd.train --task dn --sigma 25 --model small --geometry dn_df4 --gt DFWB --ckpt dn_grl_small_c3s25.ckpt ...
     python -m grl_image_restoration_amd.train --task dm --model small --geometry dm --gt DFWB ...
@@ -143,6 +144,9 @@ def _parser():
                          "crop is sharpened first and is the target")
     ap.add_argument("--degrade-crop", type=int, default=None,
                     help="--degrade: side of the GT crop that is degraded (default 400, the reference's; a multiple of 4)")
+    ap.add_argument("--camera-profiles", default=None,
+                    help="--degrade: the reference's utils/cameraprofile folder (the user's copy); turns on stage 2 of the degradation, "
+                         "the ISP camera-noise model, for a quarter of the samples (isp.CameraBank.load; --degrade-crop at least 32)")
     ap.add_argument("--val-usm", action="store_true", help="--task sr: validate against the USM-sharpened GT (val.use_usm: True)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--val-gt", default=None)
@@ -186,7 +190,7 @@ def _check(ap, a):
         ap.error("--val-every needs --val-gt")
     o = resolve_arguments(ap, a, "train", sigma_range=a.sigma_range, quality_range=a.quality_range, patch=a.patch,
                           val=bool(a.val_every), val_lq=a.val_lq is not None, usm=a.usm or a.usm_gan or a.usm_percep, val_usm=a.val_usm,
-                          degrade=a.degrade, degrade_crop=a.degrade_crop, gan=a.gan)
+                          degrade=a.degrade, degrade_crop=a.degrade_crop, gan=a.gan, camera=a.camera_profiles is not None)
     a.scale, a.sigma, a.degrade_crop = o.scale, o.sigma, o.degrade_crop
     if not a.gan and (a.disc_ckpt is not None or a.usm_gan):
         ap.error("--disc-ckpt and --usm-gan belong to --gan")
@@ -280,6 +284,11 @@ def main(argv: Optional[List[str]] = None):
 
             percep = PerceptualLoss(GAN_LAYER_WEIGHTS, load_vgg19(a.vgg)).to(device)
 
+    camera = None
+    if a.camera_profiles is not None:
+        from .isp import CameraBank
+
+        camera = CameraBank.load(a.camera_profiles)
     usm_flags = [a.usm, a.usm_gan] + ([a.usm_percep] if a.vgg is not None else [])      # the targets that are the sharpened GT
     gt_store = D.PatchStore.from_folder(a.gt, a.channels, device)
     lq_store = D.PatchStore.from_folder(a.lq, a.channels, device) if a.lq is not None else None
@@ -287,7 +296,7 @@ def main(argv: Optional[List[str]] = None):
                              sigma_range=a.sigma_range, seed=a.seed + rank, taps=taps,
                              quality=a.quality if a.quality_range is None else None, quality_range=a.quality_range,
                              usm=any(usm_flags), **(dict(plain_gt=True) if any(usm_flags) and not all(usm_flags) else {}),
-                             **(dict(degrade=True, degrade_crop=a.degrade_crop) if a.degrade else {}))
+                             **(dict(degrade=True, degrade_crop=a.degrade_crop, camera=camera) if a.degrade else {}))
 
     opt = FusedAdamW(model.parameters(), lr=a.lr, weight_decay=0.0 if a.gan else a.weight_decay)
     opt_d = FusedAdamW(model_d.parameters(), lr=a.lr, weight_decay=0.0) if a.gan else None

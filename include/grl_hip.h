@@ -23,7 +23,7 @@ extern "C" {
 
 #define GRL_ERR_BAD_ARG (-1)
 #define GRL_ERR_UNSUPPORTED (-2)
-#define GRL_ABI_VERSION 36
+#define GRL_ABI_VERSION 37
 
 /* element kinds of activation / weight buffers */
 enum { GRL_DT_F32 = 0, GRL_DT_BF16 = 1, GRL_DT_F16 = 2 };
@@ -1157,6 +1157,63 @@ typedef struct GrlLpipsTapArgs {
 
 int grl_lpips_tap_num_workgroups(int32_t B, int32_t H, int32_t W, int32_t C);
 int grl_lpips_tap(void* stream, const GrlLpipsTapArgs* args);
+
+/* ---------------------------------------------------------------------------------------------
+ * The camera-noise stage of the blind-SR degradation (ABI 37, csrc/isp.hip): stage 2 of degradation_sr2, the ISP model.
+ *   replaces  img, HR = ispmodel.forward(img.copy(), HR)                                   utils/utils_bsr/utils_sisr.py:365-370
+ *             ISPModel.forward: isp.reverse(x, True), isp.forward(., True); isp.reverse(x1, False), isp.forward(., False)
+ *                                                                                          utils/utils_bsr/utils_isp.py:539-543
+ *             ISPNet.reverse / forward (431-454) with GammaCorrect (206-212), ToneMapping (354-360), XYZ2LinearRGB (85-89),
+ *             Raw2XYZ (57-67), ExposureCompensation (105-109), Demosaic (270-309), AddNoise.reverse (374-377);
+ *             utils_color.linear2gamma colour space 0 (utils_color.py:172-180); utils_noise.add_noise (utils_noise.py:95-103)
+ * The three entries follow the contract of grl_cv_resize / grl_blur_items above: an ITEM LIST in device memory over a source and a
+ * destination arena (they may be one buffer as long as no item's destination overlaps another item's source; grl_isp_roundtrip may
+ * also run an item in place, src == dst and src_off == dst_off: a thread reads its pixel's three channels before it writes them),
+ * the host wrapper vouches for max_h / max_w (the grid is sized from them) and for disjoint destinations, the kernels skip whole
+ * any item whose images do not lie inside src_elems / dst_elems, whose tables do not lie inside tables_elems (its normals inside
+ * normals_elems), or whose side is below 3 or above 2^20.  The result of an item does not depend on the other items of the
+ * launch.  Nothing is allocated, the host does not synchronise, the launches can be captured.
+ *   items[i]  = {src_off, dst_off, h, w, yi_off, yi_inv_off, z_off, 0}: element offsets of the images into the arenas, of the
+ *               item's forward and inverse tone tables (1,000,001 fp32 each, delta = 1e-6: ToneMapping.yi / yi_inv) into `tables`,
+ *               and of its h * w unit normals into `normals` (read by grl_isp_unprocess alone).  The offsets live here and not in
+ *               the fp32 record: a float does not hold an offset beyond 2^24.
+ *   params[i] = 40 floats: W1i, W2i, W2, W1 (3 x 3 each, row major; W2 = camera -> XYZ(D50), W1 = XYZ(D50) -> linear sRGB, W1i and
+ *               W2i their inverses), 2^e, 2^-e (carried for the caller; the kernels divide by 2^e as the reference does), shot, read.
+ * All arithmetic is fp32 (the compiler may contract a multiply and an add); clamp(x) = min(max(x, 0), 1), NaN -> 0; M x is
+ * (m0 x0 + m1 x1) + m2 x2 per row; lut(t, x) = t[min(rint(x / 1e-6f), 1000000)].  Per pixel:
+ *   unprocess chain   x = clamp(x); x = x > 0.04045 ? ((200 x + 11) / 211)^2.4 : max(x, 1e-8) / 12.92; x = clamp(lut(yi_inv, clamp(x)));
+ *                     x = W1i x; x = W2i x; x = clamp(x / 2^e)
+ *   process chain     x = clamp(x * 2^e); x = W2 x; x = W1 x; x = clamp(lut(yi, clamp(x)));
+ *                     x = x > 0.0031308 ? 1.055 x^(1/2.4) - 0.055 : 12.92 x; x = clamp(x)
+ * grl_isp_unprocess: (3, h, w) -> the noisy RGGB raw plane (h, w): the unprocess chain, of which pixel (y, x) keeps channel
+ *   (y & 1) + (x & 1) -- R at even row and column, B at odd row and column, G elsewhere; only that row of W2i is evaluated --,
+ *   r = clamp(r), then r = clamp(r + sqrt(r * shot + read) * z[y * w + x]).
+ * grl_isp_process: raw plane (h, w) -> (3, h, w): the plane reflect-padded by 2 (torch's "reflect": -1 -> 1, n -> n - 2), the four
+ *   5 x 5 filters of Demosaic.__init__ (kgrb at R and B sites for G; krbg0 / krbg1 for R and B at the G sites of a red / blue row and
+ *   swapped for the other colour; krbbr for B at R sites and R at B sites; every weight is an exact binary fraction), native samples
+ *   copied, clamp, then the process chain.  0::2 / 1::2 indexing: odd sides are served.
+ * grl_isp_roundtrip: (3, h, w) -> (3, h, w): the unprocess chain on all three channels, then the process chain -- the HR pass,
+ *   without mosaic and noise.
+ * Errors (GRL_ERR_BAD_ARG, nothing is launched): a null args / src / dst / items / params / tables (normals for grl_isp_unprocess), C
+ * not 3, n_items outside 1 .. 65535, a non-positive src_elems / dst_elems (normals_elems), tables_elems below 1,000,001, max_h or
+ * max_w below 3 or above 2^20, more than 2^31 - 1 tiles, src / dst / params / tables / normals not 4-byte or items not 8-byte aligned. */
+typedef struct GrlIspArgs {
+    const float* src;           /* source arena                                                   */
+    float* dst;                 /* destination arena                                              */
+    int64_t src_elems, dst_elems; /* their lengths in floats: no item reads / writes beyond them  */
+    const int64_t* items;       /* [n_items][8] device: src_off, dst_off, h, w, yi_off, yi_inv_off, z_off, 0 */
+    const float* params;        /* [n_items][40] device                                           */
+    const float* tables;        /* the tone tables, device                                        */
+    int64_t tables_elems;
+    const float* normals;       /* unit normals, device; grl_isp_unprocess only (else NULL)       */
+    int64_t normals_elems;
+    int32_t n_items, C;         /* C = 3                                                          */
+    int32_t max_h, max_w;       /* host-known maxima of h, w over the items (vouched for)         */
+} GrlIspArgs;
+
+int grl_isp_unprocess(void* stream, const GrlIspArgs* args);
+int grl_isp_process(void* stream, const GrlIspArgs* args);
+int grl_isp_roundtrip(void* stream, const GrlIspArgs* args);
 
 /* Debug aid (ABI 21; no reference counterpart): fills the LDS of every CU with 0xFF bytes (fp32 / fp16 NaN) by a launch on
  * `stream`.  LDS keeps what the previous workgroup left in it; a kernel that reads LDS it has not written is otherwise right or
