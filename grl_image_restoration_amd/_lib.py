@@ -11,7 +11,7 @@ from . import switches as SW
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgrl_hip.so")
-ABI_VERSION = 37
+ABI_VERSION = 38
 DT_F32, DT_BF16, DT_F16 = 0, 1, 2
 
 EPI_PLAIN, EPI_GELU, EPI_GROUPNORM, EPI_LN_RES, EPI_GELU_GRAD = 0, 1, 2, 3, 4
@@ -662,6 +662,21 @@ class GrlIspArgs(_Strict):
     ]
 
 
+class GrlColorJitterArgs(_Strict):
+    _fields_ = [
+        ("src", C.c_void_p),
+        ("dst", C.c_void_p),
+        ("src_elems", C.c_int64), ("dst_elems", C.c_int64),
+        ("items", C.c_void_p),
+        ("params", C.c_void_p),
+        ("partial", C.c_void_p),
+        ("n_partial", C.c_int64),
+        ("means", C.c_void_p),
+        ("n_items", C.c_int32), ("C", C.c_int32),
+        ("max_h", C.c_int32), ("max_w", C.c_int32),
+    ]
+
+
 _I32, _I64, _PTR = C.c_int32, C.c_int64, C.c_void_p
 
 
@@ -741,6 +756,8 @@ SIGNATURES = {
     "grl_isp_unprocess": _launch(GrlIspArgs),
     "grl_isp_process": _launch(GrlIspArgs),
     "grl_isp_roundtrip": _launch(GrlIspArgs),
+    "grl_color_jitter_num_workgroups": (C.c_int, [_I32] * 2),
+    "grl_color_jitter": _launch(GrlColorJitterArgs),
     "grl_debug_dirty_lds": (C.c_int, [_PTR]),
     "grl_abi_version": (C.c_int, []),
     "grl_build_info": (C.c_char_p, []),

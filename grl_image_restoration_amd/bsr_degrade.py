@@ -18,7 +18,9 @@ not claimed (OpenCV is not a dependency).
 Stage 2 of the reference, the ISP camera-noise model (utils_sisr.py:365-370), is opt-in: it needs the camera profiles, which are the
 user's data (``isp.CameraBank.load``).  With ``camera=None`` the stage is a no-op and its draw is not made: every draw stream, plan
 and output is then what it was before the stage existed.  With a bank, ``draw_plan`` makes the stage's draws and ``apply_plans``
-runs it through ``isp`` (csrc/isp.hip on CUDA).  Not built, on purpose: the ``ColorJitter`` of restoration_bsr.py:66-68,100.
+runs it through ``isp`` (csrc/isp.hip on CUDA).  The ``ColorJitter`` of restoration_bsr.py:66-68,100 acts on the GT crop before
+this module sees it: ``jitter.py``, ``PatchSampler(jitter=True)``, ``train --jitter``.  The frozen-set command line below has none,
+as the reference's validation has none.
 Scales 2 and 4 only (``int(1 / sf * n)`` is then exact), three channels (the correlated noise has a 3 x 3 covariance), ``crop`` a
 multiple of 4 and at least ``4 * scale``.
 

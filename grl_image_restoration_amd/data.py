@@ -163,7 +163,13 @@ class PatchSampler:
                   comes back the sharpened target (restoration_bsr.py:104-110): with ``usm`` the target of an acting sample is
                   the sharpened crop after the stage's HR pass; the ``plain_gt`` output is untouched; without ``usm`` the
                   engines train on the untouched crop (engines/base_psnr.py:39-41, base_gan.py:99-131), so the HR pass is not
-                  run.  What is not built (colour jitter): bsr_degrade's docstring
+                  run.  With ``jitter`` every crop first goes through the reference's ``ColorJitter`` (restoration_bsr.py:66-68,
+                  100; ``jitter.py``, csrc/jitter.hip on CUDA), in place, right after it is cut and before the sharpening: the
+                  sharpened target, the ``plain_gt`` output and the degradation's input all derive from the jittered crop.  The
+                  parameter sets come from a CPU ``torch.Generator`` of the sampler's own, seeded with ``seed`` -- the reference
+                  takes them from torch's global generator, a stream apart from the Python ``random`` of the degradation --,
+                  one ``jitter.draw_jitter`` per sample in sample order; the Python draw stream and the noise generator are
+                  untouched, and without ``jitter`` nothing is drawn and ``rng_state()`` has no ``"jitter"`` key
       sr with ``usm`` and ``plain_gt``
                   ``next`` returns (lq, gt, gt_plain): the sharpened target as above and the unsharpened crop of the same place --
                   the GAN stage's pixel target and the discriminator's real input (use_usm_pixel: True, use_usm_gan: False of
@@ -187,7 +193,7 @@ class PatchSampler:
                  scale: int = 1, sigma: Optional[float] = None, sigma_range: Optional[Sequence[float]] = None, seed: int = 0,
                  taps: Optional[torch.Tensor] = None, quality: Optional[int] = None,
                  quality_range: Optional[Sequence[int]] = None, patchwise: bool = True, usm: bool = False, degrade: bool = False,
-                 degrade_crop: int = 400, plain_gt: bool = False, camera=None):
+                 degrade_crop: int = 400, plain_gt: bool = False, camera=None, jitter: bool = False):
         from . import tasks
 
         patch, batch, scale = int(patch), int(batch), int(scale)
@@ -196,7 +202,7 @@ class PatchSampler:
         o = resolve(task, "sampler", scale=scale, channels=gt_store.channels, lq=lq_store is not None, sigma=sigma,
                     sigma_range=sigma_range, taps=taps is not None, quality=quality, quality_range=quality_range, patch=patch,
                     patchwise=patchwise, usm=usm, degrade=degrade, degrade_crop=degrade_crop if degrade else None,
-                    camera=camera is not None)
+                    camera=camera is not None, jitter=jitter)
         if taps is not None and (taps.dim() != 2 or taps.shape[0] != taps.shape[1] or taps.shape[0] % 2 == 0 or taps.shape[0] > 31):
             raise ValueError("taps: the (K, K) fp32 table of tasks.blur_taps, K odd and at most 31")
         store_lq = tasks.TRAIN_STORE_LQ.get(task) if o.quality_range is None else None
@@ -235,12 +241,18 @@ class PatchSampler:
         # the device quality list of jpeg with a range, rewritten in place like the work list
         self.qualities = torch.zeros(batch, dtype=torch.int32, device=self.device) if quality_range is not None else None
         self._pair = tasks.TRAIN_PAIR.get(task)
+        self.jitter = bool(jitter)
+        if self.jitter:
+            from .jitter import JitterLists
+
+            self.jitter_gen = torch.Generator().manual_seed(int(seed))               # CPU: the draws are host values
+            self.jitter_lists = JitterLists(batch, o.degrade_crop, self.device)       # device lists, rewritten in place like the work list
 
     # ---- draws ---------------------------------------------------------------------------------------------------------------
     def draw(self):
         """One batch of draws: ([(image, x, y, flags)] * batch, [sigma] * batch or None); for jpeg with a quality range the second
         list holds the qualities, with ``degrade`` per sample (plan, row, column): the plan of ``bsr_degrade.draw_plan`` and the
-        place of the LQ patch."""
+        place of the LQ patch; with ``jitter`` (plan, row, column, params), ``params`` of ``jitter.draw_jitter``."""
         sizes = (self.lq_store or self.gt_store).dims
         P, work, sigmas = self.draw_patch, [], []
         for _ in range(self.batch):
@@ -260,23 +272,34 @@ class PatchSampler:
                 plan = draw_plan(self.rng, self.scale, self.degrade_crop, camera=self.camera)
                 room = self.degrade_crop // self.scale - self.patch + 1
                 sigmas.append((plan, self.rng.randrange(room), self.rng.randrange(room)))
+                if self.jitter:
+                    from .jitter import draw_jitter
+
+                    sigmas[-1] += (draw_jitter(self.jitter_gen),)
         return work, (sigmas if self.sigma_range is not None or self.quality_range is not None or self.degrade else None)
 
     def rng_state(self):
-        """What a checkpoint keeps to continue the stream of batches: the draws' state and the noise generator's."""
-        return {"draws": self.rng.getstate(), "noise": self.gen.get_state().cpu() if self.gen is not None else None}
+        """What a checkpoint keeps to continue the stream of batches: the draws' state and the noise generator's; with ``jitter``
+        also the state of the jitter's generator, under a key of its own."""
+        state = {"draws": self.rng.getstate(), "noise": self.gen.get_state().cpu() if self.gen is not None else None}
+        if self.jitter:
+            state["jitter"] = self.jitter_gen.get_state()
+        return state
 
     def set_rng_state(self, state):
         self.rng.setstate(_as_rng_state(state["draws"]))
         if self.gen is not None and state.get("noise") is not None:
             self.gen.set_state(state["noise"].cpu())
+        if self.jitter and state.get("jitter") is not None:
+            self.jitter_gen.set_state(state["jitter"].cpu())
 
     # ---- batches -------------------------------------------------------------------------------------------------------------
     def next(self, work=None, sigmas: Optional[Sequence[float]] = None, noise: Optional[torch.Tensor] = None):
         """(lq, gt) -- with ``plain_gt`` (lq, gt, gt_plain) -- on the store's device.  ``work``: an explicit work list (a sequence of (image, x, y, flags) or an int32 (B, 4)
         tensor) instead of fresh draws; ``sigmas`` with it for dn with a sigma range and for jpeg with a quality range (the
-        qualities) and for ``degrade`` (the (plan, row, column) per sample).  ``noise`` (db): a unit-variance
-        (B, 3, patch, patch) fp32 tensor used instead of the generator's draw (it is scaled by ``sigma / 255``)."""
+        qualities) and for ``degrade`` (the (plan, row, column) per sample; with ``jitter`` (plan, row, column, params)).
+        ``noise`` (db): a unit-variance (B, 3, patch, patch) fp32 tensor used instead of the generator's draw (it is scaled by
+        ``sigma / 255``)."""
         if work is None:
             work, sigmas = self.draw()
         if torch.is_tensor(work):
@@ -300,7 +323,12 @@ class PatchSampler:
 
         if extras is None or len(extras) != wt.shape[0]:
             raise ValueError("degrade: one (plan, row, column) per sample next to an explicit work list")
+        if any(len(e) != (4 if self.jitter else 3) for e in extras):
+            raise ValueError("degrade: a sample's extras are (plan, row, column), with jitter (plan, row, column, params)")
         crops = plain = self.gt_store.sample(wt, self.degrade_crop, 1)
+        if self.jitter:
+            crops = plain = self.jitter_lists.run_(crops, [e[3] for e in extras])
+        extras = [e[:3] for e in extras]
         if self.usm:
             crops = tasks.usm_sharp(crops)
         plans = [e[0] for e in extras]

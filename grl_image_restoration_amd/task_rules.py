@@ -58,7 +58,7 @@ SYNTHESISED = tuple(t for t in RULES if RULES[t].lq_from == "gt")
 
 def resolve(task, where, *, scale=None, channels=3, lq=False, sigma=None, sigma_range=None, taps=False, quality=None,
             quality_range=None, patch=None, patchwise=True, val=False, val_lq=False, usm=False, val_usm=False, degrade=False,
-            degrade_crop=None, gan=False, camera=False):
+            degrade_crop=None, gan=False, camera=False, jitter=False):
     """Checks the options of one call against ``RULES[task]``, fills the defaults and returns them as a namespace (``rule``,
     ``scale``, ``sigma``, ``sigma_range``, ``quality``, ``quality_range``).  Raises ValueError.  ``where`` is the caller: "evaluate" /
     "train" (the command lines), "evaluate_folder", "task_inputs", "sampler".  ``lq`` / ``taps``: whether an LQ folder or store / a blur
@@ -69,7 +69,7 @@ def resolve(task, where, *, scale=None, channels=3, lq=False, sigma=None, sigma_
     the scale is 2 or 4, the images have three channels, the crop is a multiple of 4 and at least 4 * scale, and ``patch`` is at
     most crop / scale.  The namespace also carries ``degrade_crop`` (None without ``degrade``).  ``gan`` (train): the GAN stage.
     ``camera`` (training with ``degrade``): stage 2 of the degradation, the camera-noise model, is on (camera profiles were given);
-    the crop is then at least 32.
+    the crop is then at least 32.  ``jitter`` (training with ``degrade``): the reference's ColorJitter on every GT crop.
     """
     training, library_eval = where in ("train", "sampler"), where in ("evaluate_folder", "task_inputs")
     r = RULES.get(task)
@@ -90,6 +90,9 @@ def resolve(task, where, *, scale=None, channels=3, lq=False, sigma=None, sigma_
         raise ValueError("degrade_crop (--degrade-crop) belongs to degrade (--degrade)")
     if camera and not (training and degrade):
         raise ValueError("the camera-noise stage (--camera-profiles, camera) is stage 2 of the on-the-fly degradation: it belongs to "
+                         "training with degrade (--degrade)")
+    if jitter and not (training and degrade):
+        raise ValueError("the colour jitter (--jitter, jitter) acts on the GT crops of the on-the-fly degradation: it belongs to "
                          "training with degrade (--degrade)")
     # kept: evaluate_folder ignores an LQ folder that the evaluate command line refuses
     if not library_eval:

@@ -19,7 +19,8 @@ Restates the pieces of the reference's training run that sit around ``model(x)``
         --usm --val-usm --weight-decay 0 --gt pairs/GT --lq pairs/LQ --val-gt Set5/GTmod12 --val-lq Set5/LRbicx4 ...
     python -m grl_image_restoration_amd.train --task sr --scale 4 --model base --geometry bsr_psnr --upsampler nearest+conv \\
         --degrade --usm --weight-decay 0 --gt DF2K/HR --val-gt frozen/GT --val-lq frozen/LQ ...      (no --lq: bsr_degrade makes it;
-        with --camera-profiles DIR, the reference's utils/cameraprofile folder, a quarter of the samples get its camera-noise stage)
+        with --camera-profiles DIR, the reference's utils/cameraprofile folder, a quarter of the samples get its camera-noise stage;
+        with --jitter every GT crop first goes through the reference's ColorJitter)
     python -m grl_image_restoration_amd.train --task sr_bicubic --scale 2 --model small --geometry sr_ckpt_df4 --gt DIV2K/HR ...
     python -m grl_image_restoration_amd.train --task dn --sigma 25 --model small --geometry dn_df4 --gt DFWB --ckpt dn_grl_small_c3s25.ckpt ...
     python -m grl_image_restoration_amd.train --task dm --model small --geometry dm --gt DFWB ...
@@ -147,6 +148,9 @@ def _parser():
     ap.add_argument("--camera-profiles", default=None,
                     help="--degrade: the reference's utils/cameraprofile folder (the user's copy); turns on stage 2 of the degradation, "
                          "the ISP camera-noise model, for a quarter of the samples (isp.CameraBank.load; --degrade-crop at least 32)")
+    ap.add_argument("--jitter", action="store_true",
+                    help="--degrade: the reference's ColorJitter (brightness, contrast, saturation 0.2, hue 0.05) on every GT crop, before "
+                         "the sharpening and the degradation (jitter.py; the validation set has none)")
     ap.add_argument("--val-usm", action="store_true", help="--task sr: validate against the USM-sharpened GT (val.use_usm: True)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--val-gt", default=None)
@@ -190,7 +194,8 @@ def _check(ap, a):
         ap.error("--val-every needs --val-gt")
     o = resolve_arguments(ap, a, "train", sigma_range=a.sigma_range, quality_range=a.quality_range, patch=a.patch,
                           val=bool(a.val_every), val_lq=a.val_lq is not None, usm=a.usm or a.usm_gan or a.usm_percep, val_usm=a.val_usm,
-                          degrade=a.degrade, degrade_crop=a.degrade_crop, gan=a.gan, camera=a.camera_profiles is not None)
+                          degrade=a.degrade, degrade_crop=a.degrade_crop, gan=a.gan, camera=a.camera_profiles is not None,
+                          jitter=a.jitter)
     a.scale, a.sigma, a.degrade_crop = o.scale, o.sigma, o.degrade_crop
     if not a.gan and (a.disc_ckpt is not None or a.usm_gan):
         ap.error("--disc-ckpt and --usm-gan belong to --gan")
@@ -296,7 +301,7 @@ def main(argv: Optional[List[str]] = None):
                              sigma_range=a.sigma_range, seed=a.seed + rank, taps=taps,
                              quality=a.quality if a.quality_range is None else None, quality_range=a.quality_range,
                              usm=any(usm_flags), **(dict(plain_gt=True) if any(usm_flags) and not all(usm_flags) else {}),
-                             **(dict(degrade=True, degrade_crop=a.degrade_crop, camera=camera) if a.degrade else {}))
+                             **(dict(degrade=True, degrade_crop=a.degrade_crop, camera=camera, jitter=a.jitter) if a.degrade else {}))
 
     opt = FusedAdamW(model.parameters(), lr=a.lr, weight_decay=0.0 if a.gan else a.weight_decay)
     opt_d = FusedAdamW(model_d.parameters(), lr=a.lr, weight_decay=0.0) if a.gan else None

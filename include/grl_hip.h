@@ -23,7 +23,7 @@ extern "C" {
 
 #define GRL_ERR_BAD_ARG (-1)
 #define GRL_ERR_UNSUPPORTED (-2)
-#define GRL_ABI_VERSION 37
+#define GRL_ABI_VERSION 38
 
 /* element kinds of activation / weight buffers */
 enum { GRL_DT_F32 = 0, GRL_DT_BF16 = 1, GRL_DT_F16 = 2 };
@@ -1214,6 +1214,67 @@ typedef struct GrlIspArgs {
 int grl_isp_unprocess(void* stream, const GrlIspArgs* args);
 int grl_isp_process(void* stream, const GrlIspArgs* args);
 int grl_isp_roundtrip(void* stream, const GrlIspArgs* args);
+
+/* ---------------------------------------------------------------------------------------------
+ * The colour jitter of the blind-SR training branch (ABI 38, csrc/jitter.hip).
+ *   replaces  self.jitter = T.ColorJitter(brightness=0.2, contrast=0.2, saturation=0.2, hue=0.05)
+ *             img_gt = self.jitter(util.uint2tensor4(img_gt))                       data/datasets/restoration_bsr.py:66-68,100
+ *             i.e. torchvision's ColorJitter.forward on a float RGB tensor in [0, 1]: the ops of get_params' permutation, each one of
+ *             adjust_brightness, adjust_contrast, adjust_saturation, adjust_hue (transforms/_functional_tensor.py: _blend,
+ *             rgb_to_grayscale, _rgb2hsv, _hsv2rgb).
+ * The statement below is written from torchvision's published source; torchvision is not a dependency and no run of it backs the
+ * tests: they hold the kernels to a float64 evaluation of this statement and its hue step to Python's colorsys.  Not claimed:
+ * bit equality with a torchvision run, and the summation order of torch.mean behind the contrast mean.
+ * The contract is that of grl_isp_roundtrip above: an ITEM LIST in device memory over a source and a destination arena (they may
+ * be one buffer as long as no item's destination overlaps another item's source; an item may run in place, src == dst and
+ * src_off == dst_off: a thread reads its pixels' three channels before it writes them), the host wrapper vouches for max_h / max_w
+ * (the grid and the partial buffer are sized from them) and for disjoint destinations, the kernels skip whole -- the image and
+ * its mean stay unwritten -- any item whose images do not lie inside src_elems / dst_elems, whose side is below 1 or above 2^20,
+ * whose h * w needs more workgroups than grl_color_jitter_num_workgroups(max_h, max_w), or whose ops are no permutation of
+ * 0 .. 3.  The result of an item does not depend on the other items of the call, and the same inputs give the same bits on every
+ * run: there are no atomics.  Nothing is allocated, the host does not synchronise, the two launches can be captured.
+ *   items[i]  = {src_off, dst_off, h, w, op0, op1, op2, op3}: element offsets of the (3, h, w) images into the arenas (the offsets
+ *               live here and not in the fp32 record: a float does not hold an offset beyond 2^24), and the ops in the order
+ *               they run: 0 brightness, 1 contrast, 2 saturation, 3 hue (get_params' torch.randperm(4)).
+ *   params[i] = 4 floats: b, c, s (ColorJitter draws them from [0.8, 1.2]) and h (from [-0.05, 0.05]).
+ * All arithmetic is fp32 (the compiler may contract a multiply and an add) except the sum behind the contrast mean;
+ * clamp(x) = min(max(x, 0), 1), NaN -> 0;  gray(x) = (0.2989 r + 0.587 g) + 0.114 b   (rgb_to_grayscale);
+ * blend(x, y, f) = clamp(f x + (1 - f) y)   (_blend).  Per image, in the order of the item:
+ *   brightness   x = blend(x, 0, b)                                                                      adjust_brightness
+ *   contrast     m = the mean of gray(x) over the h * w pixels of the image as it stands at this point of the chain;
+ *                x = blend(x, m, c) on all three channels                                                adjust_contrast
+ *                (m: gray in fp32, summed in fp64 -- per thread, per wave, per workgroup, then the workgroups' sums in a fixed
+ *                order --, divided by h * w in fp64, rounded to fp32 for the blend and written to means[i] in fp64)
+ *   saturation   x = blend(x, gray(x), s) per pixel                                                      adjust_saturation
+ *   hue          _rgb2hsv: maxc, minc the channel max / min, eq = maxc == minc, cr = maxc - minc; S = cr / (eq ? 1 : maxc);
+ *                d = eq ? 1 : cr; rc, gc, bc = (maxc - r | g | b) / d;
+ *                H = maxc == r ? bc - gc : maxc == g ? (2 + rc) - bc : (4 + gc) - rc;  H = fmod(H / 6 + 1, 1);  V = maxc
+ *                adjust_hue: H = (H + h) mod 1 with a non-negative result (torch.remainder: fmod, plus 1 when negative)
+ *                _hsv2rgb: i = floor(6 H), f = 6 H - i; p = clamp(V (1 - S)), q = clamp(V (1 - S f)), t = clamp(V (1 - S (1 - f)));
+ *                i = i mod 6 (i is 6 when the remainder rounded to 1); (r, g, b) = row i of
+ *                (V, t, p) (q, V, p) (p, V, t) (p, q, V) (t, p, V) (V, p, q)
+ * The call is two launches.  Pass 1 walks the ops that precede contrast per pixel and writes one fp64 sum of gray per (item,
+ * workgroup) to partial[i * W + g], W = grl_color_jitter_num_workgroups(max_h, max_w) (a workgroup owns 4096 consecutive pixels:
+ * a 400 x 400 image has 40 partials); pass 2 adds the item's partials, writes means[i], and walks the whole chain.
+ * Errors (GRL_ERR_BAD_ARG, nothing is launched): a null args / src / dst / items / params / partial / means, C not 3, n_items
+ * outside 1 .. 65535, a non-positive src_elems / dst_elems, max_h or max_w below 1 or above 2^20, n_partial below n_items * W,
+ * src / dst / params not 4-byte or items / partial / means not 8-byte aligned.  grl_color_jitter_num_workgroups returns
+ * GRL_ERR_BAD_ARG for a max_h or max_w out of that range. */
+typedef struct GrlColorJitterArgs {
+    const float* src;           /* source arena                                                   */
+    float* dst;                 /* destination arena                                              */
+    int64_t src_elems, dst_elems; /* their lengths in floats: no item reads / writes beyond them  */
+    const int64_t* items;       /* [n_items][8] device: src_off, dst_off, h, w, op0, op1, op2, op3 */
+    const float* params;        /* [n_items][4] device: b, c, s, h                                */
+    double* partial;            /* [n_partial] device scratch, written by pass 1                  */
+    int64_t n_partial;          /* >= n_items * grl_color_jitter_num_workgroups(max_h, max_w)     */
+    double* means;              /* [n_items] device: the contrast mean of every item that ran     */
+    int32_t n_items, C;         /* C = 3                                                          */
+    int32_t max_h, max_w;       /* host-known maxima of h, w over the items (vouched for)         */
+} GrlColorJitterArgs;
+
+int grl_color_jitter_num_workgroups(int32_t max_h, int32_t max_w);
+int grl_color_jitter(void* stream, const GrlColorJitterArgs* args);
 
 /* Debug aid (ABI 21; no reference counterpart): fills the LDS of every CU with 0xFF bytes (fp32 / fp16 NaN) by a launch on
  * `stream`.  LDS keeps what the previous workgroup left in it; a kernel that reads LDS it has not written is otherwise right or
