@@ -41,6 +41,8 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+from . import item_lists
+
 INTER_LINEAR, INTER_CUBIC, INTER_AREA = 1, 2, 3
 STAGES = tuple(range(9))
 KMAX = 31
@@ -113,24 +115,12 @@ def resize_taps(interp: int, h: int, w: int, ho: int, wo: int):
     return (4, 4) if mode == "cubic" else (2, 2)
 
 
-def _check_images(imgs, what):
-    if len(imgs) < 1:
-        raise ValueError(f"{what}: no images")
-    for im in imgs:
-        if not torch.is_tensor(im) or im.dim() != 3 or im.shape[0] != imgs[0].shape[0] or im.shape[0] not in (1, 3) or min(im.shape) < 1:
-            raise ValueError(f"{what}: a list of (C, h, w) tensors with one C of 1 or 3")
-        if im.device != imgs[0].device or im.dtype != imgs[0].dtype:
-            raise ValueError(f"{what}: the images share one device and dtype")
-    if imgs[0].is_cuda and imgs[0].dtype != torch.float32:
-        raise TypeError(f"{what} takes fp32 CUDA tensors, got {imgs[0].dtype}")
-
-
 def cv_resize(imgs: Sequence[torch.Tensor], sizes: Sequence, interps: Sequence[int]) -> List[torch.Tensor]:
     """``cv2.resize(img, (wo, ho), interpolation=interp)`` for every image of a list: ``imgs[i]`` (C, h, w) -> (C, *sizes[i]) with
     ``sizes[i] = (ho, wo)`` and ``interps[i]`` 1, 2 or 3.  CUDA (fp32): one ``grl_cv_resize`` launch.  CPU: float64 weights and sums,
     the result in the input's dtype."""
     imgs = list(imgs)
-    _check_images(imgs, "cv_resize")
+    item_lists.check_images(imgs, "cv_resize")
     sizes = [(int(s[0]), int(s[1])) for s in sizes]
     interps = [int(i) for i in interps]
     if len(sizes) != len(imgs) or len(interps) != len(imgs):
@@ -140,14 +130,11 @@ def cv_resize(imgs: Sequence[torch.Tensor], sizes: Sequence, interps: Sequence[i
         raise ValueError("cv_resize: sizes are positive")
     if imgs[0].is_cuda:
         Cn = imgs[0].shape[0]
-        src = torch.cat([im.reshape(-1) for im in imgs])
-        dst = torch.empty(sum(Cn * ho * wo for ho, wo in sizes), dtype=torch.float32, device=src.device)
-        items, so, do = [], 0, 0
-        for im, (ho, wo), ip in zip(imgs, sizes, interps):
-            items.append((so, do, im.shape[1], im.shape[2], ho, wo, ip, 0))
-            so, do = so + im.numel(), do + Cn * ho * wo
-        hip_cv_resize(src, dst, items, Cn)
-        return [dst[it[1] : it[1] + Cn * it[4] * it[5]].view(Cn, it[4], it[5]) for it in items]
+        shapes = [(Cn, ho, wo) for ho, wo in sizes]
+        (src, so), (dst, do) = item_lists.pack(imgs), item_lists.empty(shapes, imgs[0].device)
+        hip_cv_resize(src, dst, [(a, d, im.shape[1], im.shape[2], ho, wo, ip, 0)
+                                 for a, d, im, (ho, wo), ip in zip(so, do, imgs, sizes, interps)], Cn)
+        return item_lists.views(dst, do, shapes)
     out = []
     for im, (ho, wo), mode in zip(imgs, sizes, modes):
         wy, wx = _axis_matrix(im.shape[1], ho, mode), _axis_matrix(im.shape[2], wo, mode)
@@ -155,21 +142,15 @@ def cv_resize(imgs: Sequence[torch.Tensor], sizes: Sequence, interps: Sequence[i
     return out
 
 
-def _items_tensor(items, device) -> torch.Tensor:
-    return torch.tensor(items, dtype=torch.int64).reshape(-1, 8).to(device)
+_items_tensor = item_lists.table
 
 
 def hip_cv_resize(src: torch.Tensor, dst: torch.Tensor, items, Cn: int) -> None:
     """One ``grl_cv_resize`` launch.  ``src`` / ``dst``: flat fp32 CUDA arenas (they may be one tensor); ``items``: host tuples
     (src_off, dst_off, h, w, ho, wo, interp, 0).  This wrapper is what vouches for the item list: the grid maxima are taken from
     the items themselves, and the callers hand out disjoint destinations."""
-    from . import _lib
-
-    t = _items_tensor(items, src.device)
-    args = _lib.GrlCvResizeArgs(src=src.data_ptr(), dst=dst.data_ptr(), src_elems=src.numel(), dst_elems=dst.numel(),
-                                items=t.data_ptr(), n_items=len(items), C=Cn, max_ho=max(it[4] for it in items),
-                                max_wo=max(it[5] for it in items))
-    _lib.launch("grl_cv_resize", args)
+    item_lists.launch("grl_cv_resize", src, dst, _items_tensor(items, src.device), C=Cn, max_ho=max(it[4] for it in items),
+                      max_wo=max(it[5] for it in items))
 
 
 # ---- blur -------------------------------------------------------------------------------------------------------------------------
@@ -188,7 +169,7 @@ def blur_items(imgs: Sequence[torch.Tensor], taps: Sequence[torch.Tensor], strid
     them -- and ``strides[i] >= 1``; (C, h, w) -> (C, ceil(h / s), ceil(w / s)).  CUDA (fp32 images and taps): one ``grl_blur_items``
     launch, an fp32 fmaf chain per output.  CPU: float64 sums, the result in the input's dtype."""
     imgs, taps = list(imgs), list(taps)
-    _check_images(imgs, "blur_items")
+    item_lists.check_images(imgs, "blur_items")
     strides = [int(s) for s in strides]
     if len(taps) != len(imgs) or len(strides) != len(imgs):
         raise ValueError("blur_items: one tap table and one stride per image")
@@ -201,16 +182,11 @@ def blur_items(imgs: Sequence[torch.Tensor], taps: Sequence[torch.Tensor], strid
         Cn, dev = imgs[0].shape[0], imgs[0].device
         if any(t.dtype != torch.float32 for t in taps):
             raise TypeError("grl_blur_items takes fp32 taps")
-        src = torch.cat([im.reshape(-1) for im in imgs])
-        tbuf = torch.cat([t.reshape(-1) for t in taps]).to(dev)
-        outs = [(-(-im.shape[1] // s), -(-im.shape[2] // s)) for im, s in zip(imgs, strides)]
-        dst = torch.empty(sum(Cn * ho * wo for ho, wo in outs), dtype=torch.float32, device=dev)
-        items, so, do, to = [], 0, 0, 0
-        for im, t, s, (ho, wo) in zip(imgs, taps, strides, outs):
-            items.append((so, do, im.shape[1], im.shape[2], t.shape[0], s, to, 0))
-            so, do, to = so + im.numel(), do + Cn * ho * wo, to + t.numel()
-        hip_blur_items(src, dst, tbuf, items, Cn)
-        return [dst[it[1] : it[1] + Cn * ho * wo].view(Cn, ho, wo) for it, (ho, wo) in zip(items, outs)]
+        shapes = [(Cn, -(-im.shape[1] // s), -(-im.shape[2] // s)) for im, s in zip(imgs, strides)]
+        (src, so), (tbuf, to), (dst, do) = item_lists.pack(imgs), item_lists.pack(taps), item_lists.empty(shapes, dev)
+        hip_blur_items(src, dst, tbuf.to(dev), [(a, d, im.shape[1], im.shape[2], t.shape[0], s, k, 0)
+                                                for a, d, k, im, t, s in zip(so, do, to, imgs, taps, strides)], Cn)
+        return item_lists.views(dst, do, shapes)
     out = []
     for im, t, s in zip(imgs, taps, strides):
         Cn, h, w = im.shape
@@ -228,14 +204,9 @@ def hip_blur_items(src: torch.Tensor, dst: torch.Tensor, taps: torch.Tensor, ite
     """One ``grl_blur_items`` launch.  ``src`` / ``dst``: flat fp32 CUDA arenas (they may be one tensor), ``taps``: the flat fp32 taps
     buffer on that device; ``items``: host tuples (src_off, dst_off, h, w, K, s, taps_off, 0).  As ``hip_cv_resize``, this wrapper
     vouches for the list: the maxima come from the items, the callers hand out disjoint destinations."""
-    from . import _lib
-
-    t = _items_tensor(items, src.device)
-    args = _lib.GrlBlurItemsArgs(src=src.data_ptr(), dst=dst.data_ptr(), taps=taps.data_ptr(), src_elems=src.numel(),
-                                 dst_elems=dst.numel(), taps_elems=taps.numel(), items=t.data_ptr(), n_items=len(items), C=Cn,
-                                 max_ho=max(-(-it[2] // it[5]) for it in items), max_wo=max(-(-it[3] // it[5]) for it in items),
-                                 max_K=max(it[4] for it in items))
-    _lib.launch("grl_blur_items", args)
+    item_lists.launch("grl_blur_items", src, dst, _items_tensor(items, src.device), taps=taps.data_ptr(), taps_elems=taps.numel(), C=Cn,
+                      max_ho=max(-(-it[2] // it[5]) for it in items), max_wo=max(-(-it[3] // it[5]) for it in items),
+                      max_K=max(it[4] for it in items))
 
 
 # ---- the blur kernels (host, float64) ---------------------------------------------------------------------------------------------
@@ -488,36 +459,38 @@ class _Arenas:
         self.side[b], self.size[b] = 1 - self.side[b], size
 
 
-def _run_resize(ar: _Arenas, group):
-    items = [(ar.offset(b, ar.side[b]), ar.offset(b, 1 - ar.side[b]), ar.size[b], ar.size[b], op["size"], op["size"], op["interp"], 0)
-             for b, op in group]
+def _run_items(ar: _Arenas, group, on_device, on_host):
+    """One image op for the samples of ``group``, each from its side of the arenas into the other.  CUDA: ``on_device(heads)`` with
+    the items' (src_off, dst_off, h, w).  CPU: ``on_host(images)`` returns the results, which are copied over.  Then the samples
+    have moved."""
     if ar.buf.is_cuda:
-        hip_cv_resize(ar.flat, ar.flat, items, ar.C)
+        on_device([(ar.offset(b, ar.side[b]), ar.offset(b, 1 - ar.side[b]), ar.size[b], ar.size[b]) for b, _ in group])
     else:
-        outs = cv_resize([ar.view(b) for b, _ in group], [(op["size"],) * 2 for _, op in group], [op["interp"] for _, op in group])
-        for (b, op), o in zip(group, outs):
+        for (b, op), o in zip(group, on_host([ar.view(b) for b, _ in group])):
             ar.view(b, 1 - ar.side[b], op["size"]).copy_(o)
     for b, op in group:
         ar.moved(b, op["size"])
+
+
+def _run_resize(ar: _Arenas, group):
+    sizes, interps = [op["size"] for _, op in group], [op["interp"] for _, op in group]
+    _run_items(ar, group,
+               lambda heads: hip_cv_resize(ar.flat, ar.flat, [(*hd, n, n, ip, 0) for hd, n, ip in zip(heads, sizes, interps)], ar.C),
+               lambda imgs: cv_resize(imgs, [(n, n) for n in sizes], interps))
 
 
 def _run_blur(ar: _Arenas, group):
-    taps = [_taps32(op["kernel"]) for _, op in group]
-    for (b, op), t in zip(group, taps):
+    taps, strides = [_taps32(op["kernel"]) for _, op in group], [op["stride"] for _, op in group]
+    for b, op in group:
         if -(-ar.size[b] // op["stride"]) != op["size"]:
             raise ValueError(f"plan: a stride-{op['stride']} blur of side {ar.size[b]} does not give side {op['size']}")
-    if ar.buf.is_cuda:
-        items, to = [], 0
-        for (b, op), t in zip(group, taps):
-            items.append((ar.offset(b, ar.side[b]), ar.offset(b, 1 - ar.side[b]), ar.size[b], ar.size[b], t.shape[0], op["stride"], to, 0))
-            to += t.numel()
-        hip_blur_items(ar.flat, ar.flat, torch.cat([t.reshape(-1) for t in taps]).to(ar.buf.device), items, ar.C)
-    else:
-        outs = blur_items([ar.view(b) for b, _ in group], taps, [op["stride"] for _, op in group])
-        for (b, op), o in zip(group, outs):
-            ar.view(b, 1 - ar.side[b], op["size"]).copy_(o)
-    for b, op in group:
-        ar.moved(b, op["size"])
+
+    def on_device(heads):
+        tbuf, to = item_lists.pack(taps)
+        hip_blur_items(ar.flat, ar.flat, tbuf.to(ar.buf.device),
+                       [(*hd, t.shape[0], s, k, 0) for hd, t, s, k in zip(heads, taps, strides, to)], ar.C)
+
+    _run_items(ar, group, on_device, lambda imgs: blur_items(imgs, taps, strides))
 
 
 def _camera_normals(gen, side: int, device) -> torch.Tensor:
@@ -536,14 +509,10 @@ def _run_camera(ar: _Arenas, group, gen, hr):
         raise ValueError(f"plan: the camera stage needs sides of at least {isp.MIN_SIDE}")
     z = [_camera_normals(gen, ar.size[b], ar.buf.device) for b, _ in group]
     if ar.buf.is_cuda:
-        fwd, back, zo = [], [], 0
-        for b, _ in group:
-            n, here, there = ar.size[b], ar.offset(b, ar.side[b]), ar.offset(b, 1 - ar.side[b])
-            fwd.append((here, there, n, n, zo))
-            back.append((there, here, n, n, 0))
-            zo += n * n
-        isp.hip_isp("grl_isp_unprocess", ar.flat, ar.flat, fwd, params, torch.cat([n.reshape(-1) for n in z]))
-        isp.hip_isp("grl_isp_process", ar.flat, ar.flat, back, params)
+        heads = [(ar.offset(b, ar.side[b]), ar.offset(b, 1 - ar.side[b]), ar.size[b]) for b, _ in group]
+        normals, zo = item_lists.pack(z)
+        isp.hip_isp("grl_isp_unprocess", ar.flat, ar.flat, [(here, there, n, n, o) for (here, there, n), o in zip(heads, zo)], params, normals)
+        isp.hip_isp("grl_isp_process", ar.flat, ar.flat, [(there, here, n, n, 0) for here, there, n in heads], params)
         if hr is not None:
             S, flat = hr.shape[2], hr.view(-1)
             isp.hip_isp("grl_isp_roundtrip", flat, flat, [(b * 3 * S * S, b * 3 * S * S, S, S, 0) for b, _ in group], params)

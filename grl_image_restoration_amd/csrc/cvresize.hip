@@ -2,9 +2,7 @@
 // grl_cv_resize): the ``cv2.resize(img, (wo, ho), interpolation=random.choice([1, 2, 3]))`` calls of the reference's blind-SR
 // degradation (utils/utils_bsr/utils_sisr.py:299-303, 350-354, 416-420), for every sample of a batch in one launch.
 //
-// Item list (device memory, read by the kernel): per item eight int64 -- src_off, dst_off, h, w, ho, wo, interp, 0.  The source is
-// contiguous fp32 (C, h, w) at element src_off of the source arena, the result contiguous (C, ho, wo) at dst_off of the destination
-// arena.  Per axis, with scale = n / no, coordinates and weights in float64, every weight rounded once to fp32:
+// Item list (item_list.h states the shared contract): the entry's slots are ho, wo, interp, 0; (C, h, w) -> (C, ho, wo).  Per axis, with scale = n / no, coordinates and weights in float64, every weight rounded once to fp32:
 //   linear  f = (d + 0.5) scale - 0.5, i = floor(f), t = f - i; i < 0: i = 0, t = 0; i >= n - 1: i = n - 1, t = 0; taps i, i + 1
 //           with 1 - t, t
 //   cubic   the same f, i, t without the clamps of t; taps i - 1 .. i + 2 with OpenCV's A = -0.75 coefficients
@@ -19,14 +17,12 @@
 // is OpenCV's sampling rule with float64 coordinates; OpenCV rounds the coordinate to fp32 first, which moves a weight by up to
 // n * 2^-24, so equality with OpenCV's bytes is not claimed.
 //
-// Shape: the grid is (tiles of the largest output the host vouches for) x (items); a workgroup of 256 threads owns a 16 x 16 output
-// tile of one item, a thread one output position for all channels.  Workgroups beyond an item's own output leave at once.  The taps
+// Shape: a workgroup of 256 threads owns a 16 x 16 output tile of one item, a thread one output position for all channels.  The taps
 // of a thread are three numbers per axis (first index, count, and the weights: four explicit ones for linear / cubic, or the
 // left / middle / right weight of the area table), computed once per thread.  The images are small (at most 3 x 400 x 400 in the
-// pipeline) and stay in L2; the design point is many small items in one launch.  Every item is checked against the two arena
-// lengths before anything is read or written, so no list content can make the kernel touch memory outside the arenas; an item's
-// result depends on nothing but the item.
+// pipeline) and stay in L2; the design point is many small items in one launch.  An item's result depends on nothing but the item.
 #include "common.h"
+#include "item_list.h"
 
 namespace {
 
@@ -126,17 +122,19 @@ __device__ __forceinline__ float tap_chain(const Taps& t, F f) {
 }
 
 __global__ __launch_bounds__(NT) void cv_resize_kernel(Params p) {
-    const int64_t* it = p.items + 8 * (int64_t)blockIdx.y;
-    const int64_t src_off = it[0], dst_off = it[1], h64 = it[2], w64 = it[3], ho64 = it[4], wo64 = it[5], interp = it[6];
+    namespace il = item_list;
+    const int64_t* it = il::row(p.items, blockIdx.y);
+    const int64_t src_off = it[il::SRC_OFF], dst_off = it[il::DST_OFF], h64 = it[il::H], w64 = it[il::W];
+    const int64_t ho64 = it[il::SLOT], wo64 = it[il::SLOT + 1], interp = it[il::SLOT + 2];
     // an item the arenas cannot hold, or with sizes / a mode out of range, is skipped whole (wave-uniform: the item is per workgroup)
-    if (h64 < 1 || w64 < 1 || ho64 < 1 || wo64 < 1 || h64 > (1 << 20) || w64 > (1 << 20) || ho64 > (1 << 20) || wo64 > (1 << 20)) return;
+    if (!il::side_ok(h64) || !il::side_ok(w64) || !il::side_ok(ho64) || !il::side_ok(wo64)) return;
     if (interp < 1 || interp > 3) return;
-    if (src_off < 0 || dst_off < 0 || src_off + p.C * h64 * w64 > p.src_elems || dst_off + p.C * ho64 * wo64 > p.dst_elems) return;
+    if (!il::fits(src_off, p.C * h64 * w64, p.src_elems) || !il::fits(dst_off, p.C * ho64 * wo64, p.dst_elems)) return;
     const int h = (int)h64, w = (int)w64, ho = (int)ho64, wo = (int)wo64;
 
-    const int ty = blockIdx.x / p.ntx, tx = blockIdx.x - ty * p.ntx;
-    if (ty * TS >= ho || tx * TS >= wo) return;                       // a surplus workgroup of a smaller item
-    const int oy = ty * TS + threadIdx.x / TS, ox = tx * TS + threadIdx.x % TS;
+    const il::Tile tile = il::tile_of_block(p.ntx, TS, TS);
+    if (tile.surplus(ho, wo)) return;
+    const int oy = tile.y0 + threadIdx.x / TS, ox = tile.x0 + threadIdx.x % TS;
     if (oy >= ho || ox >= wo) return;
 
     int my, mx;
@@ -158,18 +156,14 @@ __global__ __launch_bounds__(NT) void cv_resize_kernel(Params p) {
 }  // namespace
 
 extern "C" int grl_cv_resize(void* stream, const GrlCvResizeArgs* a) {
-    if (!a || !a->src || !a->dst || !a->items) return GRL_ERR_BAD_ARG;
-    if (a->C != 1 && a->C != 3) return GRL_ERR_BAD_ARG;
-    if (a->n_items <= 0 || a->max_ho <= 0 || a->max_wo <= 0 || a->src_elems <= 0 || a->dst_elems <= 0) return GRL_ERR_BAD_ARG;
-    if (a->max_ho > (1 << 20) || a->max_wo > (1 << 20) || a->n_items > 65535) return GRL_ERR_BAD_ARG;
-    if ((uint64_t)a->src % 4 || (uint64_t)a->dst % 4 || (uint64_t)a->items % 8) return GRL_ERR_BAD_ARG;
-    const int64_t ntx = (a->max_wo + TS - 1) / TS, nty = (a->max_ho + TS - 1) / TS;
-    if (ntx * nty > 0x7fffffff) return GRL_ERR_BAD_ARG;
+    if (!a || (a->C != 1 && a->C != 3)) return GRL_ERR_BAD_ARG;
+    item_list::Grid g;
+    if (int e = item_list::check_tiled(*a, a->max_ho, a->max_wo, TS, TS, g)) return e;
 
     Params p;
     p.src = a->src; p.dst = a->dst; p.items = a->items; p.src_elems = a->src_elems; p.dst_elems = a->dst_elems;
-    p.C = a->C; p.ntx = (int32_t)ntx; p.nty = (int32_t)nty;
-    hipLaunchKernelGGL(cv_resize_kernel, dim3((unsigned)(ntx * nty), (unsigned)a->n_items), dim3(NT), 0, (hipStream_t)stream, p);
+    p.C = a->C; p.ntx = g.ntx; p.nty = g.nty;
+    hipLaunchKernelGGL(cv_resize_kernel, dim3(g.tiles(), (unsigned)a->n_items), dim3(NT), 0, (hipStream_t)stream, p);
     GRL_CHECK_LAUNCH();
     return 0;
 }

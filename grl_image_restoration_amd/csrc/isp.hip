@@ -4,7 +4,7 @@
 // utils_noise.py:95-103, ``ISPNet.forward`` (431-443) with the Malvar ``Demosaic`` (215-292) -- for every acting sample of a batch
 // in one launch per entry.
 //
-// Item list (device memory, read by the kernels): per item eight int64 -- src_off, dst_off, h, w, yi_off, yi_inv_off, z_off, 0 -- and
+// Item list (item_list.h states the shared contract): the entries' slots are yi_off, yi_inv_off, z_off, 0, and every item has
 // a record of REC = 40 floats in `params`: W1i, W2i, W2, W1 (3 x 3 each, row major), 2^e, 2^-e, shot, read.  The arithmetic of every
 // step is stated in the header.  All of it is fp32; clamp is to [0, 1] and sends NaN to 0, so every table index lies in the table.
 //
@@ -14,19 +14,19 @@
 // its 2-pixel halo is staged in LDS already reflected (36 x 36 floats, pitch 37), a thread owns one 2 x 2 lattice quad -- so every
 // lane runs the same four stencils and no wave diverges on pixel parity --, walks the colour chain for its four pixels and parks
 // the twelve results in a second LDS image (3 x 32 x 33), from which the workgroup stores rows of 32 contiguous floats, leaving out
-// the pixels an odd border does not have.  The grid is (tiles of the largest item the host vouches for) x items; surplus
-// workgroups leave.  Every item is checked against the arena, table and normals lengths before anything is read or written, and
-// every pixel index is folded into the image: no list content can make the kernels touch memory outside the buffers.
+// the pixels an odd border does not have.  The tone tables and the normals are checked against tables_elems / normals_elems as
+// the images against the arenas, and every pixel index is folded into the image.
 #include <math.h>
 
 #include "common.h"
+#include "item_list.h"
 
 namespace {
 
 constexpr int NT = 256, PW = 64, PH = 4;                                   // per-pixel kernels: 64 x 4 pixels per workgroup
 constexpr int QT = 16, TP = 2 * QT, SIDE = TP + 4, PITCH = SIDE + 1;       // demosaic: 16 x 16 quads, 36 x 36 staged
 constexpr int OPITCH = TP + 1;
-constexpr int REC = 40, TABLE_N = 1000001;
+constexpr int REC = 40, TABLE_N = 1000001, MIN_SIDE = 3;                    // the demosaic reflects by 2
 constexpr int W1I = 0, W2I = 9, W2 = 18, W1 = 27, P2E = 36, SHOT = 38, READ = 39;
 
 struct Params {
@@ -50,12 +50,14 @@ struct Item {
 
 // an item the buffers cannot hold, or with a side out of range, is skipped whole (uniform over the workgroup)
 __device__ __forceinline__ bool load_item(const Params& p, int item, int src_planes, int dst_planes, bool noisy, Item& it) {
-    const int64_t* t = p.items + 8 * (int64_t)item;
-    const int64_t src_off = t[0], dst_off = t[1], h = t[2], w = t[3], yi = t[4], yi_inv = t[5], z = t[6];
-    if (h < 3 || w < 3 || h > (1 << 20) || w > (1 << 20)) return false;
-    if (src_off < 0 || dst_off < 0 || src_off + src_planes * h * w > p.src_elems || dst_off + dst_planes * h * w > p.dst_elems) return false;
-    if (yi < 0 || yi_inv < 0 || yi + TABLE_N > p.tables_elems || yi_inv + TABLE_N > p.tables_elems) return false;
-    if (noisy && (z < 0 || z + h * w > p.normals_elems)) return false;
+    namespace il = item_list;
+    const int64_t* t = il::row(p.items, item);
+    const int64_t src_off = t[il::SRC_OFF], dst_off = t[il::DST_OFF], h = t[il::H], w = t[il::W];
+    const int64_t yi = t[il::SLOT], yi_inv = t[il::SLOT + 1], z = t[il::SLOT + 2];
+    if (!il::side_ok(h, MIN_SIDE) || !il::side_ok(w, MIN_SIDE)) return false;
+    if (!il::fits(src_off, src_planes * h * w, p.src_elems) || !il::fits(dst_off, dst_planes * h * w, p.dst_elems)) return false;
+    if (!il::fits(yi, TABLE_N, p.tables_elems) || !il::fits(yi_inv, TABLE_N, p.tables_elems)) return false;
+    if (noisy && !il::fits(z, h * w, p.normals_elems)) return false;
     it.src_off = src_off; it.dst_off = dst_off; it.z_off = z;
     it.yi = p.tables + yi; it.yi_inv = p.tables + yi_inv;
     it.rec = p.params + (int64_t)REC * item;
@@ -108,9 +110,9 @@ __device__ __forceinline__ void from_camera(const Item& it, float x[3]) {
 }
 
 __device__ __forceinline__ bool pixel_of_tile(const Params& p, const Item& it, int& y, int& x) {
-    const int tyb = blockIdx.x / p.ntx, txb = blockIdx.x - tyb * p.ntx;
-    y = tyb * PH + threadIdx.x / PW;
-    x = txb * PW + threadIdx.x % PW;
+    const item_list::Tile tile = item_list::tile_of_block(p.ntx, PH, PW);
+    y = tile.y0 + threadIdx.x / PW;
+    x = tile.x0 + threadIdx.x % PW;
     return y < it.h && x < it.w;
 }
 
@@ -158,9 +160,9 @@ __global__ __launch_bounds__(NT) void isp_process_kernel(Params p) {
 
     Item it;
     if (!load_item(p, blockIdx.y, 1, 3, false, it)) return;
-    const int tyb = blockIdx.x / p.ntx, txb = blockIdx.x - tyb * p.ntx;
-    const int y0 = tyb * TP, x0 = txb * TP;
-    if (y0 >= it.h || x0 >= it.w) return;                              // a surplus workgroup of a smaller item
+    const item_list::Tile tl = item_list::tile_of_block(p.ntx, TP, TP);
+    if (tl.surplus(it.h, it.w)) return;
+    const int y0 = tl.y0, x0 = tl.x0;
     const int h = it.h, w = it.w;
 
     const float* raw = p.src + it.src_off;
@@ -217,21 +219,16 @@ __global__ __launch_bounds__(NT) void isp_process_kernel(Params p) {
 
 // what the host can see; 0 with the grid's tile counts, else the error
 int check(const GrlIspArgs* a, bool noisy, int tw, int th, Params& p) {
-    if (!a || !a->src || !a->dst || !a->items || !a->params || !a->tables || (noisy && !a->normals)) return GRL_ERR_BAD_ARG;
-    if (a->C != 3) return GRL_ERR_BAD_ARG;
-    if (a->n_items <= 0 || a->n_items > 65535 || a->src_elems <= 0 || a->dst_elems <= 0 || a->tables_elems < TABLE_N ||
-        (noisy && a->normals_elems <= 0))
-        return GRL_ERR_BAD_ARG;
-    if (a->max_h < 3 || a->max_w < 3 || a->max_h > (1 << 20) || a->max_w > (1 << 20)) return GRL_ERR_BAD_ARG;
-    if ((uint64_t)a->src % 4 || (uint64_t)a->dst % 4 || (uint64_t)a->params % 4 || (uint64_t)a->tables % 4 || (uint64_t)a->normals % 4 ||
-        (uint64_t)a->items % 8)
-        return GRL_ERR_BAD_ARG;
-    const int64_t ntx = (a->max_w + tw - 1) / tw, nty = (a->max_h + th - 1) / th;
-    if (ntx * nty > 0x7fffffff) return GRL_ERR_BAD_ARG;
+    if (!a || a->C != 3) return GRL_ERR_BAD_ARG;
+    item_list::Grid g;
+    if (int e = item_list::check_tiled(*a, a->max_h, a->max_w, th, tw, g, MIN_SIDE)) return e;
+    if (!a->params || !a->tables || (noisy && !a->normals)) return GRL_ERR_BAD_ARG;
+    if (a->tables_elems < TABLE_N || (noisy && a->normals_elems <= 0)) return GRL_ERR_BAD_ARG;
+    if ((uintptr_t)a->params % 4 || (uintptr_t)a->tables % 4 || (uintptr_t)a->normals % 4) return GRL_ERR_BAD_ARG;
     p.src = a->src; p.dst = a->dst; p.items = a->items; p.params = a->params; p.tables = a->tables; p.normals = a->normals;
     p.src_elems = a->src_elems; p.dst_elems = a->dst_elems; p.tables_elems = a->tables_elems;
     p.normals_elems = noisy ? a->normals_elems : 0;
-    p.ntx = (int32_t)ntx; p.nty = (int32_t)nty;
+    p.ntx = g.ntx; p.nty = g.nty;
     return 0;
 }
 

@@ -2,24 +2,25 @@
 // ``ColorJitter.forward`` on float RGB in [0, 1] -- adjust_brightness, adjust_contrast, adjust_saturation, adjust_hue in a drawn
 // order -- as the reference applies it to every GT crop (data/datasets/restoration_bsr.py:66-68,100), for a whole batch in one call.
 //
-// Item list (device memory, read by the kernels): per item eight int64 -- src_off, dst_off, h, w, and the four ops in the order they
-// run (0 brightness, 1 contrast, 2 saturation, 3 hue) -- and a record of four floats in `params`: b, c, s, h.  The arithmetic is
+// Item list (item_list.h states the shared contract): the entry's slots are the four ops in the order they run (0 brightness,
+// 1 contrast, 2 saturation, 3 hue), and every item has a record of four floats in `params`: b, c, s, h.  The arithmetic is
 // stated in the header; all of it is fp32 but the sum behind the contrast mean, which is fp64 from the pixel on.
 //
 // Shape.  The three planes of an image are contiguous, so the image is walked as n = h * w pixels: rows follow each other in
 // memory, and a wave reads 64 (or 256) consecutive pixels of each plane.  A workgroup of 256 threads owns SPAN = 4096 consecutive
-// pixels; the grid is (workgroups of the largest item the host vouches for) x items, surplus workgroups leave, and the op order
-// is uniform over a workgroup.  Where n, both offsets and both arena pointers are multiples of 4 elements a thread moves float4s
-// (4 steps of 1024 pixels per workgroup, all twelve loads in flight before the first chain starts), else scalars (16 steps of 256).  The contrast mean needs the whole image as it stands
+// pixels (the grid's first axis counts such spans, not tiles), and the op order is uniform over a workgroup.  Where n, both
+// offsets and both arena pointers are multiples of 4 elements a thread moves float4s (4 steps of 1024 pixels per workgroup, all
+// twelve loads in flight before the first chain starts), else scalars (16 steps of 256).  The contrast mean needs the whole image as it stands
 // when contrast runs, so the entry is two launches: pass 1 walks the ops that precede contrast and sums gray(x) -- per thread,
 // over the wave by shuffles, over the four waves through LDS -- into one fp64 partial per (item, workgroup); pass 2 adds the
 // item's partials in a fixed order (every workgroup the same way: a strided sum per thread, then the same wave / LDS tree),
 // workgroup 0 writes the mean, and every thread walks the whole chain for its pixels, reading a pixel's three channels before it
 // writes them.  No atomics: the result of an item is a function of its own record, its pixels and the alignment of its planes.
-// Every item is checked against the arenas and the partial buffer before anything is read or written.
+// An item with more pixels than the grid has workgroups for (and the partial buffer slots) is skipped like one that does not fit.
 #include <math.h>
 
 #include "common.h"
+#include "item_list.h"
 
 namespace {
 
@@ -47,16 +48,17 @@ struct Item {
 // an item the buffers cannot hold, with a side out of range, with an order that is no permutation, or with more pixels than the
 // grid has workgroups for, is skipped whole (uniform over the workgroup)
 __device__ __forceinline__ bool load_item(const Params& p, int item, Item& it) {
-    const int64_t* t = p.items + 8 * (int64_t)item;
-    const int64_t src_off = t[0], dst_off = t[1], h = t[2], w = t[3];
-    if (h < 1 || w < 1 || h > (1 << 20) || w > (1 << 20)) return false;
+    namespace il = item_list;
+    const int64_t* t = il::row(p.items, item);
+    const int64_t src_off = t[il::SRC_OFF], dst_off = t[il::DST_OFF], h = t[il::H], w = t[il::W];
+    if (!il::side_ok(h) || !il::side_ok(w)) return false;
     const int64_t n = h * w;
-    if (src_off < 0 || dst_off < 0 || src_off > p.src_elems - 3 * n || dst_off > p.dst_elems - 3 * n) return false;
+    if (!il::fits(src_off, 3 * n, p.src_elems) || !il::fits(dst_off, 3 * n, p.dst_elems)) return false;
     if ((n + SPAN - 1) / SPAN > p.nwg) return false;
     int order = 0, seen = 0;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        const int64_t op = t[4 + k];
+        const int64_t op = t[il::SLOT + k];
         if (op < 0 || op > 3) return false;
         order |= (int)op << (2 * k);
         seen |= 1 << (int)op;
@@ -209,7 +211,7 @@ __global__ __launch_bounds__(NT) void jitter_apply_kernel(Params p) {
 }
 
 int64_t workgroups(int64_t max_h, int64_t max_w) {
-    if (max_h < 1 || max_w < 1 || max_h > (1 << 20) || max_w > (1 << 20)) return GRL_ERR_BAD_ARG;
+    if (!item_list::side_ok(max_h) || !item_list::side_ok(max_w)) return GRL_ERR_BAD_ARG;
     return (max_h * max_w + SPAN - 1) / SPAN;          // at most 2^28
 }
 
@@ -218,14 +220,12 @@ int64_t workgroups(int64_t max_h, int64_t max_w) {
 extern "C" int grl_color_jitter_num_workgroups(int32_t max_h, int32_t max_w) { return (int)workgroups(max_h, max_w); }
 
 extern "C" int grl_color_jitter(void* stream, const GrlColorJitterArgs* a) {
-    if (!a || !a->src || !a->dst || !a->items || !a->params || !a->partial || !a->means) return GRL_ERR_BAD_ARG;
-    if (a->C != 3 || a->n_items <= 0 || a->n_items > 65535 || a->src_elems <= 0 || a->dst_elems <= 0) return GRL_ERR_BAD_ARG;
+    if (!a || a->C != 3) return GRL_ERR_BAD_ARG;
+    if (int e = item_list::check_args(*a, a->max_h, a->max_w)) return e;
+    if (!a->params || !a->partial || !a->means) return GRL_ERR_BAD_ARG;
     const int64_t nwg = workgroups(a->max_h, a->max_w);
-    if (nwg < 0) return GRL_ERR_BAD_ARG;
     if (a->n_partial < nwg * a->n_items) return GRL_ERR_BAD_ARG;
-    if ((uintptr_t)a->src % 4 || (uintptr_t)a->dst % 4 || (uintptr_t)a->params % 4 || (uintptr_t)a->items % 8 || (uintptr_t)a->partial % 8 ||
-        (uintptr_t)a->means % 8)
-        return GRL_ERR_BAD_ARG;
+    if ((uintptr_t)a->params % 4 || (uintptr_t)a->partial % 8 || (uintptr_t)a->means % 8) return GRL_ERR_BAD_ARG;
     Params p;
     p.src = a->src; p.dst = a->dst; p.items = a->items; p.params = a->params; p.partial = a->partial; p.means = a->means;
     p.src_elems = a->src_elems; p.dst_elems = a->dst_elems; p.nwg = (int32_t)nwg;

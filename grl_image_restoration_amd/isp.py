@@ -19,6 +19,8 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+from . import item_lists
+
 CAMERAS = ("canon_eos_1d_mark_ii", "canon_eos_5d_mark_iii", "canon", "canon_eos_6d_v1", "huawei_p20", "huawei_p30", "huawei_v8",
            "nikon_d500", "nikon_d810", "nikon_d5600", "olympus_em1")                      # ISPModel.CameraType, utils_isp.py:465-477
 CURVES = (0, 1, 2, 66, 126, 115, 127, 128, 132, 133, 74)                                  # rows of tonecurves.mat, utils_isp.py:502-504
@@ -195,32 +197,15 @@ def hip_isp(entry: str, src: torch.Tensor, dst: torch.Tensor, items, params: Seq
     (they may be one tensor); ``items``: host tuples (src_off, dst_off, h, w, z_off) -- the table offsets come from the params;
     ``normals``: the flat fp32 normals on that device (unprocess).  As ``bsr_degrade.hip_cv_resize``, this wrapper vouches for the
     list: the maxima come from the items, the callers hand out disjoint destinations."""
-    from . import _lib
-
     tables = params[0].bank.tables(src.device)
     if any(p.bank is not params[0].bank for p in params):
         raise ValueError("hip_isp: the params of one call come from one bank")
     rows = [(so, do, h, w, 2 * p.curve * TABLE_N, (2 * p.curve + 1) * TABLE_N, zo, 0) for (so, do, h, w, zo), p in zip(items, params)]
-    t = torch.tensor(rows, dtype=torch.int64).reshape(-1, 8).to(src.device)
     recs = torch.stack([p.rec for p in params]).to(src.device)
-    args = _lib.GrlIspArgs(src=src.data_ptr(), dst=dst.data_ptr(), src_elems=src.numel(), dst_elems=dst.numel(), items=t.data_ptr(),
-                           params=recs.data_ptr(), tables=tables.data_ptr(), tables_elems=tables.numel(),
-                           normals=normals.data_ptr() if normals is not None else None,
-                           normals_elems=normals.numel() if normals is not None else 0, n_items=len(rows), C=3,
-                           max_h=max(r[2] for r in rows), max_w=max(r[3] for r in rows))
-    _lib.launch(entry, args)
-
-
-def _check(imgs, what):
-    for im in imgs:
-        if not torch.is_tensor(im) or im.dim() != 3 or im.shape[0] != 3:
-            raise ValueError(f"camera_noise: {what} is a list of (3, h, w) tensors")
-        if im.device != imgs[0].device or im.dtype != imgs[0].dtype:
-            raise ValueError(f"camera_noise: {what} share one device and dtype")
-        if min(im.shape[1:]) < MIN_SIDE:
-            raise ValueError(f"camera_noise: the demosaic reflects by 2, so a side is at least {MIN_SIDE}; got {tuple(im.shape[1:])}")
-    if imgs and imgs[0].is_cuda and imgs[0].dtype != torch.float32:
-        raise TypeError(f"camera_noise takes fp32 CUDA tensors, got {imgs[0].dtype}")
+    item_lists.launch(entry, src, dst, item_lists.table(rows, src.device), params=recs.data_ptr(), tables=tables.data_ptr(),
+                      tables_elems=tables.numel(), normals=normals.data_ptr() if normals is not None else None,
+                      normals_elems=normals.numel() if normals is not None else 0, C=3,
+                      max_h=max(r[2] for r in rows), max_w=max(r[3] for r in rows))
 
 
 def camera_noise(imgs: Sequence[torch.Tensor], hr: Optional[Sequence[torch.Tensor]], params: Sequence[CameraParams],
@@ -233,9 +218,9 @@ def camera_noise(imgs: Sequence[torch.Tensor], hr: Optional[Sequence[torch.Tenso
     hr = None if hr is None else list(hr)
     if not imgs or len(params) != len(imgs) or len(z) != len(imgs) or (hr is not None and len(hr) != len(imgs)):
         raise ValueError("camera_noise: one params record, one normals plane (and one HR image) per image, at least one image")
-    _check(imgs, "the images")
+    item_lists.check_images(imgs, "camera_noise (the demosaic reflects by 2)", (3,), MIN_SIDE)
     if hr is not None:
-        _check(hr, "the HR images")
+        item_lists.check_images(hr, "camera_noise, the HR images (the demosaic reflects by 2)", (3,), MIN_SIDE)
     if any(n.shape != im.shape[1:] for n, im in zip(z, imgs)):
         raise ValueError("camera_noise: the normals of an image are (h, w)")
     if not imgs[0].is_cuda:
@@ -243,15 +228,10 @@ def camera_noise(imgs: Sequence[torch.Tensor], hr: Optional[Sequence[torch.Tenso
         return lq, (None if hr is None else [process(unprocess(im, p), p) for im, p in zip(hr, params)])
 
     def run(entry, tensors, planes_out, normals=None):
-        src = torch.cat([t.reshape(-1) for t in tensors])
-        items, so, do = [], 0, 0
-        for t in tensors:
-            h, w = t.shape[-2:]
-            items.append((so, do, h, w, do if normals is not None else 0))
-            so, do = so + t.numel(), do + planes_out * h * w
-        dst = torch.empty(do, dtype=torch.float32, device=src.device)
-        hip_isp(entry, src, dst, items, params, normals)
-        return [dst[it[1] : it[1] + planes_out * it[2] * it[3]].view(*((planes_out,) if planes_out > 1 else ()), it[2], it[3]) for it in items]
+        shapes = [((planes_out,) if planes_out > 1 else ()) + tuple(t.shape[-2:]) for t in tensors]
+        (src, so), (dst, do) = item_lists.pack(tensors), item_lists.empty(shapes, tensors[0].device)
+        hip_isp(entry, src, dst, [(a, d, *t.shape[-2:], d if normals is not None else 0) for a, d, t in zip(so, do, tensors)], params, normals)
+        return item_lists.views(dst, do, shapes)
 
-    raw = run("grl_isp_unprocess", imgs, 1, torch.cat([n.reshape(-1) for n in z]).float())
+    raw = run("grl_isp_unprocess", imgs, 1, item_lists.pack(z)[0].float())
     return run("grl_isp_process", raw, 3), (None if hr is None else run("grl_isp_roundtrip", hr, 3))

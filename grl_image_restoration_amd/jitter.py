@@ -19,6 +19,8 @@ from typing import List, Sequence, Tuple
 
 import torch
 
+from . import item_lists
+
 BRIGHTNESS, CONTRAST, SATURATION, HUE = 0, 1, 2, 3
 RANGES = ((0.8, 1.2), (0.8, 1.2), (0.8, 1.2), (-0.05, 0.05))          # b, c, s, h of the reference's ColorJitter
 JitterParams = Tuple[Tuple[int, int, int, int], float, float, float, float]
@@ -115,7 +117,7 @@ def _check_params(params: Sequence[JitterParams], n: int) -> None:
 
 def item_rows(items, params: Sequence[JitterParams]):
     """Host tuples (src_off, dst_off, h, w) and their parameter sets as the (n, 8) int64 item table and the (n, 4) fp32 factors."""
-    rows = torch.tensor([[so, do, h, w, *p[0]] for (so, do, h, w), p in zip(items, params)], dtype=torch.int64).reshape(-1, 8)
+    rows = item_lists.table([[so, do, h, w, *p[0]] for (so, do, h, w), p in zip(items, params)], "cpu")
     return rows, torch.tensor([list(p[1:]) for p in params], dtype=torch.float32).reshape(-1, 4)
 
 
@@ -132,12 +134,8 @@ def hip_color_jitter(src: torch.Tensor, dst: torch.Tensor, rows: torch.Tensor, f
     """One ``grl_color_jitter`` call.  ``src`` / ``dst``: flat fp32 CUDA arenas (they may be one tensor); ``rows`` / ``factors``: the
     device tables of ``item_rows``; ``partial`` / ``means``: fp64 device buffers of at least n * ``num_workgroups(max_h, max_w)`` and n
     elements.  The caller vouches for the list: ``max_h`` / ``max_w`` bound the items, the destinations are disjoint."""
-    from . import _lib
-
-    args = _lib.GrlColorJitterArgs(src=src.data_ptr(), dst=dst.data_ptr(), src_elems=src.numel(), dst_elems=dst.numel(),
-                                   items=rows.data_ptr(), params=factors.data_ptr(), partial=partial.data_ptr(),
-                                   n_partial=partial.numel(), means=means.data_ptr(), n_items=rows.shape[0], C=3, max_h=max_h, max_w=max_w)
-    _lib.launch("grl_color_jitter", args)
+    item_lists.launch("grl_color_jitter", src, dst, rows, params=factors.data_ptr(), partial=partial.data_ptr(), n_partial=partial.numel(),
+                      means=means.data_ptr(), C=3, max_h=max_h, max_w=max_w)
 
 
 def color_jitter(imgs: Sequence[torch.Tensor], params: Sequence[JitterParams], with_means: bool = False):
@@ -145,36 +143,21 @@ def color_jitter(imgs: Sequence[torch.Tensor], params: Sequence[JitterParams], w
     new tensors of the inputs' shapes; with ``with_means`` also the contrast means, a float64 tensor on the images' device.
     CUDA (fp32 only): one ``grl_color_jitter`` call.  CPU: the restatement in the tensors' dtype."""
     imgs, params = list(imgs), list(params)
-    if not imgs:
-        raise ValueError("color_jitter: at least one image")
-    for im in imgs:
-        if not torch.is_tensor(im) or im.dim() != 3 or im.shape[0] != 3 or min(im.shape[1:]) < 1:
-            raise ValueError("color_jitter: the images are a list of (3, h, w) tensors (RGB; the hue op needs three channels)")
-        if im.device != imgs[0].device or im.dtype != imgs[0].dtype:
-            raise ValueError("color_jitter: the images share one device and dtype")
+    item_lists.check_images(imgs, "color_jitter (RGB; the hue op needs three channels)", (3,))
     _check_params(params, len(imgs))
     if not imgs[0].is_cuda:
         res = [jitter_image(im, p, with_mean=True) for im, p in zip(imgs, params)]
         out = [r[0] for r in res]
         return (out, torch.stack([r[1].double() for r in res])) if with_means else out
-    if imgs[0].dtype != torch.float32:
-        raise TypeError(f"color_jitter takes fp32 CUDA tensors, got {imgs[0].dtype}")
     dev = imgs[0].device
-    pad = lambda n: (n + 3) // 4 * 4                                     # every image starts on 16 bytes: the float4 path
-    items, at = [], 0
-    for im in imgs:
-        items.append((at, at, im.shape[1], im.shape[2]))
-        at += pad(im.numel())
-    src = torch.zeros(at, dtype=torch.float32, device=dev)
-    for im, it in zip(imgs, items):
-        src[it[0] : it[0] + im.numel()] = im.reshape(-1)
+    src, offs = item_lists.pack(imgs, align=4)                           # every image starts on 16 bytes: the float4 path
     dst = torch.empty_like(src)
-    rows, factors = item_rows(items, params)
-    max_h, max_w = max(it[2] for it in items), max(it[3] for it in items)
+    rows, factors = item_rows([(o, o, im.shape[1], im.shape[2]) for o, im in zip(offs, imgs)], params)
+    max_h, max_w = max(im.shape[1] for im in imgs), max(im.shape[2] for im in imgs)
     partial = torch.empty(len(imgs) * num_workgroups(max_h, max_w), dtype=torch.float64, device=dev)
     means = torch.empty(len(imgs), dtype=torch.float64, device=dev)
     hip_color_jitter(src, dst, rows.to(dev), factors.to(dev), partial, means, max_h, max_w)
-    out = [dst[it[1] : it[1] + 3 * it[2] * it[3]].view(3, it[2], it[3]) for it in items]
+    out = item_lists.views(dst, offs, [im.shape for im in imgs])
     return (out, means) if with_means else out
 
 

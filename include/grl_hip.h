@@ -939,19 +939,28 @@ typedef struct GrlUsmArgs {
 int64_t grl_usm_workspace_bytes(int32_t N, int32_t C, int32_t H, int32_t W);
 int grl_usm_sharp(void* stream, const GrlUsmArgs* args);
 
-/* The two image kernels of the blind-SR degradation pipeline (ABI 32; the on-the-fly LQ of real-world SR training,
- * bsr_degrade.py).  Inside one batch every sample has its own size, taps and mode, so both work on an ITEM LIST in DEVICE memory,
- * the idiom of grl_sample_patches: one launch serves all items of a call, nothing is allocated, the host does not synchronise, and
- * the launch stays valid inside a captured graph while the list's contents change.  An item names a source image, contiguous fp32
- * (C, h, w) at an ELEMENT offset into the source arena, and a destination image, contiguous fp32 at an element offset into the
- * destination arena; the two arenas may be one buffer as long as no item's destination overlaps any item's source.  The result of
- * an item does not depend on which other items share the launch.
- * What the host can see is checked on the host (GRL_ERR_BAD_ARG, nothing is launched).  The sizes, offsets and parameters of an item
- * exist in the device table only; for them the HOST WRAPPER VOUCHES: that max_ho / max_wo (and max_K) are at least every item's
- * output size (and K) -- the grid is sized from them, surplus workgroups leave, and an item beyond them would be computed only
- * where the grid reaches -- and that the destinations of a call do not overlap.  Everything else the kernel checks itself: an item
- * whose source or destination does not lie inside src_elems / dst_elems (its taps inside taps_elems), or whose size, mode, K or
- * stride is out of range, is skipped whole, so no list content makes the kernels read or write outside the buffers.
+/* ITEM LIST: the contract of the six entries of the blind-SR data path that work on lists of images whose sizes differ --
+ * grl_cv_resize, grl_blur_items (ABI 32, bsr_degrade.py), grl_isp_unprocess / grl_isp_process / grl_isp_roundtrip (ABI 37, isp.py)
+ * and grl_color_jitter (ABI 38, jitter.py); csrc/item_list.h is its code.  Inside one batch every sample has its own size and
+ * parameters, so an entry reads an item list from DEVICE memory, the idiom of grl_sample_patches: one launch serves all items of a
+ * call, nothing is allocated, the host does not synchronise, and the launch stays valid inside a captured graph while the list's
+ * contents change.
+ *   items[i] = eight int64: {src_off, dst_off, h, w, and four slots the entry names}.  The source image is contiguous fp32 (C, h, w)
+ *   at ELEMENT offset src_off of the source arena `src` (src_elems floats), the destination image contiguous fp32 at element offset
+ *   dst_off of the destination arena `dst` (dst_elems floats).  The two arenas may be one buffer as long as no item's destination
+ *   overlaps any item's source (an entry that may run an item in place, src_off == dst_off, says so).  The result of an item does
+ *   not depend on which other items share the launch.
+ *   On the host (GRL_ERR_BAD_ARG, nothing is launched): a null args / src / dst / items, src / dst not 4-byte or items not 8-byte
+ *   aligned, n_items (times C where a workgroup owns one plane) outside 1 .. 65535, a non-positive src_elems or dst_elems, a vouched
+ *   maximum below 1 (the entry's least side) or above 2^20, more than 2^31 - 1 tiles; and what the entry adds.
+ *   The HOST WRAPPER VOUCHES for what exists in the device table only: that the maxima it passes (max_ho / max_wo, max_h / max_w,
+ *   max_K) are at least every item's -- the grid is sized from them, surplus workgroups leave, and an item beyond them would be
+ *   computed only where the grid reaches -- and that the destinations of a call do not overlap.
+ *   Everything else THE KERNEL CHECKS: an item with a side (or stride) below 1 (the entry's least side) or above 2^20, or of which
+ *   any part -- source, destination, and the taps, tables or normals the entry names -- does not lie inside the buffer's stated
+ *   length, or whose entry-specific slots are out of range, is skipped whole.  "Lies inside" is off >= 0, count <= elems and
+ *   off <= elems - count: no sum is formed, so no offset, however large, wraps into range, and no list content makes a kernel read
+ *   or write outside the buffers its arguments describe.
  *
  * grl_cv_resize: OpenCV's resize, INTER_LINEAR / INTER_CUBIC / INTER_AREA
  *   replaces  cv2.resize(img, (int(1/2 w), int(1/2 h)), interpolation=random.choice([1, 2, 3]))        utils/utils_bsr/utils_sisr.py:299-303
@@ -972,8 +981,7 @@ int grl_usm_sharp(void* stream, const GrlUsmArgs* args);
  *   order: the horizontal pass, then the vertical one.
  * This is OpenCV's sampling rule with float64 coordinates.  OpenCV rounds the coordinate to fp32 first, which moves a weight by up to
  * n * 2^-24; equality with OpenCV's bytes is not claimed.
- * Errors (GRL_ERR_BAD_ARG): a null args / src / dst / items, C not 1 / 3, a non-positive n_items, max_ho, max_wo, src_elems or
- * dst_elems, max_ho or max_wo above 2^20, more than 65535 items, src / dst not 4-byte or items not 8-byte aligned. */
+ * Errors (GRL_ERR_BAD_ARG): those of ITEM LIST (the maxima are max_ho, max_wo), C not 1 / 3. */
 typedef struct GrlCvResizeArgs {
     const float* src;           /* source arena                                                   */
     float* dst;                 /* destination arena                                              */
@@ -995,9 +1003,8 @@ int grl_cv_resize(void* stream, const GrlCvResizeArgs* args);
  * (after a large downscale the image is smaller than the kernel).  One fp32 fmaf chain from 0 in that order, as grl_blur_depthwise.
  * The taps are CORRELATION taps: ndimage.convolve convolves, so the caller passes the kernel flipped over both axes
  * (tasks.blur_taps).  Only the strided outputs are computed.
- * Errors (GRL_ERR_BAD_ARG): a null args / src / dst / taps / items, C not 1 / 3, max_K even or outside 1 .. 31, a non-positive n_items,
- * max_ho, max_wo, src_elems, dst_elems or taps_elems, max_ho or max_wo above 2^20, n_items * C above 65535, src / dst / taps not
- * 4-byte or items not 8-byte aligned. */
+ * Errors (GRL_ERR_BAD_ARG): those of ITEM LIST (the maxima are max_ho, max_wo; n_items * C at most 65535), C not 1 / 3, max_K even or
+ * outside 1 .. 31, a null or not 4-byte aligned taps, a non-positive taps_elems. */
 typedef struct GrlBlurItemsArgs {
     const float* src;           /* source arena                                                   */
     float* dst;                 /* destination arena                                              */
@@ -1166,13 +1173,9 @@ int grl_lpips_tap(void* stream, const GrlLpipsTapArgs* args);
  *             ISPNet.reverse / forward (431-454) with GammaCorrect (206-212), ToneMapping (354-360), XYZ2LinearRGB (85-89),
  *             Raw2XYZ (57-67), ExposureCompensation (105-109), Demosaic (270-309), AddNoise.reverse (374-377);
  *             utils_color.linear2gamma colour space 0 (utils_color.py:172-180); utils_noise.add_noise (utils_noise.py:95-103)
- * The three entries follow the contract of grl_cv_resize / grl_blur_items above: an ITEM LIST in device memory over a source and a
- * destination arena (they may be one buffer as long as no item's destination overlaps another item's source; grl_isp_roundtrip may
- * also run an item in place, src == dst and src_off == dst_off: a thread reads its pixel's three channels before it writes them),
- * the host wrapper vouches for max_h / max_w (the grid is sized from them) and for disjoint destinations, the kernels skip whole
- * any item whose images do not lie inside src_elems / dst_elems, whose tables do not lie inside tables_elems (its normals inside
- * normals_elems), or whose side is below 3 or above 2^20.  The result of an item does not depend on the other items of the
- * launch.  Nothing is allocated, the host does not synchronise, the launches can be captured.
+ * The three entries follow the ITEM LIST contract above (before grl_cv_resize), with a least side of 3; the tone tables and the
+ * normals are checked against tables_elems / normals_elems as the images against the arenas.  grl_isp_roundtrip may also run an
+ * item in place, src == dst and src_off == dst_off: a thread reads its pixel's three channels before it writes them.
  *   items[i]  = {src_off, dst_off, h, w, yi_off, yi_inv_off, z_off, 0}: element offsets of the images into the arenas, of the
  *               item's forward and inverse tone tables (1,000,001 fp32 each, delta = 1e-6: ToneMapping.yi / yi_inv) into `tables`,
  *               and of its h * w unit normals into `normals` (read by grl_isp_unprocess alone).  The offsets live here and not in
@@ -1194,9 +1197,9 @@ int grl_lpips_tap(void* stream, const GrlLpipsTapArgs* args);
  *   copied, clamp, then the process chain.  0::2 / 1::2 indexing: odd sides are served.
  * grl_isp_roundtrip: (3, h, w) -> (3, h, w): the unprocess chain on all three channels, then the process chain -- the HR pass,
  *   without mosaic and noise.
- * Errors (GRL_ERR_BAD_ARG, nothing is launched): a null args / src / dst / items / params / tables (normals for grl_isp_unprocess), C
- * not 3, n_items outside 1 .. 65535, a non-positive src_elems / dst_elems (normals_elems), tables_elems below 1,000,001, max_h or
- * max_w below 3 or above 2^20, more than 2^31 - 1 tiles, src / dst / params / tables / normals not 4-byte or items not 8-byte aligned. */
+ * Errors (GRL_ERR_BAD_ARG, nothing is launched): those of ITEM LIST (the maxima are max_h, max_w, at least 3), C not 3, a null params /
+ * tables (normals for grl_isp_unprocess), a non-positive normals_elems there, tables_elems below 1,000,001, params / tables /
+ * normals not 4-byte aligned. */
 typedef struct GrlIspArgs {
     const float* src;           /* source arena                                                   */
     float* dst;                 /* destination arena                                              */
@@ -1225,14 +1228,11 @@ int grl_isp_roundtrip(void* stream, const GrlIspArgs* args);
  * The statement below is written from torchvision's published source; torchvision is not a dependency and no run of it backs the
  * tests: they hold the kernels to a float64 evaluation of this statement and its hue step to Python's colorsys.  Not claimed:
  * bit equality with a torchvision run, and the summation order of torch.mean behind the contrast mean.
- * The contract is that of grl_isp_roundtrip above: an ITEM LIST in device memory over a source and a destination arena (they may
- * be one buffer as long as no item's destination overlaps another item's source; an item may run in place, src == dst and
- * src_off == dst_off: a thread reads its pixels' three channels before it writes them), the host wrapper vouches for max_h / max_w
- * (the grid and the partial buffer are sized from them) and for disjoint destinations, the kernels skip whole -- the image and
- * its mean stay unwritten -- any item whose images do not lie inside src_elems / dst_elems, whose side is below 1 or above 2^20,
- * whose h * w needs more workgroups than grl_color_jitter_num_workgroups(max_h, max_w), or whose ops are no permutation of
- * 0 .. 3.  The result of an item does not depend on the other items of the call, and the same inputs give the same bits on every
- * run: there are no atomics.  Nothing is allocated, the host does not synchronise, the two launches can be captured.
+ * The entry follows the ITEM LIST contract above (before grl_cv_resize).  An item may run in place, src == dst and
+ * src_off == dst_off: a thread reads its pixels' three channels before it writes them.  The grid and the partial buffer are sized
+ * from max_h / max_w; beyond the shared checks the kernels skip whole -- the image and its mean stay unwritten -- an item whose
+ * h * w needs more workgroups than grl_color_jitter_num_workgroups(max_h, max_w), or whose ops are no permutation of 0 .. 3.  The
+ * same inputs give the same bits on every run: there are no atomics.
  *   items[i]  = {src_off, dst_off, h, w, op0, op1, op2, op3}: element offsets of the (3, h, w) images into the arenas (the offsets
  *               live here and not in the fp32 record: a float does not hold an offset beyond 2^24), and the ops in the order
  *               they run: 0 brightness, 1 contrast, 2 saturation, 3 hue (get_params' torch.randperm(4)).
@@ -1256,9 +1256,9 @@ int grl_isp_roundtrip(void* stream, const GrlIspArgs* args);
  * The call is two launches.  Pass 1 walks the ops that precede contrast per pixel and writes one fp64 sum of gray per (item,
  * workgroup) to partial[i * W + g], W = grl_color_jitter_num_workgroups(max_h, max_w) (a workgroup owns 4096 consecutive pixels:
  * a 400 x 400 image has 40 partials); pass 2 adds the item's partials, writes means[i], and walks the whole chain.
- * Errors (GRL_ERR_BAD_ARG, nothing is launched): a null args / src / dst / items / params / partial / means, C not 3, n_items
- * outside 1 .. 65535, a non-positive src_elems / dst_elems, max_h or max_w below 1 or above 2^20, n_partial below n_items * W,
- * src / dst / params not 4-byte or items / partial / means not 8-byte aligned.  grl_color_jitter_num_workgroups returns
+ * Errors (GRL_ERR_BAD_ARG, nothing is launched): those of ITEM LIST (the maxima are max_h, max_w; the tile count does not apply), C not
+ * 3, a null params / partial / means, n_partial below n_items * W, params not 4-byte or partial / means not 8-byte aligned.
+ * grl_color_jitter_num_workgroups returns
  * GRL_ERR_BAD_ARG for a max_h or max_w out of that range. */
 typedef struct GrlColorJitterArgs {
     const float* src;           /* source arena                                                   */

@@ -91,6 +91,48 @@ def test_blur_mixed_launch_against_the_fixture(fx):
                 assert torch.equal(alone, g), n
 
 
+# (h, w) of the mixed lists below: the sides around the 16 x 16 tile (one short, exact, one over), one pixel, three tiles, non-square
+TILE_SHAPES = [(1, 1), (1, 33), (15, 16), (16, 16), (17, 15), (33, 17), (16, 33)]
+
+
+@pytest.mark.parametrize("Cn", [1, 3])
+def test_mixed_lists_around_the_tile_size(Cn):
+    """One list per entry through ``item_lists`` (``cv_resize`` / ``blur_items`` pack, launch and slice with it): every shape of
+    TILE_SHAPES, for resize at interp 1, 2, 3 with a downscale and an upscale each, for blur with K = 1 and K = 31 at strides 1, 2
+    and 5 (5 is past the staged path).  Every item equals the same item run alone, bit for bit, and lies within the bounds of the
+    module docstring of the float64 CPU path."""
+    g = torch.Generator().manual_seed(7 + Cn)
+    xs = [torch.rand(Cn, h, w, generator=g) for h, w in TILE_SHAPES]
+    imgs, sizes, interps = [], [], []
+    for x in xs:
+        h, w = x.shape[1:]
+        for size in ((max(1, h // 2), max(1, (w + 2) // 3)), (2 * h + 1, 3 * w - 1)):
+            for ip in (1, 2, 3):
+                imgs.append(x), sizes.append(size), interps.append(ip)
+    got = B.cv_resize([x.to(DEV) for x in imgs], sizes, interps)
+    want = B.cv_resize([x.double() for x in imgs], sizes, interps)
+    for x, size, ip, gi, w in zip(imgs, sizes, interps, got, want):
+        err, b = float((gi.double().cpu() - w).abs().max()), resize_bound(ip, x.shape[1], x.shape[2], *size)
+        print(f"resize {tuple(x.shape)} -> {size} interp {ip}: max|err| = {err / U24:.2f} u, bound {b / U24:.0f} u")
+        assert gi.shape == w.shape and err <= b
+        assert torch.equal(B.cv_resize([x.to(DEV)], [size], [ip])[0], gi), (tuple(x.shape), size, ip)
+
+    taps = {1: torch.ones(1, 1), 31: torch.rand(31, 31, generator=g)}
+    taps[31] = taps[31] / taps[31].sum()
+    imgs, ks, strides = [], [], []
+    for x in xs:
+        for K in (1, 31):
+            for s in (1, 2, 5):
+                imgs.append(x), ks.append(K), strides.append(s)
+    got = B.blur_items([x.to(DEV) for x in imgs], [taps[K] for K in ks], strides)
+    want = B.blur_items([x.double() for x in imgs], [taps[K].double() for K in ks], strides)
+    for x, K, s, gi, w in zip(imgs, ks, strides, got, want):
+        err, b = float((gi.double().cpu() - w).abs().max()), blur_bound(K, x)
+        print(f"blur {tuple(x.shape)} K = {K} stride {s}: max|err| = {err / U24:.2f} u, bound {b / U24:.0f} u")
+        assert gi.shape == w.shape and err <= b
+        assert torch.equal(B.blur_items([x.to(DEV)], [taps[K]], [s])[0], gi), (tuple(x.shape), K, s)
+
+
 def _refused(fn, struct, fields):
     """The call returns GRL_ERR_BAD_ARG and leaves a sentinel-filled destination untouched.  ``dst`` absent: the sentinel buffer."""
     out = torch.full((3 * 8 * 8,), -7.0, device=DEV)

@@ -23,7 +23,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
-from grl_image_restoration_amd import _lib, bsr_degrade as B, tasks as T  # noqa: E402
+from grl_image_restoration_amd import _lib, bsr_degrade as B, item_lists, tasks as T  # noqa: E402
 from tools.bench_metrics import _median_ms  # noqa: E402
 
 U24 = 2.0 ** -24
@@ -111,8 +111,7 @@ def main(argv=None):
         lines.append(json.dumps(line))
 
     items, table = _resize_case(dev)
-    args = _lib.GrlCvResizeArgs(src=src.data_ptr(), dst=dst.data_ptr(), src_elems=src.numel(), dst_elems=dst.numel(), items=table.data_ptr(),
-                                n_items=N, C=3, max_ho=max(i[4] for i in items), max_wo=max(i[5] for i in items))
+    args = item_lists.args("grl_cv_resize", src, dst, table, C=3, max_ho=max(i[4] for i in items), max_wo=max(i[5] for i in items))
 
     def resize():
         for _ in range(a.inner):
@@ -124,9 +123,8 @@ def main(argv=None):
           "error_over_bound_vs_cpu": round(r_ok, 3)})
     for K, stride in ((25, 1), (25, 4), (9, 1)):
         items, table, taps = _blur_case(dev, K, stride)
-        bargs = _lib.GrlBlurItemsArgs(src=src.data_ptr(), dst=dst.data_ptr(), taps=taps.data_ptr(), src_elems=src.numel(), dst_elems=dst.numel(),
-                                      taps_elems=taps.numel(), items=table.data_ptr(), n_items=N, C=3, max_ho=-(-CROP // stride),
-                                      max_wo=-(-CROP // stride), max_K=K)
+        bargs = item_lists.args("grl_blur_items", src, dst, table, taps=taps.data_ptr(), taps_elems=taps.numel(), C=3,
+                                max_ho=-(-CROP // stride), max_wo=-(-CROP // stride), max_K=K)
 
         def blur():
             for _ in range(a.inner):

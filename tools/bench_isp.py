@@ -27,7 +27,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
-from grl_image_restoration_amd import _lib, bsr_degrade as B, isp  # noqa: E402
+from grl_image_restoration_amd import _lib, bsr_degrade as B, isp, item_lists  # noqa: E402
 from tools.bench_degrade import _train_step_ms  # noqa: E402
 from tools.bench_metrics import _median_ms  # noqa: E402
 
@@ -108,18 +108,15 @@ def main(argv=None):
             imgs = _images(kind, sides, gen)
             if src_planes == 1:
                 imgs = [i[0] for i in imgs]
-            src = torch.cat([i.reshape(-1) for i in imgs]).to(dev)
+            src, so = item_lists.pack(imgs)
+            src = src.to(dev)
             pixels = sum(s * s for s in sides)
-            dst = torch.empty(dst_planes * pixels, dtype=torch.float32, device=dev)
+            dst, do = item_lists.empty([(dst_planes, s, s) for s in sides], dev)
             normals = torch.randn(pixels, generator=gen).to(dev)
-            rows, so, do, zo = [], 0, 0, 0
-            for b, s in enumerate(sides):
-                rows.append((so, do, s, s, 2 * b * isp.TABLE_N, (2 * b + 1) * isp.TABLE_N, zo, 0))
-                so, do, zo = so + src_planes * s * s, do + dst_planes * s * s, zo + s * s
-            table = torch.tensor(rows, dtype=torch.int64).to(dev)
-            args = _lib.GrlIspArgs(src=src.data_ptr(), dst=dst.data_ptr(), src_elems=src.numel(), dst_elems=dst.numel(), items=table.data_ptr(),
-                                   params=recs.data_ptr(), tables=tables.data_ptr(), tables_elems=tables.numel(), normals=normals.data_ptr(),
-                                   normals_elems=normals.numel(), n_items=N, C=3, max_h=max(sides), max_w=max(sides))
+            zo = [sum(s * s for s in sides[:b]) for b in range(N)]
+            table = item_lists.table([(so[b], do[b], s, s, 2 * b * isp.TABLE_N, (2 * b + 1) * isp.TABLE_N, zo[b], 0) for b, s in enumerate(sides)], dev)
+            args = item_lists.args(entry, src, dst, table, params=recs.data_ptr(), tables=tables.data_ptr(), tables_elems=tables.numel(),
+                                   normals=normals.data_ptr(), normals_elems=normals.numel(), C=3, max_h=max(sides), max_w=max(sides))
             fn = getattr(L, entry)
 
             def run():
