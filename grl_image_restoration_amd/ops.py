@@ -48,7 +48,9 @@ def deterministic() -> bool:
     """GRL_DETERMINISTIC=1: bit-identical training gradients run to run.  The cross-workgroup reductions of the backward pass --
     the M slabs of the weight-gradient GEMM, the bias-table gradient of the attention backward -- are accumulated as 64-bit fixed
     point with integer atomics (integer addition commutes, fp32 addition does not), and the attention backward does not split
-    its launches (grl_hip.h: GrlGemmTnArgs.c_fix, GrlAttnBwdArgs.d_table_fix).  Slower; read per call."""
+    its launches (grl_hip.h: GrlGemmTnArgs.c_fix, GrlAttnBwdArgs.d_table_fix).  The smaller fp32-atomic reductions give way to
+    code without atomics: se_mlp_bwd walks the batch in one workgroup, se_colsum, LayerNorm, the CPB tables and the head planes
+    take torch's kernels.  Slower; read per call (tests/test_gpu_deterministic.py)."""
     return SW.on("GRL_DETERMINISTIC")
 
 
@@ -1086,10 +1088,15 @@ def _rows_ok(t: torch.Tensor) -> bool:
 
 
 def se_colsum(a: torch.Tensor, rows_per_image: int, k: float = 1.0, f: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """grl_se_colsum: [M / rows_per_image, C] = k * per-image column sums of a (* f): the CAB's average pool / the gate's gradient."""
+    """grl_se_colsum: [M / rows_per_image, C] = k * per-image column sums of a (* f): the CAB's average pool / the gate's gradient.
+    The kernel adds one fp32 atomic per 64-row workgroup and address, in hardware order: GRL_DETERMINISTIC=1 takes torch's reduction
+    (no atomics) instead, as layer_norm and cpb_tables do."""
     _dev_check(a, f)
     M, C_ = a.shape
     assert _rows_ok(a) and (f is None or (_rows_ok(f) and f.shape == a.shape)) and C_ % 4 == 0 and C_ <= 256 and M % rows_per_image == 0
+    if deterministic():
+        t = a if f is None else a * f
+        return t.reshape(M // rows_per_image, rows_per_image, C_).sum(dim=1).mul_(k)
     out = zeros_f32((M // rows_per_image) * C_, a.device).view(M // rows_per_image, C_)
     args = L.GrlSeRowsArgs(a=_ptr(a), lda=a.stride(0), f=_ptr(f), ldf=f.stride(0) if f is not None else 0, out=_ptr(out), ldo=C_, k=k,
                            M=M, C=C_, rows_per_image=rows_per_image)

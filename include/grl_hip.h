@@ -455,7 +455,9 @@ typedef struct GrlGemmTnArgs {
     int64_t* c_fix;         /* optional (ABI 21): deterministic accumulation.  The slabs' partial tiles are added as 64-bit  */
                             /* fixed point (2^30 x the a_scale-d sums; integer atomics commute, fp32 atomics do not) into     */
                             /* this zeroed [taps][N][ldc] array instead of `c`; the caller converts:                          */
-                            /* c = c_fix * 2^-30 * out_scale.  Bit-identical results run to run.                              */
+                            /* c = c_fix * 2^-30 * out_scale.  Bit-identical results run to run.  Range: a slab's a_scale-d   */
+                            /* partial sum and the total must stay below 2^33 in magnitude (int64 / 2^30; the conversion      */
+                            /* saturates, the sum wraps); resolution 2^-30, i.e. one rounding of at most 2^-31 per slab.       */
     /* ABI 22: a / b at their real widths -- N, K multiples of 4 (fp32 operands), lda >= N, ldb >= K, nothing is read beyond   */
     /* column N / K of a row -- and the bias gradient without a ones column in memory:                                          */
     int32_t b_ones;         /* != 0: b has a VIRTUAL column K that holds 1.0 (taps = 9: inside the image); its products, the   */
@@ -489,7 +491,9 @@ typedef struct GrlAttnBwdArgs {
                             /* meet in fp32 atomics), the dq kernel runs one wave per workgroup (its LDS histogram is then      */
                             /* filled in program order) and the workgroups' tables are added as 64-bit fixed point (2^32 x the   */
                             /* g_scale-d sums) into this zeroed [nh, tstride] array instead of `d_table`; the caller converts:   */
-                            /* d_table = d_table_fix * 2^-32 / g_scale.  Bit-identical gradients run to run.                     */
+                            /* d_table = d_table_fix * 2^-32 / g_scale.  Bit-identical gradients run to run.  Range: a           */
+                            /* workgroup's g_scale-d sum per entry and the total must stay below 2^31 in magnitude (int64 /       */
+                            /* 2^32); resolution 2^-32, i.e. one rounding of at most 2^-33 per workgroup and entry.                */
     int64_t d_o_ld;         /* optional (ABI 22): row stride of d_o in floats when it differs from o's (0 = o's): d_o as a column  */
                             /* block of a wider gradient matrix -- the two branches' outputs are concatenated along the channels     */
                             /* before the projection (mixed_attn_block_efficient.py:374-379), so their gradients arrive that way     */
