@@ -11,7 +11,7 @@ from . import switches as SW
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgrl_hip.so")
-ABI_VERSION = 38
+ABI_VERSION = 39
 DT_F32, DT_BF16, DT_F16 = 0, 1, 2
 
 EPI_PLAIN, EPI_GELU, EPI_GROUPNORM, EPI_LN_RES, EPI_GELU_GRAD = 0, 1, 2, 3, 4
@@ -513,6 +513,28 @@ class GrlPatchArgs(_Strict):
     ]
 
 
+class GrlPatchView(_Strict):
+    _fields_ = [
+        ("store", C.c_void_p),
+        ("offsets", C.c_void_p),
+        ("dims", C.c_void_p),
+        ("N", C.c_int32), ("C", C.c_int32),
+        ("scale", C.c_int32),
+        ("Ctot", C.c_int32), ("c0", C.c_int32),
+        ("reserved0", C.c_int32),
+        ("out", C.c_void_p),
+    ]
+
+
+class GrlPatchViewsArgs(_Strict):
+    _fields_ = [
+        ("view", GrlPatchView * 4),
+        ("work", C.c_void_p),
+        ("B", C.c_int32), ("P", C.c_int32), ("V", C.c_int32),
+        ("reserved0", C.c_int32),
+    ]
+
+
 class GrlBlurArgs(_Strict):
     _fields_ = [
         ("x", C.c_void_p),
@@ -732,6 +754,7 @@ SIGNATURES = {
     "grl_image_niqe_workspace_bytes": (_I64, [_I32] * 3),
     "grl_image_niqe_features": _launch(GrlNiqeArgs),
     "grl_sample_patches": _launch(GrlPatchArgs),
+    "grl_sample_patch_views": _launch(GrlPatchViewsArgs),
     "grl_blur_depthwise": _launch(GrlBlurArgs),
     "grl_jpeg_workspace_bytes": (_I64, [_I32] * 4),
     "grl_jpeg_roundtrip": _launch(GrlJpegArgs),

@@ -19,31 +19,48 @@
 // distinct banks; the channel planes are offset by 11 banks so that the de-interleaving writes of C = 3 spread over the banks.
 // Every global read is bounds-checked against the image, and a work-list entry whose image index is outside the store reads as
 // zeros, so no list content can make the kernel read outside the store.
+//
+// grl_sample_patch_views (ABI 39) cuts up to four VIEWS of one work list in one launch: every view has its own store, scale and
+// channel window (c0 .. c0 + C - 1 of Ctot) of an output batch, so the dual-pixel batch -- left view into lq[:, 0:3], right view
+// into lq[:, 3:6], GT into gt -- is one launch with no torch.cat behind it.  The tile body below is the one both entries run; a
+// workgroup of the view launch finds its view in a prefix table of first workgroups that travels in the by-value parameter struct,
+// and takes the float4 store or not by its own view's S.
 #include "common.h"
 
 namespace {
 
-constexpr int T = 32, NT = 256, LROW = T + 1, LPLANE = T * LROW + 11, CMAX = 3;
+constexpr int T = 32, NT = 256, LROW = T + 1, LPLANE = T * LROW + 11, CMAX = 3, VMAX = 4;
 
-struct Params {
+// one view of one launch: a store and the window of output channels it fills
+struct View {
     const uint8_t* store;
     const int64_t* offsets;
     const int32_t* dims;
-    const int32_t* work;
     float* out;
-    int32_t N, C, S, scale, nt;
+    int32_t N, C, S, scale, nt, Ctot, c0;
+    int32_t first;                      // the view's first workgroup (grl_sample_patch_views; 0 in grl_sample_patches)
 };
 
-template <int C, bool VEC>
-__global__ __launch_bounds__(NT) void sample_patches_kernel(Params p) {
-    __shared__ float s[CMAX * LPLANE];
+struct Params {
+    View v;
+    const int32_t* work;
+};
 
+struct ViewsParams {
+    View v[VMAX];
+    const int32_t* work;
+    int32_t V;
+};
+
+// One T x T output tile of one sample of view `p`; `blk` counts the view's workgroups, `s` is the workgroup's CMAX * LPLANE floats.
+template <int C, bool VEC>
+__device__ __forceinline__ void sample_tile(const View& p, const int32_t* work, int blk, float* s) {
     const int tiles = p.nt * p.nt;
-    const int b = blockIdx.x / tiles, t = blockIdx.x - b * tiles;
+    const int b = blk / tiles, t = blk - b * tiles;
     const int I0 = (t / p.nt) * T, J0 = (t - (t / p.nt) * p.nt) * T;      // output tile origin
     const int S = p.S;
 
-    const int4 w = *reinterpret_cast<const int4*>(p.work + 4 * (int64_t)b);
+    const int4 w = *reinterpret_cast<const int4*>(work + 4 * (int64_t)b);
     const int img = w.x, flags = w.w;
     const bool fr = flags & 1, fc = flags & 2, sw = flags & 4;
     const bool have = (uint32_t)img < (uint32_t)p.N;
@@ -72,7 +89,7 @@ __global__ __launch_bounds__(NT) void sample_patches_kernel(Params p) {
     const int a = threadIdx.x / (T / 4), b4 = (threadIdx.x % (T / 4)) * 4;
     const int i = I0 + a, j = J0 + b4;
     if (i >= S || j >= S) return;
-    float* o = p.out + (((int64_t)b * C) * S + i) * S + j;
+    float* o = p.out + (((int64_t)b * p.Ctot + p.c0) * S + i) * S + j;
     const int64_t plane = (int64_t)S * S;
 #pragma unroll
     for (int ch = 0; ch < C; ++ch, o += plane) {
@@ -92,27 +109,82 @@ __global__ __launch_bounds__(NT) void sample_patches_kernel(Params p) {
     }
 }
 
+template <int C, bool VEC>
+__global__ __launch_bounds__(NT) void sample_patches_kernel(Params p) {
+    __shared__ float s[CMAX * LPLANE];
+    sample_tile<C, VEC>(p.v, p.work, blockIdx.x, s);
+}
+
+// Every workgroup of the launch belongs to one view: the last one whose first workgroup is not after it.  The choice and the two
+// branches below are uniform over the workgroup.
+__global__ __launch_bounds__(NT) void sample_patch_views_kernel(ViewsParams p) {
+    __shared__ float s[CMAX * LPLANE];
+    View v = p.v[0];                    // constant indices only: the table stays in scalar registers, never in scratch
+#pragma unroll
+    for (int q = 1; q < VMAX; ++q)
+        if (q < p.V && (int)blockIdx.x >= p.v[q].first) v = p.v[q];
+    const int blk = blockIdx.x - v.first;
+    const bool vec = v.S % 4 == 0;
+    if (v.C == 3) {
+        if (vec) sample_tile<3, true>(v, p.work, blk, s);
+        else sample_tile<3, false>(v, p.work, blk, s);
+    } else {
+        if (vec) sample_tile<1, true>(v, p.work, blk, s);
+        else sample_tile<1, false>(v, p.work, blk, s);
+    }
+}
+
+// The checks of one view that both entries share (GRL_ERR_BAD_ARG as 0); fills `v` but for `first`.
+bool fill_view(View& v, const uint8_t* store, const int64_t* offsets, const int32_t* dims, float* out, int32_t N, int32_t C,
+               int32_t scale, int32_t Ctot, int32_t c0, int32_t P) {
+    if (!store || !offsets || !dims || !out) return false;
+    if (C != 1 && C != 3) return false;
+    if (N <= 0 || P <= 0 || scale < 1) return false;
+    if (c0 < 0 || (int64_t)c0 + C > Ctot) return false;
+    if ((uint64_t)out % 16 || (uint64_t)offsets % 8 || (uint64_t)dims % 4) return false;
+    const int64_t S = (int64_t)P * scale;
+    if (S > (1 << 20)) return false;
+    v.store = store; v.offsets = offsets; v.dims = dims; v.out = out;
+    v.N = N; v.C = C; v.S = (int32_t)S; v.scale = scale; v.nt = (int32_t)((S + T - 1) / T); v.Ctot = Ctot; v.c0 = c0; v.first = 0;
+    return true;
+}
+
 }  // namespace
 
 extern "C" int grl_sample_patches(void* stream, const GrlPatchArgs* a) {
-    if (!a || !a->store || !a->offsets || !a->dims || !a->work || !a->out) return GRL_ERR_BAD_ARG;
-    if (a->C != 1 && a->C != 3) return GRL_ERR_BAD_ARG;
-    if (a->N <= 0 || a->B <= 0 || a->P <= 0 || a->scale < 1) return GRL_ERR_BAD_ARG;
-    if ((uint64_t)a->out % 16 || (uint64_t)a->work % 16 || (uint64_t)a->offsets % 8 || (uint64_t)a->dims % 4) return GRL_ERR_BAD_ARG;
-    const int64_t S = (int64_t)a->P * a->scale;
-    if (S > (1 << 20)) return GRL_ERR_BAD_ARG;
-    const int64_t nt = (S + T - 1) / T, grid = (int64_t)a->B * nt * nt;
+    if (!a || !a->work || a->B <= 0 || (uint64_t)a->work % 16) return GRL_ERR_BAD_ARG;
+    Params p;
+    if (!fill_view(p.v, a->store, a->offsets, a->dims, a->out, a->N, a->C, a->scale, a->C, 0, a->P)) return GRL_ERR_BAD_ARG;
+    p.work = a->work;
+    const int64_t grid = (int64_t)a->B * p.v.nt * p.v.nt;
     if (grid > 0x7fffffff) return GRL_ERR_BAD_ARG;
 
-    Params p;
-    p.store = a->store; p.offsets = a->offsets; p.dims = a->dims; p.work = a->work; p.out = a->out;
-    p.N = a->N; p.C = a->C; p.S = (int32_t)S; p.scale = a->scale; p.nt = (int32_t)nt;
     const dim3 g((unsigned)grid), blk(NT);
     const hipStream_t st = (hipStream_t)stream;
-    if (a->C == 3 && S % 4 == 0) hipLaunchKernelGGL((sample_patches_kernel<3, true>), g, blk, 0, st, p);
+    const bool vec = p.v.S % 4 == 0;
+    if (a->C == 3 && vec) hipLaunchKernelGGL((sample_patches_kernel<3, true>), g, blk, 0, st, p);
     else if (a->C == 3) hipLaunchKernelGGL((sample_patches_kernel<3, false>), g, blk, 0, st, p);
-    else if (S % 4 == 0) hipLaunchKernelGGL((sample_patches_kernel<1, true>), g, blk, 0, st, p);
+    else if (vec) hipLaunchKernelGGL((sample_patches_kernel<1, true>), g, blk, 0, st, p);
     else hipLaunchKernelGGL((sample_patches_kernel<1, false>), g, blk, 0, st, p);
+    GRL_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int grl_sample_patch_views(void* stream, const GrlPatchViewsArgs* a) {
+    if (!a || !a->work || a->B <= 0 || (uint64_t)a->work % 16) return GRL_ERR_BAD_ARG;
+    if (a->V < 1 || a->V > VMAX) return GRL_ERR_BAD_ARG;
+    ViewsParams p = {};
+    int64_t grid = 0;
+    for (int k = 0; k < a->V; ++k) {
+        const GrlPatchView& w = a->view[k];
+        if (!fill_view(p.v[k], w.store, w.offsets, w.dims, w.out, w.N, w.C, w.scale, w.Ctot, w.c0, a->P)) return GRL_ERR_BAD_ARG;
+        if (grid > 0x7fffffff) return GRL_ERR_BAD_ARG;
+        p.v[k].first = (int32_t)grid;
+        grid += (int64_t)a->B * p.v[k].nt * p.v[k].nt;
+    }
+    if (grid > 0x7fffffff) return GRL_ERR_BAD_ARG;
+    p.work = a->work; p.V = a->V;
+    hipLaunchKernelGGL(sample_patch_views_kernel, dim3((unsigned)grid), dim3(NT), 0, (hipStream_t)stream, p);
     GRL_CHECK_LAUNCH();
     return 0;
 }

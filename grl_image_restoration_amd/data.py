@@ -9,8 +9,12 @@
   PatchSampler   the draws of one training batch (``random.Random``: image, _random_index of base_image.py:252-256, the three
                  flips) and the task's (lq, gt) pair built from them
 
+  sample_views   several stores cut by ONE work list into channel windows of shared batches (the dual-pixel batch: left view, right
+                 view, GT)
+
 CUDA stores go through ``grl_sample_patches`` of libgrl_hip.so (csrc/patches.hip): one launch per batch and store, the work list
-read from device memory, so the launch can be captured and replayed while the list changes.  There is no torch fallback for them.
+read from device memory, so the launch can be captured and replayed while the list changes.  ``sample_views`` on CUDA stores is one
+``grl_sample_patch_views`` launch for all of its views.  There is no torch fallback for either.
 CPU stores take the plain torch restatement below; the two are bitwise equal (tests/test_gpu_patches.py), and both equal the
 reference's numpy chain (tests/test_patches.py): a value is ``float(v) / 255`` by IEEE division.
 
@@ -138,6 +142,41 @@ class PatchStore:
         return out
 
 
+def sample_views(views, work: torch.Tensor, patch: int):
+    """Cuts several stores by one work list.  ``views``: a sequence of at most four ``(store, scale, out, c0)`` -- the view's
+    patches, ``store.sample(work, patch, scale)``, go to channels ``c0 .. c0 + store.channels - 1`` of ``out``, a contiguous fp32
+    (B, Ctot, patch * scale, patch * scale) batch on the stores' device; views may share an ``out`` (overlapping channel windows
+    are not checked).  CUDA stores: one ``grl_sample_patch_views`` launch (csrc/patches.hip).  CPU stores: the torch restatement per
+    view, copied into its window.  The two are bitwise equal (tests/test_gpu_dual_pixel.py).  Returns the ``out`` tensors."""
+    views, patch = list(views), int(patch)
+    if not 1 <= len(views) <= 4:
+        raise ValueError(f"sample_views takes 1 to 4 views, got {len(views)}")
+    if work.dtype != torch.int32 or work.dim() != 2 or work.shape[1] != 4 or work.shape[0] < 1 or not work.is_contiguous():
+        raise ValueError("work list: a contiguous int32 (B, 4) tensor")
+    if patch < 1:
+        raise ValueError(f"patch must be positive, got {patch}")
+    B = work.shape[0]
+    for store, scale, out, c0 in views:
+        S = patch * int(scale)
+        if work.device != store.device or out.device != store.device:
+            raise ValueError(f"work list on {work.device}, out on {out.device}, store on {store.device}")
+        if int(scale) < 1:
+            raise ValueError(f"scale must be positive, got {scale}")
+        if out.dim() != 4 or out.shape[0] != B or tuple(out.shape[2:]) != (S, S) or out.dtype != torch.float32 or not out.is_contiguous():
+            raise ValueError("out: a contiguous fp32 (B, Ctot, patch * scale, patch * scale) tensor")
+        if c0 < 0 or c0 + store.channels > out.shape[1]:
+            raise ValueError(f"channels {c0} .. {c0 + store.channels - 1} do not lie in an out of {out.shape[1]} channels")
+    if work.is_cuda:
+        from . import ops
+
+        ops.sample_patch_views([(st.data, st.offsets, st.dims_t, len(st), st.channels, int(scale), out, int(c0))
+                                for st, scale, out, c0 in views], work, patch)
+    else:
+        for store, scale, out, c0 in views:
+            out[:, c0 : c0 + store.channels] = store.sample(work, patch, int(scale))
+    return [v[2] for v in views]
+
+
 class PatchSampler:
     """(lq, gt) training batches of a task from PatchStores.  The tasks, what each accepts and its defaults:
     ``task_rules.RULES`` (``scale`` is the SR factor, 1 for the tasks that restore at scale 1).  How each LQ is made:
@@ -150,6 +189,16 @@ class PatchSampler:
                   it.  The one deliberate difference from the reference's bsr path: the target is rounded to 8 bits (at most
                   1 / 510 off), and it is sharpened on the whole image rather than on a 400 x 400 crop, so a patch carries no
                   reflected crop border
+      sr with ``lq_r_store``
+                  dual-pixel defocus deblurring (the reference's paired data set with ``dual_pixel: True``,
+                  restoration_paired_dataset.py:144-162): scale 1, RGB, three stores of equal image count, sizes and device.
+                  ``lq_store`` is the left sub-aperture view, ``lq_r_store`` the right one; ``next`` returns
+                  (lq [B, 6, P, P], gt [B, 3, P, P]) with the left view in channels 0 .. 2, the engine's
+                  ``torch.cat([img_lq_l, img_lq_r], dim=1)`` (engines/base.py:119-120).  The reference draws ONE position
+                  (_random_index on the first LQ view) and ONE set of flips for the three images (_augment(img_lq + [img_gt])): the
+                  draws, the work list and ``rng_state()`` are exactly those of the same sampler without the right store.  CUDA
+                  stores: one ``sample_views`` launch writes the three views in place, no cat; CPU stores: three ``sample`` calls
+                  and a cat.  ``usm``, ``degrade``, ``jitter`` and ``plain_gt`` are refused next to it
       sr with ``degrade``
                   GT store only, scale 2 or 4: the reference's real-world-SR data path (restoration_bsr.py:83-110).  Per sample a
                   ``degrade_crop`` x ``degrade_crop`` crop of a GT image is drawn (image, position and flags as for every task, at
@@ -193,7 +242,8 @@ class PatchSampler:
                  scale: int = 1, sigma: Optional[float] = None, sigma_range: Optional[Sequence[float]] = None, seed: int = 0,
                  taps: Optional[torch.Tensor] = None, quality: Optional[int] = None,
                  quality_range: Optional[Sequence[int]] = None, patchwise: bool = True, usm: bool = False, degrade: bool = False,
-                 degrade_crop: int = 400, plain_gt: bool = False, camera=None, jitter: bool = False):
+                 degrade_crop: int = 400, plain_gt: bool = False, camera=None, jitter: bool = False,
+                 lq_r_store: Optional[PatchStore] = None):
         from . import tasks
 
         patch, batch, scale = int(patch), int(batch), int(scale)
@@ -202,7 +252,9 @@ class PatchSampler:
         o = resolve(task, "sampler", scale=scale, channels=gt_store.channels, lq=lq_store is not None, sigma=sigma,
                     sigma_range=sigma_range, taps=taps is not None, quality=quality, quality_range=quality_range, patch=patch,
                     patchwise=patchwise, usm=usm, degrade=degrade, degrade_crop=degrade_crop if degrade else None,
-                    camera=camera is not None, jitter=jitter)
+                    camera=camera is not None, jitter=jitter, dual_pixel=lq_r_store is not None)
+        if lq_r_store is not None and plain_gt:
+            raise ValueError("task sr with a right view (lq_r_store, --lq-r) has no USM-sharpened target: plain_gt is not used")
         if taps is not None and (taps.dim() != 2 or taps.shape[0] != taps.shape[1] or taps.shape[0] % 2 == 0 or taps.shape[0] > 31):
             raise ValueError("taps: the (K, K) fp32 table of tasks.blur_taps, K odd and at most 31")
         store_lq = tasks.TRAIN_STORE_LQ.get(task) if o.quality_range is None else None
@@ -222,7 +274,11 @@ class PatchSampler:
             for n, ((h, w), (H, W)) in enumerate(zip(lq_store.dims, gt_store.dims)):
                 if (H, W) != (h * scale, w * scale):
                     raise ValueError(f"task sr: image {n} is {h} x {w} (LQ) and {H} x {W} (GT), not a x{scale} pair")
-        self.task, self.gt_store, self.lq_store = task, gt_store, lq_store
+        if lq_r_store is not None and (len(lq_r_store) != len(lq_store) or lq_r_store.channels != lq_store.channels
+                                       or lq_r_store.device != lq_store.device or lq_r_store.dims != lq_store.dims):
+            raise ValueError("task sr with a right view: the left and the right store need the same number of images, image sizes, "
+                             "channel count and device")
+        self.task, self.gt_store, self.lq_store, self.lq_r_store = task, gt_store, lq_store, lq_r_store
         self.patch, self.batch, self.scale = patch, batch, scale
         self.sigma, self.sigma_range = o.sigma, (tuple(float(v) for v in sigma_range) if sigma_range is not None else None)
         self.quality, self.quality_range = o.quality, o.quality_range
@@ -308,6 +364,15 @@ class PatchSampler:
             wt = self.in_place(self.work, torch.tensor([list(w) for w in work], dtype=torch.int32).reshape(-1, 4))
         if self.degrade:
             return self._degraded(wt, sigmas)
+        if self.lq_r_store is not None:              # dual-pixel: left and right view side by side, one crop and one set of flips
+            B, P = wt.shape[0], self.patch
+            if not wt.is_cuda:
+                lq = torch.cat([self.lq_store.sample(wt, P, 1), self.lq_r_store.sample(wt, P, 1)], dim=1)
+                return lq, self.gt_store.sample(wt, P, 1)
+            lq = torch.empty(B, 6, P, P, dtype=torch.float32, device=self.device)
+            gt = torch.empty(B, 3, P, P, dtype=torch.float32, device=self.device)
+            sample_views([(self.lq_store, 1, lq, 0), (self.lq_r_store, 1, lq, 3), (self.gt_store, 1, gt, 0)], wt, P)
+            return lq, gt
         if self.lq_store is not None:                # paired stores, given or made at construction
             lq = self.lq_store.sample(wt, self.patch, 1)
             gt = self.gt_store.sample(wt, self.patch, self.scale)

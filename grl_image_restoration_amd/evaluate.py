@@ -34,6 +34,9 @@ Restates, for the MI355X module, the three pieces of the reference's evaluation 
         --niqe-params niqe_pris_params.npz
     python -m grl_image_restoration_amd.evaluate --model base --geometry bsr_psnr --upsampler nearest+conv --scale 4 \\
         --ckpt bsr_psnr.ckpt --lq Set5/LRbicx4 --gt Set5/GTmod12 --usm-gt      scores against the USM-sharpened GT (val.use_usm: True)
+    python -m grl_image_restoration_amd.evaluate --task sr --scale 1 --model base --geometry defocus --tile 480 --overlap 48 \\
+        --ckpt db_defocus_dual_pixel_grl_base.ckpt --lq DPDD/test/inputL --lq-r DPDD/test/inputR --gt DPDD/test/target
+                                                  dual-pixel defocus deblurring: the two views side by side, a 6-in / 3-out model
     ... --save-dir results [--save-gt]    also writes results/X4/<data set>/<stem>_{LQ,HQ,GT}.png (image8.py), as the reference does
 """
 import argparse
@@ -156,6 +159,22 @@ def image_pairs(lq_dir: str, gt_dir: str) -> List[Tuple[str, str]]:
     return list(zip(lq, gt))
 
 
+def image_triples(lq_dir: str, lq_r_dir: str, gt_dir: str) -> List[Tuple[str, str, str]]:
+    """(left view, right view, gt) paths of a dual-pixel set, matched by sorted order like ``image_pairs`` (the reference lists
+    the three folders the same way, data/datasets/restoration_paired_dataset.py)."""
+    lq, lq_r, gt = _list_images(lq_dir), _list_images(lq_r_dir), _list_images(gt_dir)
+    if not (len(lq) == len(lq_r) == len(gt)) or not lq:
+        raise ValueError(f"{lq_dir}: {len(lq)} images, {lq_r_dir}: {len(lq_r)} images, {gt_dir}: {len(gt)} images")
+    return list(zip(lq, lq_r, gt))
+
+
+def _side_by_side(left: torch.Tensor, right: torch.Tensor) -> torch.Tensor:
+    """The model input of a dual-pixel pair: ``torch.cat([img_lq_l, img_lq_r], dim=1)`` (engines/base.py:119-120)."""
+    if left.shape != right.shape:
+        raise ValueError(f"dual-pixel views differ in size: {tuple(left.shape[-2:])} (left) and {tuple(right.shape[-2:])} (right)")
+    return torch.cat([left, right], dim=1)
+
+
 @torch.no_grad()
 def evaluate_pairs(model, pairs: Iterable[Tuple[torch.Tensor, torch.Tensor]], scale: int, tile: int = 0, overlap: int = 32,
                    device: str = "cuda:0", metric_group: Optional[str] = None, niqe_params=None, on_result=None, lpips_model=None):
@@ -173,7 +192,7 @@ def evaluate_pairs(model, pairs: Iterable[Tuple[torch.Tensor, torch.Tensor]], sc
     for index, (lq, gt) in enumerate(pairs):
         lq = lq.to(device)
         if tile and tile < min(lq.shape[-2:]):
-            sr = tiling.forward_tiled(model, lq, tile, overlap, scale)
+            sr = tiling.forward_tiled(model, lq, tile, overlap, scale, out_channels=getattr(model, "out_channels", None))
         else:
             sr = model(lq)
         if gt is None:
@@ -229,7 +248,8 @@ def evaluate_folder(model, lq_dir: Optional[str], gt_dir: Optional[str], scale: 
                     device: str = "cuda:0", verbose: bool = True, metric_group: Optional[str] = None, channels: int = 3,
                     task: str = "sr", sigma: Optional[float] = None, noise_prefix: Optional[str] = None, niqe_params=None,
                     taps: Optional[torch.Tensor] = None, quality: Optional[int] = None, save_dir: Optional[str] = None,
-                    save_gt: bool = False, save_workers: int = 4, usm_gt: bool = False, lpips_model=None):
+                    save_gt: bool = False, save_workers: int = 4, usm_gt: bool = False, lpips_model=None,
+                    lq_r_dir: Optional[str] = None):
     """Mean PSNR-Y over the image pairs of two folders; with ``metric_group``, {metric name: mean} of that group.  ``channels`` 1
     reads the images as grayscale.  A ``task`` that synthesises its input ignores ``lq_dir`` and builds the LQ from the GT
     (``task_inputs``, with ``sigma``, ``taps``, ``quality`` and ``scale`` as the task's rule takes them).  A task without a ground
@@ -241,12 +261,20 @@ def evaluate_folder(model, lq_dir: Optional[str], gt_dir: Optional[str], scale: 
     when the call returns.  The metrics do not depend on it.  ``usm_gt`` (task "sr" only; ValueError elsewhere): every GT is cropped
     to a multiple of ``scale`` and sharpened by ``tasks.usm_sharp(..., quantise=True)`` on ``device`` before anything else sees it,
     as the reference's validation set does under ``use_usm`` (restoration_sr.py:94,105-109, base_image.py:404): the metrics are
-    taken against the sharpened GT and ``save_gt`` writes it."""
-    o = resolve(task, "evaluate_folder", scale=scale, channels=channels, sigma=sigma, quality=quality, usm=usm_gt)
+    taken against the sharpened GT and ``save_gt`` writes it.  ``lq_r_dir`` (task "sr" at scale 1, RGB): dual-pixel defocus
+    deblurring -- ``lq_dir`` holds the left views, ``lq_r_dir`` the right ones, matched to each other and to the GT by sorted order;
+    the model (``GRL(in_channels=6, out_channels=3)``) gets the two side by side, ``<stem>_LQ.png`` is the LEFT view
+    (engines/base.py:536-537) and the saved images go straight under the data set's name (engines/base.py:521-524)."""
+    dual = lq_r_dir is not None
+    o = resolve(task, "evaluate_folder", scale=scale, channels=channels, sigma=sigma, quality=quality, usm=usm_gt,
+                **(dict(dual_pixel=True, lq=lq_dir is not None) if dual else {}))
     rule = o.rule
     mode = "L" if channels == 1 else "RGB"
     if rule.lq_from == "gt":
         items = task_inputs(gt_dir, task, channels, sigma, noise_prefix, device, scale, taps, quality)
+    elif dual:
+        items = ((os.path.basename(l_p), _side_by_side(_read_image(l_p, mode), _read_image(r_p, mode)), _read_image(gt_p, mode))
+                 for l_p, r_p, gt_p in image_triples(lq_dir, lq_r_dir, gt_dir))
     elif rule.has_gt:
         items = ((os.path.basename(lq_p), _read_image(lq_p, mode), _read_image(gt_p, mode)) for lq_p, gt_p in image_pairs(lq_dir, gt_dir))
         if usm_gt:
@@ -269,10 +297,10 @@ def evaluate_folder(model, lq_dir: Optional[str], gt_dir: Optional[str], scale: 
         writer = ImageWriter(save_workers)
 
         def save(name, lq, sr, gt):
-            paths = save_paths(save_dir, task, name, scale, o.sigma, o.quality, dataset)
+            paths = save_paths(save_dir, task, name, scale, o.sigma, o.quality, dataset, flat=dual)
             os.makedirs(os.path.dirname(paths["HQ"]), exist_ok=True)
             writer.write(paths["HQ"], sr.float())
-            writer.write(paths["LQ"], lq, rep=scale)
+            writer.write(paths["LQ"], lq[:, :3] if dual else lq, rep=scale)
             if save_gt and gt is not None:
                 writer.write(paths["GT"], gt)
     with writer:                                          # closed, every file in place, before the mean is returned
@@ -305,6 +333,9 @@ def _parser():
     add_task_arguments(ap, TASKS)
     ap.add_argument("--ckpt", default=None, help="reference checkpoint (.ckpt / .pth); random init without it")
     ap.add_argument("--lq", default=None, help="LQ folder (--task sr and bsr)")
+    ap.add_argument("--lq-r", default=None,
+                    help="--task sr --scale 1: folder of the RIGHT sub-aperture views of a dual-pixel set (--lq holds the left ones); the "
+                         "model is built with 6 input and 3 output channels (db_defocus_dual_pixel_grl_base.ckpt)")
     ap.add_argument("--gt", default=None, help="GT folder (required, except with --task bsr)")
     ap.add_argument("--niqe-params", default=None,
                     help="restorer_niqe: the reference's utils/metrics/niqe_pris_params.npz (default: the environment variable "
@@ -344,7 +375,7 @@ def _check(ap, a):
         if a.metric not in (None, "restorer_niqe"):
             ap.error(f"--task {a.task} is scored by --metric restorer_niqe")
         a.metric = "restorer_niqe"
-    o = resolve_arguments(ap, a, "evaluate", usm=a.usm_gt)
+    o = resolve_arguments(ap, a, "evaluate", usm=a.usm_gt, dual_pixel=a.lq_r is not None)
     a.scale, a.sigma = o.scale, o.sigma
 
 
@@ -384,13 +415,16 @@ def main(argv: Optional[List[str]] = None):
         except ValueError as e:
             ap.error(str(e))
     overrides = {"upsampler": a.upsampler} if a.upsampler and a.scale > 1 else {}
-    model = GRL(**make_config(a.model, a.geometry, upscale=a.scale, in_channels=a.channels, **overrides)).eval()
+    # two views side by side: GRL(in_channels=6, out_channels=3) of db_defocus/grl_dual_p480
+    channels = dict(in_channels=6, out_channels=3) if a.lq_r is not None else dict(in_channels=a.channels)
+    model = GRL(**make_config(a.model, a.geometry, upscale=a.scale, **channels, **overrides)).eval()
     if a.ckpt:
         load_checkpoint(model, a.ckpt)
     model = model.to(a.device)
     return evaluate_folder(model, a.lq, a.gt, a.scale, a.tile, a.overlap, a.device, metric_group=a.metric, channels=a.channels,
                            task=a.task, sigma=a.sigma, noise_prefix=a.noise_prefix, niqe_params=niqe_params, taps=taps,
-                           quality=a.quality, save_dir=a.save_dir, save_gt=a.save_gt, usm_gt=a.usm_gt, lpips_model=lpips_model)
+                           quality=a.quality, save_dir=a.save_dir, save_gt=a.save_gt, usm_gt=a.usm_gt, lpips_model=lpips_model,
+                           lq_r_dir=a.lq_r)
 
 
 if __name__ == "__main__":

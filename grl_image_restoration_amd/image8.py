@@ -175,11 +175,13 @@ class ImageWriter:
 
 
 def save_paths(save_dir: str, task: str, name: str, scale: int = 1, sigma: Optional[float] = None, quality: Optional[int] = None,
-               dataset: str = "") -> Dict[str, str]:
+               dataset: str = "", flat: bool = False) -> Dict[str, str]:
     """{"LQ", "HQ", "GT"} -> file path of image ``name`` under the reference's layout (engines/base.py:500-524):
     ``<save_dir>/X<scale>/<dataset>/<stem>_HQ.png`` for the SR tasks, ``Sigma<sigma>`` for dn, ``QF<quality>`` for jpeg and
-    ``<save_dir>/<dataset>/`` for the rest, as ``RULES[task].save_tag`` says.  ``stem``: the base name without its extension."""
-    tag = RULES[task].save_tag
+    ``<save_dir>/<dataset>/`` for the rest, as ``RULES[task].save_tag`` says.  ``stem``: the base name without its extension.
+    ``flat``: straight under the data set's name whatever the task's tag is -- the reference's ``paired`` data module
+    (engines/base.py:521-524), which the dual-pixel pairs of task sr come from."""
+    tag = None if flat else RULES[task].save_tag
     sub = {"scale": f"X{scale}", "sigma": f"Sigma{float(sigma):g}" if tag == "sigma" else "", "quality": f"QF{quality}", None: ""}[tag]
     folder = os.path.join(*(p for p in (save_dir, sub, dataset) if p))
     stem = os.path.splitext(os.path.basename(name))[0]

@@ -1301,3 +1301,27 @@ def lpips_tap(f: torch.Tensor, w: torch.Tensor, B: int, H: int, W: int, out: tor
     with _timed("lpips_tap"):
         L.launch("grl_lpips_tap", args)
     return pool_out if pool else None
+
+
+# ---- training patches, several views of one work list (csrc/patches.hip) --------------------------------------------------------------
+def sample_patch_views(views, work: torch.Tensor, patch: int) -> None:
+    """grl_sample_patch_views: one launch cuts every view of ``views`` -- a sequence of at most four
+    ``(data, offsets, dims, N, C, scale, out, c0)``: a store's uint8 buffer, its int64 offsets and int32 (N, 2) sizes, the number of
+    images, the channel count (1 or 3), the view's scale, the fp32 (B, Ctot, patch * scale, patch * scale) batch it writes into and
+    its first channel there -- for the int32 (B, 4) work list ``work`` on the same device.  Views may share an ``out``; overlapping
+    channel windows are not checked (include/grl_hip.h)."""
+    views = list(views)
+    if not 1 <= len(views) <= 4:
+        raise ValueError(f"grl_sample_patch_views takes 1 to 4 views, got {len(views)}")
+    assert work.dtype == torch.int32 and work.dim() == 2 and work.shape[1] == 4 and work.is_contiguous()
+    B, patch = work.shape[0], int(patch)
+    args = L.GrlPatchViewsArgs(work=_ptr(work), B=B, P=patch, V=len(views))
+    for k, (data, offsets, dims, N, C_, scale, out, c0) in enumerate(views):
+        _dev_check(work, data, offsets, dims, out)
+        S = patch * int(scale)
+        assert data.dtype == torch.uint8 and offsets.dtype == torch.int64 and dims.dtype == torch.int32
+        assert out.dtype == torch.float32 and out.is_contiguous() and out.dim() == 4 and out.shape[0] == B and out.shape[2:] == (S, S)
+        args.view[k] = L.GrlPatchView(store=_ptr(data), offsets=_ptr(offsets), dims=_ptr(dims), N=int(N), C=int(C_), scale=int(scale),
+                                      Ctot=out.shape[1], c0=int(c0), out=_ptr(out))
+    with _timed("sample_patch_views"):
+        L.launch("grl_sample_patch_views", args)

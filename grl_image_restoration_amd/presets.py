@@ -60,6 +60,8 @@ GEOMETRIES = {
     "dn_df2": dict(window_size=32, stripe_size=[64, 128], stripe_groups=[None, None], anchor_window_down_factor=2),
     # motion deblurring Base (db_motion/grl_p480.yaml:33-44)
     "deblur": dict(window_size=12, stripe_size=[48, 96], stripe_groups=[None, None], anchor_window_down_factor=4),
+    # defocus deblurring Base, single- and dual-pixel (db_defocus/grl_p480.yaml:36-43; the dual-pixel model is in_channels=6, out_channels=3)
+    "defocus": dict(window_size=16, stripe_size=[48, 96], stripe_groups=[None, None], anchor_window_down_factor=4),
     # demosaicking Small (dm/grl.yaml:27-37, grl_test.md:11-15)
     "dm": dict(window_size=8, stripe_size=[32, 32], stripe_groups=[None, None], anchor_window_down_factor=4),
     # blind / real-world SR Base (bsr/grl.yaml:53-67, grl_test.md:100-106); its tail is upsampler="nearest+conv"

@@ -58,7 +58,7 @@ SYNTHESISED = tuple(t for t in RULES if RULES[t].lq_from == "gt")
 
 def resolve(task, where, *, scale=None, channels=3, lq=False, sigma=None, sigma_range=None, taps=False, quality=None,
             quality_range=None, patch=None, patchwise=True, val=False, val_lq=False, usm=False, val_usm=False, degrade=False,
-            degrade_crop=None, gan=False, camera=False, jitter=False):
+            degrade_crop=None, gan=False, camera=False, jitter=False, dual_pixel=False):
     """Checks the options of one call against ``RULES[task]``, fills the defaults and returns them as a namespace (``rule``,
     ``scale``, ``sigma``, ``sigma_range``, ``quality``, ``quality_range``).  Raises ValueError.  ``where`` is the caller: "evaluate" /
     "train" (the command lines), "evaluate_folder", "task_inputs", "sampler".  ``lq`` / ``taps``: whether an LQ folder or store / a blur
@@ -70,6 +70,9 @@ def resolve(task, where, *, scale=None, channels=3, lq=False, sigma=None, sigma_
     most crop / scale.  The namespace also carries ``degrade_crop`` (None without ``degrade``).  ``gan`` (train): the GAN stage.
     ``camera`` (training with ``degrade``): stage 2 of the degradation, the camera-noise model, is on (camera profiles were given);
     the crop is then at least 32.  ``jitter`` (training with ``degrade``): the reference's ColorJitter on every GT crop.
+    ``dual_pixel``: a second LQ folder or store, the right sub-aperture view, was given (--lq-r, lq_r_store; the reference's paired
+    data module with ``dual_pixel: True``, config/data_module/paired.yaml, engines/base.py:119-120): task sr at scale 1 on RGB images
+    with an LQ folder or store present, and none of usm, degrade, jitter, camera, gan.  It is an option of task sr, not a task.
     """
     training, library_eval = where in ("train", "sampler"), where in ("evaluate_folder", "task_inputs")
     r = RULES.get(task)
@@ -77,6 +80,21 @@ def resolve(task, where, *, scale=None, channels=3, lq=False, sigma=None, sigma_
         raise ValueError(f"unknown task {task!r}: one of {TRAIN_TASKS if training else TASKS}")
     if where == "task_inputs" and r.lq_from != "gt":
         raise ValueError(f"task {task!r} reads its LQ from a folder; synthesised tasks: {', '.join(SYNTHESISED)}")
+    if dual_pixel:
+        if task != "sr":
+            raise ValueError(f"task {task} takes no right view (--lq-r, lq_r_store): dual-pixel inputs belong to task sr at scale 1")
+        if (r.default_scale if scale is None else scale) != 1:
+            raise ValueError(f"task sr with a right view (--lq-r, lq_r_store) restores at scale 1 (--scale 1), got "
+                             f"{r.default_scale if scale is None else scale}")
+        if channels != 3:
+            raise ValueError("task sr with a right view (--lq-r, lq_r_store) works on RGB images: the model takes 6 channels and gives 3")
+        if not lq:
+            raise ValueError("task sr with a right view (--lq-r, lq_r_store) needs the left view as its LQ folder (--lq) or store")
+        for on, what in ((usm or val_usm, "USM-sharpened targets (--usm, --usm-gt, --val-usm, usm)"), (degrade, "the on-the-fly degradation (--degrade, degrade)"),
+                         (jitter, "the colour jitter (--jitter, jitter)"), (camera, "the camera-noise stage (--camera-profiles, camera)"),
+                         (gan, "the GAN stage (--gan)")):
+            if on:
+                raise ValueError(f"task sr with a right view (--lq-r, lq_r_store) does not go with {what}")
     if gan and (not training or not r.gan):
         raise ValueError(f"task {task} has no GAN stage (--gan): only training of {', '.join(t for t in RULES if RULES[t].gan)} runs "
                          "against the discriminator")

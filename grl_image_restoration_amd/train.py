@@ -21,6 +21,10 @@ Restates the pieces of the reference's training run that sit around ``model(x)``
         --degrade --usm --weight-decay 0 --gt DF2K/HR --val-gt frozen/GT --val-lq frozen/LQ ...      (no --lq: bsr_degrade makes it;
         with --camera-profiles DIR, the reference's utils/cameraprofile folder, a quarter of the samples get its camera-noise stage;
         with --jitter every GT crop first goes through the reference's ColorJitter)
+    python -m grl_image_restoration_amd.train --task sr --scale 1 --model base --geometry defocus --patch 480 --batch 1 \\
+        --gt DPDD/train/target --lq DPDD/train/inputL --lq-r DPDD/train/inputR --steps 80000 --milestones 20000+40000+60000+70000 \\
+        --val-gt DPDD/val/target --val-lq DPDD/val/inputL --val-lq-r DPDD/val/inputR ...     (dual-pixel defocus deblurring: the two
+        views side by side, a 6-in / 3-out model; one crop and one set of flips for the three images)
     python -m grl_image_restoration_amd.train --task sr_bicubic --scale 2 --model small --geometry sr_ckpt_df4 --gt DIV2K/HR ...
     python -m grl_image_restoration_amd.train --task dn --sigma 25 --model small --geometry dn_df4 --gt DFWB --ckpt dn_grl_small_c3s25.ckpt ...
     python -m grl_image_restoration_amd.train --task dm --model small --geometry dm --gt DFWB ...
@@ -121,6 +125,9 @@ def _parser():
     add_task_arguments(ap, D.TASKS)
     ap.add_argument("--gt", required=True, help="GT training folder")
     ap.add_argument("--lq", default=None, help="LQ training folder (--task sr)")
+    ap.add_argument("--lq-r", default=None,
+                    help="--task sr --scale 1: training folder of the RIGHT sub-aperture views of a dual-pixel set (--lq holds the left "
+                         "ones); the model is built with 6 input and 3 output channels")
     ap.add_argument("--depths", default=None, help="blocks per stage as a+b+c instead of the model size's (short experiments)")
     ap.add_argument("--ckpt", default=None, help="start weights (a reference checkpoint); random init without it")
     ap.add_argument("--patch", type=int, default=64, help="LQ patch side")
@@ -155,6 +162,7 @@ def _parser():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--val-gt", default=None)
     ap.add_argument("--val-lq", default=None)
+    ap.add_argument("--val-lq-r", default=None, help="--lq-r: the right views of the validation set")
     ap.add_argument("--val-every", type=int, default=0)
     ap.add_argument("--metric", default=None, help="a metric group of metrics.ALL_GROUPS or metrics.PERCEPTUAL_GROUPS instead of PSNR-Y")
     ap.add_argument("--lpips-vgg", default=None, metavar="PATH",
@@ -195,8 +203,12 @@ def _check(ap, a):
     o = resolve_arguments(ap, a, "train", sigma_range=a.sigma_range, quality_range=a.quality_range, patch=a.patch,
                           val=bool(a.val_every), val_lq=a.val_lq is not None, usm=a.usm or a.usm_gan or a.usm_percep, val_usm=a.val_usm,
                           degrade=a.degrade, degrade_crop=a.degrade_crop, gan=a.gan, camera=a.camera_profiles is not None,
-                          jitter=a.jitter)
+                          jitter=a.jitter, dual_pixel=a.lq_r is not None)
     a.scale, a.sigma, a.degrade_crop = o.scale, o.sigma, o.degrade_crop
+    if a.val_lq_r is not None and a.lq_r is None:
+        ap.error("--val-lq-r belongs to --lq-r")
+    if a.lq_r is not None and a.val_every and a.val_lq_r is None:
+        ap.error("--lq-r validates on --val-lq / --val-lq-r / --val-gt")
     if not a.gan and (a.disc_ckpt is not None or a.usm_gan):
         ap.error("--disc-ckpt and --usm-gan belong to --gan")
     if not a.gan and (a.vgg is not None or a.usm_percep or a.perceptual_weight != 1.0):
@@ -265,7 +277,9 @@ def main(argv: Optional[List[str]] = None):
     if a.depth_list:
         heads = make_config(a.model, a.geometry)["num_heads_window"][0]
         over.update(depths=a.depth_list, num_heads_window=[heads] * len(a.depth_list), num_heads_stripe=[heads] * len(a.depth_list))
-    model = GRL(**make_config(a.model, a.geometry, upscale=a.scale, img_size=a.patch, in_channels=a.channels, **over))
+    # two views side by side: GRL(in_channels=6, out_channels=3) of db_defocus/grl_dual_p480
+    channels = dict(in_channels=6, out_channels=3) if a.lq_r is not None else dict(in_channels=a.channels)
+    model = GRL(**make_config(a.model, a.geometry, upscale=a.scale, img_size=a.patch, **channels, **over))
     resume = torch.load(a.resume, map_location="cpu", weights_only=False) if a.resume else None
     if resume is not None:
         load_checkpoint(model, resume)
@@ -297,10 +311,12 @@ def main(argv: Optional[List[str]] = None):
     usm_flags = [a.usm, a.usm_gan] + ([a.usm_percep] if a.vgg is not None else [])      # the targets that are the sharpened GT
     gt_store = D.PatchStore.from_folder(a.gt, a.channels, device)
     lq_store = D.PatchStore.from_folder(a.lq, a.channels, device) if a.lq is not None else None
+    lq_r_store = D.PatchStore.from_folder(a.lq_r, a.channels, device) if a.lq_r is not None else None
     sampler = D.PatchSampler(a.task, gt_store, lq_store, patch=a.patch, batch=a.batch, scale=a.scale, sigma=a.sigma,
                              sigma_range=a.sigma_range, seed=a.seed + rank, taps=taps,
                              quality=a.quality if a.quality_range is None else None, quality_range=a.quality_range,
-                             usm=any(usm_flags), **(dict(plain_gt=True) if any(usm_flags) and not all(usm_flags) else {}),
+                             usm=any(usm_flags), **(dict(lq_r_store=lq_r_store) if lq_r_store is not None else {}),
+                             **(dict(plain_gt=True) if any(usm_flags) and not all(usm_flags) else {}),
                              **(dict(degrade=True, degrade_crop=a.degrade_crop, camera=camera, jitter=a.jitter) if a.degrade else {}))
 
     opt = FusedAdamW(model.parameters(), lr=a.lr, weight_decay=0.0 if a.gan else a.weight_decay)
@@ -372,7 +388,7 @@ def main(argv: Optional[List[str]] = None):
             with torch.no_grad():
                 v = evaluate_folder(model, a.val_lq, a.val_gt, a.scale, device=a.device, verbose=False, metric_group=a.metric,
                                     channels=a.channels, task=a.task, sigma=a.sigma, taps=taps, quality=a.quality, usm_gt=a.val_usm,
-                                    niqe_params=niqe_params, lpips_model=lpips_model)
+                                    niqe_params=niqe_params, lpips_model=lpips_model, lq_r_dir=a.val_lq_r)
             model.train()
             out["val"].append((done, v))
             print(f"step {n:8d}  validation {v}", flush=True)

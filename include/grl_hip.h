@@ -23,7 +23,7 @@ extern "C" {
 
 #define GRL_ERR_BAD_ARG (-1)
 #define GRL_ERR_UNSUPPORTED (-2)
-#define GRL_ABI_VERSION 38
+#define GRL_ABI_VERSION 39
 
 /* element kinds of activation / weight buffers */
 enum { GRL_DT_F32 = 0, GRL_DT_BF16 = 1, GRL_DT_F16 = 2 };
@@ -827,6 +827,46 @@ typedef struct GrlPatchArgs {
 } GrlPatchArgs;
 
 int grl_sample_patches(void* stream, const GrlPatchArgs* args);
+
+/* Up to four VIEWS of one work list cut in one launch (ABI 39; the data path of dual-pixel defocus deblurring, csrc/patches.hip):
+ *   replaces  the paired data set's dual-pixel item       data/datasets/restoration_paired_dataset.py:144-162 (left view, right view
+ *             and GT padded, cropped at ONE position and augmented by ONE set of flips)
+ *             _pad_images / _sample_patches               data/datasets/base_image.py:276-293
+ *             _augment                                    data/datasets/base_image.py:356-372
+ *             and torch.cat([img_lq_l, img_lq_r], dim=1)  engines/base.py:119-120
+ * A view is a store (store, offsets, dims, N, C as in GrlPatchArgs), its scale, and the place of its patches in an output batch:
+ * out is contiguous fp32 (B, Ctot, P * scale, P * scale), 16-byte aligned, and the view writes channels c0 .. c0 + C - 1 of it;
+ * the other channels are not touched.  Several views may share one out (left view: c0 = 0, right view: c0 = 3, Ctot = 6), so no
+ * concatenation follows the launch.  work, B and P are shared: work[b] = (image index, x, y, flags) in DEVICE memory, read by the
+ * kernel, so the launch takes no per-sample scalar and stays valid inside a captured graph while the list's contents change.
+ * Per view the semantics are those of grl_sample_patches, word for word: with S = P * scale the crop of rows x * scale ..
+ * x * scale + S - 1 and columns y * scale .. y * scale + S - 1 (pixels outside the image read as 0), then flags bit 0: rows
+ * reversed, bit 1: columns reversed, bit 2: the two axes swapped, in that order; every value is float(v) / 255 by IEEE division;
+ * an image index outside 0 .. N - 1 of a view's store yields zeros in that view.  Views may differ in scale and C; whether a view
+ * stores float4 (S a multiple of 4) is decided per view.  One launch on `stream` whatever V is.
+ * NOT checked: two views whose channel windows of one out overlap -- which of them is left in the overlap is undefined.
+ * Errors (GRL_ERR_BAD_ARG): those of grl_sample_patches for every view 0 .. V - 1 and the shared fields (a null pointer, C not 1 / 3,
+ * N, B or P <= 0, scale < 1, out or work not 16-byte aligned, a grid beyond 2^31 - 1 workgroups over all views), V outside 1 .. 4,
+ * c0 < 0 or c0 + C > Ctot.  view[V ..] is ignored. */
+typedef struct GrlPatchView {
+    const uint8_t* store;
+    const int64_t* offsets;     /* [N] byte offset of every image                               */
+    const int32_t* dims;        /* [N][2] H, W                                                  */
+    int32_t N, C;
+    int32_t scale;
+    int32_t Ctot, c0;           /* the view fills channels c0 .. c0 + C - 1 of Ctot             */
+    int32_t reserved0;
+    float* out;                 /* (B, Ctot, P * scale, P * scale)                              */
+} GrlPatchView;
+
+typedef struct GrlPatchViewsArgs {
+    GrlPatchView view[4];
+    const int32_t* work;        /* [B][4] image, x (top row), y (left column), flags            */
+    int32_t B, P, V;
+    int32_t reserved0;
+} GrlPatchViewsArgs;
+
+int grl_sample_patch_views(void* stream, const GrlPatchViewsArgs* args);
 
 /* Depthwise K x K blur of an image batch (ABI 28; the LQ synthesis of non-blind deblurring, data module `db`):
  *   replaces  input_ += F.conv2d(target, blur_kernel, groups=3, padding=(bkh, bkw))   engines/base.py:131-139
