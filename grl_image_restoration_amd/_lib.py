@@ -11,7 +11,7 @@ from . import switches as SW
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgrl_hip.so")
-ABI_VERSION = 39
+ABI_VERSION = 40
 DT_F32, DT_BF16, DT_F16 = 0, 1, 2
 
 EPI_PLAIN, EPI_GELU, EPI_GROUPNORM, EPI_LN_RES, EPI_GELU_GRAD = 0, 1, 2, 3, 4
@@ -642,6 +642,27 @@ class GrlVggTapArgs(_Strict):
     ]
 
 
+class GrlVggGramArgs(_Strict):
+    _fields_ = [
+        ("f", C.c_void_p),
+        ("ldf", C.c_int64),
+        ("nb", C.c_int32), ("B", C.c_int32), ("hw", C.c_int32), ("C", C.c_int32),
+        ("gram", C.c_void_p),
+        ("ws", C.c_void_p),
+        ("ws_bytes", C.c_int64),
+        ("rowbound", C.c_void_p),
+        ("diff", C.c_void_p),
+        ("partial", C.c_void_p),
+        ("n_partial", C.c_int32), ("accumulate", C.c_int32),
+        ("loss", C.c_void_p),
+        ("layer_sum", C.c_void_p),
+        ("coef", C.c_float),
+        ("k", C.c_float),
+        ("d", C.c_void_p),
+        ("ldd", C.c_int64),
+    ]
+
+
 class GrlLpipsPrepArgs(_Strict):
     _fields_ = [
         ("image", C.c_void_p),
@@ -773,6 +794,11 @@ SIGNATURES = {
     "grl_vgg_tap_num_workgroups": (C.c_int, [_I32] * 4),
     "grl_vgg_tap_fwd": _launch(GrlVggTapArgs),
     "grl_vgg_tap_bwd": _launch(GrlVggTapArgs),
+    "grl_vgg_gram_workspace_bytes": (_I64, [_I32] * 3),
+    "grl_vgg_gram_loss_num_workgroups": (C.c_int, [_I32] * 2),
+    "grl_vgg_gram_fwd": _launch(GrlVggGramArgs),
+    "grl_vgg_gram_loss": _launch(GrlVggGramArgs),
+    "grl_vgg_gram_bwd": _launch(GrlVggGramArgs),
     "grl_lpips_prep": _launch(GrlLpipsPrepArgs),
     "grl_lpips_tap_num_workgroups": (C.c_int, [_I32] * 4),
     "grl_lpips_tap": _launch(GrlLpipsTapArgs),

@@ -5,8 +5,8 @@
   GanStep    engines/base_gan.py:86-147 as Lightning runs it with two optimizers: optimizer 0 (generator) with the discriminator's
              parameters toggled off, then optimizer 1 (discriminator) on a fresh forward of the updated generator
 
-The perceptual (VGG19) loss of the reference's criterion is ``perceptual.PerceptualLoss``, handed in as ``perceptual=``; the style
-loss is not built.
+The perceptual (VGG19) loss of the reference's criterion is ``perceptual.PerceptualLoss``, handed in as ``perceptual=``; with the
+style loss on it is ``perceptual.PerceptualStyleLoss`` (base_gan.py:113-116).
 """
 from typing import Callable, Dict, Optional
 
@@ -37,8 +37,9 @@ class GanStep:
     """One call = one Lightning iteration of the reference's GAN engine.  ``pixel_loss(restored, target)``; both optimizers step
     once; returns the reference's logged scalars (detached tensors).  ``perceptual``: a ``perceptual.PerceptualLoss`` (or any callable
     returning ``(percep_loss, style_loss)``); its term, times ``perceptual_weight``, joins the generator's loss between the pixel and
-    the GAN term (base_gan.py:105-112) against ``gt_usm`` under ``usm_percep``, and ``loss_g_percep`` joins the scalars.  With
-    ``perceptual=None`` nothing of it exists."""
+    the GAN term (base_gan.py:105-112) against ``gt_usm`` under ``usm_percep``, and ``loss_g_percep`` joins the scalars.  A style
+    term that is not None is multiplied by ``perceptual_weight`` as well (base_gan.py:113-116), joins the loss after the perceptual
+    term and the scalars as ``loss_g_style``.  With ``perceptual=None`` nothing of either exists."""
 
     def __init__(self, model_g, model_d, opt_g, opt_d, pixel_loss: Callable, pixel_weight: float = 1.0, gan_weight: float = 1.0,
                  gan_loss_weight: float = 0.1, usm_pixel: bool = False, usm_gan: bool = False, perceptual=None,
@@ -60,16 +61,19 @@ class GanStep:
         try:
             restored = G(lq)
             loss_g_pix = self.pixel_loss(restored, gt_usm if self.usm_pixel else gt) * self.pixel_weight
-            loss_g_percep = None
+            loss_g_percep = loss_g_style = None
             if self.perceptual is not None:
-                loss_g_percep, style = self.perceptual(restored, gt_usm if self.usm_percep else gt)
-                if style is not None:
-                    raise NotImplementedError("the style loss is not part of this package")
+                loss_g_percep, loss_g_style = self.perceptual(restored, gt_usm if self.usm_percep else gt)
                 if loss_g_percep is not None:
                     loss_g_percep = loss_g_percep * self.perceptual_weight
+                if loss_g_style is not None:
+                    loss_g_style = loss_g_style * self.perceptual_weight
             loss_g_gan = gan_loss(D_(restored), True, is_disc=False, weight=self.gan_loss_weight) * self.gan_weight
             self.opt_g.zero_grad(set_to_none=True)
-            total = loss_g_pix + loss_g_gan if loss_g_percep is None else loss_g_pix + loss_g_percep + loss_g_gan
+            total = loss_g_pix
+            for term in (loss_g_percep, loss_g_style, loss_g_gan):
+                if term is not None:
+                    total = total + term
             total.backward()
             self.opt_g.step()
             self.opt_g.zero_grad(set_to_none=True)      # (gradients do not outlive their step: nothing of one optimizer's pass is
@@ -79,6 +83,8 @@ class GanStep:
         out["loss_g_pix"] = loss_g_pix.detach()
         if loss_g_percep is not None:
             out["loss_g_percep"] = loss_g_percep.detach()
+        if loss_g_style is not None:
+            out["loss_g_style"] = loss_g_style.detach()
         out["loss_g_gan"] = loss_g_gan.detach()
         # ---- optimizer 1: the discriminator (base_gan.py:129-145); training_step calls self(batch) again ----
         with torch.no_grad():

@@ -1260,6 +1260,64 @@ def vgg_tap_bwd(fx: torch.Tensor, fg: torch.Tensor, B: int, H: int, W: int, k: f
     return dfx
 
 
+# ---- the style loss (csrc/gram.hip): Gram matrices of the tapped features, their L1 distance and its adjoint ---------------------------
+def _gram_features(f, images, hw):
+    _dev_check(f)
+    assert f.dim() == 2 and f.shape[0] == images * hw and f.dtype == torch.float32 and f.stride(1) == 1, "features: [images*hw, C] fp32"
+
+
+def vgg_gram(f: torch.Tensor, nb: int, hw: int, rowbound: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """grl_vgg_gram_fwd: the token matrix [nb*hw, C] fp32 of nb images -> G [nb, C, C] fp32 = F_b^T F_b / (C*hw), exactly symmetric, the
+    same bits on every run (f32-input MFMA, token chunks added in float64 in a fixed order).  ``rowbound`` [nb] fp32 receives
+    sum_c max_t |F_b[t, c]| (>= max_t sum_c |F_b[t, c]|).  C: 64 / 128 / 256 / 512."""
+    _gram_features(f, nb, hw)
+    _dev_check(rowbound)
+    C_ = f.shape[1]
+    nbytes = L.lib().grl_vgg_gram_workspace_bytes(nb, hw, C_)
+    L.check(min(nbytes, 0), "grl_vgg_gram_workspace_bytes")
+    ws = empty(nbytes // 4, dtype=torch.float32, device=f.device)
+    gram = empty(nb, C_, C_, dtype=torch.float32, device=f.device)
+    if rowbound is not None:
+        assert rowbound.shape == (nb,) and rowbound.dtype == torch.float32 and rowbound.is_contiguous()
+    args = L.GrlVggGramArgs(f=_ptr(f), ldf=f.stride(0), nb=nb, hw=hw, C=C_, gram=_ptr(gram), ws=_ptr(ws), ws_bytes=nbytes, rowbound=_ptr(rowbound))
+    with _timed("vgg_gram"):
+        L.launch("grl_vgg_gram_fwd", args)
+    return gram
+
+
+def vgg_gram_loss(gram: torch.Tensor, loss: torch.Tensor, coef: float, *, accumulate: bool = True,
+                  layer_sum: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """grl_vgg_gram_loss on G [2B, C, C] (restored images first, then the targets): returns D = G[:B] - G[B:] [B, C, C] fp32 and
+    loss[0] (+)= coef * sum |D| (float64 in a fixed order, no atomics); ``layer_sum`` [1] receives the sum itself."""
+    _dev_check(gram, loss, layer_sum)
+    assert gram.dim() == 3 and gram.shape[0] % 2 == 0 and gram.shape[1] == gram.shape[2] and gram.dtype == torch.float32 and gram.is_contiguous()
+    B, C_ = gram.shape[0] // 2, gram.shape[1]
+    nwg = L.lib().grl_vgg_gram_loss_num_workgroups(B, C_)
+    L.check(min(nwg, 0), "grl_vgg_gram_loss_num_workgroups")
+    assert loss.dtype == torch.float32 and loss.numel() >= 1
+    partial = empty(nwg, dtype=torch.float64, device=gram.device)
+    diff = empty(B, C_, C_, dtype=torch.float32, device=gram.device)
+    args = L.GrlVggGramArgs(nb=2 * B, B=B, hw=1, C=C_, gram=_ptr(gram), diff=_ptr(diff), partial=_ptr(partial), n_partial=nwg,
+                            accumulate=int(accumulate), loss=_ptr(loss), layer_sum=_ptr(layer_sum), coef=coef)
+    with _timed("vgg_gram_loss"):
+        L.launch("grl_vgg_gram_loss", args)
+    return diff
+
+
+def vgg_gram_bwd(f: torch.Tensor, diff: torch.Tensor, hw: int, k: float, d: torch.Tensor) -> torch.Tensor:
+    """grl_vgg_gram_bwd, in place: d[b*hw + t, :C] += k * F_b[t] @ sign(D_b) for the B images of ``diff`` [B, C, C]; f / d [>= B*hw, C]
+    fp32 (the first B*hw rows are read / updated; later rows and columns >= C of d are not touched)."""
+    _dev_check(f, diff, d)
+    assert diff.dim() == 3 and diff.shape[1] == diff.shape[2] and diff.dtype == torch.float32 and diff.is_contiguous()
+    B, C_ = diff.shape[0], diff.shape[1]
+    assert f.dim() == 2 and f.shape[0] >= B * hw and f.shape[1] == C_ and f.dtype == torch.float32 and f.stride(1) == 1
+    assert d.dim() == 2 and d.shape[0] >= B * hw and d.shape[1] >= C_ and d.dtype == torch.float32 and d.stride(1) == 1
+    args = L.GrlVggGramArgs(f=_ptr(f), ldf=f.stride(0), B=B, hw=hw, C=C_, diff=_ptr(diff), k=k, d=_ptr(d), ldd=d.stride(0))
+    with _timed("vgg_gram_bwd"):
+        L.launch("grl_vgg_gram_bwd", args)
+    return d
+
+
 # ---- LPIPS (csrc/lpips.hip): input scaling, and the tapped layers' normalise / weight / mean with ReLU + max pool -----------------------
 def lpips_prep(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """grl_lpips_prep: an fp32 image [B, 3, H, W] in [0, 1] (any strides) -> the token matrix [B*H*W, 4] of ((2x - 1) - shift) / scale

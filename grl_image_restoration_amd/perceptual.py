@@ -3,6 +3,7 @@ conv2_2, conv3_4, conv4_4, conv5_4 with weights 0.1 / 0.1 / 1 / 1 / 1, L1 per la
 
   replaces  VGGFeatureExtractor (vgg19, no batch norm)     models/aux_archs/vgg.py:154-268
             PerceptualLoss at style_weight = 0             losses/losses.py:59-172
+            PerceptualLoss with the style loss             losses/losses.py:147-187   (PerceptualStyleLoss)
 
 CUDA tensors: ONE ``torch.autograd.Function``.  The forward runs the restored image and the target through the frozen VGG as one
 batch of 2B -- sixteen ``grl_conv3x3_fwd`` launches on filter banks packed once when the weights are loaded, ReLU in the epilogue of
@@ -21,8 +22,9 @@ CPU tensors: ``composite`` -- plain differentiable torch in float64, the yardsti
 emulates the kernels' operand rounding; ``decisions`` replaces the ReLU masks, pool indices and L1 signs by given ones, because the
 derivative jumps wherever one of them flips and gradients of two arithmetics compare only under the same decisions).
 
-Not built: the style loss (``style_weight > 0``) and the ``l2`` / ``fro`` criteria raise NotImplementedError (the reference's own
-``l2`` branch cannot be constructed: it names ``torch.nn.L2loss``).  On CUDA a tap must be a ``convN_M`` layer that closes its block
+The style loss (``style_weight > 0``) is ``PerceptualStyleLoss`` below (csrc/gram.hip); ``PerceptualLoss`` itself keeps refusing it.
+Not built: the ``l2`` / ``fro`` criteria raise NotImplementedError (the reference's own ``l2`` branch cannot be constructed: it names
+``torch.nn.L2loss``).  On CUDA a tap must be a ``convN_M`` layer that closes its block
 (or the last layer borrowed) -- the yaml's five are, and so is a single ``conv5_4``: an untapped block-closing convolution goes
 through the tap kernel with coefficient 0 for its ReLU + pool; ``relu`` / ``pool`` taps and mid-block taps work on the CPU
 composite only.
@@ -246,13 +248,16 @@ def operand_scale(coefs: Sequence[float], upstream: float = 1.0) -> float:
 
 
 def _hip_chain(vgg: VGG19Features, x: torch.Tensor, gt: Optional[torch.Tensor], coefs: Optional[Sequence[float]], trace: Optional[list] = None,
-               keep: bool = True):
+               keep: bool = True, style: Optional[dict] = None):
     """The forward launches.  ``coefs``: one per convolution, 0 where it is not tapped.  ``gt`` None: features of x alone (the pools
     run through the tap kernel on (x, x) with coefficient 0).  ``keep``: hold what a backward pass reads -- per tap-kernel layer the
     fp32 pre-activation of both halves, per other layer the activated 16-bit output of the restored half alone (a copy: the 2B
     matrix is released once the next layer has read it).  ``trace`` receives the pre-ReLU output of every convolution [2B, C, h, w]:
     fp32 where the tap kernel reads it, else from one more launch of the same convolution without the ReLU, at the 16 bits the layer
-    stores.  Returns (loss [1] fp32 or None, per-layer sums of |fx - fg|, saved, per-layer (h, w))."""
+    stores.  ``style`` ({"coefs": one per convolution}): per tapped layer one ``grl_vgg_gram_fwd`` on the 2B-image matrix and one
+    ``grl_vgg_gram_loss`` (csrc/gram.hip); the dict receives "loss" [1], "sums" (per-layer sums of |D|), "diffs" {convolution index: D
+    [B, C, C]} and "bounds" [convolutions, 2B] (per image sum_c max_t |F[t, c]|, 0 where not tapped).
+    Returns (loss [1] fp32 or None, per-layer sums of |fx - fg|, saved, per-layer (h, w))."""
     from . import ops
 
     vgg._check_size(x)
@@ -268,6 +273,10 @@ def _hip_chain(vgg: VGG19Features, x: torch.Tensor, gt: Optional[torch.Tensor], 
     loss = ops.empty(1, dtype=torch.float32, device=x.device)
     sums = ops.empty(len(plan), dtype=torch.float32, device=x.device)
     saved, dims, h, w, first = [], [], H, W, True
+    if style is not None:
+        assert gt is not None
+        style.update(loss=torch.zeros(1, dtype=torch.float32, device=x.device), sums=torch.zeros(len(plan), dtype=torch.float32, device=x.device),
+                     diffs={}, bounds=torch.zeros(len(plan), nb, dtype=torch.float32, device=x.device))
     for i, (tapped, pooled) in enumerate(plan):
         wp, bp = fw[i]
         kw = dict(x_cols=4) if i == 0 else {}
@@ -279,6 +288,9 @@ def _hip_chain(vgg: VGG19Features, x: torch.Tensor, gt: Optional[torch.Tensor], 
             pool = ops.vgg_tap(fx, fg, B, h, w, loss, coefs[i] if coefs is not None else 0.0, accumulate=not first, pool=pooled,
                                layer_sum=sums[i:i + 1])
             first = False
+            if style is not None and tapped:
+                gram = ops.vgg_gram(f, nb, h * w, rowbound=style["bounds"][i])
+                style["diffs"][i] = ops.vgg_gram_loss(gram, style["loss"], style["coefs"][i], accumulate=True, layer_sum=style["sums"][i:i + 1])
             saved.append(f if keep else None)
             pre = f
             if pooled:
@@ -301,10 +313,11 @@ def _hip_features(vgg: VGG19Features, x: torch.Tensor) -> Dict[str, torch.Tensor
     return {name: trace[i].contiguous() for i, (name, _, _, _) in enumerate(vgg.convs) if name in vgg.layer_name_list}
 
 
-def decisions_from_trace(vgg: VGG19Features, trace: Sequence[torch.Tensor], B: int) -> dict:
+def decisions_from_trace(vgg: VGG19Features, trace: Sequence[torch.Tensor], B: int, diffs: Optional[Dict[str, torch.Tensor]] = None) -> dict:
     """Tests: the ``decisions`` of the composite read off the traced features [2B, C, h, w] of a run (restored first, then target):
     ReLU masks ``f > 0``, ``max_pool2d(return_indices=True)`` on relu(f) where a pool follows, ``sign(fx - fg)`` at the taps -- each in
-    the trace's own arithmetic.  CPU tensors."""
+    the trace's own arithmetic.  ``diffs`` ({layer: D [B, C, C]}, the Gram differences of that run: PerceptualStyleLoss.forward_traced)
+    adds "gram_signs" {layer: sign(D)}.  CPU tensors."""
     masks, pools, signs = [], [], {}
     for (name, idx, _, _), t in zip(vgg.convs, trace):
         t = t.detach().cpu()
@@ -314,7 +327,10 @@ def decisions_from_trace(vgg: VGG19Features, trace: Sequence[torch.Tensor], B: i
             pools.append(F.max_pool2d(F.relu(fx), 2, 2, return_indices=True)[1])
         if name in vgg.layer_name_list:
             signs[name] = torch.sign(fx - t[B:])
-    return dict(masks=masks, pool_idx=pools, signs=signs)
+    dec = dict(masks=masks, pool_idx=pools, signs=signs)
+    if diffs is not None:
+        dec["gram_signs"] = {k: torch.sign(v.detach().cpu()) for k, v in diffs.items()}
+    return dec
 
 
 class _PerceptualFn(torch.autograd.Function):
@@ -334,31 +350,73 @@ class _PerceptualFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dloss):
-        from . import ops
-
         if not ctx.needs_input_grad[0]:
             return None, None, None
-        mod, vgg = ctx.mod, ctx.mod.vgg
+        mod = ctx.mod
         B, H, W = ctx.shape
-        saved = ctx.saved_tensors
-        plan = vgg._hip_plan()
-        _, bw = vgg._hip_packs(dloss.device)
         coefs = mod._coefs(B, H, W)
         up = float(dloss)                       # one host read per pass: S and the tap coefficients are launch arguments
         S = mod.last_scale = operand_scale(coefs, up)
-        g = None
-        for i in reversed(range(len(plan))):
-            tapped, pooled = plan[i]
-            h, w = ctx.dims[i]
-            n = B * h * w
-            if tapped or pooled:
-                d = ops.vgg_tap_bwd(saved[i][:n], saved[i][n:], B, h, w, S * coefs[i] * up, g)
-            else:
-                d = torch.where(saved[i] > 0, g, 0.0)         # ReLU: the mask is y > 0 on the saved activated output
-            wt, zb = bw[i]
-            # the gradient arrives as S * g in fp32: nothing is left for the launch to scale
-            g = ops.conv3x3(d, wt, zb, B, h, w, x_scale=1.0, out_scale=1.0, n_store=4 if i == 0 else 0)
-        dx = ops.vgg_prep_bwd(g, B, H, W, scale=1.0 / S, use_input_norm=vgg.use_input_norm, range_norm=vgg.range_norm)
+        dx = _hip_chain_bwd(mod.vgg, ctx.saved_tensors, ctx.dims, ctx.shape, [S * c * up for c in coefs], S, dloss.device)
+        return dx.to(ctx.xdtype), None, None
+
+
+def _hip_chain_bwd(vgg: VGG19Features, saved, dims, shape, tap_k: Sequence[float], S: float, device, gram_k: Optional[Sequence[float]] = None,
+                   diffs: Optional[dict] = None) -> torch.Tensor:
+    """The backward launches for the restored half: dL/dx [B, 3, H, W] fp32.  ``tap_k``: per convolution S * coefficient * upstream;
+    ``gram_k`` / ``diffs`` (the style loss): per convolution the k of ``grl_vgg_gram_bwd`` and the forward's D -- one launch after
+    ``grl_vgg_tap_bwd`` adds k * F * sign(D) into the gradient matrix that kernel has just written."""
+    from . import ops
+
+    B, H, W = shape
+    plan = vgg._hip_plan()
+    _, bw = vgg._hip_packs(device)
+    g = None
+    for i in reversed(range(len(plan))):
+        tapped, pooled = plan[i]
+        h, w = dims[i]
+        n = B * h * w
+        if tapped or pooled:
+            d = ops.vgg_tap_bwd(saved[i][:n], saved[i][n:], B, h, w, tap_k[i], g)
+            if gram_k is not None and i in diffs and gram_k[i] != 0.0:
+                ops.vgg_gram_bwd(saved[i], diffs[i], h * w, gram_k[i], d)
+        else:
+            d = torch.where(saved[i] > 0, g, 0.0)         # ReLU: the mask is y > 0 on the saved activated output
+        wt, zb = bw[i]
+        # the gradient arrives as S * g in fp32: nothing is left for the launch to scale
+        g = ops.conv3x3(d, wt, zb, B, h, w, x_scale=1.0, out_scale=1.0, n_store=4 if i == 0 else 0)
+    return ops.vgg_prep_bwd(g, B, H, W, scale=1.0 / S, use_input_norm=vgg.use_input_norm, range_norm=vgg.range_norm)
+
+
+class _PerceptualStyleFn(torch.autograd.Function):
+    """(perceptual, style) of one VGG pass on the HIP chain; backward: dL/dx alone, both terms in one reverse pass."""
+
+    @staticmethod
+    def forward(ctx, x, gt, mod):
+        B, _, H, W = x.shape
+        keep = ctx.needs_input_grad[0]
+        style = dict(coefs=mod._style_coefs(B))
+        loss, sums, saved, dims = _hip_chain(mod.vgg, x, gt, mod._coefs(B, H, W), mod._trace, keep=keep, style=style)
+        mod._layer_sums, mod._style_sums, mod._diffs = sums, style["sums"], style["diffs"]
+        ctx.mod, ctx.dims, ctx.shape, ctx.xdtype = mod, dims, (B, H, W), x.dtype
+        ctx.diffs, ctx.bounds = style["diffs"], style["bounds"]
+        if keep:
+            ctx.save_for_backward(*saved)
+        return loss.view(()), style["loss"].view(())
+
+    @staticmethod
+    def backward(ctx, dpercep, dstyle):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        mod = ctx.mod
+        B, H, W = ctx.shape
+        coefs, gk = mod._coefs(B, H, W), mod._gram_ks(B, ctx.dims)
+        # one host read per pass: both upstream gradients and, per layer, the forward's bound on |F sign(D)| over the restored images
+        host = torch.cat([dpercep.reshape(1).float(), dstyle.reshape(1).float(), ctx.bounds[:, :B].amax(dim=1)]).tolist()
+        up_p, up_s, bounds = host[0], host[1], host[2:]
+        S = mod.last_scale = operand_scale([abs(c * up_p) + abs(k * up_s) * m for c, k, m in zip(coefs, gk, bounds)])
+        dx = _hip_chain_bwd(mod.vgg, ctx.saved_tensors, ctx.dims, ctx.shape, [S * c * up_p for c in coefs], S, dpercep.device,
+                            gram_k=[S * k * up_s for k in gk], diffs=ctx.diffs)
         return dx.to(ctx.xdtype), None, None
 
 
@@ -367,8 +425,8 @@ class PerceptualLoss(nn.Module):
     percep_loss = perceptual_weight * sum_l layer_weights[l] * L1(f_l(x), f_l(gt)), features before ReLU, gt detached.
 
     ``layer_weights``: {layer name: weight} (``GAN_LAYER_WEIGHTS``: the GAN stage's yaml); ``weights``: the VGG19 state dict
-    (``load_vgg19(path)``).  Not built, NotImplementedError: ``style_weight > 0`` and the criteria ``l2`` / ``fro`` (the reference's
-    ``l2`` branch cannot be constructed either: it names ``torch.nn.L2loss``).  ``perceptual_weight <= 0`` returns ``(None, None)``
+    (``load_vgg19(path)``).  NotImplementedError: ``style_weight > 0`` (the style loss lives in ``PerceptualStyleLoss``) and the
+    criteria ``l2`` / ``fro`` (not built; the reference's ``l2`` branch cannot be constructed either: it names ``torch.nn.L2loss``).  ``perceptual_weight <= 0`` returns ``(None, None)``
     as the reference does.  CUDA tensors take the HIP chain (module docstring), CPU tensors the float64 composite;
     ``operand_dtype`` / ``decisions`` / ``grad_scale`` belong to the composite."""
 
@@ -376,7 +434,7 @@ class PerceptualLoss(nn.Module):
                  perceptual_weight: float = 1.0, style_weight: float = 0.0, criterion: str = "l1"):
         super().__init__()
         if style_weight > 0:
-            raise NotImplementedError("the style loss (style_weight > 0) is not part of this package")
+            raise NotImplementedError("PerceptualLoss is the reference's class at style_weight = 0; the style loss is PerceptualStyleLoss")
         if criterion != "l1":
             raise NotImplementedError(f"criterion {criterion!r}: only 'l1' is built")
         self.layer_weights = dict(layer_weights)
@@ -413,16 +471,22 @@ class PerceptualLoss(nn.Module):
                   grad_scale: Optional[float] = None, trace: Optional[list] = None) -> torch.Tensor:
         """The yardstick: float64 torch.  ``decisions`` adds {"signs": {layer: sign(fx - fg)}} to VGG19Features.composite's: the L1
         term of a layer becomes mean(sign * (fx - fg)).  The target's own path always decides for itself (it has no gradient)."""
-        x64, gt64 = x.double(), gt.detach().double()
-        fx = self.vgg.composite(x64, operand_dtype, decisions, grad_scale, trace)
+        fx, fg = self._features64(x, gt, operand_dtype, decisions, grad_scale, trace)
+        return self._percep_term(fx, fg, decisions, torch.float64)
+
+    def _features64(self, x, gt, operand_dtype, decisions, grad_scale, trace):
+        fx = self.vgg.composite(x.double(), operand_dtype, decisions, grad_scale, trace)
         with torch.no_grad():
-            fg = self.vgg.composite(gt64, operand_dtype)
+            fg = self.vgg.composite(gt.detach().double(), operand_dtype)
+        return fx, fg
+
+    def _percep_term(self, fx, fg, decisions, dtype):
         total, means = 0, []
         for k in fx:
             if decisions is None:
                 m = F.l1_loss(fx[k], fg[k])
             else:
-                m = (decisions["signs"][k].to(x64.dtype) * (fx[k] - fg[k])).mean()
+                m = (decisions["signs"][k].to(dtype) * (fx[k] - fg[k])).mean()
             means.append(m.detach())
             total = total + m * self.layer_weights[k]
         self.last_layer_means = means
@@ -449,5 +513,100 @@ class PerceptualLoss(nn.Module):
         try:
             loss = self.forward(x, gt)[0]
             return loss, self._trace
+        finally:
+            self._trace = None
+
+
+class PerceptualStyleLoss(PerceptualLoss):
+    """The reference's PerceptualLoss with the style term (losses/losses.py:59-187, criterion "l1"): ``forward(x, gt)`` returns
+    ``(percep_loss, style_loss)``; a term is None exactly when its weight is <= 0.
+
+        G_b      = F_b^T F_b / (C*h*w)            F_b [h*w, C]: the tapped pre-ReLU feature of image b       losses.py:174-187
+        style    = style_weight * sum_l layer_weights[l] * mean over (b, c, c') of |G_b(x) - G_b(gt)|        losses.py:160-168
+        dL/dF_b  = k_l / (C*h*w) * F_b (Sigma_b + Sigma_b^T),  Sigma_b = sign(G_b(x) - G_b(gt)),  k_l = upstream * style_weight * w_l / (B*C^2)
+
+    ``PerceptualLoss`` keeps refusing ``style_weight > 0`` (its tests pin that); ``l2`` / ``fro`` stay NotImplementedError here too.
+
+    CUDA: one autograd.Function with two outputs on ONE VGG pass -- the chain of ``PerceptualLoss`` plus, per tapped layer, one
+    ``grl_vgg_gram_fwd`` on the 2B-image matrix and one ``grl_vgg_gram_loss`` (csrc/gram.hip: f32-input MFMA, the features are never
+    rounded below fp32), and in the backward one ``grl_vgg_gram_bwd`` after ``grl_vgg_tap_bwd``.  ``perceptual_weight <= 0`` gives the
+    tap kernels coefficient 0.  G is exactly symmetric there, so Sigma + Sigma^T = 2 Sigma.
+
+    The operand scale S covers both terms.  The gradient at a tap is S * (coef_l * up_p * sign(fx - fg) + k'_l * up_s * (F Sigma)[t, c])
+    with k'_l = 2 * style_weight * w_l / (B*C^2 * C*h*w); Sigma has entries -1 / 0 / 1, so |(F Sigma)[t, c]| <= sum_c |F[t, c]| <=
+    m_l := max over the restored images of sum_c max_t |F[t, c]|, which the Gram forward leaves per image.  S is the power of two that
+    puts  max_l (|coef_l * up_p| + |k'_l * up_s| * m_l)  -- a bound on every tap gradient, not its value -- into (2^-4, 2^-3]; the
+    backward reads both upstream gradients and the five m_l with one host read.  ``last_scale`` holds S of the last backward.
+
+    CPU: ``composite`` returns (percep, style) in float64; its ``decisions`` gain {"gram_signs": {layer: sign(D)}} (the style term of
+    a layer becomes mean(sign * D)); ``last_style_means`` / ``style_layer_means`` are the per-layer means of |D| before their weights."""
+
+    def __init__(self, layer_weights: Dict[str, float], weights: Dict[str, torch.Tensor], use_input_norm: bool = True, range_norm: bool = False,
+                 perceptual_weight: float = 1.0, style_weight: float = 0.0, criterion: str = "l1"):
+        super().__init__(layer_weights, weights, use_input_norm, range_norm, perceptual_weight, 0.0, criterion)
+        self.style_weight = float(style_weight)
+        self.last_style_means: Optional[list] = None     # CPU: the per-layer means of |D| of the last call (before their weights)
+        self.last_diffs: Optional[dict] = None           # CPU: {layer: D [B, C, C]} of the last call, detached
+        self._style_sums, self._diffs = None, None
+
+    def _style_coefs(self, B: int):
+        """Per convolution: style_weight * layer weight / (B*C^2), 0 where it is not tapped."""
+        return [self.layer_weights[n] * self.style_weight / (B * c * c) if n in self.layer_weights else 0.0 for n, _, _, c in self.vgg.convs]
+
+    def _gram_ks(self, B: int, dims):
+        """Per convolution: the k of grl_vgg_gram_bwd before S and the upstream gradient, 2 * style coefficient / (C*h*w)."""
+        return [2.0 * k / (c * h * w) for k, (_, _, _, c), (h, w) in zip(self._style_coefs(B), self.vgg.convs, dims)]
+
+    def style_layer_means(self, B: int) -> torch.Tensor:
+        """CUDA: the per-layer means of |D| of the last forward (a device tensor; no host read)."""
+        at = [i for i, (n, _, _, _) in enumerate(self.vgg.convs) if n in self.layer_weights]
+        return self._style_sums[at] / torch.tensor([float(B * self.vgg.convs[i][3] ** 2) for i in at], device=self._style_sums.device)
+
+    def composite(self, x: torch.Tensor, gt: torch.Tensor, operand_dtype=None, decisions: Optional[dict] = None,
+                  grad_scale: Optional[float] = None, trace: Optional[list] = None):
+        """The yardstick: (percep, style) in float64 torch, both always formed (``forward`` drops the one whose weight is <= 0)."""
+        fx, fg = self._features64(x, gt, operand_dtype, decisions, grad_scale, trace)
+        percep = self._percep_term(fx, fg, decisions, torch.float64)
+        total, means, diffs = 0, [], {}
+        for k in fx:
+            _, c, h, w = fx[k].shape
+            tx, tg = fx[k].flatten(2), fg[k].flatten(2)
+            d = (tx @ tx.transpose(1, 2) - tg @ tg.transpose(1, 2)) / (c * h * w)
+            m = d.abs().mean() if decisions is None else (decisions["gram_signs"][k].to(torch.float64) * d).mean()
+            means.append(m.detach())
+            diffs[k] = d.detach()
+            total = total + m * self.layer_weights[k]
+        self.last_style_means, self.last_diffs = means, diffs
+        return percep, total * self.style_weight
+
+    def forward(self, x: torch.Tensor, gt: torch.Tensor, operand_dtype=None):
+        self.vgg._check_size(x)
+        if x.shape != gt.shape:
+            raise ValueError(f"PerceptualStyleLoss: x {tuple(x.shape)} and gt {tuple(gt.shape)} differ")
+        want_p, want_s = self.perceptual_weight > 0, self.style_weight > 0
+        if not (want_p or want_s):
+            return None, None
+        if x.is_cuda:
+            if operand_dtype is not None:
+                raise ValueError("operand_dtype belongs to the CPU composite path")
+            if not want_s:                                   # no Gram launch: the chain of PerceptualLoss as it is
+                return _PerceptualFn.apply(x, gt.detach(), self), None
+            percep, style = _PerceptualStyleFn.apply(x, gt.detach(), self)
+        else:
+            percep, style = self.composite(x, gt, operand_dtype)
+        return (percep if want_p else None), (style if want_s else None)
+
+    def _coefs(self, B: int, H: int, W: int):
+        """A perceptual term that is off (weight <= 0) gives the tap kernels coefficient 0."""
+        return super()._coefs(B, H, W) if self.perceptual_weight > 0 else [0.0] * len(self.vgg.convs)
+
+    def forward_traced(self, x: torch.Tensor, gt: torch.Tensor):
+        """Tests: ((percep, style), the sixteen traced feature matrices of PerceptualLoss.forward_traced, {layer: D [B, C, C]} of that
+        run) of one CUDA forward."""
+        self._trace = []
+        try:
+            losses = self.forward(x, gt)
+            names = [n for n, _, _, _ in self.vgg.convs]
+            return losses, self._trace, {names[i]: d for i, d in (self._diffs or {}).items()}
         finally:
             self._trace = None

@@ -51,6 +51,9 @@ discriminator's (``discriminator.UNetDiscriminatorSN``), eagerly and single-proc
 Checkpoints carry both networks (``model.model_g.`` / ``model.model_d.``, u / v included) and both optimizers; ``evaluate`` reads
 the generator out of them.  ``--vgg vgg19-dcbb9e9d.pth`` adds the third term of config/loss/gan_training_loss.yaml, the VGG19
 perceptual loss (``perceptual.PerceptualLoss``); the frozen VGG is not written into checkpoints, so ``--resume`` takes ``--vgg`` again.
+``--style-weight W`` (W > 0) adds the style half of that criterion (losses/losses.py:147-187: L1 between the Gram matrices of the same
+five features, ``perceptual.PerceptualStyleLoss``); its scalar ``loss_g_style`` joins the log line, and the weight is kept in the
+checkpoint's ``args`` (``--resume`` takes ``--style-weight`` again, as it takes ``--vgg``).
 
     python -m grl_image_restoration_amd.train --task sr --scale 4 --model base --geometry bsr --upsampler nearest+conv --gan \\
         --vgg vgg19-dcbb9e9d.pth --usm-percep --degrade --usm --ckpt runs/psnr/step_N.ckpt --lr 1e-4 --gt DF2K/HR --out runs/gan ...
@@ -193,6 +196,9 @@ def _parser():
                          "is downloaded.  The frozen VGG is not written into checkpoints: --resume takes --vgg again")
     ap.add_argument("--perceptual-weight", type=float, default=1.0, help="--gan --vgg: weight of the perceptual loss (base_gan.py:110)")
     ap.add_argument("--usm-percep", action="store_true", help="--gan --vgg: the perceptual target is the USM-sharpened GT (use_usm_percep)")
+    ap.add_argument("--style-weight", type=float, default=0.0, metavar="W",
+                    help="--gan --vgg: W > 0 turns the style loss on (style_weight of losses.py:147-187: L1 between the Gram matrices of "
+                         "the five tapped features, times W); 0: exactly the perceptual loss alone")
     ap.add_argument("--device", default="cuda:0")
     return ap
 
@@ -215,6 +221,10 @@ def _check(ap, a):
         ap.error("--vgg, --perceptual-weight and --usm-percep belong to --gan")
     if a.vgg is None and (a.usm_percep or a.perceptual_weight != 1.0):
         ap.error("--perceptual-weight and --usm-percep need --vgg")
+    if a.style_weight != 0.0 and not (a.gan and a.vgg is not None):
+        ap.error("--style-weight needs --gan --vgg")
+    if a.style_weight < 0.0:
+        ap.error("--style-weight must not be negative")
     if a.vgg is not None and a.patch * a.scale < 16:
         ap.error("--vgg: the GT patch side (--patch times --scale) must be at least 16 (VGG19 pools four times)")
     if a.gan and int(os.environ.get("WORLD_SIZE", "1")) > 1:
@@ -299,9 +309,12 @@ def main(argv: Optional[List[str]] = None):
         model_d = model_d.to(device).train()
         percep = None
         if a.vgg is not None:
-            from .perceptual import GAN_LAYER_WEIGHTS, PerceptualLoss, load_vgg19
+            from .perceptual import GAN_LAYER_WEIGHTS, PerceptualLoss, PerceptualStyleLoss, load_vgg19
 
-            percep = PerceptualLoss(GAN_LAYER_WEIGHTS, load_vgg19(a.vgg)).to(device)
+            if a.style_weight > 0:
+                percep = PerceptualStyleLoss(GAN_LAYER_WEIGHTS, load_vgg19(a.vgg), style_weight=a.style_weight).to(device)
+            else:
+                percep = PerceptualLoss(GAN_LAYER_WEIGHTS, load_vgg19(a.vgg)).to(device)
 
     camera = None
     if a.camera_profiles is not None:
@@ -366,7 +379,7 @@ def main(argv: Optional[List[str]] = None):
             plain, sharp = (batch[2], gt) if len(batch) == 3 else (gt, gt if any(usm_flags) else None)
             logged = gan_step(lq, plain, sharp)
             out["gan"].append({k: float(v) for k, v in logged.items()})
-            loss = sum(logged[k] for k in ("loss_g_pix", "loss_g_percep", "loss_g_gan") if k in logged)
+            loss = sum(logged[k] for k in ("loss_g_pix", "loss_g_percep", "loss_g_style", "loss_g_gan") if k in logged)
         elif a.eager:
             opt.zero_grad(set_to_none=True)
             loss = loss_fn(model(lq), gt)
@@ -381,7 +394,8 @@ def main(argv: Optional[List[str]] = None):
         loss = float(loss.detach())
         out["steps"].append(n); out["losses"].append(loss); out["lrs"].append(lr); out["work"].append(work)
         if rank == 0:
-            print(f"step {n:8d}  lr {lr:.3e}  loss {loss:.6f}", flush=True)
+            style = f"  loss_g_style {out['gan'][-1]['loss_g_style']:.6f}" if gan_step is not None and "loss_g_style" in out["gan"][-1] else ""
+            print(f"step {n:8d}  lr {lr:.3e}  loss {loss:.6f}{style}", flush=True)
         done = n + 1
         if a.val_every and done % a.val_every == 0 and rank == 0:
             model.eval()

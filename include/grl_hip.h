@@ -23,7 +23,7 @@ extern "C" {
 
 #define GRL_ERR_BAD_ARG (-1)
 #define GRL_ERR_UNSUPPORTED (-2)
-#define GRL_ABI_VERSION 39
+#define GRL_ABI_VERSION 40
 
 /* element kinds of activation / weight buffers */
 enum { GRL_DT_F32 = 0, GRL_DT_BF16 = 1, GRL_DT_F16 = 2 };
@@ -1161,6 +1161,48 @@ typedef struct GrlVggTapArgs {
 int grl_vgg_tap_num_workgroups(int32_t B, int32_t H, int32_t W, int32_t C);
 int grl_vgg_tap_fwd(void* stream, const GrlVggTapArgs* args);
 int grl_vgg_tap_bwd(void* stream, const GrlVggTapArgs* args);
+
+/* The style half of that PerceptualLoss (ABI 40, csrc/gram.hip): Gram matrices of the tapped features, criterion "l1".
+ *   replaces  PerceptualLoss._gram_mat and the style branch of PerceptualLoss.forward                 losses/losses.py:147-187
+ * f: the pre-ReLU token matrix [images*hw, ldf] fp32 of a tapped layer (restored images first, then the targets), C real channels,
+ * C one of 64 / 128 / 256 / 512 (GRL_ERR_UNSUPPORTED otherwise), ldf % 4 == 0, 16-byte aligned.  f32-input MFMA throughout: the
+ * features are never rounded below fp32.
+ * grl_vgg_gram_fwd (losses.py:174-187): gram [nb, C, C] fp32 = F_b^T F_b / (C*hw) per image.  The token axis is cut into chunks inside
+ *   an image (never across two), each chunk an fp32 fmaf chain of at most 2048 terms; the chunks are added in float64 in a fixed
+ *   order, no atomics: the same bits on every run, and gram[b] is exactly symmetric (the upper triangle is computed and mirrored).
+ *   ws: workspace of ws_bytes >= grl_vgg_gram_workspace_bytes(nb, hw, C).  rowbound (NULL or [nb]): rowbound[b] = sum_c max_t
+ *   |F_b[t, c]| >= max_t sum_c |F_b[t, c]|, a bound on every entry of F_b * Sigma for Sigma of entries -1 / 0 / 1.
+ * grl_vgg_gram_loss (losses.py:160-168): nb == 2 * B; diff [B, C, C] = gram[:B] - gram[B:]; loss[0] = (accumulate ? loss[0] : 0) +
+ *   (float)(coef * sum |diff|), layer_sum[0] = (float)sum when not NULL; the sum in float64 in a fixed order through partial (fp64,
+ *   n_partial >= grl_vgg_gram_loss_num_workgroups(B, C)) as grl_vgg_tap_fwd forms its own.  NaN features give a NaN loss.
+ * grl_vgg_gram_bwd (autograd through losses.py:147-187): d[b*hw + t, c'] += k * sum_c f[b*hw + t, c] * sign(diff[b, c, c']) for the B
+ *   restored images, sign(0) = 0; rows of other images and columns >= C of d are not touched.  gram being symmetric, Sigma + Sigma^T =
+ *   2 * Sigma, so k = S * upstream * style_weight * layer_weight / (B*C*C) * 2 / (C*hw) with S the chain's operand scale.
+ * Bad pointers / leading dimensions: GRL_ERR_BAD_ARG, nothing is launched. */
+typedef struct GrlVggGramArgs {
+    const float* f;
+    int64_t ldf;
+    int32_t nb, B, hw, C;       /* fwd: nb images; loss: nb == 2 * B; bwd: the B restored images  */
+    float* gram;                /* fwd: written; loss: read                                       */
+    void* ws;
+    int64_t ws_bytes;
+    float* rowbound;
+    float* diff;                /* loss: written; bwd: read                                       */
+    double* partial;
+    int32_t n_partial, accumulate;
+    float* loss;
+    float* layer_sum;
+    float coef;                 /* loss: style_weight * layer_weight / (B*C*C)                    */
+    float k;                    /* bwd                                                            */
+    float* d;
+    int64_t ldd;
+} GrlVggGramArgs;
+
+int64_t grl_vgg_gram_workspace_bytes(int32_t nb, int32_t hw, int32_t C);
+int grl_vgg_gram_loss_num_workgroups(int32_t B, int32_t C);
+int grl_vgg_gram_fwd(void* stream, const GrlVggGramArgs* args);
+int grl_vgg_gram_loss(void* stream, const GrlVggGramArgs* args);
+int grl_vgg_gram_bwd(void* stream, const GrlVggGramArgs* args);
 
 /* ---------------------------------------------------------------------------------------------
  * LPIPS, net = "vgg" (ABI 36, csrc/lpips.hip): everything between the 3x3 convolutions of the metric's VGG16 trunk.

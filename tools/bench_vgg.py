@@ -14,6 +14,17 @@ outputs written; backward: both read, dpool read, dfx written) over the median. 
 to --out.
 
     python tools/bench_vgg.py [--reps 20] [--warmup 3] [--inner 200] [--batch 8] [--out profiles/vgg_bench_line.json]
+
+``--style`` times the style loss instead (csrc/gram.hip, perceptual.PerceptualStyleLoss) at --batch images of 3 x 256 x 256 and writes
+profiles/style_bench_line.json:
+  ``PerceptualLoss`` and ``PerceptualStyleLoss`` (style weight 400), forward and forward + backward, the two classes alternating in one
+    process (a, b, a, b; the lower-median run of each, both medians beside it);
+  each Gram launch alone at the five tap shapes -- ``grl_vgg_gram_fwd`` on the 2 x batch images, ``grl_vgg_gram_loss``, and
+    ``grl_vgg_gram_bwd`` on the batch restored images -- with ``gbs_algorithmic``, the bytes the launch must move over the median
+    (forward: the features read once, G written; loss: G read, D written; backward: the features and D read, the gradient matrix
+    read and written), and for the two contractions ``tflops`` (forward: the upper triangle's 64 x 64 blocks that are computed).
+
+    python tools/bench_vgg.py --style [--batch 8] [--out profiles/style_bench_line.json]
 """
 import argparse
 import json
@@ -32,6 +43,62 @@ from tools.bench_metrics import _median_ms  # noqa: E402
 TAP_SHAPES = (("conv1_2", 64, 256), ("conv2_2", 128, 128), ("conv3_4", 256, 64), ("conv4_4", 512, 32), ("conv5_4", 512, 16))
 
 
+def style_bench(a, g, emit, timed, ab):
+    """--style: the two loss classes alternating, then each Gram launch alone at the five tap shapes."""
+    from grl_image_restoration_amd import ops
+    from grl_image_restoration_amd import perceptual as P
+
+    B = a.batch
+    sd = P.seeded_state_dict(0)
+    pl = P.PerceptualLoss(P.GAN_LAYER_WEIGHTS, sd).cuda()
+    ps = P.PerceptualStyleLoss(P.GAN_LAYER_WEIGHTS, sd, style_weight=400.0).cuda()
+    gt = torch.rand(B, 3, 256, 256, device="cuda", generator=g)
+    x = (gt + 0.1 * torch.randn(B, 3, 256, 256, device="cuda", generator=g)).clamp(0, 1)
+
+    def fwd(mod):
+        def run():
+            with torch.no_grad():
+                return mod(x, gt)
+        return run
+
+    def fwd_bwd(mod):
+        def run():
+            leaf = x.detach().requires_grad_(True)
+            percep, style = mod(leaf, gt)
+            (percep if style is None else percep + style).backward()
+            return leaf.grad
+        return run
+
+    r = dict(inner=10, reps=max(5, a.reps // 2))
+    for what, make in (("forward", fwd), ("forward + backward", fwd_bwd)):
+        t = [timed(make(pl), **r), timed(make(ps), **r), timed(make(pl), **r), timed(make(ps), **r)]
+        for label, u, v in ((f"PerceptualLoss {what} {B}x3x256x256", t[0], t[2]), (f"PerceptualStyleLoss {what} {B}x3x256x256 (style weight 400)", t[1], t[3])):
+            best = u if u["us_median"] <= v["us_median"] else v
+            emit(workload=label, ms_median=round(best["us_median"] / 1e3, 3), ms_min=round(best["us_min"] / 1e3, 3), ms_max=round(best["us_max"] / 1e3, 3),
+                 ms_medians=[round(u["us_median"] / 1e3, 3), round(v["us_median"] / 1e3, 3)], **r)
+    emit(workload="operand scale of the last backward", perceptual_log2=int(math.log2(pl.last_scale)), perceptual_style_log2=int(math.log2(ps.last_scale)))
+    del x, gt
+    nb = 2 * B
+    for name, C_, H in TAP_SHAPES:
+        hw = H * H
+        f = torch.randn(nb * hw, C_, device="cuda", generator=g)
+        d = torch.randn(B * hw, C_, device="cuda", generator=g)
+        loss = torch.zeros(1, device="cuda")
+        gram = ops.vgg_gram(f, nb, hw)
+        diff = ops.vgg_gram_loss(gram, loss, 1.0, accumulate=False)
+        tag = f"{name} C{C_} {H}x{H}"
+        inner = max(10, a.inner // 10)
+        nT = C_ // 64
+        for label, fn, nbytes, flop in (
+                (f"vgg_gram fwd {nb} images {tag}", lambda: ops.vgg_gram(f, nb, hw), nb * hw * C_ * 4 + nb * C_ * C_ * 4, 2.0 * nb * hw * 64 * 64 * (nT * (nT + 1) / 2 - nT / 4)),
+                (f"vgg_gram_loss {B}+{B} images {tag}", lambda: ops.vgg_gram_loss(gram, loss, 1.0, accumulate=False), 3 * B * C_ * C_ * 4, None),
+                (f"vgg_gram_bwd {B} images {tag}", lambda: ops.vgg_gram_bwd(f, diff, hw, 1e-9, d), 3 * B * hw * C_ * 4 + B * C_ * C_ * 4, 2.0 * B * hw * C_ * C_)):
+            t = timed(fn, inner=inner)
+            extra = dict(tflops=round(flop / (t["us_median"] * 1e-6) / 1e12, 1)) if flop else {}
+            emit(workload=label, **t, mbytes=round(nbytes / 1e6, 1), gbs_algorithmic=round(nbytes / (t["us_median"] * 1e-6) / 1e9, 1), **extra)
+        del f, d, gram, diff
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--reps", type=int, default=20)
@@ -39,8 +106,11 @@ def main(argv=None):
     ap.add_argument("--inner", type=int, default=200, help="back-to-back calls per timed window of the tap kernels (200 x ~15 us = ~3 ms)")
     ap.add_argument("--batch", type=int, default=8, help="the whole loss is timed at batch 1 and at this batch")
     ap.add_argument("--no-step", action="store_true")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "vgg_bench_line.json"))
+    ap.add_argument("--style", action="store_true", help="time the style loss (csrc/gram.hip) instead; writes profiles/style_bench_line.json")
+    ap.add_argument("--out", default=None, help="default: profiles/vgg_bench_line.json (--style: profiles/style_bench_line.json)")
     a = ap.parse_args(argv)
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "style_bench_line.json" if a.style else "vgg_bench_line.json")
     if not torch.cuda.is_available():
         raise SystemExit("bench_vgg needs the GPU")
     from grl_image_restoration_amd import ops
@@ -67,6 +137,12 @@ def main(argv=None):
         return pick(t[0], t[2]), pick(t[1], t[3]), [t[0]["us_median"], t[2]["us_median"]], [t[1]["us_median"], t[3]["us_median"]]
 
     g = torch.Generator(device="cuda").manual_seed(0)
+    if a.style:
+        style_bench(a, g, emit, timed, ab)
+        os.makedirs(os.path.dirname(a.out), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+        return
     B = 1
     for name, C_, H in TAP_SHAPES:
         W = H
