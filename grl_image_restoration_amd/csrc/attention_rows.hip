@@ -25,7 +25,17 @@
 //     which converts, MFMA and v_dot2c keep (ROWS_REST below) -- and a workgroup starts at the chunk that holds the key rows
 //     nearest to its queries, then wraps cyclically, so that the prime pass sees the keys its queries attend to most.
 //     tools/attn_trip_model.py replays both choices on the bench network: trips per wave 3.9 / 2.4 / 6.0 -> 1.9 / 0.7 / 3.0
-//     (window / tokens->anchors / anchors->tokens); profiles/r07_attention_trips.txt.
+//     (window / tokens->anchors / anchors->tokens); profiles/r07_attention_trips.txt;
+//   * round 8, work the result does not need: in a window (stripe) on the bottom border of a shifted view the key rows of the other
+//     row region carry the mask addend -144.27 * |id difference| for EVERY query of a workgroup whose query rows lie in one region
+//     (always, at the shipped geometries): against offsets set from visible keys their weights are fp16 zeros.  Such a workgroup
+//     steps over those chunks -- no DMA, no barrier, no MFMA, no exponential for them (rows_visit below: 4 of 8 chunks of a 32x32
+//     window, 16 of 32 of a 64x64 stripe) -- and, where no column border is left either, runs the unmasked statement (about 28 VALU
+//     instructions per key row less).  The order is the round-7 one minus the chunks stepped over; buffer parity, prime and
+//     the loop end count VISITED chunks.  Outputs
+//     are bit-identical as long as logit - offset < 119 binades for the masked keys (with the one transient
+//     case of corner windows); a non-finite K or V in a row that is stepped over no longer reaches the output.
+//     profiles/r08_attention_skip_ab.txt.
 // Timing-ablation switches of this file compute WRONG results by construction (they remove work to see what it costs).  They only
 // build together with -DGRL_ABLATION, which tools/attn_asm/build_variants_generic.sh passes for its throw-away variant libraries.
 #if !defined(GRL_ABLATION) && (defined(ROWS_ABL_NOBARRIER) || defined(ROWS_ABL_NODMA) || defined(ROWS_ABL_REPEAT))
@@ -86,6 +96,39 @@ __host__ __device__ inline void rows_span(const RowsGeom& g, int qs, int& hqa, i
     else { sga = 0; sgb = g.qseg - 1; }
 }
 
+// Round 8: the chunk rows a workgroup visits.  In a window (stripe) on the bottom border of a shifted view the rows carry the
+// region labels 1 | 2, split at n - sh (region1d).  A chunk none of whose RROWS key rows has the row label of the workgroup's
+// queries is masked for every (query, key) pair of every wave, whatever the columns are (the combined id is 3 * ry + rx): its
+// weights are zero in fp16 against any offset set from a visible key (DESIGN.md section 5 states the bound) and the workgroup steps over it.
+//   * on only where the mask is, on the bottom border, for a workgroup whose query rows hqa .. hqb carry ONE row label, and whose
+//     start chunk stays; everywhere else [lo, hi) = [0, k.wh) and the workgroup runs as before round 8;
+//   * labels do not decrease along an axis, so the chunk rows that stay are one range [lo, hi) around the start chunk;
+//   * mixed: a chunk that stays holds a key row of the other label (a boundary that is no multiple of RROWS): the row mask is still needed.
+struct RowsVisit {
+    int lo, hi;      // first key rows of the chunks visited: lo, lo + RROWS, .. < hi, in every 32-wide strip
+    bool skip, mixed;
+};
+__host__ __device__ inline bool rows_chunk_skippable(const GrlTokenGrid& k, int wy, int hk0, int rq) {
+    for (int r = 0; r < RROWS; ++r)
+        if (region1d(wy * k.wh + hk0 + r, k.Himg, k.wh, k.shy) == rq) return false;
+    return true;
+}
+__host__ __device__ inline RowsVisit rows_visit(const GrlAttnArgs& p, int wy, int hqa, int hqb, int hk_s) {
+    RowsVisit v;
+    v.lo = 0; v.hi = p.k.wh; v.skip = false; v.mixed = false;
+    if (!p.masked || p.q.shy <= 0 || wy != p.nwy - 1) return v;
+    const int rq = region1d(wy * p.q.wh + hqa, p.q.Himg, p.q.wh, p.q.shy);
+    if (rq != region1d(wy * p.q.wh + hqb, p.q.Himg, p.q.wh, p.q.shy)) return v;   // the workgroup straddles the boundary
+    if (rows_chunk_skippable(p.k, wy, hk_s, rq)) return v;
+    int lo = hk_s, hi = hk_s + RROWS;
+    while (lo > 0 && !rows_chunk_skippable(p.k, wy, lo - RROWS, rq)) lo -= RROWS;
+    while (hi < p.k.wh && !rows_chunk_skippable(p.k, wy, hi, rq)) hi += RROWS;
+    if (lo == 0 && hi == p.k.wh) return v;
+    v.lo = lo; v.hi = hi; v.skip = true;
+    v.mixed = region1d(wy * p.k.wh + lo, p.k.Himg, p.k.wh, p.k.shy) != rq || region1d(wy * p.k.wh + hi - 1, p.k.Himg, p.k.wh, p.k.shy) != rq;
+    return v;
+}
+
 #ifdef ROWS_DEBUG
 __device__ unsigned long long rows_dbg[8];
 #define DBG_T(x) const long long x = __builtin_amdgcn_s_memtime()
@@ -129,12 +172,11 @@ __global__ __launch_bounds__(RW * 64, D32 ? 3 : 4) void attn_rows_kernel(GrlAttn
     // LDS: K[2][KBUF] | V[2][KBUF] | T[2][TBUF]
     constexpr uint32_t VOFF = 2 * KBUF, TOFF = 4 * KBUF;
 
-    const bool border = p.masked && ((p.q.shy > 0 && wy == p.nwy - 1) || (p.q.shx > 0 && wx == p.nwx - 1));
     int hqa, hqb, sga, sgb;
     rows_span(g, qs, hqa, hqb, sga, sgb);
     // reversed table entry of (query (hq, wq), key (hk, wk)) = R0 + (hk - hq) * D + (wk - wq)
     const int R0 = p.trows - 1 - (p.k.wh - 1) * D - (p.k.ww - 1);
-    const int nrc = p.k.wh / RROWS, nch = (p.k.ww >> 5) * nrc;
+    const int nrc = p.k.wh / RROWS;
 
     // ---- this wave's unit: query rows 2*pr, 2*pr+1, segment sg ----
     int unit = qs * g.upw + wave_u;                       // (wave-uniform values stay in SGPRs: the VGPR budget is 128)
@@ -243,6 +285,19 @@ __global__ __launch_bounds__(RW * 64, D32 ? 3 : 4) void attn_rows_kernel(GrlAttn
     }
 #endif
     prefetch(sk_s, hk_s, 0);
+    // Round 8: the chunk rows this workgroup visits (rows_visit; workgroup-uniform, three SGPRs across the loop) and which instance
+    // of the loop it needs: BORDER = some visited chunk can hold a key whose label differs from some query's.  A workgroup that
+    // steps over the other row region's chunks only has the column border left, and its visited chunks' row labels where `mixed`.
+    int hk_lo, hk_hi, nvis;
+    bool border;
+    {
+        const RowsVisit vis = rows_visit(p, wy, hqa, hqb, hk_s);
+        hk_lo = __builtin_amdgcn_readfirstlane(vis.lo);
+        hk_hi = __builtin_amdgcn_readfirstlane(vis.hi);
+        nvis = __builtin_amdgcn_readfirstlane((p.k.ww >> 5) * ((vis.hi - vis.lo) / RROWS));
+        const bool row_border = vis.skip ? vis.mixed : (p.q.shy > 0 && wy == p.nwy - 1);
+        border = p.masked && (row_border || (p.q.shx > 0 && wx == p.nwx - 1));
+    }
 
     // lane parts of the LDS addresses.  K fragment of key l31 of a row: 16-B segment (2 * kstep + half) ^ sw of its 64-B row
     // (k-step 1: ^ 32, inside the statement); V^T through ds_read_b64_tr_b16; bias of (tile 0, key row): table entry
@@ -269,7 +324,7 @@ __global__ __launch_bounds__(RW * 64, D32 ? 3 : 4) void attn_rows_kernel(GrlAttn
     DBG_T(t_loop);
     DBG_ADD(0, t_loop - t_start);
 #pragma unroll 1
-    for (int ch = 0; ch < nch; ++ch) {
+    for (int ch = 0; ch < nvis; ++ch) {   // ch counts VISITED chunks (round 8): buffer parity, prime and the loop end go by it
         DBG_T(t_c0);
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // own DMA pieces of chunk ch landed, own LDS reads retired
         DBG_T(t_c1);
@@ -281,9 +336,9 @@ __global__ __launch_bounds__(RW * 64, D32 ? 3 : 4) void attn_rows_kernel(GrlAttn
         DBG_ADD(2, t_c2 - t_c1);
         const int sk_c = sk, hk_c = hk0;
         hk0 += RROWS;
-        if (hk0 == p.k.wh) { hk0 = 0; ++sk; if (sk == (p.k.ww >> 5)) sk = 0; }
+        if (hk0 == hk_hi) { hk0 = hk_lo; ++sk; if (sk == (p.k.ww >> 5)) sk = 0; }   // the next chunk that is visited
 #ifndef ROWS_ABL_NODMA
-        if (ch + 1 < nch) prefetch(sk, hk0, (ch + 1) & 1);
+        if (ch + 1 < nvis) prefetch(sk, hk0, (ch + 1) & 1);
 #endif
         if (!active) continue;
         const uint32_t par = (uint32_t)(ch & 1) * KBUF;

@@ -31,7 +31,7 @@ __device__ __forceinline__ void load_table(float* tab, const float* src, int tro
     }
 }
 
-__device__ __forceinline__ int region1d(int p, int n, int s, int sh) {
+__host__ __device__ __forceinline__ int region1d(int p, int n, int s, int sh) {
     // ops.py:76-100: labels 0 | 1 | 2 split at n-s and n-sh; a zero shift labels the whole axis alike
     if (sh == 0) return 0;
     return p < n - s ? 0 : (p < n - sh ? 1 : 2);

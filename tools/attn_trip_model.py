@@ -9,7 +9,13 @@ the kernel's waves (2 query rows x 32 queries) and chunks (4 key rows x 32 keys)
   * in later chunks a key row whose logit - offset reaches 14 for any of the wave's 64 queries trips the wave: exact maxima
     of that row and the rest of the chunk, offsets of the queries raised to ceil(max) - REST (never lowered);
   * offsets within EXTRA under msafe = ceil(lazy_ceil - 13.5) go straight there; once every query of the wave is at
-    msafe the wave stops testing (no trips any more).
+    msafe the wave stops testing (no trips any more);
+  * round 8: in a bottom-border window (stripe) of a shifted block a workgroup whose query rows carry one row label steps over
+    the chunks of the other row region (rows_visit of the kernel); the order is the same, minus those chunks, and the share of
+    chunks a wave visits is printed per launch.  Against offsets set from visible keys such a chunk never trips (144 binades under);
+    it could trip in a CORNER window, for a wave with queries whose start chunk lies wholly in the other column region: their offsets
+    sit at the masked level until the first visible chunk arrives.  Those trips go with the chunks (anchors->tokens at side 64, where
+    the only stripe is a corner stripe: 3.01 -> 2.69 trips per wave); the final offsets are the same.
 Not modelled: transposed grid views (the bench geometry has none) and the 2^-12 by which the packed fp16 weight
 reaches 2^14 before the logit reaches 14.
 
@@ -29,9 +35,39 @@ LOG2E = 1.4426950408889634
 RW, RROWS = 4, 4
 
 
-def visit_order(qwin, kwin, order="own"):
+def region1d(p, n, s, sh):
+    """csrc/attn_common.h: labels 0 | 1 | 2 split at n - s and n - sh; a zero shift labels the whole axis alike."""
+    if sh == 0:
+        return 0
+    return 0 if p < n - s else (1 if p < n - sh else 2)
+
+
+def rows_visit(qwh, kwh, qshy, kshy, hqa, hqb, hk_s):
+    """rows_visit of csrc/attention_rows.hip for a window in the LAST window row of a masked launch (the image height drops out:
+    rows qwh - qshy .. of such a window carry label 2, the rows above label 1): first key rows [lo, hi) of the chunks visited."""
+    def lab(h, wh, sh):
+        return region1d(h, wh, wh, sh)
+
+    def skippable(hk0, rq):
+        return all(lab(hk0 + r, kwh, kshy) != rq for r in range(RROWS))
+
+    if qshy <= 0:
+        return 0, kwh
+    rq = lab(hqa, qwh, qshy)
+    if rq != lab(hqb, qwh, qshy) or skippable(hk_s, rq):
+        return 0, kwh
+    lo, hi = hk_s, hk_s + RROWS
+    while lo > 0 and not skippable(lo - RROWS, rq):
+        lo -= RROWS
+    while hi < kwh and not skippable(hi, rq):
+        hi += RROWS
+    return lo, hi
+
+
+def visit_order(qwin, kwin, order="own", bottom=False, qshy=0, kshy=0):
     """Per workgroup: (units = [(first query row, first query column)], chunks = [(sk, chunk row)] in visiting order).
-    Mirrors rows_geom / rows_span and the start chunk of attn_rows_kernel."""
+    Mirrors rows_geom / rows_span, the start chunk and rows_visit of attn_rows_kernel.  bottom: the window lies in the last window
+    row of a launch whose rows are shifted by qshy (queries) / kshy (keys)."""
     (qwh, qww), (kwh, kww) = qwin, kwin
     qseg, nks, nrc = qww // 32, kww // 32, kwh // RROWS
     units = (qwh // 2) * qseg
@@ -56,18 +92,32 @@ def visit_order(qwin, kwin, order="own"):
                     seq.append(lo); lo -= 1
         else:
             seq = [(c0 + i) % n for i in range(n)]
+        if bottom:
+            lo, hi = rows_visit(qwh, kwh, qshy, kshy, hqa, hqb, RROWS * (c0 % nrc))
+            seq = [c for c in seq if lo <= RROWS * (c % nrc) < hi]
         out.append(([(2 * (u // qseg), 32 * (u % qseg)) for u in range(u0, u1 + 1)], [divmod(c, nrc) for c in seq]))
     return out
 
 
-def simulate(S, qwin, kwin, floor, ceil_, rest, extra, order="own"):
+def simulate(S, qwin, kwin, floor, ceil_, rest, extra, order="own", bottom=None, shy=(0, 0)):
     """S: (n, qwh, qww, kwh, kww) log2-domain logits (bias and mask included) of n (window, head) pairs; floor / ceil_: (n,)
-    lazy_floor / lazy_ceil of each pair's head.  Returns (trips (n, waves) int, final offsets (n, qwh, qww))."""
+    lazy_floor / lazy_ceil of each pair's head; bottom: (n,) bool, the pair's window lies in the last window row of a launch
+    shifted by shy = (query rows, key rows).  Returns (trips (n, waves) int, final offsets (n, qwh, qww), chunks visited (n, waves))."""
+    if bottom is not None and bottom.any() and not bottom.all():
+        parts = [(sel, simulate(S[sel], qwin, kwin, floor[sel], ceil_[sel], rest, extra, order, bottom[sel], shy)) for sel in (bottom, ~bottom)]
+        outs = []
+        for j in range(3):
+            t = torch.empty(S.shape[0], *parts[0][1][j].shape[1:], dtype=parts[0][1][j].dtype)
+            for sel, res in parts:
+                t[sel] = res[j]
+            outs.append(t)
+        return tuple(outs)
+    is_bottom = bottom is not None and bool(bottom.all())
     n = S.shape[0]
     msafe = torch.ceil(ceil_ - 13.5).view(n, 1)
     m_all = floor.view(n, 1, 1).expand(n, qwin[0], qwin[1]).clone()
-    trips = []
-    for units, chunks in visit_order(qwin, kwin, order):
+    trips, visited = [], []
+    for units, chunks in visit_order(qwin, kwin, order, is_bottom, shy[0], shy[1]):
         for (r0, c0) in units:
             Sw = S[:, r0:r0 + 2, c0:c0 + 32].reshape(n, 64, kwin[0], kwin[1])
             m = m_all[:, r0:r0 + 2, c0:c0 + 32].reshape(n, 64).clone()
@@ -96,8 +146,9 @@ def simulate(S, qwin, kwin, floor, ceil_, rest, extra, order="own"):
                 repair(mx, trip)
                 t += trip.long()
             trips.append(t)
+            visited.append(torch.full((n,), len(chunks), dtype=torch.long))
             m_all[:, r0:r0 + 2, c0:c0 + 32] = m.view(n, 2, 32)
-    return torch.stack(trips, dim=1), m_all
+    return torch.stack(trips, dim=1), m_all, torch.stack(visited, dim=1)
 
 
 def fp16_weight_error(S, V, m):
@@ -144,12 +195,15 @@ def main():
     def window_attention(qkv, x_size, window, shift, nh, p, prefix):
         geom["w"] = (tuple(window), tuple(window))
         geom["kinds"] = ["window"]
+        geom["nw"], geom["shy"] = (x_size[0] // window[0], x_size[1] // window[1]), {"window": (shift, shift)}
         return win_attn(qkv, x_size, window, shift, nh, p, prefix)
 
     def anchor_stripe_attention(qkv, anchor, x_size, stripe, shift, do_shift, df, nh, p, prefix):
         astripe = tuple(s // df for s in stripe)
         geom["kinds"] = ["anchors->tokens", "tokens->anchors"]
         geom["anchors->tokens"], geom["tokens->anchors"] = (astripe, tuple(stripe)), (tuple(stripe), astripe)
+        sy = shift[0] if do_shift else 0
+        geom["nw"], geom["shy"] = (x_size[0] // stripe[0], x_size[1] // stripe[1]), {"anchors->tokens": (sy // df, sy), "tokens->anchors": (sy, sy // df)}
         return stripe_attn(qkv, anchor, x_size, stripe, shift, do_shift, df, nh, p, prefix)
 
     def cosine_attention(q, k, v, p, prefix, table, index, mask):
@@ -167,11 +221,13 @@ def main():
         S = (s * LOG2E).reshape(B_ * nh, Nq, Nk).float()
         floor = tables.lazy_floor(scale).repeat(B_)
         ceil_ = tables.lazy_ceil(scale, tables.kernel_table(bt)).repeat(B_)
+        nwy, nwx = geom["nw"]
+        bottom = ((torch.arange(B_) % (nwy * nwx)) // nwx == nwy - 1).repeat_interleave(nh) if mask is not None else None
         for rest, extra, order in combos:
-            trips, m = simulate(S.view(-1, *qwin, *kwin), qwin, kwin, floor, ceil_, rest, extra, order)
+            trips, m, vis = simulate(S.view(-1, *qwin, *kwin), qwin, kwin, floor, ceil_, rest, extra, order, bottom, geom["shy"][kind])
             err = fp16_weight_error(S, v.reshape(B_ * nh, Nk, -1), m.reshape(B_ * nh, Nq))
-            st = stats.setdefault((rest, order, kind), [0, 0, 0.0, kwin[0] * kwin[1] // (RROWS * 32)])
-            st[0] += int(trips.sum()); st[1] += trips.numel(); st[2] = max(st[2], err)
+            st = stats.setdefault((rest, order, kind), [0, 0, 0.0, kwin[0] * kwin[1] // (RROWS * 32), 0])
+            st[0] += int(trips.sum()); st[1] += trips.numel(); st[2] = max(st[2], err); st[4] += int(vis.sum())
         return cos_attn(q, k, v, p, prefix, table, index, mask)
 
     O.window_attention, O.anchor_stripe_attention, O.cosine_attention = window_attention, anchor_stripe_attention, cosine_attention
@@ -179,11 +235,11 @@ def main():
         O.grl_forward(x, cfg, sd)
     for rest, extra, order in combos:
         print(f"# side {a.side}  rest {rest:g}  extra {extra:g}  order {order}  scales {'random-init' if a.random_init_scales else 'checkpoint-like (seed 7)'}")
-        print(f"{'launch (chunks per wave)':28s} {'trips/wave':>10s} {'waves':>8s} {'fp16-weight rel. error':>24s}")
+        print(f"{'launch (chunks per wave)':28s} {'trips/wave':>10s} {'waves':>8s} {'fp16-weight rel. error':>24s} {'chunks visited':>15s}")
         for kind in ("window", "tokens->anchors", "anchors->tokens"):
             if (rest, order, kind) in stats:
-                t, w, e, nch = stats[(rest, order, kind)]
-                print(f"{kind + ' (' + str(nch) + ')':28s} {t / w:10.3f} {w:8d} {e:24.3e}")
+                t, w, e, nch, v = stats[(rest, order, kind)]
+                print(f"{kind + ' (' + str(nch) + ')':28s} {t / w:10.3f} {w:8d} {e:24.3e} {v / (w * nch):15.3f}")
 
 
 if __name__ == "__main__":
