@@ -36,11 +36,6 @@
 //     are bit-identical as long as logit - offset < 119 binades for the masked keys (with the one transient
 //     case of corner windows); a non-finite K or V in a row that is stepped over no longer reaches the output.
 //     profiles/r08_attention_skip_ab.txt.
-// Timing-ablation switches of this file compute WRONG results by construction (they remove work to see what it costs).  They only
-// build together with -DGRL_ABLATION, which tools/attn_asm/build_variants_generic.sh passes for its throw-away variant libraries.
-#if !defined(GRL_ABLATION) && (defined(ROWS_ABL_NOBARRIER) || defined(ROWS_ABL_NODMA) || defined(ROWS_ABL_REPEAT))
-#error "timing-ablation switch without -DGRL_ABLATION: the results of such a build are wrong"
-#endif
 #include "common.h"
 #include "grl_hip_internal.h"
 #include "attn_common.h"
@@ -65,13 +60,9 @@ constexpr int rows_lds(bool d32) { return 4 * KBUF + 2 * rows_tbuf(d32); }
 // a relative one of 2^-11.  Bound of what that costs: 1024 keys all rounding the same way move the denominator by 2^-15, so
 // the lowest level a row maximum may rest at is -3, i.e. in (2^-4, 2^-3]: at most 2^-11 = 4.9e-4 of the denominator, a third of
 // the tests' tolerance (random signs: 32 x less).  ROWS_REST - ROWS_EXTRA is that lowest level.
-// (-DROWS_REST_LEVEL / -DROWS_EXTRA_LEVEL / -DROWS_ORDER_TOP: the variant builds behind profiles/r07_attention_trips.txt.)
-#ifndef ROWS_REST_LEVEL
-#define ROWS_REST_LEVEL (-2)
-#endif
-#ifndef ROWS_EXTRA_LEVEL
-#define ROWS_EXTRA_LEVEL (ROWS_REST_LEVEL + 3 > 3 ? 3 : ROWS_REST_LEVEL + 3)
-#endif
+// (Other levels and the top-first chunk order: the variant builds, since removed, behind profiles/r07_attention_trips.txt.)
+constexpr int ROWS_REST_LEVEL = -2;
+constexpr int ROWS_EXTRA_LEVEL = 1;
 constexpr float ROWS_REST = (float)(ROWS_REST_LEVEL);
 constexpr float ROWS_EXTRA = (float)(ROWS_EXTRA_LEVEL);   // an offset this close under msafe (overflow test no longer needed) goes straight there
 static_assert(ROWS_EXTRA_LEVEL >= 0 && ROWS_REST_LEVEL - ROWS_EXTRA_LEVEL >= -3 && ROWS_REST_LEVEL <= 8, "resting level outside what the fp16 weights allow");
@@ -129,17 +120,6 @@ __host__ __device__ inline RowsVisit rows_visit(const GrlAttnArgs& p, int wy, in
     return v;
 }
 
-#ifdef ROWS_DEBUG
-__device__ unsigned long long rows_dbg[8];
-#define DBG_T(x) const long long x = __builtin_amdgcn_s_memtime()
-#define DBG_ADD(i, v) dbg_acc[i] += (unsigned long long)(v)
-#define DBG_FLUSH() do { if (lane_id() == 0) for (int i_ = 0; i_ < 8; ++i_) atomicAdd(&rows_dbg[i_], dbg_acc[i_]); } while (0)
-#else
-#define DBG_T(x)
-#define DBG_ADD(i, v)
-#define DBG_FLUSH()
-#endif
-
 // D32: head_dim 32 (GRL-Small).  All 32 head-dim slots of Q / K / V are data, so the running offset lives in two VGPRs
 // (nm0 / nm1 = -m of the lane's query in tile 0 / 1) that the statement adds to the logits, and the softmax denominator is
 // summed from the packed fp16 weights (l0 / l1, one partial sum per half-wave); 48 KB of LDS -> 3 workgroups per CU.
@@ -147,10 +127,6 @@ template <bool D32>
 __global__ __launch_bounds__(RW * 64, D32 ? 3 : 4) void attn_rows_kernel(GrlAttnArgs p) {
     constexpr int TB = rows_tbuf(D32);
     extern __shared__ __attribute__((aligned(1024))) char smem[];
-#ifdef ROWS_DEBUG
-    unsigned long long dbg_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#endif
-    DBG_T(t_start);
     const int wave = threadIdx.x >> 6;
     // the lane id is recomputed (2 VALU) wherever it is needed instead of being kept in a VGPR across the key loop
     // (volatile asm: the compiler would hoist a builtin out of the chunk loop and spill what it derives from it)
@@ -268,22 +244,16 @@ __global__ __launch_bounds__(RW * 64, D32 ? 3 : 4) void attn_rows_kernel(GrlAttn
             }
         }
     };
-#ifdef ROWS_STAGGER
-    __builtin_amdgcn_s_sleep(1);
-    for (int i_ = 0; i_ < (int)(blockIdx.x >> 3 & 3) * 4; ++i_) __builtin_amdgcn_s_sleep(8);   // experiment: de-phase the workgroups of a CU
-#endif
     // Chunk order (round 7): start at the chunk that holds the key rows nearest to the workgroup's queries (centre of its query rows
     // and segments mapped to key coordinates: the same rows for window attention, x df / : df between anchors and tokens), then
     // cyclically over (sk, hk0).  The prime pass takes the offsets from the first chunk, and the keys a query attends to most are
-    // the ones around it: fewer later chunks exceed what the first one set.  ROWS_ORDER_TOP: the old order, (0, 0) upward.
+    // the ones around it: fewer later chunks exceed what the first one set.  The old order was (0, 0) upward.
     int sk_s = 0, hk_s = 0;
-#ifndef ROWS_ORDER_TOP
     {
         const int rc = ((hqa + hqb + 1) * p.k.wh) / (2 * p.q.wh * RROWS), sc = ((sga + sgb + 1) * p.k.ww) / (2 * p.q.ww);
         hk_s = __builtin_amdgcn_readfirstlane(RROWS * (rc < nrc ? rc : nrc - 1));
         sk_s = __builtin_amdgcn_readfirstlane(sc < (p.k.ww >> 5) ? sc : (p.k.ww >> 5) - 1);
     }
-#endif
     prefetch(sk_s, hk_s, 0);
     // Round 8: the chunk rows this workgroup visits (rows_visit; workgroup-uniform, three SGPRs across the loop) and which instance
     // of the loop it needs: BORDER = some visited chunk can hold a key whose label differs from some query's.  A workgroup that
@@ -321,25 +291,14 @@ __global__ __launch_bounds__(RW * 64, D32 ? 3 : 4) void attn_rows_kernel(GrlAttn
     constexpr bool BORDER = decltype(border_tag)::value;
     int sk = sk_s, hk0 = hk_s;
     int nochk = 0;   // wave-uniform: every query's offset is within 13.5 of the head's logit bound, no weight can reach 2^14 any more
-    DBG_T(t_loop);
-    DBG_ADD(0, t_loop - t_start);
 #pragma unroll 1
     for (int ch = 0; ch < nvis; ++ch) {   // ch counts VISITED chunks (round 8): buffer parity, prime and the loop end go by it
-        DBG_T(t_c0);
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // own DMA pieces of chunk ch landed, own LDS reads retired
-        DBG_T(t_c1);
-#ifndef ROWS_ABL_NOBARRIER
         __builtin_amdgcn_s_barrier();                                  // everybody's; and all are done with the buffers of chunk ch-1
-#endif
-        DBG_T(t_c2);
-        DBG_ADD(1, t_c1 - t_c0);
-        DBG_ADD(2, t_c2 - t_c1);
         const int sk_c = sk, hk_c = hk0;
         hk0 += RROWS;
         if (hk0 == hk_hi) { hk0 = hk_lo; ++sk; if (sk == (p.k.ww >> 5)) sk = 0; }   // the next chunk that is visited
-#ifndef ROWS_ABL_NODMA
         if (ch + 1 < nvis) prefetch(sk, hk0, (ch + 1) & 1);
-#endif
         if (!active) continue;
         const uint32_t par = (uint32_t)(ch & 1) * KBUF;
         // scalar part of the bias address of (tile 0, key row hk_c), advanced by the statement row by row
@@ -357,13 +316,6 @@ __global__ __launch_bounds__(RW * 64, D32 ? 3 : 4) void attn_rows_kernel(GrlAttn
             ids = __builtin_amdgcn_readfirstlane(ids);
         }
         int rs = 0, last_trip = -1;
-#ifdef ROWS_ABL_REPEAT   // timing experiment: the rows of chunk 0 ROWS_ABL_REPEAT times, no other chunks (results are wrong)
-        if (ch > 0) continue;
-        for (int rep_ = 0; rep_ < ROWS_ABL_REPEAT; ++rep_) {
-        rs = 0; sb = (uint32_t)(ch & 1) * TB + 4 * (R0 + (hk_c - hq0) * D + 32 * (sk_c - sg) - window_lo(sk_c, hk_c));
-#endif
-        DBG_T(t_c3);
-        DBG_ADD(3, t_c3 - t_c2);
         // The offsets start at the logit floor, so the very first row of a wave always "tripped": half a row of wasted work, the exit
         // from the statement and the repair -- 2.5 rows of 32 (measured).  The first chunk now enters the repair code directly
         // (`prime`): its exact maxima set the offsets before any exponential is taken.
@@ -399,8 +351,7 @@ __global__ __launch_bounds__(RW * 64, D32 ? 3 : 4) void attn_rows_kernel(GrlAttn
                                [d4] "s"(d4), [rs] "s"(rs_u), [par] "s"(par), [nochk] "s"(nochk_u)
                              : ATTN_ROWS_CLOBBER);
             }
-            if (!prime && done == RROWS) { DBG_T(t_c4); DBG_ADD(4, t_c4 - t_c3); break; }
-            DBG_ADD(6, 1);
+            if (!prime && done == RROWS) break;
             // ---- cold: a weight of key row `done` reached 2^14.  Exact row maxima -> raise the offsets, rescale O, redo the row ----
             if (!prime && done == last_trip) {
                 // the row tripped again right after its offsets were raised: only non-finite logits do that.  Poison the
@@ -424,7 +375,7 @@ __global__ __launch_bounds__(RW * 64, D32 ? 3 : 4) void attn_rows_kernel(GrlAttn
                 uint32_t blx = bl;
                 asm volatile("" : "+v"(blx));
                 // Exact maxima of the tripping row AND of the rows of the chunk still to come (round 4): at checkpoint-like logit
-                // scales 20 of a wave's 32 key rows tripped and a trip costs 2.5 rows (measured, tools/attn_asm/dbg_rows.py); the
+                // scales 20 of a wave's 32 key rows tripped and a trip costs 2.5 rows (measured with a timing-probe build, since removed); the
                 // chunk's K rows and table window are in LDS anyway, so one repair now covers the whole chunk.
                 float mx0 = NEG_BIG, mx1 = NEG_BIG;
 #pragma unroll 1
@@ -478,18 +429,10 @@ __global__ __launch_bounds__(RW * 64, D32 ? 3 : 4) void attn_rows_kernel(GrlAttn
             }
             rs = done;
         }
-#ifdef ROWS_ABL_REPEAT
-        }
-#endif
     }
     };
-    DBG_T(t_l0);
     if (border) chunks(std::true_type{});
     else chunks(std::false_type{});
-    DBG_T(t_l1);
-    DBG_ADD(5, t_l1 - t_l0);
-    DBG_ADD(7, 1);
-    DBG_FLUSH();
     if (!active) return;
 
     {
@@ -532,15 +475,6 @@ bool grl_attn_rows_supported(const GrlAttnArgs& p) {
     }
     return true;
 }
-
-#ifdef ROWS_DEBUG
-extern "C" int grl_attn_rows_debug(unsigned long long* out8, int reset) {
-    hipDeviceSynchronize();
-    hipMemcpyFromSymbol(out8, HIP_SYMBOL(rows_dbg), sizeof(unsigned long long) * 8);
-    if (reset) { unsigned long long z[8] = {0}; hipMemcpyToSymbol(HIP_SYMBOL(rows_dbg), z, sizeof(z)); }
-    return 0;
-}
-#endif
 
 int grl_attn_rows_launch(const GrlAttnArgs& p, hipStream_t st) {
     const RowsGeom g = rows_geom(p);

@@ -18,10 +18,6 @@
 //   * weight rows are 32 bytes, so a b128 fragment read has a 32-byte lane stride: the two 16-byte halves of row n sit at position
 //     h ^ ((n >> 3) & 1) (source-side for the DMA) -- 16 rows with distinct n mod 16 cover 16 distinct 16-byte bank groups; the 64-byte
 //     pixel rows are swizzled by (pix >> 2) & 3 to the same effect (conflict-free for every tap shift).
-// Timing-ablation switches (C9_ABL_*) compute WRONG results by construction; they only build together with -DGRL_ABLATION.
-#if !defined(GRL_ABLATION) && (defined(C9_ABL_NOMFMA) || defined(C9_ABL_NOSTORE) || defined(C9_ABL_NORESID) || defined(C9_ABL_NOINPUT) || defined(C9_ABL_NODMA))
-#error "timing-ablation switch without -DGRL_ABLATION: the results of such a build are wrong"
-#endif
 #include "common.h"
 #include "grl_hip_internal.h"
 #include <stdlib.h>
@@ -151,11 +147,7 @@ __global__ __launch_bounds__(C9_THREADS) void conv192_kernel(GrlConvArgs p) {
             // own DMA pieces of chunk c landed (and, at cc = 0, own LDS writes).  The memory counter retires in order: at cc = 1 the
             // C9_INV halo loads of the next group were issued BEHIND the pieces of this chunk and may stay in flight (they get two
             // chunks, ~7 k cycles, before the wait of cc = 2 retires them with the next pieces)
-#if defined(C9_ABL_NOINPUT) || defined(C9_ABL_NODMA)
-            if (false) {}
-#else
             if (cc == 1 && g + 1 < ngroups) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(C9_INV) : "memory");
-#endif
             else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();                                  // everybody's; all readers of the other weight buffer are done
             // The seven DMA pieces of the next chunk are NOT issued here in one burst: an LDS-DMA instruction holds the issuing wave for
@@ -181,22 +173,14 @@ __global__ __launch_bounds__(C9_THREADS) void conv192_kernel(GrlConvArgs p) {
 #pragma unroll
             for (int tap = 0; tap < 9; ++tap) {
                 const int cur = tap & 1;
-#ifndef C9_ABL_NODMA
                 if (tap < WPW && more) dma_piece(tap, c + 1, buf ^ 1);
-#endif
-#ifndef C9_ABL_NOINPUT
                 if (tap == WPW && cc == 0 && g + 1 < ngroups) load_input(g + 1);
-#endif
                 if (tap + 1 < 9) frags(tap + 1, fa[cur ^ 1], fb[cur ^ 1]);
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int i = 0; i < 3; ++i) {
-#ifndef C9_ABL_NOMFMA
                     acc[i][0] = mfma32_f16(fa[cur][i], fb[cur][0], acc[i][0]);
                     acc[i][1] = mfma32_f16(fa[cur][i], fb[cur][1], acc[i][1]);
-#else
-                    acc[i][0][0] += (float)fa[cur][i][0] + (float)fb[cur][0][0]; acc[i][1][0] += (float)fa[cur][i][1] + (float)fb[cur][1][0];
-#endif
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -238,18 +222,11 @@ __global__ __launch_bounds__(C9_THREADS) void conv192_kernel(GrlConvArgs p) {
             const int gx = x0 + px;
             float4 v = *(const float4*)(et + px * EROW + q * 16);
             if (gy < p.H && gx < p.W) {
-#ifndef C9_ABL_NORESID
                 const int64_t row = ((int64_t)b * p.H + gy) * p.W + gx;
                 if (p.resid != nullptr) {
                     const float4 r4 = *(const float4*)(p.resid + row * p.ldr + 96 * wn + 4 * q);
                     v.x += r4.x; v.y += r4.y; v.z += r4.z; v.w += r4.w;
                 }
-#else
-                const int64_t row = ((int64_t)b * p.H + gy) * p.W + gx;
-#endif
-#ifdef C9_ABL_NOSTORE
-                if (v.x == 12345.678f)
-#endif
                 *(float4*)((float*)p.out + row * p.ldo + 96 * wn + 4 * q) = v;
             }
         }

@@ -14,11 +14,6 @@
 //     2*SPC n-tiles x K/32 MFMAs, the per-slot L2 normalisation needs two cross-lane adds, and the store of a slot
 //     is 1 KiB contiguous per wave (head-plane layout).
 // DMA ordering is by hand (inline asm, counted s_waitcnt before the publishing barrier) as in csrc/mlp.hip.
-// Timing-ablation switches of this file compute WRONG results by construction (they remove work to see what it costs).  They only
-// build together with -DGRL_ABLATION, which tools/attn_asm/build_variants_generic.sh passes for its throw-away variant libraries.
-#if !defined(GRL_ABLATION) && (defined(QKV_ABL_NOXDMA) || defined(QKV_ABL_NOMFMA) || defined(QKV_ABL_NOSTORE))
-#error "timing-ablation switch without -DGRL_ABLATION: the results of such a build are wrong"
-#endif
 #include "common.h"
 #include <stdlib.h>
 
@@ -119,9 +114,7 @@ __global__ __launch_bounds__(WV * 64) void qkv_kernel(GrlQkvArgs p) {
             __builtin_amdgcn_s_barrier();
             const char* cur = smem + (it & 1) * S::BUFP;
             fetch(c + 1 < nchunks ? c + 1 : 0, ((it + 1) & 1) * S::BUFP);
-#ifndef QKV_ABL_NOXDMA
             for (int q = c * WV + wave_u; q < XPIECES; q += nchunks * WV) fetch_x(next_tile, q);
-#endif
 #pragma unroll
             for (int si = 0; si < SPC / SLS; ++si) {
                 const int sl = sl0 + si * SLS;
@@ -138,11 +131,7 @@ __global__ __launch_bounds__(WV * 64) void qkv_kernel(GrlQkvArgs p) {
                 __builtin_amdgcn_sched_barrier(0);
                 f32x4 h0 = f32x4{0, 0, 0, 0}, h1 = f32x4{0, 0, 0, 0};
 #pragma unroll
-#ifdef QKV_ABL_NOMFMA
-                for (int s = 0; s < 1; ++s) {
-#else
                 for (int s = 0; s < KSTEPS; ++s) {
-#endif
                     h0 = mfma16_gemm(wa[s], a[s], h0);
                     h1 = mfma16_gemm(wb_[s], a[s], h1);
                 }
@@ -161,11 +150,7 @@ __global__ __launch_bounds__(WV * 64) void qkv_kernel(GrlQkvArgs p) {
                 lo.x = pack_f16(h0[0] * f, h0[1] * f); lo.y = pack_f16(h0[2] * f, h0[3] * f);
                 hi.x = pack_f16(h1[0] * f, h1[1] * f); hi.y = pack_f16(h1[2] * f, c31);
                 if (si == SPC / SLS - 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // next chunk + token pieces landed; older stores long done
-#ifdef QKV_ABL_NOSTORE
-                if (valid && lo.x == 0x12345678u) {
-#else
                 if (valid) {
-#endif
                     f16* o = orow + (int64_t)(c * SPC + sl) * p.out_plane_stride;
                     *(uint2*)(o) = lo;           // channels 4*g4 + [0..3]
                     *(uint2*)(o + 16) = hi;      // channels 16 + 4*g4 + [0..3]

@@ -6,7 +6,7 @@
 // (models/common/mixed_attn_block_efficient.py:85-90,:39).  Round 2 ran two kernels (csrc/qkv.hip + the pooled variant of
 // csrc/linear.hip) that both read x; the anchor launch cost 44 us alone and 168 us inside the two-stream bench.
 //
-// Why it is built the way it is (measured on the round-2 kernel, tools/attn_asm/build_variants_generic.sh): without any HBM
+// Why it is built the way it is (measured on the round-2 kernel, timing-ablation build, since removed): without any HBM
 // traffic that kernel still took 105 of its 160 us -- 193 instructions per (slot, 16 tokens) of which 12 were MFMAs: it was
 // bound by instruction issue, not by bandwidth or LDS.  So:
 //   * mfma_f32_32x32x16_f16, a wave owns 32 tokens (2 image rows x 16 columns): half the MFMA / LDS-read instructions per
@@ -17,11 +17,6 @@
 //   * tiles are 2 image rows x 64 columns (128 tokens), token pieces and weight chunks arrive by LDS-DMA as in round 2;
 //     DMA completion is awaited right before a chunk's stores (vmcnt also counts stores: a wait at the chunk top would sit out
 //     the write acknowledgements of the previous chunk every time).
-// Timing-ablation switches of this file compute WRONG results by construction (they remove work to see what it costs).  They only
-// build together with -DGRL_ABLATION, which tools/attn_asm/build_variants_generic.sh passes for its throw-away variant libraries.
-#if !defined(GRL_ABLATION) && (defined(QA_ABL_NOXDMA) || defined(QA_ABL_NOSTORE) || defined(QA_TOKEN_MAJOR) || defined(QS_ABL_NOLO) || defined(QS_ABL_NOFP8))
-#error "timing-ablation switch without -DGRL_ABLATION: the results of such a build are wrong"
-#endif
 #include "common.h"
 #include "grl_hip_internal.h"
 #include <stdlib.h>
@@ -158,9 +153,7 @@ __global__ __launch_bounds__(QW * 64) void qkv_anchor_kernel(GrlQkvAnchorArgs p)
             __builtin_amdgcn_s_barrier();
             const char* cur = smem + (it & 1) * S::BUFP;
             fetch(c + 1 < nchunks ? c + 1 : 0, ((it + 1) & 1) * S::BUFP);
-#ifndef QA_ABL_NOXDMA
             for (int q = c * QW + wave_u; q < S::XPIECES; q += nchunks * QW) fetch_x(next_origin, q);
-#endif
             const int slot = 2 * c + hs;
             if (slot >= tslots) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); continue; }   // pad slot of an odd total
             const char* wb = cur + hs * S::SLOT;
@@ -211,18 +204,11 @@ __global__ __launch_bounds__(QW * 64) void qkv_anchor_kernel(GrlQkvAnchorArgs p)
             for (int r = 0; r < 16; ++r) v[r] *= f;
             if (gs < 0.0f && half) v[15] = 1.0f;   // channel (15 & 3) + 8 * (15 >> 2) + 4 = 31
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // next chunk + token pieces landed; older stores long done
-#ifdef QA_ABL_NOSTORE
-            if (v[0] != 12345.678f) continue;
-#endif
             if (is_anc) {
                 f16* o = (f16*)p.anc + (int64_t)(slot - p.nslots) * p.anc_plane_stride + m_anc * 32;
                 if (gs != 0.0f) store_slot<false>(o, v, half, anc_lane); else store_slot<true>(o, v, half, anc_lane);
             } else {
-#ifdef QA_TOKEN_MAJOR   // timing experiment: token-major output rows [m][nslots * 32]
-                f16* o = (f16*)p.out + m_tok * (p.nslots * 32) + slot * 32;
-#else
                 f16* o = (f16*)p.out + (int64_t)slot * p.out_plane_stride + m_tok * 32;
-#endif
                 if (gs != 0.0f) store_slot<false>(o, v, half); else store_slot<true>(o, v, half);
             }
         }
@@ -477,20 +463,8 @@ __device__ __forceinline__ f32x16 mfma64_fp8(i32x8 a, i32x8 b, f32x16 c) {
     return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, c, 0, 0, 0, 0, 0, 0);
 }
 
-#ifdef QS_DEBUG   // timing probes (s_memtime ticks, 10 ns): [wave 0..7][region 0..7], summed over workgroups and tiles
-__device__ unsigned long long qs_dbg[64];
-#define QS_T(x) const long long x = __builtin_amdgcn_s_memtime()
-#define QS_ADD(i, v) qs_acc[i] += (unsigned long long)(v)
-#else
-#define QS_T(x)
-#define QS_ADD(i, v)
-#endif
-
 __global__ __launch_bounds__(QR_W * 64) void qkv_split_kernel(GrlQkvAnchorArgs p) {
     using S = QaShape<QR_KS>;
-#ifdef QS_DEBUG
-    unsigned long long qs_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#endif
     extern __shared__ __attribute__((aligned(1024))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int half = lane >> 5, j = lane & 31;
@@ -597,28 +571,16 @@ __global__ __launch_bounds__(QR_W * 64) void qkv_split_kernel(GrlQkvAnchorArgs p
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (the compiler-tracked loads of the prologue)
         if (nsub > 1) issue(1);
         for (int it = 0; it < nsub; ++it) {
-            QS_T(l0);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
-            QS_T(l1);
-            QS_ADD(0, l1 - l0);
             if (it + 1 >= nsub) continue;
             char* xn = smem + ((it + 1) & 1) * QS_XBUF;
             landed();
-            QS_T(l2);
-            QS_ADD(1, l2 - l1);
 #pragma unroll
             for (int k = 0; k < 24; ++k)
                 x_put(xn, (k / 3) * 4 * QR_XROW + woff[k % 3], (k / 3) * 4 * QS_X8ROW + woff8[k % 3], float4{nb[k][0], nb[k][1], nb[k][2], nb[k][3]});
-            QS_T(l3);
-            QS_ADD(2, l3 - l2);
             if (it + 2 < nsub) issue(it + 2);
-            QS_T(l4);
-            QS_ADD(3, l4 - l3);
         }
-#ifdef QS_DEBUG
-        if (lane == 0) for (int i = 0; i < 8; ++i) atomicAdd(&qs_dbg[8 * wave_u + i], qs_acc[i]);
-#endif
         return;
     }
 
@@ -714,39 +676,25 @@ __global__ __launch_bounds__(QR_W * 64) void qkv_split_kernel(GrlQkvAnchorArgs p
             const int c = s >> 2, u = s & 3;
             f16x8 nh = bh, nl = bl;
             if (s + 1 < QR_KS) { nh = *(const f16x8*)(rowp + 32 * (s + 1)); nl = *(const f16x8*)(rowp + QS_XT + 32 * (s + 1)); }
-#ifndef QS_ABL_NOFP8
             if (u == 0) {
                 x8 = ld32(row8 + 64 * c, row8 + 64 * c + 16);
                 wa8 = ld32(la + 64 * c + seg0, la + 64 * c + seg1);
                 wb8 = ld32(lb + 64 * c + seg0, lb + 64 * c + seg1);
             }
-#endif
             __builtin_amdgcn_sched_barrier(0);
             acc0 = mfma32_f16(A[0][s], bh, acc0);
             acc1 = mfma32_f16(A[1][s], bh, acc1);
-#ifndef QS_ABL_NOLO
             acc0 = mfma32_f16(A[0][s], bl, acc0);
             acc1 = mfma32_f16(A[1][s], bl, acc1);
-#endif
-#ifndef QS_ABL_NOFP8
             if (u == 3) {
                 acc0 = mfma64_fp8(wa8, x8, acc0);
                 acc1 = mfma64_fp8(wb8, x8, acc1);
             }
-#endif
             __builtin_amdgcn_sched_barrier(0);
             bh = nh; bl = nl;
         }
-#ifdef QS_DEBUG
-        asm volatile("s_nop 0" : "+v"(acc0), "+v"(acc1));   // the MFMA results have arrived
-#endif
-        QS_T(c2);
         finish(acc0, sa, two_2e, m_tok, m_anc);
-        QS_T(c3);
         finish(acc1, sb, two_2e, m_tok, m_anc);
-        QS_T(c4);
-        QS_ADD(2, c3 - c2);
-        QS_ADD(3, c4 - c3);
     };
     auto do_single = [&](const char* rowp, const char* row8, int64_t m_tok, int64_t m_anc) {
         if (c_split) {
@@ -758,20 +706,14 @@ __global__ __launch_bounds__(QR_W * 64) void qkv_split_kernel(GrlQkvAnchorArgs p
                 const int c = s >> 2, u = s & 3;
                 f16x8 nh = bh, nl = bl;
                 if (s + 1 < QR_KS) { nh = *(const f16x8*)(rowp + 32 * (s + 1)); nl = *(const f16x8*)(rowp + QS_XT + 32 * (s + 1)); }
-#ifndef QS_ABL_NOFP8
                 if (u == 0) {
                     x8 = ld32(row8 + 64 * c, row8 + 64 * c + 16);
                     wc8 = ld32(lc + 64 * c + seg0, lc + 64 * c + seg1);
                 }
-#endif
                 __builtin_amdgcn_sched_barrier(0);
                 acc = mfma32_f16(A[2][s], bh, acc);
-#ifndef QS_ABL_NOLO
                 acc = mfma32_f16(A[2][s], bl, acc);
-#endif
-#ifndef QS_ABL_NOFP8
                 if (u == 3) acc = mfma64_fp8(wc8, x8, acc);
-#endif
                 __builtin_amdgcn_sched_barrier(0);
                 bh = nh; bl = nl;
             }
@@ -791,15 +733,9 @@ __global__ __launch_bounds__(QR_W * 64) void qkv_split_kernel(GrlQkvAnchorArgs p
             finish(acc, sc, 1.0f, m_tok, m_anc);
         }
     };
-#ifdef QS_ORDER
-    const bool single_first = wave_u >= 4;   // the two compute waves of a SIMD run their MFMA-heavy and VALU-heavy phases out of step
-#else
-    const bool single_first = false;
-#endif
 
 #pragma unroll 1
     for (int it = 0; it < nsub; ++it) {
-        QS_T(c0);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // (not vmcnt: the stores of the previous tile need not have landed)
         __builtin_amdgcn_s_barrier();   // tile `it` is complete in its buffer; everybody is done reading the other one
         const char* xt = smem + (it & 1) * QS_XBUF;
@@ -809,33 +745,10 @@ __global__ __launch_bounds__(QR_W * 64) void qkv_split_kernel(GrlQkvAnchorArgs p
         const int64_t m_anc = cell0 + ((j & 15) >> 1);                          // its pooling cell
         const char* rowp = xt + j * QR_XROW + 16 * half;
         const char* row8 = xt + 2 * QS_XT + j * QS_X8ROW + 32 * half;
-        QS_T(c1);
-        QS_ADD(0, c1 - c0);
-        if (single_first) {
-            do_single(rowp, row8, m_tok, m_anc);
-            do_pair(rowp, row8, m_tok, m_anc);
-        } else {
-            do_pair(rowp, row8, m_tok, m_anc);
-            QS_T(c5);
-            QS_ADD(1, c5 - c1);     // the whole pair phase (regions 2, 3 = its two epilogues)
-            do_single(rowp, row8, m_tok, m_anc);
-            QS_T(c6);
-            QS_ADD(4, c6 - c5);
-        }
+        do_pair(rowp, row8, m_tok, m_anc);
+        do_single(rowp, row8, m_tok, m_anc);
     }
-#ifdef QS_DEBUG
-    if (lane == 0) for (int i = 0; i < 8; ++i) atomicAdd(&qs_dbg[8 * wave_u + i], qs_acc[i]);
-#endif
 }
-
-#ifdef QS_DEBUG
-extern "C" int grl_qs_debug(unsigned long long* out64, int reset) {
-    hipDeviceSynchronize();
-    hipMemcpyFromSymbol(out64, HIP_SYMBOL(qs_dbg), sizeof(unsigned long long) * 64);
-    if (reset) { unsigned long long z[64] = {0}; hipMemcpyToSymbol(HIP_SYMBOL(qs_dbg), z, sizeof(z)); }
-    return 0;
-}
-#endif
 
 int launch_qs(const GrlQkvAnchorArgs& p, hipStream_t st) {
     const int ntiles = p.B * (p.H >> 1) * (p.W >> 6);

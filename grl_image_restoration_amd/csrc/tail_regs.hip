@@ -53,15 +53,6 @@ constexpr int TR_LDS = TR_OFF_VEC + TR_VECF * 4;              // 152 KB
 constexpr int TR_FRAGS = 48;                                  // A fragments (1 KiB each) per wave in the blob
 static_assert(TR_LDS <= 160 * 1024, "LDS budget");
 
-#ifdef TR_DEBUG   // timing probes (s_memtime ticks): [wave][region], summed over workgroups and tiles
-__device__ unsigned long long tr_dbg[64];
-#define TR_TIME(x) const long long x = __builtin_amdgcn_s_memtime()
-#define TR_ADD(i, v) tr_acc[i] += (unsigned long long)(v)
-#else
-#define TR_TIME(x)
-#define TR_ADD(i, v)
-#endif
-
 #define TR_SB() __builtin_amdgcn_sched_barrier(0)
 
 // The lane id, recomputed (2 VALU) at the head of every phase instead of living in a VGPR -- together with everything derived
@@ -131,9 +122,6 @@ __device__ __forceinline__ void tr_ln_combine(const float2* st, int j, float n5,
 
 __global__ __launch_bounds__(TR_THREADS) void tail_regs_kernel(GrlTailArgs p) {
     extern __shared__ __attribute__((aligned(1024))) char smem[];
-#ifdef TR_DEBUG
-    unsigned long long tr_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#endif
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const bool cw = wave < 6;                      // channel wave: proj / fc2 tile `wave`, fc1 tile `wave`; else fc1 tiles 6 + 3 (wave - 6) ..
     const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)smem;
@@ -347,14 +335,11 @@ __global__ __launch_bounds__(TR_THREADS) void tail_regs_kernel(GrlTailArgs p) {
         }
         int it = 0;
         for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x, ++it) {
-            TR_TIME(t0);
             const int buf = it & 1;
             const int64_t m0 = (int64_t)tile * TR_T;
             stage_gate((int)(m0 / p.rows_per_image));
             if (it == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // first tile's DMA pieces
             tr_barrier();                                  // B0: tile `it` is in its buffers; the other buffers are free
-            TR_TIME(t1);
-            TR_ADD(0, t1 - t0);
             f32x16 acc;
             {
                 // ---- P1: projection + per-wave norm statistics ----
@@ -364,8 +349,6 @@ __global__ __launch_bounds__(TR_THREADS) void tail_regs_kernel(GrlTailArgs p) {
                 if (wave < 5) tr_ln_local<false>(acc, 0, inv_nw, st1 + wave * TR_T, j, half);
                 else tr_ln_local<true>(acc, realmask_of(ch0), inv_nw, st1 + wave * TR_T, j, half);
             }
-            TR_TIME(t2);
-            TR_ADD(1, t2 - t1);
             tr_barrier();                                  // B1
             {
                 TR_LANE();
@@ -395,32 +378,23 @@ __global__ __launch_bounds__(TR_THREADS) void tail_regs_kernel(GrlTailArgs p) {
                     TR_SB();   // (bounds the live range of the per-channel vectors: the register budget is 256 - 192)
                 }
             }
-            TR_TIME(t3);
-            TR_ADD(2, t3 - t2);
             tr_barrier();                                  // B2: r1 tile complete
             {
                 // ---- P2: fc1 + GELU -> hidden tile; then fc2, in two halves around B3b: the first on the hidden channels 0..191 the
                 // channel waves produced themselves, while the fc1-only waves' channels get their GELU (see fc1_pre) ----
                 TR_LANE();
                 fc1_tile(Wt + 12, wave, j, half);
-                TR_TIME(t4);
-                TR_ADD(3, t4 - t3);
                 tr_barrier();                              // B3a: hidden channels 0..191 complete
                 tr_bias(acc, vec + 3 * TR_CP, ch0);
                 const char* hb = smem + TR_OFF_H + j * TR_HROW + 16 * half;
                 tr_gemm<TR_KS2 / 2>(Wt + 24, hb, acc);
                 gelu_slice(wave / 3, 48 + 16 * (wave % 3) + 8 * half, 2, j, buf, false);   // this wave's share of the fc1-only waves' GELUs
-                TR_TIME(t4b);
-                TR_ADD(7, t4b - t4);
                 tr_barrier();                              // B3b: hidden tile complete
                 tr_gemm<TR_KS2 / 2>(Wt + 36, hb + 32 * (TR_KS2 / 2), acc);
                 if (wave < 5) tr_ln_local<false>(acc, 0, inv_nw, st2 + wave * TR_T, j, half);
                 else tr_ln_local<true>(acc, realmask_of(ch0), inv_nw, st2 + wave * TR_T, j, half);
             }
-            TR_TIME(t5);
             tr_barrier();                                  // B4
-            TR_TIME(t6);
-            TR_ADD(5, t6 - t5);
             {
                 TR_LANE();
                 float mean, rstd;
@@ -441,8 +415,6 @@ __global__ __launch_bounds__(TR_THREADS) void tail_regs_kernel(GrlTailArgs p) {
                     TR_SB();
                 }
             }
-            TR_TIME(t7);
-            TR_ADD(6, t7 - t6);
         }
     } else {
         {
@@ -452,24 +424,16 @@ __global__ __launch_bounds__(TR_THREADS) void tail_regs_kernel(GrlTailArgs p) {
         }
         int it = 0;
         for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x, ++it) {
-            TR_TIME(t0);
             const int buf = it & 1;
             stage_gate((int)(((int64_t)tile * TR_T) / p.rows_per_image));
             if (it == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             tr_barrier();                                  // B0
-            TR_TIME(t1);
-            TR_ADD(0, t1 - t0);
             const int next = tile + (int)gridDim.x;
             if (next < ntiles) load_next(next, 0);
-            TR_TIME(t2);
-            TR_ADD(1, t2 - t1);
             tr_barrier();                                  // B1
             if (next < ntiles) { store_next(buf ^ 1, 0); load_next(next, 1); }
-            TR_TIME(t3a);
-            TR_ADD(2, t3a - t2);
             tr_barrier();                                  // B2
             if (next < ntiles) store_next(buf ^ 1, 1);
-            TR_TIME(t3);
             TR_LANE();
             char* region = smem + (wave == 6 ? TR_OFF_ATT : TR_OFF_CAB) + buf * TR_ABUF;   // dead since the first norm of this tile
             fc1_pre(Wt, 0, region, j, half);
@@ -477,34 +441,15 @@ __global__ __launch_bounds__(TR_THREADS) void tail_regs_kernel(GrlTailArgs p) {
             fc1_pre(Wt + 12, 1, region, j, half);
             TR_SB();
             fc1_pre(Wt + 24, 2, region, j, half);
-            TR_TIME(t4);
-            TR_ADD(3, t4 - t3);
             tr_barrier();                                  // B3a: hidden channels 0..191 and all pre-activations complete
             gelu_slice(wave - 6, 24 * half, 6, j, buf, true);
-            TR_TIME(t4b);
-            TR_ADD(7, t4b - t4);
             tr_barrier();                                  // B3b
-            TR_TIME(t5);
             tr_barrier();                                  // B4
-            TR_TIME(t6);
-            TR_ADD(5, t6 - t5);
         }
     }
-#ifdef TR_DEBUG
-    if (tr_lane() == 0) for (int i = 0; i < 8; ++i) atomicAdd(&tr_dbg[8 * wave + i], tr_acc[i]);
-#endif
 }
 
 }  // namespace
-
-#ifdef TR_DEBUG
-extern "C" int grl_tr_debug(unsigned long long* out64, int reset) {
-    hipDeviceSynchronize();
-    hipMemcpyFromSymbol(out64, HIP_SYMBOL(tr_dbg), sizeof(unsigned long long) * 64);
-    if (reset) { unsigned long long z[64] = {0}; hipMemcpyToSymbol(HIP_SYMBOL(tr_dbg), z, sizeof(z)); }
-    return 0;
-}
-#endif
 
 extern "C" int64_t grl_tail_regs_blob_bytes(void) { return (int64_t)TR_W * TR_FRAGS * 1024 + TR_HP * 4; }
 

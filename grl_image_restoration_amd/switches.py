@@ -3,7 +3,9 @@
 This module is the only place in the package that touches ``os.environ`` for a ``GRL_*`` name.  A new switch is one row here, one
 accessor call where it is read (``grl_env_int`` in csrc/common.h on the C side) and one row in DESIGN.md's "Knobs" table;
 tests/test_switches.py fails when the three disagree.  No switch selects a kernel: a path is chosen from what the code can observe
-(shape, precision, device), and an A/B toggle lives on a development branch and is removed before merge.
+(shape, precision, device), and an A/B toggle lives on a development branch and is removed before merge.  Nor does a ``-D`` flag:
+csrc has one build, its only preprocessor conditionals test the compiler's own ``__HIPCC__``, and instrumented or ablated builds
+live on a development branch.
 
 kind   on     default-on:  off only for the exact string "0"
        off    default-off: on only for the exact string "1"

@@ -1,6 +1,7 @@
 """The GRL_* environment switches have one definition (grl_image_restoration_amd/switches.py): the sources read exactly the switches
 the table declares, DESIGN.md's "Knobs" section lists exactly those, the accessors parse as the hand-written expressions they replaced,
-and an undeclared or C-side name cannot be read from Python.  No GPU, no library: sources, the document and os.environ only."""
+and an undeclared or C-side name cannot be read from Python.  The same rule at compile time: csrc has one build.  No GPU, no
+library: sources, the document and os.environ only."""
 import glob
 import os
 import re
@@ -38,6 +39,22 @@ def test_sources_read_exactly_the_declared_switches():
     assert csrc == {n for n, s in SW.TABLE.items() if s.where == "csrc"}
     assert all(n == s.name and s.kind in ("on", "off", "int", "float", "str") and s.when in ("import", "plan", "call") and s.doc
                for n, s in SW.TABLE.items())
+
+
+def test_csrc_has_one_build():
+    """No compile-time toggle either: the only preprocessor conditionals of csrc test the compiler's own __HIPCC__, and the
+    Makefile defines nothing."""
+    paths = glob.glob(os.path.join(PKG, "csrc", "*.hip")) + glob.glob(os.path.join(PKG, "csrc", "*.h"))
+    assert paths
+    toggles = []
+    for path in paths:
+        for n, line in enumerate(_read(path).split("\n"), 1):
+            m = re.match(r"\s*#\s*(?:if|ifdef|ifndef|elif)\b(.*)", line)
+            if m and set(re.findall(r"[A-Za-z_]\w*", m.group(1).split("//")[0])) - {"defined"} != {"__HIPCC__"}:
+                toggles.append(f"{os.path.basename(path)}:{n}: {line.strip()}")
+    assert not toggles, toggles
+    defines = [w for w in _read(os.path.join(PKG, "csrc", "Makefile")).split() if w.startswith("-D")]
+    assert not defines, defines
 
 
 def test_design_knobs_section_lists_exactly_the_declared_switches():

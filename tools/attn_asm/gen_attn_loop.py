@@ -35,7 +35,7 @@ def f32bits(x):
     return struct.unpack("<I", struct.pack("<f", x))[0]
 
 
-def gen(rows, mask, kstride=2048, abl=(), d32=False):
+def gen(rows, mask, kstride=2048, d32=False):
     """Two copies of the row loop in one statement: with the overflow test, and -- entered when %[nochk] != 0: the offsets of
     all the wave's queries are within 13.5 of the head's logit bound, nothing can trip -- without it (a per-row skip would be
     a taken branch per row)."""
@@ -44,23 +44,22 @@ def gen(rows, mask, kstride=2048, abl=(), d32=False):
         L.append(f"s_mov_b32 %[t2], 0x{f32bits(-MASK_L2):08x}")    # +144.27: multiplied by -|id_k - id_q|
     L.append("s_cmp_lg_u32 %[nochk], 0")
     L.append("s_cbranch_scc1 200f")
-    L += body(rows, mask, kstride, abl, True, 0, d32)
+    L += body(rows, mask, kstride, True, 0, d32)
     L.append("s_branch 99f")
     L.append("200:")
-    L += body(rows, mask, kstride, abl + ("nocheck",), False, 100, d32)
-    if "nocheck" not in abl:
-        L.append("s_branch 99f")
-        for r in range(rows):
-            L.append(f"{90 + r}:")
-            L.append("s_waitcnt lgkmcnt(0)")        # the V^T reads of the abandoned row still target VF
-            L.append(f"s_mov_b32 %[done], {r}")
-            if r + 1 < rows:
-                L.append("s_branch 99f")
+    L += body(rows, mask, kstride, False, 100, d32)
+    L.append("s_branch 99f")
+    for r in range(rows):
+        L.append(f"{90 + r}:")
+        L.append("s_waitcnt lgkmcnt(0)")        # the V^T reads of the abandoned row still target VF
+        L.append(f"s_mov_b32 %[done], {r}")
+        if r + 1 < rows:
+            L.append("s_branch 99f")
     L.append("99:")
     return L
 
 
-def body(rows, mask, kstride, abl, check, lb, d32=False):
+def body(rows, mask, kstride, check, lb, d32=False):
     """d32: head_dim 32 fills all 32 slots of the Q / K fragments and of V, so the two things the spare slot 31 carries for
     free elsewhere are done on the VALU: the running offset (-m per query, operands %[nm0] / %[nm1]) is added to the logits
     (folded into the mask value where there is one), and the softmax denominator is summed from the packed fp16 weights
@@ -99,8 +98,7 @@ def body(rows, mask, kstride, abl, check, lb, d32=False):
         e(f"ds_read_b128 {v(KF, 4)}, {v(KF)} offset:{off}")
         e(f"ds_read_b128 {v(KF + 4, 4)}, {v(KF + 4)} offset:{off}")
         e(f"v_add_u32 {v(X + 15)}, %[sb], %[bl]")
-        if "nobias" not in abl or r == 0:
-            gather(X)
+        gather(X)
         e(f"v_add_u32 {v(VF + 6)}, %[par], %[va]")
         for i in range(4):
             e(f"ds_read_b64_tr_b16 {v(VF + 2 * i, 2)}, {v(VF + 6)} offset:{off + 512 * i}")
@@ -108,14 +106,10 @@ def body(rows, mask, kstride, abl, check, lb, d32=False):
             e(f"s_bfe_u32 %[t0], %[ids], 0x{(4 << 16) | (8 * r):x}")
             e(f"s_bfe_u32 %[t1], %[ids], 0x{(4 << 16) | (8 * r + 4):x}")
         e("s_waitcnt lgkmcnt(4)")
-        if "prio" in abl:
-            e("s_setprio 1")
         e(f"v_mfma_f32_32x32x16_f16 {v(Z, 16)}, {v(KF, 4)}, %[q00], {v(X, 16)}")
         e(f"v_mfma_f32_32x32x16_f16 {v(Y, 16)}, {v(KF, 4)}, %[q10], {v(Y, 16)}")
         e(f"v_mfma_f32_32x32x16_f16 {v(Z, 16)}, {v(KF + 4, 4)}, %[q01], {v(Z, 16)}")
         e(f"v_mfma_f32_32x32x16_f16 {v(Y, 16)}, {v(KF + 4, 4)}, %[q11], {v(Y, 16)}")
-        if "prio" in abl:
-            e("s_setprio 0")
         if mask:
             # mask value per (tile, 16-key band): -144.27 * |id_key_band - id_query|  (0 when the regions agree)
             ops = (("%[t0]", "%[idq0]"), ("%[t1]", "%[idq0]"), ("%[t0]", "%[idq1]"), ("%[t1]", "%[idq1]"))
@@ -144,41 +138,33 @@ def body(rows, mask, kstride, abl, check, lb, d32=False):
                 for i in range(8):
                     e(f"v_pk_add_f32 {v(S + 2 * i, 2)}, {v(S + 2 * i, 2)}, {v(KF + 2 * ti, 2)} op_sel_hi:[1,0]")
             for i in range(16):
-                if "noexp" in abl:
-                    e(f"v_mov_b32 {v(S + i)}, {v(S + i)}")
-                else:
-                    e(f"v_exp_f32 {v(S + i)}, {v(S + i)}")
+                e(f"v_exp_f32 {v(S + i)}, {v(S + i)}")
                 if i % 2 == 1 and i >= 3:
                     j = (i - 3) // 2
                     e(f"v_cvt_pk_f16_f32 {v(S + j)}, {v(S + 2 * j)}, {v(S + 2 * j + 1)}")
             e(f"v_cvt_pk_f16_f32 {v(S + 7)}, {v(S + 14)}, {v(S + 15)}")
         # overflow test: largest packed weight of the two tiles >= 2^14 ?
         t = [KF, KF + 1, KF + 2, KF + 3]
-        if "nocheck" in abl:
+        if check:
+            e(f"v_pk_maximum3_f16 {v(t[0])}, {v(Z)}, {v(Z + 1)}, {v(Z + 2)}")
+            e(f"v_pk_maximum3_f16 {v(t[1])}, {v(Z + 3)}, {v(Z + 4)}, {v(Z + 5)}")
+            e(f"v_pk_maximum3_f16 {v(t[2])}, {v(Z + 6)}, {v(Z + 7)}, {v(Y)}")
+            e(f"v_pk_maximum3_f16 {v(t[3])}, {v(Y + 1)}, {v(Y + 2)}, {v(Y + 3)}")
+            e(f"v_pk_maximum3_f16 {v(t[0])}, {v(t[0])}, {v(Y + 4)}, {v(Y + 5)}")
+            e(f"v_pk_maximum3_f16 {v(t[1])}, {v(t[1])}, {v(Y + 6)}, {v(Y + 7)}")
+            e(f"v_pk_maximum3_f16 {v(t[0])}, {v(t[0])}, {v(t[2])}, {v(t[3])}")
+            e(f"v_pk_max_f16 {v(t[0])}, {v(t[0])}, {v(t[1])}")
+            e(f"v_pk_max_f16 {v(t[0])}, {v(t[0])}, {v(t[0])} op_sel:[0,1] op_sel_hi:[1,0]")
+            e(f"v_cmp_le_u32 vcc, 0x{TRIP:08x}, {v(t[0])}")
+            e(f"s_cbranch_vccnz {lab(90 + r)}f")
+            e("s_waitcnt lgkmcnt(0)")
+        else:
             e("s_waitcnt lgkmcnt(0)")
             e("s_nop 1")                   # the last cvt_pk is 2 states ahead of the MFMA that reads it
-        if "nocheck" not in abl:
-          e(f"v_pk_maximum3_f16 {v(t[0])}, {v(Z)}, {v(Z + 1)}, {v(Z + 2)}")
-          e(f"v_pk_maximum3_f16 {v(t[1])}, {v(Z + 3)}, {v(Z + 4)}, {v(Z + 5)}")
-          e(f"v_pk_maximum3_f16 {v(t[2])}, {v(Z + 6)}, {v(Z + 7)}, {v(Y)}")
-          e(f"v_pk_maximum3_f16 {v(t[3])}, {v(Y + 1)}, {v(Y + 2)}, {v(Y + 3)}")
-          e(f"v_pk_maximum3_f16 {v(t[0])}, {v(t[0])}, {v(Y + 4)}, {v(Y + 5)}")
-          e(f"v_pk_maximum3_f16 {v(t[1])}, {v(t[1])}, {v(Y + 6)}, {v(Y + 7)}")
-          e(f"v_pk_maximum3_f16 {v(t[0])}, {v(t[0])}, {v(t[2])}, {v(t[3])}")
-          e(f"v_pk_max_f16 {v(t[0])}, {v(t[0])}, {v(t[1])}")
-          e(f"v_pk_max_f16 {v(t[0])}, {v(t[0])}, {v(t[0])} op_sel:[0,1] op_sel_hi:[1,0]")
-          e(f"v_cmp_le_u32 vcc, 0x{TRIP:08x}, {v(t[0])}")
-          e(f"s_cbranch_vccnz {lab(90 + r)}f")
-          e("s_waitcnt lgkmcnt(0)")
-        if "prio" in abl or "priopv" in abl:
-            e("s_setprio 1")
-        if "nopv" not in abl:
-            e(f"v_mfma_f32_32x32x16_f16 %[o0], {v(VF, 4)}, {v(Z, 4)}, %[o0]")
-            e(f"v_mfma_f32_32x32x16_f16 %[o1], {v(VF, 4)}, {v(Y, 4)}, %[o1]")
-            e(f"v_mfma_f32_32x32x16_f16 %[o0], {v(VF + 4, 4)}, {v(Z + 4, 4)}, %[o0]")
-            e(f"v_mfma_f32_32x32x16_f16 %[o1], {v(VF + 4, 4)}, {v(Y + 4, 4)}, %[o1]")
-        if "prio" in abl or "priopv" in abl:
-            e("s_setprio 0")
+        e(f"v_mfma_f32_32x32x16_f16 %[o0], {v(VF, 4)}, {v(Z, 4)}, %[o0]")
+        e(f"v_mfma_f32_32x32x16_f16 %[o1], {v(VF, 4)}, {v(Y, 4)}, %[o1]")
+        e(f"v_mfma_f32_32x32x16_f16 %[o0], {v(VF + 4, 4)}, {v(Z + 4, 4)}, %[o0]")
+        e(f"v_mfma_f32_32x32x16_f16 %[o1], {v(VF + 4, 4)}, {v(Y + 4, 4)}, %[o1]")
         if d32:
             for j in range(8):
                 e(f"v_dot2c_f32_f16 %[l0], 0x3c003c00, {v(Z + j)}")
@@ -191,15 +177,13 @@ def body(rows, mask, kstride, abl, check, lb, d32=False):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", required=True)
-    ap.add_argument("--abl", default="", help="timing experiments: comma list of nobias,noexp,nocheck,nopv (results are wrong)")
     a = ap.parse_args()
-    abl = tuple(x for x in a.abl.split(",") if x)
     with open(a.out, "w") as f:
         f.write("// generated by tools/attn_asm/gen_attn_loop.py -- do not edit (regenerate: python3 tools/attn_asm/gen_attn_loop.py --out <this file>)\n")
         for d32 in (False, True):
             for mask in (0, 1):
                 f.write(f"#define ATTN_ROWS4_MASK{mask}{'_D32' if d32 else ''} \\\n")
-                f.write(" \\\n".join('    "' + ln + '\\n"' for ln in gen(4, mask, abl=abl, d32=d32)) + "\n\n")
+                f.write(" \\\n".join('    "' + ln + '\\n"' for ln in gen(4, mask, d32=d32)) + "\n\n")
         f.write("#define ATTN_ROWS_CLOBBER " + ", ".join(f'"v{i}"' for i in range(64)) + ', "vcc", "scc", "memory"\n')
 
 

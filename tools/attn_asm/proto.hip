@@ -1,6 +1,6 @@
 // Prototype of the hand-scheduled attention key-row loop (tools/attn_asm/gen_attn_loop.py): cycles per 32x32 S tile at
-// 2 / 3 / 4 waves per SIMD, synthetic LDS contents, no DMA.  Build: python3 gen_attn_loop.py --out attn_loop.inc &&
-// hipcc --offload-arch=gfx950 -O3 proto.hip -o proto
+// 2 / 3 / 4 waves per SIMD, synthetic LDS contents, no DMA.  Includes the committed csrc/attn_rows_asm.inc.
+// Build: hipcc --offload-arch=gfx950 -O3 proto.hip -o proto
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
