@@ -11,7 +11,7 @@ from . import switches as SW
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgrl_hip.so")
-ABI_VERSION = 40
+ABI_VERSION = 41
 DT_F32, DT_BF16, DT_F16 = 0, 1, 2
 
 EPI_PLAIN, EPI_GELU, EPI_GROUPNORM, EPI_LN_RES, EPI_GELU_GRAD = 0, 1, 2, 3, 4
@@ -720,6 +720,27 @@ class GrlColorJitterArgs(_Strict):
     ]
 
 
+class GrlDihedralPackArgs(_Strict):
+    _fields_ = [
+        ("x", C.c_void_p),
+        ("stride", C.c_int64 * 4),
+        ("B", C.c_int32), ("C", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+        ("out_a", C.c_void_p),
+        ("out_b", C.c_void_p),
+    ]
+
+
+class GrlDihedralMergeArgs(_Strict):
+    _fields_ = [
+        ("member", C.c_void_p * 8),
+        ("stride", (C.c_int64 * 4) * 8),
+        ("dtype", C.c_int32),
+        ("B", C.c_int32), ("C", C.c_int32), ("Ho", C.c_int32), ("Wo", C.c_int32),
+        ("reserved0", C.c_int32),
+        ("out", C.c_void_p),
+    ]
+
+
 _I32, _I64, _PTR = C.c_int32, C.c_int64, C.c_void_p
 
 
@@ -807,6 +828,8 @@ SIGNATURES = {
     "grl_isp_roundtrip": _launch(GrlIspArgs),
     "grl_color_jitter_num_workgroups": (C.c_int, [_I32] * 2),
     "grl_color_jitter": _launch(GrlColorJitterArgs),
+    "grl_dihedral_pack": _launch(GrlDihedralPackArgs),
+    "grl_dihedral_merge": _launch(GrlDihedralMergeArgs),
     "grl_debug_dirty_lds": (C.c_int, [_PTR]),
     "grl_abi_version": (C.c_int, []),
     "grl_build_info": (C.c_char_p, []),

@@ -37,6 +37,7 @@ Restates, for the MI355X module, the three pieces of the reference's evaluation 
     python -m grl_image_restoration_amd.evaluate --task sr --scale 1 --model base --geometry defocus --tile 480 --overlap 48 \\
         --ckpt db_defocus_dual_pixel_grl_base.ckpt --lq DPDD/test/inputL --lq-r DPDD/test/inputR --gt DPDD/test/target
                                                   dual-pixel defocus deblurring: the two views side by side, a 6-in / 3-out model
+    ... --self-ensemble                   the x8 geometric self-ensemble (ensemble.py): the "+" rows of the tables
     ... --save-dir results [--save-gt]    also writes results/X4/<data set>/<stem>_{LQ,HQ,GT}.png (image8.py), as the reference does
 """
 import argparse
@@ -177,16 +178,23 @@ def _side_by_side(left: torch.Tensor, right: torch.Tensor) -> torch.Tensor:
 
 @torch.no_grad()
 def evaluate_pairs(model, pairs: Iterable[Tuple[torch.Tensor, torch.Tensor]], scale: int, tile: int = 0, overlap: int = 32,
-                   device: str = "cuda:0", metric_group: Optional[str] = None, niqe_params=None, on_result=None, lpips_model=None):
+                   device: str = "cuda:0", metric_group: Optional[str] = None, niqe_params=None, on_result=None, lpips_model=None,
+                   self_ensemble: bool = False):
     """PSNR-Y of ``model`` on (lq, gt) tensors in [0, 1], (1,3,h,w) / (1,3,h*scale,w*scale): a list, one value per pair.
     ``tile > 0`` uses the reference's tiled inference (engines/base.py:90-116) through ``tiling.forward_tiled``.
     With ``metric_group`` (a key of ``metrics.ALL_GROUPS`` or ``metrics.PERCEPTUAL_GROUPS``): {metric name: mean over the pairs} of
     that group instead.  ``gt`` may be None for the group "restorer_niqe", which scores the output alone against ``niqe_params``;
     "restorer_perceptual" takes ``lpips_model`` (an ``lpips.LPIPS`` on ``device``) alongside ``niqe_params``.  ``on_result(index, lq, sr, gt)`` is
     called for every pair with the tensors on ``device``, after ``sr`` and ``gt`` were cropped to each other and before the metrics:
-    the images the reference saves (engines/base.py:259-264, before ``shave``)."""
+    the images the reference saves (engines/base.py:259-264, before ``shave``).  ``self_ensemble``: every forward is the x8
+    geometric self-ensemble of ``ensemble.SelfEnsemble`` -- of the whole image, or with ``tile`` of every tile on its own."""
     from . import tiling
     from .metrics import image_metrics
+
+    if self_ensemble:
+        from .ensemble import SelfEnsemble
+
+        model = SelfEnsemble(model)
 
     out = []
     for index, (lq, gt) in enumerate(pairs):
@@ -249,7 +257,7 @@ def evaluate_folder(model, lq_dir: Optional[str], gt_dir: Optional[str], scale: 
                     task: str = "sr", sigma: Optional[float] = None, noise_prefix: Optional[str] = None, niqe_params=None,
                     taps: Optional[torch.Tensor] = None, quality: Optional[int] = None, save_dir: Optional[str] = None,
                     save_gt: bool = False, save_workers: int = 4, usm_gt: bool = False, lpips_model=None,
-                    lq_r_dir: Optional[str] = None):
+                    lq_r_dir: Optional[str] = None, self_ensemble: bool = False):
     """Mean PSNR-Y over the image pairs of two folders; with ``metric_group``, {metric name: mean} of that group.  ``channels`` 1
     reads the images as grayscale.  A ``task`` that synthesises its input ignores ``lq_dir`` and builds the LQ from the GT
     (``task_inputs``, with ``sigma``, ``taps``, ``quality`` and ``scale`` as the task's rule takes them).  A task without a ground
@@ -264,7 +272,13 @@ def evaluate_folder(model, lq_dir: Optional[str], gt_dir: Optional[str], scale: 
     taken against the sharpened GT and ``save_gt`` writes it.  ``lq_r_dir`` (task "sr" at scale 1, RGB): dual-pixel defocus
     deblurring -- ``lq_dir`` holds the left views, ``lq_r_dir`` the right ones, matched to each other and to the GT by sorted order;
     the model (``GRL(in_channels=6, out_channels=3)``) gets the two side by side, ``<stem>_LQ.png`` is the LEFT view
-    (engines/base.py:536-537) and the saved images go straight under the data set's name (engines/base.py:521-524)."""
+    (engines/base.py:536-537) and the saved images go straight under the data set's name (engines/base.py:521-524).
+    ``self_ensemble``: the model runs as ``ensemble.SelfEnsemble(model)``, the x8 geometric self-ensemble (per tile with ``tile``); it
+    sits at the model boundary, after the task's front end, so every task, metric and saved image goes with it."""
+    if self_ensemble:
+        from .ensemble import SelfEnsemble
+
+        model = SelfEnsemble(model)
     dual = lq_r_dir is not None
     o = resolve(task, "evaluate_folder", scale=scale, channels=channels, sigma=sigma, quality=quality, usm=usm_gt,
                 **(dict(dual_pixel=True, lq=lq_dir is not None) if dual else {}))
@@ -346,6 +360,9 @@ def _parser():
                     help="restorer_perceptual: the lpips package's weights/v0.1/vgg.pth (the five 1x1 layers)")
     ap.add_argument("--tile", type=int, default=0)
     ap.add_argument("--overlap", type=int, default=32)
+    ap.add_argument("--self-ensemble", action="store_true",
+                    help="x8 geometric self-ensemble: restore the image under the eight flips and rotations and average the results "
+                         "mapped back (with --tile: every tile on its own)")
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--metric", default=None, choices=sorted(ALL_GROUPS) + sorted(PERCEPTUAL_GROUPS),
                     help="report this metric group of the reference (config/metric/*.yaml) instead of PSNR-Y alone")
@@ -424,7 +441,7 @@ def main(argv: Optional[List[str]] = None):
     return evaluate_folder(model, a.lq, a.gt, a.scale, a.tile, a.overlap, a.device, metric_group=a.metric, channels=a.channels,
                            task=a.task, sigma=a.sigma, noise_prefix=a.noise_prefix, niqe_params=niqe_params, taps=taps,
                            quality=a.quality, save_dir=a.save_dir, save_gt=a.save_gt, usm_gt=a.usm_gt, lpips_model=lpips_model,
-                           lq_r_dir=a.lq_r)
+                           lq_r_dir=a.lq_r, self_ensemble=a.self_ensemble)
 
 
 if __name__ == "__main__":

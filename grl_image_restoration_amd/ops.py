@@ -1383,3 +1383,38 @@ def sample_patch_views(views, work: torch.Tensor, patch: int) -> None:
                                       Ctot=out.shape[1], c0=int(c0), out=_ptr(out))
     with _timed("sample_patch_views"):
         L.launch("grl_sample_patch_views", args)
+
+
+# ---- x8 self-ensemble (csrc/ensemble.hip): the eight flips / rotations in one launch, and their fixed-order mean in another ----------
+def dihedral_pack(x: torch.Tensor, out_a: torch.Tensor, out_b: torch.Tensor) -> None:
+    """grl_dihedral_pack: an fp32 image batch [B, C, H, W] (any strides, read in place) -> ``out_a`` [4B, C, H, W] = T0, T2, T4, T6
+    and ``out_b`` [4B, C, W, H] = T1, T3, T5, T7 of include/grl_hip.h, member-major, both contiguous (for H == W: the two halves of
+    one [8B, C, H, H] buffer)."""
+    _dev_check(x, out_a, out_b)
+    assert x.dim() == 4 and x.dtype == torch.float32
+    B, C_, H, W = x.shape
+    for o, shape in ((out_a, (4 * B, C_, H, W)), (out_b, (4 * B, C_, W, H))):
+        assert o.shape == shape and o.dtype == torch.float32 and o.is_contiguous()
+    args = L.GrlDihedralPackArgs(x=_ptr(x), stride=(C.c_int64 * 4)(*x.stride()), B=B, C=C_, H=H, W=W, out_a=_ptr(out_a), out_b=_ptr(out_b))
+    with _timed("dihedral_pack"):
+        L.launch("grl_dihedral_pack", args)
+
+
+def dihedral_merge(members, out: torch.Tensor) -> None:
+    """grl_dihedral_merge: ``members[k]`` = what the model made of T_k(x), all fp32 or all fp16, [B, C, Ho, Wo] for even k and
+    [B, C, Wo, Ho] for odd k, each read through its own strides -> ``out`` [B, C, Ho, Wo] fp32 contiguous =
+    (((m0 + m1) + (m2 + m3)) + ((m4 + m5) + (m6 + m7))) * 0.125 of the members mapped back."""
+    members = list(members)
+    _dev_check(out, *members)
+    assert len(members) == 8 and out.dim() == 4 and out.dtype == torch.float32 and out.is_contiguous()
+    B, C_, Ho, Wo = out.shape
+    dt = members[0].dtype
+    assert dt in (torch.float32, torch.float16)
+    args = L.GrlDihedralMergeArgs(dtype=L.DT_F32 if dt == torch.float32 else L.DT_F16, B=B, C=C_, Ho=Ho, Wo=Wo, out=_ptr(out))
+    for k, m in enumerate(members):
+        assert m.dtype == dt and m.shape == ((B, C_, Wo, Ho) if k % 2 else (B, C_, Ho, Wo)), (k, tuple(m.shape), m.dtype)
+        args.member[k] = m.data_ptr()
+        for d in range(4):
+            args.stride[k][d] = m.stride(d)
+    with _timed("dihedral_merge"):
+        L.launch("grl_dihedral_merge", args)

@@ -3,7 +3,7 @@ is written as ``<out>/<stem><suffix>.png``.  Nothing is synthesised and nothing 
 and the PNG writer are ``image8.pack8`` / ``image8.ImageWriter``, the rounding is the reference's (engines/base.py:259-264,545-550).
 
     python -m grl_image_restoration_amd.restore --model base --geometry sr_ckpt_df2 --scale 4 --ckpt sr_grl_base_c3x4.ckpt \\
-        --lq photos --out restored [--tile 256 --overlap 32]
+        --lq photos --out restored [--tile 256 --overlap 32] [--self-ensemble]
     python -m grl_image_restoration_amd.restore --model small --geometry dn_df4 --ckpt dn_grl_small_c3s25.ckpt --lq noisy --out clean
     python -m grl_image_restoration_amd.restore --model base --geometry defocus --ckpt db_defocus_dual_pixel_grl_base.ckpt \\
         --lq shots/left --lq-r shots/right --out sharp --tile 480 --overlap 48      (dual-pixel: the two views side by side, 6 in / 3 out)
@@ -22,14 +22,20 @@ from .image8 import ImageWriter
 @torch.no_grad()
 def restore_folder(model, lq_dir: str, out_dir: str, scale: int = 1, tile: int = 0, overlap: int = 32, device: str = "cuda:0",
                    channels: int = 3, suffix: str = "_HQ", workers: int = 4, compress_level: int = 6, verbose: bool = False,
-                   lq_r_dir: Optional[str] = None) -> List[str]:
+                   lq_r_dir: Optional[str] = None, self_ensemble: bool = False) -> List[str]:
     """Writes ``<out_dir>/<stem><suffix>.png`` for every image of ``lq_dir`` in sorted order and returns the paths; every file is
     complete when the call returns.  ``tile > 0`` restores images larger than the tile through ``tiling.forward_tiled``.  One reader
     thread decodes the next image while the device works on the current one; ``workers`` threads compress the PNGs.  ``lq_r_dir``
     (scale 1, RGB): dual-pixel inputs -- ``lq_dir`` holds the left views, ``lq_r_dir`` the right ones, matched by sorted order; the
     model (``GRL(in_channels=6, out_channels=3)``) gets the two side by side (engines/base.py:119-120) and the written file takes
-    the LEFT view's stem."""
+    the LEFT view's stem.  ``self_ensemble``: the model runs as ``ensemble.SelfEnsemble(model)``, the x8 geometric self-ensemble (with
+    ``tile``: every tile on its own)."""
     from . import tiling
+
+    if self_ensemble:
+        from .ensemble import SelfEnsemble
+
+        model = SelfEnsemble(model)
 
     files = gt_images(lq_dir)
     mode = "L" if channels == 1 else "RGB"
@@ -81,6 +87,9 @@ def _parser():
     ap.add_argument("--depths", default=None, help="blocks per stage as a+b+c instead of the model size's (short experiments)")
     ap.add_argument("--tile", type=int, default=0)
     ap.add_argument("--overlap", type=int, default=32)
+    ap.add_argument("--self-ensemble", action="store_true",
+                    help="x8 geometric self-ensemble: restore the image under the eight flips and rotations and average the results "
+                         "mapped back (with --tile: every tile on its own)")
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--suffix", default="_HQ", help="written files are <stem><suffix>.png")
     ap.add_argument("--workers", type=int, default=4, help="PNG writer threads (at most 8)")
@@ -111,7 +120,7 @@ def main(argv: Optional[List[str]] = None):
         load_checkpoint(model, a.ckpt)
     model = model.to(a.device)
     return restore_folder(model, a.lq, a.out, a.scale, a.tile, a.overlap, a.device, a.channels, a.suffix, a.workers,
-                          a.compress_level, verbose=True, lq_r_dir=a.lq_r)
+                          a.compress_level, verbose=True, lq_r_dir=a.lq_r, self_ensemble=a.self_ensemble)
 
 
 if __name__ == "__main__":

@@ -23,7 +23,7 @@ extern "C" {
 
 #define GRL_ERR_BAD_ARG (-1)
 #define GRL_ERR_UNSUPPORTED (-2)
-#define GRL_ABI_VERSION 40
+#define GRL_ABI_VERSION 41
 
 /* element kinds of activation / weight buffers */
 enum { GRL_DT_F32 = 0, GRL_DT_BF16 = 1, GRL_DT_F16 = 2 };
@@ -1361,6 +1361,60 @@ typedef struct GrlColorJitterArgs {
 
 int grl_color_jitter_num_workgroups(int32_t max_h, int32_t max_w);
 int grl_color_jitter(void* stream, const GrlColorJitterArgs* args);
+
+/* ---------------------------------------------------------------------------------------------
+ * x8 geometric self-ensemble at test time (ABI 41, csrc/ensemble.hip, ensemble.py): the image under the eight flips and rotations of
+ * the square, each result mapped back, the eight averaged.
+ *   restates  Augment_RGB_torch.transform0 .. transform7                            utils/dataset_utils.py:6-39
+ *             (torch.rot90(t, k, dims=[-1, -2]) for k = 0 .. 3, and the same with .flip(-2) after it for k = 4 .. 7; the reference
+ *             lists the transforms and never calls them from its engine)
+ * y = T_k(x), x of H rows and W columns:
+ *   k   y[i][j] =               shape of y   inverse
+ *   0   x[i][j]                 H x W        T0
+ *   1   x[H-1-j][i]             W x H        T3
+ *   2   x[H-1-i][W-1-j]         H x W        T2
+ *   3   x[j][W-1-i]             W x H        T1
+ *   4   x[H-1-i][j]             H x W        T4
+ *   5   x[H-1-j][W-1-i]         W x H        T5
+ *   6   x[i][W-1-j]             H x W        T6
+ *   7   x[j][i]                 W x H        T7
+ * Group A = T0, T2, T4, T6 keeps the shape; group B = T1, T3, T5, T7 transposes it.
+ *
+ * grl_dihedral_pack: x fp32 (B, C, H, W), read in place through four ELEMENT strides (batch, channel, row, column), every value
+ * once.  out_a: contiguous (4 B, C, H, W) = T0, T2, T4, T6 of the batch; out_b: contiguous (4 B, C, W, H) = T1, T3, T5, T7; the batch
+ * index inside a group is member-major, (position in the group) * B + b.  For H == W the two may be the halves of one
+ * (8 B, C, H, H) buffer: a square tile becomes one batch of eight.  One launch.
+ *
+ * grl_dihedral_merge: member[k] is what the model made of T_k(x): (B, C, Ho, Wo) for group A, (B, C, Wo, Ho) for group B, all fp32
+ * or all fp16 (dtype), each with its own base pointer and its own four element strides, read where the model left it.  With
+ * m_k = T_k^-1(member[k]) (the inverse column above; (B, C, Ho, Wo) each),
+ *   out = (((m0 + m1) + (m2 + m3)) + ((m4 + m5) + (m6 + m7))) * 0.125f
+ * in fp32: fp16 values are widened first, the adds are IEEE adds in exactly this order and the scaling is exact, so the same
+ * expression in torch on the CPU gives the same bits, on every run; NaN and Inf propagate.  out: contiguous fp32 (B, C, Ho, Wo).
+ * One launch, no workspace, no atomics.
+ *
+ * Errors, nothing is launched.  GRL_ERR_BAD_ARG: a null args / x / out_a / out_b / member / out, a non-positive B, C, H or W, a dtype
+ * other than GRL_DT_F32 / GRL_DT_F16.  GRL_ERR_UNSUPPORTED: a pointer not aligned to its element, 4 B C H W (one group) of 2^31
+ * elements or more, H above 32 * 65535 or B above 65535. */
+typedef struct GrlDihedralPackArgs {
+    const float* x;
+    int64_t stride[4];          /* element strides of batch, channel, row, column                */
+    int32_t B, C, H, W;
+    float* out_a;               /* (4 B, C, H, W): T0, T2, T4, T6                                 */
+    float* out_b;               /* (4 B, C, W, H): T1, T3, T5, T7                                 */
+} GrlDihedralPackArgs;
+
+typedef struct GrlDihedralMergeArgs {
+    const void* member[8];      /* member[k] = model(T_k(x))                                      */
+    int64_t stride[8][4];       /* element strides of member k: batch, channel, row, column      */
+    int32_t dtype;              /* GRL_DT_F32 or GRL_DT_F16, of all eight                         */
+    int32_t B, C, Ho, Wo;       /* the OUTPUT's shape                                             */
+    int32_t reserved0;
+    float* out;                 /* (B, C, Ho, Wo)                                                 */
+} GrlDihedralMergeArgs;
+
+int grl_dihedral_pack(void* stream, const GrlDihedralPackArgs* args);
+int grl_dihedral_merge(void* stream, const GrlDihedralMergeArgs* args);
 
 /* Debug aid (ABI 21; no reference counterpart): fills the LDS of every CU with 0xFF bytes (fp32 / fp16 NaN) by a launch on
  * `stream`.  LDS keeps what the previous workgroup left in it; a kernel that reads LDS it has not written is otherwise right or
