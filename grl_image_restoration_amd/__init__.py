@@ -9,10 +9,11 @@ from .train import charbonnier, multistep_warmup_lr  # noqa: F401
 from .image8 import ImageWriter, pack8  # noqa: F401
 from .restore import restore_folder  # noqa: F401
 from .ensemble import SelfEnsemble  # noqa: F401
+from .remix import BatchRemix  # noqa: F401
 from .discriminator import UNetDiscriminatorSN  # noqa: F401
 from .gan import GanStep, gan_loss  # noqa: F401
 from .perceptual import PerceptualLoss, VGG19Features, load_vgg19  # noqa: F401
 
 __all__ = ["GRL", "FusedAdamW", "GraphedTrainStep", "make_config", "baseline_config", "PatchStore", "PatchSampler",
            "charbonnier", "multistep_warmup_lr", "pack8", "ImageWriter", "restore_folder", "UNetDiscriminatorSN", "GanStep", "gan_loss",
-           "PerceptualLoss", "VGG19Features", "load_vgg19", "SelfEnsemble"]
+           "PerceptualLoss", "VGG19Features", "load_vgg19", "SelfEnsemble", "BatchRemix"]

@@ -11,7 +11,7 @@ from . import switches as SW
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgrl_hip.so")
-ABI_VERSION = 41
+ABI_VERSION = 42
 DT_F32, DT_BF16, DT_F16 = 0, 1, 2
 
 EPI_PLAIN, EPI_GELU, EPI_GROUPNORM, EPI_LN_RES, EPI_GELU_GRAD = 0, 1, 2, 3, 4
@@ -741,6 +741,29 @@ class GrlDihedralMergeArgs(_Strict):
     ]
 
 
+class GrlRemixItem(_Strict):
+    _fields_ = [
+        ("src_a", C.c_int32), ("src_b", C.c_int32),
+        ("x0", C.c_int32), ("y0", C.c_int32),
+        ("lam", C.c_float),
+    ]
+
+
+class GrlBatchRemixArgs(_Strict):
+    _fields_ = [
+        ("lq", C.c_void_p),
+        ("lq_stride", C.c_int64 * 4),
+        ("gt", C.c_void_p),
+        ("gt_stride", C.c_int64 * 4),
+        ("B", C.c_int32), ("P", C.c_int32), ("Cl", C.c_int32), ("Cg", C.c_int32),
+        ("b", C.c_int32), ("p", C.c_int32), ("s", C.c_int32),
+        ("mix", C.c_int32),
+        ("items", C.c_void_p),
+        ("lq_out", C.c_void_p),
+        ("gt_out", C.c_void_p),
+    ]
+
+
 _I32, _I64, _PTR = C.c_int32, C.c_int64, C.c_void_p
 
 
@@ -830,6 +853,7 @@ SIGNATURES = {
     "grl_color_jitter": _launch(GrlColorJitterArgs),
     "grl_dihedral_pack": _launch(GrlDihedralPackArgs),
     "grl_dihedral_merge": _launch(GrlDihedralMergeArgs),
+    "grl_batch_remix": _launch(GrlBatchRemixArgs),
     "grl_debug_dirty_lds": (C.c_int, [_PTR]),
     "grl_abi_version": (C.c_int, []),
     "grl_build_info": (C.c_char_p, []),

@@ -1418,3 +1418,24 @@ def dihedral_merge(members, out: torch.Tensor) -> None:
             args.stride[k][d] = m.stride(d)
     with _timed("dihedral_merge"):
         L.launch("grl_dihedral_merge", args)
+
+
+# ---- progressive training and MixUp (csrc/remix.hip): mini-batch, mini-patch and blend of lq and gt in one launch ----------------------
+def batch_remix(lq: torch.Tensor, gt: torch.Tensor, items: torch.Tensor, b: int, p: int, scale: int, mix: bool,
+                lq_out: torch.Tensor, gt_out: torch.Tensor) -> None:
+    """grl_batch_remix: fp32 ``lq`` [B, Cl, P, P] and ``gt`` [B, Cg, sP, sP] (any strides, read in place) -> contiguous ``lq_out``
+    [b, Cl, p, p] and ``gt_out`` [b, Cg, sp, sp]; ``items`` is the device table of include/grl_hip.h, int32 [>= b, 5] contiguous:
+    src_a, src_b, x0, y0 and the bits of the fp32 lam."""
+    _dev_check(lq, gt, items, lq_out, gt_out)
+    assert lq.dim() == 4 and gt.dim() == 4 and lq.dtype == gt.dtype == torch.float32
+    B, Cl, P, _ = lq.shape
+    Cg = gt.shape[1]
+    assert lq.shape[3] == P and tuple(gt.shape) == (B, Cg, scale * P, scale * P), (tuple(lq.shape), tuple(gt.shape), scale)
+    assert items.dtype == torch.int32 and items.dim() == 2 and items.shape[1] == 5 and items.shape[0] >= b and items.is_contiguous()
+    for o, shape in ((lq_out, (b, Cl, p, p)), (gt_out, (b, Cg, scale * p, scale * p))):
+        assert tuple(o.shape) == shape and o.dtype == torch.float32 and o.is_contiguous(), (tuple(o.shape), shape)
+    args = L.GrlBatchRemixArgs(lq=_ptr(lq), lq_stride=(C.c_int64 * 4)(*lq.stride()), gt=_ptr(gt), gt_stride=(C.c_int64 * 4)(*gt.stride()),
+                               B=B, P=P, Cl=Cl, Cg=Cg, b=int(b), p=int(p), s=int(scale), mix=int(bool(mix)), items=_ptr(items),
+                               lq_out=_ptr(lq_out), gt_out=_ptr(gt_out))
+    with _timed("batch_remix"):
+        L.launch("grl_batch_remix", args)

@@ -58,6 +58,16 @@ checkpoint's ``args`` (``--resume`` takes ``--style-weight`` again, as it takes 
     python -m grl_image_restoration_amd.train --task sr --scale 4 --model base --geometry bsr --upsampler nearest+conv --gan \\
         --vgg vgg19-dcbb9e9d.pth --usm-percep --degrade --usm --ckpt runs/psnr/step_N.ckpt --lr 1e-4 --gt DF2K/HR --out runs/gan ...
 
+Progressive training and MixUp.  ``--stage-steps 1000+2000 --batch-sizes 8+4 --patch-sizes 32+64`` and ``--mixup [--mixup-after N]``
+restate what the reference's engine does to a batch between the loader and the model (engines/base.py:144-169; the transform is
+stated in include/grl_hip.h, ``grl_batch_remix``).  The sampler builds the full ``--batch`` x ``--patch`` batch as without them;
+``remix.BatchRemix`` then picks the stage's mini-batch, cuts its mini-patch and blends, one launch for lq and gt, from two streams
+of its own (``--seed`` + rank): the sampler's draws are those of the same run without the options.  A captured step has its shapes
+baked in: at a stage change it is finished and dropped, and the next one is built on the new shapes like the first step of a run
+(its warm-up step is that step's optimizer step); between replays the remix writes straight into the step's static buffers.
+Checkpoints carry the two streams under ``remix_rng``; ``--resume`` derives the stage from the step.  The result gains ``"stages"``.
+Not with ``--gan``.
+
 Data-parallel.  Under ``torchrun`` (torch.distributed initialised from the environment) the bare module goes to
 ``GraphedTrainStep``, which owns the gradient all-reduce; each rank's sampler is seeded ``seed + rank``; rank 0 validates and
 writes checkpoints.  ``--eager`` is single-process only.
@@ -105,7 +115,8 @@ LOSSES = {"l1": l1, "charbonnier": charbonnier}
 RECALIBRATE_EVERY = 200        # captured Charbonnier steps: eager re-measurement of the gradient scale (train_graph.py)
 
 
-def save_checkpoint(path: str, model, optimizer, step: int, sampler: D.PatchSampler, args: dict, model_d=None, optimizer_d=None):
+def save_checkpoint(path: str, model, optimizer, step: int, sampler: D.PatchSampler, args: dict, model_d=None, optimizer_d=None,
+                    remix=None):
     """``model_d`` / ``optimizer_d`` (--gan): the reference's GAN-stage layout -- ``model.model_g.<k>`` and ``model.model_d.<k>``, the
     u / v buffers of the spectral normalisation among them -- and the second optimizer under ``optimizer_d``."""
     if model_d is None:
@@ -117,6 +128,8 @@ def save_checkpoint(path: str, model, optimizer, step: int, sampler: D.PatchSamp
            "step": int(step), "optimizer": optimizer.state_dict(), "sampler_rng": sampler.rng_state(), "args": dict(args)}
     if optimizer_d is not None:
         obj["optimizer_d"] = optimizer_d.state_dict()
+    if remix is not None:                               # the streams of remix.BatchRemix; the stage follows from the step
+        obj["remix_rng"] = remix.rng_state()
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     torch.save(obj, path + ".tmp")
     os.replace(path + ".tmp", path)
@@ -199,6 +212,17 @@ def _parser():
     ap.add_argument("--style-weight", type=float, default=0.0, metavar="W",
                     help="--gan --vgg: W > 0 turns the style loss on (style_weight of losses.py:147-187: L1 between the Gram matrices of "
                          "the five tapped features, times W); 0: exactly the perceptual loss alone")
+    ap.add_argument("--stage-steps", default="", metavar="a+b",
+                    help="progressive training (engines/base.py:144-169): optimizer steps of every stage; with --batch-sizes and "
+                         "--patch-sizes, one entry per stage.  The sampler builds --batch x --patch; a stage trains on a drawn "
+                         "mini-batch and a drawn window of it (remix.BatchRemix, one grl_batch_remix launch)")
+    ap.add_argument("--batch-sizes", default="", metavar="a+b", help="--stage-steps: samples per step of every stage, at most --batch")
+    ap.add_argument("--patch-sizes", default="", metavar="a+b", help="--stage-steps: LQ patch side of every stage, at most --patch")
+    ap.add_argument("--mixup", action="store_true",
+                    help="blend every sample of a batch with a permuted partner, weights from Beta(1.2, 1.2) (the reference's "
+                         "MixUp_AUG, mixup: True of config/defaults.yaml)")
+    ap.add_argument("--mixup-after", type=int, default=0, metavar="STEP",
+                    help="--mixup: from this optimizer step on (the reference waits for its sixth epoch)")
     ap.add_argument("--device", default="cuda:0")
     return ap
 
@@ -240,6 +264,27 @@ def _check(ap, a):
         a.depth_list = [int(d) for d in a.depths.split("+")] if a.depths else None
     except ValueError:
         ap.error("--milestones and --depths are integers joined by +")
+    try:
+        a.stage_lists = [[int(v) for v in t.split("+") if v != ""] for t in (a.stage_steps, a.batch_sizes, a.patch_sizes)]
+    except ValueError:
+        ap.error("--stage-steps, --batch-sizes and --patch-sizes are integers joined by +")
+    stages, batches, patches = a.stage_lists
+    if not len(stages) == len(batches) == len(patches):
+        ap.error("--stage-steps, --batch-sizes and --patch-sizes take one entry per stage")
+    if any(v < 1 for t in a.stage_lists for v in t):
+        ap.error("--stage-steps, --batch-sizes and --patch-sizes hold positive integers")
+    if any(b > a.batch for b in batches) or any(p > a.patch for p in patches):
+        ap.error("--batch-sizes / --patch-sizes: a stage cannot exceed --batch / --patch, which the sampler builds")
+    if stages and sum(stages) < a.steps:
+        ap.error("--stage-steps must cover --steps: the reference would index past its lists")
+    if a.mixup_after and not a.mixup:
+        ap.error("--mixup-after belongs to --mixup")
+    if a.mixup_after < 0:
+        ap.error("--mixup-after is an optimizer step")
+    a.remix = bool(stages) or a.mixup
+    if a.remix and a.gan:
+        ap.error("--stage-steps, --batch-sizes, --patch-sizes and --mixup do not go with --gan: the GAN step carries up to three "
+                 "targets, the reference's engine remixes two")
     if a.metric is not None:
         from .metrics import ALL_GROUPS, PERCEPTUAL_GROUPS
 
@@ -249,7 +294,8 @@ def _check(ap, a):
 
 def main(argv: Optional[List[str]] = None):
     """Returns {"steps", "losses", "lrs", "work", "val", "checkpoint"}: per step taken in this call its index, loss, rate and work
-    list; (step, result) of every validation; the last checkpoint written."""
+    list; (step, result) of every validation; the last checkpoint written.  With the progressive / MixUp options also "stages":
+    (step, batch, patch) at the first step taken and at every change."""
     import torch.distributed as dist
 
     from . import GRL, FusedAdamW, GraphedTrainStep, make_config
@@ -332,6 +378,13 @@ def main(argv: Optional[List[str]] = None):
                              **(dict(plain_gt=True) if any(usm_flags) and not all(usm_flags) else {}),
                              **(dict(degrade=True, degrade_crop=a.degrade_crop, camera=camera, jitter=a.jitter) if a.degrade else {}))
 
+    remix = None
+    if a.remix:
+        from .remix import BatchRemix
+
+        remix = BatchRemix(a.batch, a.patch, a.scale, *a.stage_lists, mixup=a.mixup, mixup_after=a.mixup_after, seed=a.seed + rank,
+                           device=device)
+
     opt = FusedAdamW(model.parameters(), lr=a.lr, weight_decay=0.0 if a.gan else a.weight_decay)
     opt_d = FusedAdamW(model_d.parameters(), lr=a.lr, weight_decay=0.0) if a.gan else None
     start = 0
@@ -340,6 +393,8 @@ def main(argv: Optional[List[str]] = None):
         if opt_d is not None:
             opt_d.load_state_dict(resume["optimizer_d"])
         sampler.set_rng_state(resume["sampler_rng"])
+        if remix is not None and resume.get("remix_rng") is not None:
+            remix.set_rng_state(resume["remix_rng"])
         start = int(resume["step"])
 
     loss_fn = LOSSES[a.loss]
@@ -355,6 +410,9 @@ def main(argv: Optional[List[str]] = None):
     out = {"steps": [], "losses": [], "lrs": [], "work": [], "val": [], "checkpoint": None}
     step_fn = None
     gan_step = None
+    sizes = None                                        # (batch, patch) of the stage the captured step was built for
+    if remix is not None:
+        out["stages"] = []                              # (step, batch, patch) at the first step taken and at every change
     if a.gan:
         out["gan"] = []                                 # per step the reference's logged scalars (base_gan.py:103-140)
         gan_step = GanStep(model, model_d, opt, opt_d, loss_fn, pixel_weight=a.pixel_weight, gan_weight=a.gan_weight,
@@ -365,7 +423,8 @@ def main(argv: Optional[List[str]] = None):
         if step_fn is not None:
             step_fn.finish()
         if rank == 0 and a.out is not None:
-            out["checkpoint"] = save_checkpoint(os.path.join(a.out, f"step_{n}.ckpt"), model, opt, n, sampler, vars(a), model_d, opt_d)
+            out["checkpoint"] = save_checkpoint(os.path.join(a.out, f"step_{n}.ckpt"), model, opt, n, sampler, vars(a), model_d, opt_d,
+                                                remix)
 
     for n in range(start, a.steps):
         lr = lr_at(n)
@@ -374,6 +433,18 @@ def main(argv: Optional[List[str]] = None):
         work, sigmas = sampler.draw()
         batch = sampler.next(work, sigmas)
         lq, gt = batch[:2]
+        if remix is not None:
+            if remix.sizes(n) != sizes:
+                # a new stage has new shapes, and a captured step has its shapes baked in: drop it; the branch below builds the
+                # next one on this step's batch, exactly as the first step of a run is built
+                if step_fn is not None:
+                    step_fn.finish()
+                    step_fn = None
+                    seen.clear()
+                sizes = remix.sizes(n)
+                out["stages"].append((n,) + sizes)
+            # between replays the remix writes straight into the captured step's static buffers (its __call__ then copies nothing)
+            lq, gt = remix(n, lq, gt, out=(step_fn.lq, step_fn.gt) if step_fn is not None else None)
         if gan_step is not None:
             # (lq, sharpened, plain) when the two targets differ; else one target serves both roles
             plain, sharp = (batch[2], gt) if len(batch) == 3 else (gt, gt if any(usm_flags) else None)

@@ -23,7 +23,7 @@ extern "C" {
 
 #define GRL_ERR_BAD_ARG (-1)
 #define GRL_ERR_UNSUPPORTED (-2)
-#define GRL_ABI_VERSION 41
+#define GRL_ABI_VERSION 42
 
 /* element kinds of activation / weight buffers */
 enum { GRL_DT_F32 = 0, GRL_DT_BF16 = 1, GRL_DT_F16 = 2 };
@@ -1415,6 +1415,60 @@ typedef struct GrlDihedralMergeArgs {
 
 int grl_dihedral_pack(void* stream, const GrlDihedralPackArgs* args);
 int grl_dihedral_merge(void* stream, const GrlDihedralMergeArgs* args);
+
+/* ---------------------------------------------------------------------------------------------
+ * Progressive training and MixUp (ABI 42, csrc/remix.hip, remix.py): what the reference's engine does to every training batch
+ * between the data loader and the model.
+ *   restates  the progressive mini-batch / mini-patch of the training forward       engines/base.py:144-169
+ *             MixUp_AUG.aug                                                          utils/dataset_utils.py:43-60
+ * Inputs: lq (B, Cl, P, P) fp32 and gt (B, Cg, s P, s P) fp32, s the scale; Cl != Cg is legal (dual-pixel: 6 / 3).  Stage lengths
+ * L_0 .. L_{k-1} with cumulative sums S_g, batches b_g <= B, patches p_g <= P (LQ side).
+ *   Stage        the stage of optimizer step n is bisect.bisect_left(S, n): step n == S_0 still belongs to stage 0.
+ *   Mini-batch   idx = rng.sample(range(B), k=b) when b < B; sample i of the output is sample idx[i] of the input, in that order.
+ *                No draw when b == B.
+ *   Mini-patch   x0 = rng.randrange(P - p + 1), then y0 likewise, when p < P.  LQ rows x0 : x0 + p, columns y0 : y0 + p (x0 indexes
+ *                ROWS, as in the reference); the target is the same window times s.  No draw when p == P.
+ *   MixUp        perm = randperm(b), then lam = Beta(1.2, 1.2).rsample((b, 1)); out_i = lam_i * x_i + (1 - lam_i) * x_perm[i] for
+ *                lq and gt alike, in fp32, on the already reduced batch.  A fixed point of the permutation is still computed:
+ *                lam * x + (1 - lam) * x is not x in floating point.
+ *   Draw order   per step: sample, x0, y0 from a random.Random; then randperm, Beta from a CPU torch.Generator.
+ *
+ * grl_batch_remix does the whole transform for both tensors in one launch.  items[i], i < b, in DEVICE memory (rewritten in place
+ * from step to step, so a captured launch follows the table on replay):
+ *   out[i] = mix ? lam * A + (1 - lam) * B : A,   A / B = the window (x0, y0) of input sample src_a / src_b
+ * evaluated as __fadd_rn(__fmul_rn(lam, a), __fmul_rn(__fsub_rn(1.0f, lam), b)): four IEEE operations, no FMA, so the torch
+ * expression lam * a + (1 - lam) * b on the CPU gives the same bits; NaN and Inf propagate.  With mix == 0 the kernel copies A and
+ * reads neither B nor lam.  For the reference's transform src_a = idx[i], src_b = idx[perm[i]] and (x0, y0) is the same for every i.
+ * lq and gt are read in place through four ELEMENT strides (batch, channel, row, column); lq_out (b, Cl, p, p) and gt_out
+ * (b, Cg, s p, s p) are contiguous.  16-byte accesses are used for a row segment only where source A, source B and the destination
+ * are all 16-byte aligned there, 4-byte accesses elsewhere; no byte outside a window or outside the outputs is touched.
+ * The host validates a plan before it uploads it; the kernel still leaves an output sample unwritten rather than follow an item
+ * whose src_a / src_b is outside [0, B) or whose window leaves [0, P).  One launch, no workspace, no atomics, no host
+ * synchronisation.
+ *
+ * Errors, nothing is launched.  GRL_ERR_BAD_ARG: a null args / lq / gt / items / lq_out / gt_out, a non-positive B, P, Cl, Cg, b,
+ * p or s, p > P.  GRL_ERR_UNSUPPORTED: a pointer not aligned to 4 bytes, B C s P s P or b C s p s p of 2^31 elements or more for
+ * either tensor, b above 65535, 2^31 or more four-element row slots in one output sample of lq and gt together. */
+typedef struct GrlRemixItem {
+    int32_t src_a, src_b;       /* input samples blended into this output sample                  */
+    int32_t x0, y0;             /* LQ-side window origin: first row, first column                 */
+    float lam;                  /* weight of src_a; read only when mix != 0                       */
+} GrlRemixItem;
+
+typedef struct GrlBatchRemixArgs {
+    const float* lq;            /* (B, Cl, P, P)                                                  */
+    int64_t lq_stride[4];       /* element strides of batch, channel, row, column                */
+    const float* gt;            /* (B, Cg, s P, s P)                                              */
+    int64_t gt_stride[4];
+    int32_t B, P, Cl, Cg;
+    int32_t b, p, s;            /* output batch, LQ-side output patch, scale                      */
+    int32_t mix;
+    const GrlRemixItem* items;  /* [b], device                                                    */
+    float* lq_out;              /* (b, Cl, p, p)                                                  */
+    float* gt_out;              /* (b, Cg, s p, s p)                                              */
+} GrlBatchRemixArgs;
+
+int grl_batch_remix(void* stream, const GrlBatchRemixArgs* args);
 
 /* Debug aid (ABI 21; no reference counterpart): fills the LDS of every CU with 0xFF bytes (fp32 / fp16 NaN) by a launch on
  * `stream`.  LDS keeps what the previous workgroup left in it; a kernel that reads LDS it has not written is otherwise right or

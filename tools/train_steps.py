@@ -13,6 +13,7 @@ from grl_image_restoration_amd import GRL, FusedAdamW, GraphedTrainStep, baselin
 ap = argparse.ArgumentParser()
 ap.add_argument("--steps", type=int, default=3)
 ap.add_argument("--batch", type=int, default=8)
+ap.add_argument("--patch", type=int, default=64, help="LQ patch side (a stage of a progressive run: train --patch-sizes)")
 ap.add_argument("--graph", action="store_true", help="replay the captured step instead of eager steps (and print its time)")
 a = ap.parse_args()
 torch.manual_seed(0)
@@ -20,8 +21,8 @@ cfg = baseline_config(5)
 m = GRL(**cfg).cuda().train()
 opt = FusedAdamW(m.parameters(), lr=2e-4, weight_decay=1e-4)
 g = torch.Generator().manual_seed(100)
-lq = torch.rand(a.batch, 3, 64, 64, generator=g).cuda()
-gt = torch.rand(a.batch, 3, 64 * cfg["upscale"], 64 * cfg["upscale"], generator=g).cuda()
+lq = torch.rand(a.batch, 3, a.patch, a.patch, generator=g).cuda()
+gt = torch.rand(a.batch, 3, a.patch * cfg["upscale"], a.patch * cfg["upscale"], generator=g).cuda()
 loss_fn = lambda y, t: (y - t).abs().mean()
 if a.graph:
     import time
@@ -32,7 +33,7 @@ if a.graph:
     for _ in range(a.steps):
         loss = step(lq, gt)
     torch.cuda.synchronize()
-    print(f"graphed: {(time.perf_counter() - t0) / a.steps * 1e3:.2f} ms per step, loss {float(loss):.5f}")
+    print(f"graphed {a.batch} x {a.patch} x {a.patch}: {(time.perf_counter() - t0) / a.steps * 1e3:.2f} ms per step, loss {float(loss):.5f}")
 else:
     for _ in range(a.steps):
         opt.zero_grad(set_to_none=True)
