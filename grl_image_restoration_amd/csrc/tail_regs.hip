@@ -19,8 +19,9 @@
 //     belong to ONE wave and one lane per token, so the fp32 r1 simply overwrites the lane's x values in the LDS tile until
 //     the output epilogue needs it); waves 6, 7 hold fc1 tiles 6..8 / 9..11 (144 VGPRs);
 //   * NO weights in LDS: it holds the activations of a 32-token tile -- att, x (fp32) and cab, double buffered, brought in one
-//     tile ahead by the two fc1-only waves through their spare registers (see load_next); r1 and the hidden activations (fp16)
-//     are written by their producers in the natural K order of the consumers' B fragments;
+//     tile ahead by the two fc1-only waves through their spare registers, in two rounds that each fly for several phases and
+//     are waited for only where those waves are idle (round 9, see load_next); r1 and the hidden activations (fp16) are
+//     written by their producers in the natural K order of the consumers' B fragments;
 //   * a wave sees 32 of a token's 192 channels: the LayerNorms combine per-wave (mean, M2) pairs through LDS (Chan);
 //   * 192 of 256 VGPRs hold weights.  Everything else is written to keep few values alive: lane-derived offsets are recomputed
 //     at the head of every phase from an opaque lane id, epilogues run four channels at a time between scheduling barriers,
@@ -193,15 +194,29 @@ __global__ __launch_bounds__(TR_THREADS) void tail_regs_kernel(GrlTailArgs p) {
     fetch(blockIdx.x, 0);
     // After the first tile the two fc1-only waves bring the next tile in through REGISTERS: 51 LDS-DMA instructions cost every wave
     // ~2.3 k cycles of issue time at the head of a tile (an LDS-DMA of a wave does not overlap with its next one: measured ~300
-    // cycles apiece whoever issues them), while plain loads are all in flight at once.  Waves 6, 7 are idle during the projection
-    // and the first norm: each issues 12 loads of 16 B per lane after B0 (att, cab) and, once those are copied to the LDS buffers,
-    // 12 more after B1 (x), copied after B2 -- 48 registers, which these waves can spare.  Inline asm as in qkv_split_kernel (the compiler's
-    // wait-count bookkeeping would sit the loads out right after issuing them).
+    // cycles apiece whoever issues them), while plain loads are all in flight at once.  Each of waves 6, 7 issues 12 loads of
+    // 16 B per lane per round -- 48 registers, which these waves can spare, serve both rounds one after the other.  Inline asm as
+    // in qkv_split_kernel (the compiler's wait-count bookkeeping would sit the loads out right after issuing them).
+    // WHEN (round 9).  These waves work from B2 to B3b (fc1_pre, gelu_slice) and are idle from B3b to the next B2.  Neither wait may
+    // sit in their working stretch: the channel waves wait for them at B3a and B3b.  Until round 9 round 0 was issued after B0 and
+    // awaited after B1, round 1 issued before B2 and awaited right after it: 0.3 k + 0.7 k ticks of a 15.7 k-tick tile spent in
+    // the two s_waitcnt, the second at the head of the critical B2 -> B3a stretch.  Now:
+    //     B0 -> store x(this tile) ; issue att/cab(next) -> B1 -> B2 -> fc1_pre x3 -> B3a -> gelu_slice -> B3b
+    //        -> store att/cab(next) ; issue x(next) -> B4 -> next B0
+    // Round 0 flies from B0 to B3b (four phases), round 1 from B3b to the next B0 (second fc2 half, norm2, output epilogue); both
+    // s_waitcnt measure ~15 ticks, i.e. the data has always landed.  Buffer lifetimes: att / cab of the other parity are dead since
+    // B3b of the previous tile (last use: the parked pre-activations of gelu_slice); x is written into the CURRENT tile's buffer
+    // between B0 and B1 -- its last reader was the output epilogue two tiles ago, its first reader is the first norm after B1.
+    // stage_gate's extra barrier on an image change is run by all eight waves and may fall inside round 1's flight: harmless.
+    // HAZARD: the loads' destination registers are in flight across fc1_pre / gelu_slice code and the compiler does not know; the
+    // hardware has no interlock.  store_next's "+v" operands pin the values to the wait, and the generated code of the tile loop
+    // must name none of the 48 registers between a load and its s_waitcnt vmcnt(0) -- check the disassembly after any change
+    // here or in the compiler (profiles/r09_kernel_resources.txt records the check for this build).
     // Only the real 16-B segments travel, in groups of 192 = 3 wave-wide loads: 8 rows of att / cab (24 segments each) or 4 rows of
     // x (48): a lane's offsets inside a group are three constants per tensor kind (recomputed per call: ~30 instructions), the
     // group itself moves through the scalar offset -- 3 instructions per load instead of ~15 (the loader waves issue one
-    // instruction per ~10 cycles, and everybody waits for them at B1 / B2).  Round 0: wave 6 loads att, wave 7 cab (4 groups
-    // of 8 rows); round 1: x, wave 6 rows 0..15, wave 7 rows 16..31 (4 groups of 4 rows).
+    // instruction per ~10 cycles).  Round 0: wave 6 loads att, wave 7 cab (4 groups of 8 rows); round 1: x, wave 6 rows 0..15,
+    // wave 7 rows 16..31 (4 groups of 4 rows).
     f32x4 nb[12];
     auto lane_maps = [&](int segs, uint32_t rb, uint32_t pitch, uint32_t (&vo)[3], uint32_t (&lo)[3]) {
         const int lane = tr_lane();
@@ -294,8 +309,11 @@ __global__ __launch_bounds__(TR_THREADS) void tail_regs_kernel(GrlTailArgs p) {
     // The fc1-only waves have three fc1 tiles where a channel wave has one, and a tile is mostly GELU (16 per lane: ~150 of its ~190
     // instructions).  So they only run the MFMAs and park the fp32 PRE-activations (bias included) of their 2 x 96 hidden channels in
     // the att / cab buffers of the current tile -- dead since the first norm -- and after B3a all eight waves apply the GELU: a
-    // fc1-only wave to the first 48 channels of its own region (24 values per lane), channel wave w to 16 of the remaining 2 x 48
-    // (8 per lane, after its first fc2 half).  Phase lengths 2.7 k + 2.1 k cycles instead of 2.7 k + 3.8 k.
+    // fc1-only wave to the first 32 channels of its own region (16 values per lane); of the remaining 2 x 64, channel waves 0..3
+    // take 24 each (12 per lane) and waves 4, 5 take 16 (8 per lane), after their first fc2 half.  (Until round 9 the split was
+    // 48 per fc1-only wave and 16 per channel wave; the probes showed the fc1-only waves' 24 GELUs per lane taking 3.0 k ticks
+    // against 1.3 - 2.0 k of the channel waves' fc2 half + 8, i.e. everybody waiting 1.4 k ticks per tile at B3b; waves 4, 5 are
+    // the slowest channel waves of that stretch and keep their share.  Now 2.5 k against 1.7 - 2.3 k.)
     auto fc1_pre = [&](const f16x8* A, int t, char* region, int j, int half) {   // hidden channels 192 + 96 R + 32 t ..: pre-activations
         f32x16 h;
         tr_bias(h, vec + 7 * TR_CP, 192 + 96 * (wave - 6) + 32 * t + 4 * half);
@@ -388,7 +406,9 @@ __global__ __launch_bounds__(TR_THREADS) void tail_regs_kernel(GrlTailArgs p) {
                 tr_bias(acc, vec + 3 * TR_CP, ch0);
                 const char* hb = smem + TR_OFF_H + j * TR_HROW + 16 * half;
                 tr_gemm<TR_KS2 / 2>(Wt + 24, hb, acc);
-                gelu_slice(wave / 3, 48 + 16 * (wave % 3) + 8 * half, 2, j, buf, false);   // this wave's share of the fc1-only waves' GELUs
+                // this wave's share of the fc1-only waves' GELUs (see fc1_pre): waves 0..3 take 24 channels, waves 4, 5 take 16
+                if (wave < 4) gelu_slice(wave & 1, 32 + 24 * (wave >> 1) + 12 * half, 3, j, buf, false);
+                else gelu_slice(wave - 4, 80 + 8 * half, 2, j, buf, false);
                 tr_barrier();                              // B3b: hidden tile complete
                 tr_gemm<TR_KS2 / 2>(Wt + 36, hb + 32 * (TR_KS2 / 2), acc);
                 if (wave < 5) tr_ln_local<false>(acc, 0, inv_nw, st2 + wave * TR_T, j, half);
@@ -429,11 +449,11 @@ __global__ __launch_bounds__(TR_THREADS) void tail_regs_kernel(GrlTailArgs p) {
             if (it == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             tr_barrier();                                  // B0
             const int next = tile + (int)gridDim.x;
-            if (next < ntiles) load_next(next, 0);
+            // The loader's two rounds (see load_next); both waits sit where these two waves are idle and nobody waits for them.
+            if (it > 0) store_next(buf, 1);                // x of THIS tile, requested after B3b of the previous one; first read after B1
+            if (next < ntiles) load_next(next, 0);         // att / cab of the next tile: in flight until B3b
             tr_barrier();                                  // B1
-            if (next < ntiles) { store_next(buf ^ 1, 0); load_next(next, 1); }
             tr_barrier();                                  // B2
-            if (next < ntiles) store_next(buf ^ 1, 1);
             TR_LANE();
             char* region = smem + (wave == 6 ? TR_OFF_ATT : TR_OFF_CAB) + buf * TR_ABUF;   // dead since the first norm of this tile
             fc1_pre(Wt, 0, region, j, half);
@@ -442,8 +462,9 @@ __global__ __launch_bounds__(TR_THREADS) void tail_regs_kernel(GrlTailArgs p) {
             TR_SB();
             fc1_pre(Wt + 24, 2, region, j, half);
             tr_barrier();                                  // B3a: hidden channels 0..191 and all pre-activations complete
-            gelu_slice(wave - 6, 24 * half, 6, j, buf, true);
-            tr_barrier();                                  // B3b
+            gelu_slice(wave - 6, 16 * half, 4, j, buf, true);
+            tr_barrier();                                  // B3b (idle from here to the next B0)
+            if (next < ntiles) { store_next(buf ^ 1, 0); load_next(next, 1); }   // x of the next tile: in flight until its B0
             tr_barrier();                                  // B4
         }
     }
