@@ -11,7 +11,7 @@ from . import switches as SW
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgrl_hip.so")
-ABI_VERSION = 42
+ABI_VERSION = 43
 DT_F32, DT_BF16, DT_F16 = 0, 1, 2
 
 EPI_PLAIN, EPI_GELU, EPI_GROUPNORM, EPI_LN_RES, EPI_GELU_GRAD = 0, 1, 2, 3, 4
@@ -686,6 +686,34 @@ class GrlLpipsTapArgs(_Strict):
         ("partial", C.c_void_p),
         ("out", C.c_void_p),
         ("n_partial", C.c_int32), ("reserved0", C.c_int32),
+        ("gpartial", C.c_void_p),
+        ("gmax", C.c_void_p),
+    ]
+
+
+class GrlLpipsTapBwdArgs(_Strict):
+    _fields_ = [
+        ("f", C.c_void_p),
+        ("ldf", C.c_int64),
+        ("w", C.c_void_p),
+        ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("C", C.c_int32),
+        ("dpool", C.c_void_p),
+        ("lddp", C.c_int64),
+        ("d", C.c_void_p),
+        ("ldd", C.c_int64),
+        ("k", C.c_float),
+        ("reserved0", C.c_int32),
+    ]
+
+
+class GrlLpipsPrepBwdArgs(_Strict):
+    _fields_ = [
+        ("tok", C.c_void_p),
+        ("ldt", C.c_int64),
+        ("dx", C.c_void_p),
+        ("stride", C.c_int64 * 4),
+        ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+        ("scale", C.c_float),
     ]
 
 
@@ -846,6 +874,8 @@ SIGNATURES = {
     "grl_lpips_prep": _launch(GrlLpipsPrepArgs),
     "grl_lpips_tap_num_workgroups": (C.c_int, [_I32] * 4),
     "grl_lpips_tap": _launch(GrlLpipsTapArgs),
+    "grl_lpips_tap_bwd": _launch(GrlLpipsTapBwdArgs),
+    "grl_lpips_prep_bwd": _launch(GrlLpipsPrepBwdArgs),
     "grl_isp_unprocess": _launch(GrlIspArgs),
     "grl_isp_process": _launch(GrlIspArgs),
     "grl_isp_roundtrip": _launch(GrlIspArgs),

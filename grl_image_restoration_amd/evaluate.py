@@ -396,16 +396,17 @@ def _check(ap, a):
     a.scale, a.sigma = o.scale, o.sigma
 
 
-def load_lpips_arguments(ap, a):
+def load_lpips_arguments(ap, a, needed_by=None):
     """The ``lpips.LPIPS`` that ``--metric restorer_perceptual`` needs, from ``--lpips-vgg`` and ``--lpips-lin`` (evaluate and train);
-    None for every other group.  A missing option, file or key ends through ``ap.error``."""
-    if a.metric != "restorer_perceptual":
+    None for every other group -- unless ``needed_by`` names another option that takes the model (train's ``--lpips-weight``).  A
+    missing option, file or key ends through ``ap.error``."""
+    if a.metric != "restorer_perceptual" and needed_by is None:
         if a.lpips_vgg is not None or a.lpips_lin is not None:
             ap.error("--lpips-vgg and --lpips-lin belong to --metric restorer_perceptual")
         return None
     for opt, path in (("--lpips-vgg", a.lpips_vgg), ("--lpips-lin", a.lpips_lin)):
         if path is None:
-            ap.error(f"--metric restorer_perceptual needs {opt} (torchvision's vgg16-397923af.pth / the lpips package's vgg.pth)")
+            ap.error(f"{needed_by or '--metric restorer_perceptual'} needs {opt} (torchvision's vgg16-397923af.pth / the lpips package's vgg.pth)")
         if not os.path.isfile(path):
             ap.error(f"{opt}: file {path!r} not found")
     from .lpips import load_lpips

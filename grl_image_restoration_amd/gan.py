@@ -39,19 +39,23 @@ class GanStep:
     returning ``(percep_loss, style_loss)``); its term, times ``perceptual_weight``, joins the generator's loss between the pixel and
     the GAN term (base_gan.py:105-112) against ``gt_usm`` under ``usm_percep``, and ``loss_g_percep`` joins the scalars.  A style
     term that is not None is multiplied by ``perceptual_weight`` as well (base_gan.py:113-116), joins the loss after the perceptual
-    term and the scalars as ``loss_g_style``.  With ``perceptual=None`` nothing of either exists."""
+    term and the scalars as ``loss_g_style``.  With ``perceptual=None`` nothing of either exists.  ``lpips``: an ``lpips.LPIPSLoss`` (or
+    any callable returning a scalar); its term, times ``lpips_weight``, joins the generator's loss after the style term and before the
+    GAN term, against ``gt_usm`` under ``usm_lpips``, and ``loss_g_lpips`` joins the scalars in that position (the reference's engine has
+    no such term: it only scores LPIPS).  With ``lpips=None`` nothing of it exists."""
 
     def __init__(self, model_g, model_d, opt_g, opt_d, pixel_loss: Callable, pixel_weight: float = 1.0, gan_weight: float = 1.0,
                  gan_loss_weight: float = 0.1, usm_pixel: bool = False, usm_gan: bool = False, perceptual=None,
-                 perceptual_weight: float = 1.0, usm_percep: bool = False):
+                 perceptual_weight: float = 1.0, usm_percep: bool = False, lpips=None, lpips_weight: float = 1.0, usm_lpips: bool = False):
         self.model_g, self.model_d, self.opt_g, self.opt_d = model_g, model_d, opt_g, opt_d
         self.pixel_loss, self.pixel_weight, self.gan_weight, self.gan_loss_weight = pixel_loss, pixel_weight, gan_weight, gan_loss_weight
         self.usm_pixel, self.usm_gan = usm_pixel, usm_gan
         self.perceptual, self.perceptual_weight, self.usm_percep = perceptual, perceptual_weight, usm_percep and perceptual is not None
+        self.lpips, self.lpips_weight, self.usm_lpips = lpips, lpips_weight, usm_lpips and lpips is not None
 
     def __call__(self, lq: torch.Tensor, gt: torch.Tensor, gt_usm: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
-        if (self.usm_pixel or self.usm_gan or self.usm_percep) and gt_usm is None:
-            raise ValueError("usm_pixel / usm_gan / usm_percep need the sharpened target")
+        if (self.usm_pixel or self.usm_gan or self.usm_percep or self.usm_lpips) and gt_usm is None:
+            raise ValueError("usm_pixel / usm_gan / usm_percep / usm_lpips need the sharpened target")
         G, D_ = self.model_g, self.model_d
         out = {}
         # ---- optimizer 0: the generator (base_gan.py:96-126); toggle_optimizer: the discriminator's parameters are off ----
@@ -68,10 +72,13 @@ class GanStep:
                     loss_g_percep = loss_g_percep * self.perceptual_weight
                 if loss_g_style is not None:
                     loss_g_style = loss_g_style * self.perceptual_weight
+            loss_g_lpips = None
+            if self.lpips is not None:
+                loss_g_lpips = self.lpips(restored, gt_usm if self.usm_lpips else gt) * self.lpips_weight
             loss_g_gan = gan_loss(D_(restored), True, is_disc=False, weight=self.gan_loss_weight) * self.gan_weight
             self.opt_g.zero_grad(set_to_none=True)
             total = loss_g_pix
-            for term in (loss_g_percep, loss_g_style, loss_g_gan):
+            for term in (loss_g_percep, loss_g_style, loss_g_lpips, loss_g_gan):
                 if term is not None:
                     total = total + term
             total.backward()
@@ -85,6 +92,8 @@ class GanStep:
             out["loss_g_percep"] = loss_g_percep.detach()
         if loss_g_style is not None:
             out["loss_g_style"] = loss_g_style.detach()
+        if loss_g_lpips is not None:
+            out["loss_g_lpips"] = loss_g_lpips.detach()
         out["loss_g_gan"] = loss_g_gan.detach()
         # ---- optimizer 1: the discriminator (base_gan.py:129-145); training_step calls self(batch) again ----
         with torch.no_grad():

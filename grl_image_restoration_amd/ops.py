@@ -1335,11 +1335,12 @@ def lpips_prep(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Ten
 
 
 def lpips_tap(f: torch.Tensor, w: torch.Tensor, B: int, H: int, W: int, out: torch.Tensor, *, accumulate: bool = True, pool: bool = True,
-              pool_out: Optional[torch.Tensor] = None):
+              pool_out: Optional[torch.Tensor] = None, gmax: Optional[torch.Tensor] = None):
     """grl_lpips_tap on one tapped layer.  f [2*B*H*W, C] fp32: the pre-activation, restored rows first, then the target's; w [C]
     fp32.  out [B] float64 (+)= the layer's distance per image (fixed order, no atomics).  With ``pool`` returns
-    maxpool2x2(relu(f)) [2 * B*(H/2)*(W/2), C] as the 16-bit operand of the next block, else None."""
-    _dev_check(f, w, out, pool_out)
+    maxpool2x2(relu(f)) [2 * B*(H/2)*(W/2), C] as the 16-bit operand of the next block, else None.  ``gmax`` [1] fp32 (the training
+    forward) receives the layer's gradient bound G: the largest tap gradient of ``lpips_tap_bwd`` before its k."""
+    _dev_check(f, w, out, pool_out, gmax)
     assert f.dim() == 2 and f.shape[0] == 2 * B * H * W and f.dtype == torch.float32 and f.stride(1) == 1
     C_ = f.shape[1]
     assert w.shape == (C_,) and w.dtype == torch.float32 and w.is_contiguous()
@@ -1353,12 +1354,47 @@ def lpips_tap(f: torch.Tensor, w: torch.Tensor, B: int, H: int, W: int, out: tor
         if pool_out is None:
             pool_out = empty(2 * rows, C_, dtype=GEMM_DTYPE, device=f.device)
         assert pool_out.shape == (2 * rows, C_) and pool_out.dtype == GEMM_DTYPE and pool_out.is_contiguous()
+    gpartial = None
+    if gmax is not None:
+        assert gmax.shape == (1,) and gmax.dtype == torch.float32
+        gpartial = empty(nwg, dtype=torch.float32, device=f.device)
     args = L.GrlLpipsTapArgs(f=_ptr(f), ldf=f.stride(0), w=_ptr(w), B=B, H=H, W=W, C=C_, pool=int(pool), accumulate=int(accumulate),
                              pool_out=_ptr(pool_out) if pool else None, ldp=C_ if pool else 0, partial=_ptr(partial), out=_ptr(out),
-                             n_partial=nwg)
+                             n_partial=nwg, gpartial=_ptr(gpartial), gmax=_ptr(gmax))
     with _timed("lpips_tap"):
         L.launch("grl_lpips_tap", args)
     return pool_out if pool else None
+
+
+def lpips_tap_bwd(f: torch.Tensor, w: torch.Tensor, B: int, H: int, W: int, k: float, dpool: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """grl_lpips_tap_bwd: d [B*H*W, C] fp32 = k * (the tap term's gradient at the restored half of f [2*B*H*W, C]) + the gradient
+    ``dpool`` [B*(H/2)*(W/2), C] routed through the 2 x 2 max pool (first maximum of a window), all under the select pre > 0;
+    ``dpool`` None: the last tap.  k = S * upstream / (B*H*W)."""
+    _dev_check(f, w, dpool)
+    assert f.dim() == 2 and f.shape[0] == 2 * B * H * W and f.dtype == torch.float32 and f.stride(1) == 1
+    C_ = f.shape[1]
+    assert w.shape == (C_,) and w.dtype == torch.float32 and w.is_contiguous()
+    if dpool is not None:
+        assert dpool.shape == (B * (H // 2) * (W // 2), C_) and dpool.dtype == torch.float32 and dpool.stride(1) == 1
+    d = empty(B * H * W, C_, dtype=torch.float32, device=f.device)
+    args = L.GrlLpipsTapBwdArgs(f=_ptr(f), ldf=f.stride(0), w=_ptr(w), B=B, H=H, W=W, C=C_, dpool=_ptr(dpool),
+                                lddp=dpool.stride(0) if dpool is not None else 0, d=_ptr(d), ldd=C_, k=k)
+    with _timed("lpips_tap_bwd"):
+        L.launch("grl_lpips_tap_bwd", args)
+    return d
+
+
+def lpips_prep_bwd(dtok: torch.Tensor, B: int, H: int, W: int, *, scale: float = 1.0) -> torch.Tensor:
+    """grl_lpips_prep_bwd: the gradient token matrix [B*H*W, >= 4] -> the image gradient [B, 3, H, W] fp32 = 2 * g / scale_c times
+    ``scale`` (the removal of the chain's operand scale)."""
+    _dev_check(dtok)
+    assert dtok.dim() == 2 and dtok.shape[0] == B * H * W and dtok.shape[1] >= 4 and dtok.dtype == torch.float32 and dtok.stride(1) == 1
+    dx = empty(B, 3, H, W, dtype=torch.float32, device=dtok.device)
+    args = L.GrlLpipsPrepBwdArgs(tok=_ptr(dtok), ldt=dtok.stride(0), dx=_ptr(dx), stride=(C.c_int64 * 4)(*dx.stride()), B=B, H=H, W=W,
+                                 scale=scale)
+    with _timed("lpips_prep_bwd"):
+        L.launch("grl_lpips_prep_bwd", args)
+    return dx
 
 
 # ---- training patches, several views of one work list (csrc/patches.hip) --------------------------------------------------------------

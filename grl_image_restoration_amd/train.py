@@ -54,6 +54,10 @@ perceptual loss (``perceptual.PerceptualLoss``); the frozen VGG is not written i
 ``--style-weight W`` (W > 0) adds the style half of that criterion (losses/losses.py:147-187: L1 between the Gram matrices of the same
 five features, ``perceptual.PerceptualStyleLoss``); its scalar ``loss_g_style`` joins the log line, and the weight is kept in the
 checkpoint's ``args`` (``--resume`` takes ``--style-weight`` again, as it takes ``--vgg``).
+``--lpips-weight W`` (W > 0, with ``--lpips-vgg`` and ``--lpips-lin``) adds W times LPIPS (``lpips.LPIPSLoss``, the VGG16 trunk the metric
+group ``restorer_perceptual`` scores with) after the style term, against the sharpened GT under ``--usm-lpips``; its scalar is
+``loss_g_lpips``.  One loaded model serves the loss and, with ``--metric restorer_perceptual``, the validation.  The reference's engine
+has no such term.  The weight is kept in the checkpoint's ``args``; the frozen trunk is not written, ``--resume`` takes the files again.
 
     python -m grl_image_restoration_amd.train --task sr --scale 4 --model base --geometry bsr --upsampler nearest+conv --gan \\
         --vgg vgg19-dcbb9e9d.pth --usm-percep --degrade --usm --ckpt runs/psnr/step_N.ckpt --lr 1e-4 --gt DF2K/HR --out runs/gan ...
@@ -212,6 +216,11 @@ def _parser():
     ap.add_argument("--style-weight", type=float, default=0.0, metavar="W",
                     help="--gan --vgg: W > 0 turns the style loss on (style_weight of losses.py:147-187: L1 between the Gram matrices of "
                          "the five tapped features, times W); 0: exactly the perceptual loss alone")
+    ap.add_argument("--lpips-weight", type=float, default=None, metavar="W",
+                    help="--gan: W > 0 adds W times LPIPS (lpips.LPIPSLoss: the mean over the batch, VGG16 trunk) to the generator's loss, "
+                         "after the style term; needs --lpips-vgg and --lpips-lin, which then also serve --metric restorer_perceptual. "
+                         "The frozen trunk is not written into checkpoints: --resume takes the two files again")
+    ap.add_argument("--usm-lpips", action="store_true", help="--gan --lpips-weight: the LPIPS target is the USM-sharpened GT")
     ap.add_argument("--stage-steps", default="", metavar="a+b",
                     help="progressive training (engines/base.py:144-169): optimizer steps of every stage; with --batch-sizes and "
                          "--patch-sizes, one entry per stage.  The sampler builds --batch x --patch; a stage trains on a drawn "
@@ -231,7 +240,8 @@ def _check(ap, a):
     if a.val_every and a.val_gt is None:
         ap.error("--val-every needs --val-gt")
     o = resolve_arguments(ap, a, "train", sigma_range=a.sigma_range, quality_range=a.quality_range, patch=a.patch,
-                          val=bool(a.val_every), val_lq=a.val_lq is not None, usm=a.usm or a.usm_gan or a.usm_percep, val_usm=a.val_usm,
+                          val=bool(a.val_every), val_lq=a.val_lq is not None, usm=a.usm or a.usm_gan or a.usm_percep or a.usm_lpips,
+                          val_usm=a.val_usm,
                           degrade=a.degrade, degrade_crop=a.degrade_crop, gan=a.gan, camera=a.camera_profiles is not None,
                           jitter=a.jitter, dual_pixel=a.lq_r is not None)
     a.scale, a.sigma, a.degrade_crop = o.scale, o.sigma, o.degrade_crop
@@ -251,6 +261,18 @@ def _check(ap, a):
         ap.error("--style-weight must not be negative")
     if a.vgg is not None and a.patch * a.scale < 16:
         ap.error("--vgg: the GT patch side (--patch times --scale) must be at least 16 (VGG19 pools four times)")
+    if a.lpips_weight is None:
+        if a.usm_lpips:
+            ap.error("--usm-lpips needs --lpips-weight")
+    else:
+        if not a.gan:
+            ap.error("--lpips-weight belongs to --gan")
+        if not a.lpips_weight > 0.0:
+            ap.error("--lpips-weight must be positive")
+        if a.lpips_vgg is None or a.lpips_lin is None:
+            ap.error("--lpips-weight needs --lpips-vgg and --lpips-lin (torchvision's vgg16-397923af.pth / the lpips package's vgg.pth)")
+        if a.patch * a.scale < 16:
+            ap.error("--lpips-weight: the GT patch side (--patch times --scale) must be at least 16 (VGG16 pools four times)")
     if a.gan and int(os.environ.get("WORLD_SIZE", "1")) > 1:
         ap.error("--gan runs eagerly: --eager is single-process; the captured step owns the gradient all-reduce")
     if a.gan and (a.patch * a.scale) % 8:
@@ -305,7 +327,8 @@ def main(argv: Optional[List[str]] = None):
     a = ap.parse_args(argv)
     _check(ap, a)
     taps = load_taps(ap, a)
-    lpips_model, niqe_params = load_lpips_arguments(ap, a), None
+    # one loaded model serves the loss (--lpips-weight) and, if asked, the metric
+    lpips_model, niqe_params = load_lpips_arguments(ap, a, needed_by="--lpips-weight" if a.lpips_weight is not None else None), None
     if a.metric == "restorer_perceptual":
         from .metrics import load_niqe_params
 
@@ -361,13 +384,19 @@ def main(argv: Optional[List[str]] = None):
                 percep = PerceptualStyleLoss(GAN_LAYER_WEIGHTS, load_vgg19(a.vgg), style_weight=a.style_weight).to(device)
             else:
                 percep = PerceptualLoss(GAN_LAYER_WEIGHTS, load_vgg19(a.vgg)).to(device)
+        lpips_loss = None
+        if a.lpips_weight is not None:
+            from .lpips import LPIPSLoss
+
+            lpips_loss = LPIPSLoss(lpips_model).to(device)
 
     camera = None
     if a.camera_profiles is not None:
         from .isp import CameraBank
 
         camera = CameraBank.load(a.camera_profiles)
-    usm_flags = [a.usm, a.usm_gan] + ([a.usm_percep] if a.vgg is not None else [])      # the targets that are the sharpened GT
+    # the targets that are the sharpened GT
+    usm_flags = [a.usm, a.usm_gan] + ([a.usm_percep] if a.vgg is not None else []) + ([a.usm_lpips] if a.lpips_weight is not None else [])
     gt_store = D.PatchStore.from_folder(a.gt, a.channels, device)
     lq_store = D.PatchStore.from_folder(a.lq, a.channels, device) if a.lq is not None else None
     lq_r_store = D.PatchStore.from_folder(a.lq_r, a.channels, device) if a.lq_r is not None else None
@@ -417,7 +446,8 @@ def main(argv: Optional[List[str]] = None):
         out["gan"] = []                                 # per step the reference's logged scalars (base_gan.py:103-140)
         gan_step = GanStep(model, model_d, opt, opt_d, loss_fn, pixel_weight=a.pixel_weight, gan_weight=a.gan_weight,
                            gan_loss_weight=a.gan_loss_weight, usm_pixel=a.usm, usm_gan=a.usm_gan, perceptual=percep,
-                           perceptual_weight=a.perceptual_weight, usm_percep=a.usm_percep)
+                           perceptual_weight=a.perceptual_weight, usm_percep=a.usm_percep, lpips=lpips_loss,
+                           lpips_weight=a.lpips_weight if a.lpips_weight is not None else 1.0, usm_lpips=a.usm_lpips)
 
     def checkpoint(n):
         if step_fn is not None:
@@ -450,7 +480,7 @@ def main(argv: Optional[List[str]] = None):
             plain, sharp = (batch[2], gt) if len(batch) == 3 else (gt, gt if any(usm_flags) else None)
             logged = gan_step(lq, plain, sharp)
             out["gan"].append({k: float(v) for k, v in logged.items()})
-            loss = sum(logged[k] for k in ("loss_g_pix", "loss_g_percep", "loss_g_style", "loss_g_gan") if k in logged)
+            loss = sum(logged[k] for k in ("loss_g_pix", "loss_g_percep", "loss_g_style", "loss_g_lpips", "loss_g_gan") if k in logged)
         elif a.eager:
             opt.zero_grad(set_to_none=True)
             loss = loss_fn(model(lq), gt)

@@ -23,7 +23,7 @@ extern "C" {
 
 #define GRL_ERR_BAD_ARG (-1)
 #define GRL_ERR_UNSUPPORTED (-2)
-#define GRL_ABI_VERSION 42
+#define GRL_ABI_VERSION 43
 
 /* element kinds of activation / weight buffers */
 enum { GRL_DT_F32 = 0, GRL_DT_BF16 = 1, GRL_DT_F16 = 2 };
@@ -1234,6 +1234,10 @@ int grl_lpips_prep(void* stream, const GrlLpipsPrepArgs* args);
  *       image), a finishing launch adds them in a fixed order.  No atomics: bit-identical from run to run; equal halves give 0.
  *   (b) pool != 0: pool_out [2*B*(H/2)*(W/2), ldp] 16-bit (GRL_DT_F16) = maxpool2x2(relu(f)) of both halves in f's order, floor
  *       sizes as nn.MaxPool2d(2, 2) (an odd last row / column is not pooled, and still counts in (a)); NaN is kept.
+ *   (c) gmax != NULL (ABI 43, the training forward): gmax[0] (fp32) = G = max over the restored half's pixels and the channels with
+ *       f0_c > 0 of |r * (e_c - (f0_c / n) * sum_j e_j u0_j)|, the tap term's gradient of grl_lpips_tap_bwd before its k (0 where no
+ *       channel qualifies); gpartial [n_partial] fp32 holds one maximum per (workgroup, image), the finishing launch reduces them.
+ *       No atomics.  (a) and (b) are the same bits with and without (c); gmax == NULL is the call of ABI 36.
  * Bad pointers / leading dimensions: GRL_ERR_BAD_ARG, nothing is launched. */
 typedef struct GrlLpipsTapArgs {
     const float* f;
@@ -1246,10 +1250,52 @@ typedef struct GrlLpipsTapArgs {
     double* partial;
     double* out;
     int32_t n_partial, reserved0;
+    float* gpartial;            /* (c): [n_partial] fp32, else NULL                               */
+    float* gmax;                /* (c): [1] fp32; NULL: no gradient bound                         */
 } GrlLpipsTapArgs;
 
 int grl_lpips_tap_num_workgroups(int32_t B, int32_t H, int32_t W, int32_t C);
 int grl_lpips_tap(void* stream, const GrlLpipsTapArgs* args);
+
+/* LPIPS as a training loss (ABI 43): the adjoints of grl_lpips_tap and grl_lpips_prep for the restored half.
+ *   replaces  torch autograd through lpips.LPIPS(net="vgg").forward(img1, img2, normalize=True): normalize_tensor, the 1x1 lin
+ *             layers, spatial_average, and the ReLU + MaxPool2d(2, 2) of torchvision's vgg16().features that follow a tapped layer
+ * loss = mean_b sum_l mean_pixels sum_c w_c (u0_c - u1_c)^2.  Per pixel of the restored half, with f0 = relu(pre0), n = ||f0||_2 over
+ * channels, r = 1 / (n + 1e-10), u0 = f0 * r (u1 likewise from the target), e_c = 2 w_c (u0_c - u1_c), k_l = upstream / (B*H*W):
+ *     dL/df0_c   = k_l * r * (e_c - (f0_c / n) * sum_j e_j u0_j),   f0_c / n := 0 where n = 0
+ *     dL/dpre0_c = pre0_c > 0 ? dL/df0_c + (the pool gradient where this pixel holds the first maximum of its 2 x 2 window) : 0
+ * grl_lpips_tap_bwd: f, w, B, H, W, C as in grl_lpips_tap (only the restored half gets a gradient; the target half is read);
+ *   dpool [B*(H/2)*(W/2), lddp] fp32 or NULL (the last tap): the gradient of the pooled output, already under the scale S;
+ *   d [B*H*W, ldd] fp32 = k * r * (...) + routed dpool under the select, k = S * k_l.  u0 - u1 is evaluated as in the forward
+ *   (normalise, then subtract).  Pixels MaxPool's floor drops (odd H or W) get the tap term and no pool term; masked entries and
+ *   pixels whose post-ReLU features are all zero are exactly 0.  No atomics: bit-identical from run to run. */
+typedef struct GrlLpipsTapBwdArgs {
+    const float* f;
+    int64_t ldf;
+    const float* w;
+    int32_t B, H, W, C;
+    const float* dpool;
+    int64_t lddp;
+    float* d;
+    int64_t ldd;
+    float k;                    /* S * upstream / (B*H*W)                                         */
+    int32_t reserved0;
+} GrlLpipsTapBwdArgs;
+
+int grl_lpips_tap_bwd(void* stream, const GrlLpipsTapBwdArgs* args);
+
+/* grl_lpips_prep_bwd: tok [B*H*W, ldt >= 4] fp32 (the gradient token matrix, columns 0..2) -> dx (fp32, element strides stride[0..3]
+ *   over (b, c, y, x)): dx_c = 2 * tok_c / scale[c] * scale, scale = 1 / S. */
+typedef struct GrlLpipsPrepBwdArgs {
+    const float* tok;
+    int64_t ldt;
+    float* dx;
+    int64_t stride[4];
+    int32_t B, H, W;
+    float scale;
+} GrlLpipsPrepBwdArgs;
+
+int grl_lpips_prep_bwd(void* stream, const GrlLpipsPrepBwdArgs* args);
 
 /* ---------------------------------------------------------------------------------------------
  * The camera-noise stage of the blind-SR degradation (ABI 37, csrc/isp.hip): stage 2 of degradation_sr2, the ISP model.
