@@ -11,7 +11,7 @@ from . import switches as SW
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgrl_hip.so")
-ABI_VERSION = 43
+ABI_VERSION = 44
 DT_F32, DT_BF16, DT_F16 = 0, 1, 2
 
 EPI_PLAIN, EPI_GELU, EPI_GROUPNORM, EPI_LN_RES, EPI_GELU_GRAD = 0, 1, 2, 3, 4
@@ -335,6 +335,31 @@ class GrlAdamWArgs(_Strict):
         ("grad_scale", C.c_float),
         ("bias_corrections_dev", C.c_void_p),
         ("hyper_dev", C.c_void_p),
+        ("grad_clip_dev", C.c_void_p),
+        ("ema", C.c_void_p),
+        ("ema_decay", C.c_float),
+    ]
+
+
+class GrlGradNormArgs(_Strict):
+    _fields_ = [
+        ("grads", C.c_void_p),
+        ("numel", C.c_void_p),
+        ("chunk_tensor", C.c_void_p),
+        ("chunk_offset", C.c_void_p),
+        ("num_chunks", C.c_int32),
+        ("partials", C.c_void_p),
+        ("base", C.c_int64),
+    ]
+
+
+class GrlGradClipArgs(_Strict):
+    _fields_ = [
+        ("partials", C.c_void_p),
+        ("n_partials", C.c_int64),
+        ("grad_scale", C.c_float),
+        ("max_norm", C.c_float),
+        ("out", C.c_void_p),
     ]
 
 
@@ -827,6 +852,8 @@ SIGNATURES = {
     "grl_gemm_tn": _launch(GrlGemmTnArgs),
     "grl_attention_bwd": _launch(GrlAttnBwdArgs),
     "grl_adamw_step": _launch(GrlAdamWArgs),
+    "grl_grad_sqnorm": _launch(GrlGradNormArgs),
+    "grl_grad_clip_finish": _launch(GrlGradClipArgs),
     "grl_layernorm_train_fwd": _launch(GrlLnTrainArgs),
     "grl_layernorm_bwd": _launch(GrlLnTrainArgs),
     "grl_pack_conv3x3": (C.c_int, [_PTR] * 5 + [_I32] * 5),

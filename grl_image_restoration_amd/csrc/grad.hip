@@ -9,7 +9,11 @@
 //       with taps = 16 the sixteen taps of a 4x4 stride-2 convolution (models/aux_archs/discriminator.py:102-104):
 //       dW[ky*4+kx][co][ci] = sum_{oy,ox} dY[oy, ox, co] * X[2 oy + ky - 1, 2 ox + kx - 1, ci].
 //   grl_adamw_step : torch.optim.AdamW (config/optimizer/adamw.yaml) over a list of tensors in ONE launch
-//       (1390 parameter tensors for GRL-Base: a per-tensor launch would be host-bound).
+//       (1390 parameter tensors for GRL-Base: a per-tensor launch would be host-bound).  Optionally (ABI 44) with the
+//       gradient scaled by a device-resident clip coefficient and an exponential moving average of the new weights.
+//   grl_grad_sqnorm, grl_grad_clip_finish : gradient clipping by global norm (torch.nn.utils.clip_grad_norm_) without a
+//       host read or a rewrite of the gradients: per-chunk sums of squares in double, then one workgroup turns them into
+//       {coefficient, norm} in device memory, which the AdamW launch reads.
 //
 // gemm_tn design: the reduction dimension (tokens) is the long one (M ~ 10^4..10^6, N, K <= 576), i.e. both operands
 // are tall-skinny matrices read once per output tile column/row.  A workgroup owns a 64 x 64 output tile and a slab of
@@ -159,6 +163,9 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(GrlGemmTnArgs p) {
 }
 
 // ---- multi-tensor AdamW ----------------------------------------------------------------------------------------------
+// CLIP / EMA are compile-time: the (false, false) instance is the kernel as it was before ABI 44 -- same arithmetic, same
+// seven memory streams -- so a run without the two features pays nothing for them.
+template <bool CLIP, bool EMA>
 __global__ __launch_bounds__(256) void adamw_kernel(GrlAdamWArgs p) {
     // chunk -> (tensor, offset): one workgroup per 4096-element chunk of one tensor
     const int ch = blockIdx.x;
@@ -169,6 +176,7 @@ __global__ __launch_bounds__(256) void adamw_kernel(GrlAdamWArgs p) {
     const float* g = (const float*)p.grads[t];
     float* m = (float*)p.exp_avg[t];
     float* v = (float*)p.exp_avg_sq[t];
+    float* e = EMA ? (float*)p.ema[t] : nullptr;
     // (captured launches: learning rate and weight decay come from device memory, refreshed by the host before each replay)
     const float lr = p.hyper_dev != nullptr ? p.hyper_dev[0] : p.lr;
     const float wd_all = p.hyper_dev != nullptr ? p.hyper_dev[1] : p.weight_decay;
@@ -178,9 +186,12 @@ __global__ __launch_bounds__(256) void adamw_kernel(GrlAdamWArgs p) {
         bc1 = p.bias_corrections_dev[0];
         bc2s = p.bias_corrections_dev[1];
     }
+    // the clip coefficient (grl_grad_clip_finish wrote it earlier on this stream) folds into the gradient scale, once, in fp32
+    const float gs = CLIP ? p.grad_scale * p.grad_clip_dev[0] : p.grad_scale;
+    const float ema_w = 1.0f - p.ema_decay;
 #pragma unroll 4
     for (int64_t i = off + threadIdx.x; i < min(n, off + 4096); i += 256) {
-        const float gi = g[i] * p.grad_scale;
+        const float gi = g[i] * gs;
         float wi = w[i];
         wi *= 1.0f - lr * wd;                               // decoupled weight decay (torch.optim.AdamW)
         const float mi = p.beta1 * m[i] + (1.0f - p.beta1) * gi;
@@ -188,7 +199,55 @@ __global__ __launch_bounds__(256) void adamw_kernel(GrlAdamWArgs p) {
         m[i] = mi;
         v[i] = vi;
         const float denom = sqrtf(vi) / bc2s + p.eps;
-        w[i] = wi - (lr / bc1) * (mi / denom);
+        const float wn = wi - (lr / bc1) * (mi / denom);
+        w[i] = wn;
+        if (EMA) {                                          // the average moves towards the weight just written (still in a register)
+            const float ei = e[i];
+            e[i] = fmaf(ema_w, wn - ei, ei);
+        }
+    }
+}
+
+// ---- gradient clipping by global norm (ABI 44) -------------------------------------------------------------------------
+// Sum of 256 doubles, one per thread, in a fixed order: a wave's 64 by a shuffle tree, the four waves' by thread 0 in wave
+// order.  No atomics: the result is bit-reproducible.  (fp64 adds run at a fraction of the fp32 rate; both kernels below are
+// bound by the one read of the gradients / partials, 16 adds per thread do not show.)
+__device__ __forceinline__ double block_sum_256(double x, double* lds4) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) x += __shfl_down(x, d, 64);
+    if ((threadIdx.x & 63) == 0) lds4[threadIdx.x >> 6] = x;
+    __syncthreads();
+    return ((lds4[0] + lds4[1]) + lds4[2]) + lds4[3];
+}
+
+__global__ __launch_bounds__(256) void grad_sqnorm_kernel(GrlGradNormArgs p) {
+    __shared__ double lds4[4];
+    const int ch = blockIdx.x;
+    const int t = p.chunk_tensor[ch];
+    const int64_t off = (int64_t)p.chunk_offset[ch];
+    const int64_t end = min((int64_t)p.numel[t], off + 4096);
+    const float* g = (const float*)p.grads[t];
+    double acc = 0.0;
+#pragma unroll 4
+    for (int64_t i = off + threadIdx.x; i < end; i += 256) {
+        const double gi = (double)g[i];
+        acc += gi * gi;
+    }
+    const double s = block_sum_256(acc, lds4);
+    if (threadIdx.x == 0) p.partials[p.base + ch] = s;
+}
+
+__global__ __launch_bounds__(256) void grad_clip_finish_kernel(GrlGradClipArgs p) {
+    __shared__ double lds4[4];
+    double acc = 0.0;
+    for (int64_t i = threadIdx.x; i < p.n_partials; i += 256) acc += p.partials[i];
+    const double s = block_sum_256(acc, lds4);
+    if (threadIdx.x == 0) {
+        const double norm = sqrt(s) * fabs((double)p.grad_scale);
+        double coef = (double)p.max_norm / (norm + 1e-6);
+        coef = coef > 1.0 ? 1.0 : coef;      // torch.clamp(max=1): NaN stays NaN (fmin would answer 1), an infinite norm gives 0
+        p.out[0] = (float)coef;
+        p.out[1] = (float)norm;
     }
 }
 
@@ -218,7 +277,29 @@ extern "C" int grl_adamw_step(void* stream, const GrlAdamWArgs* args) {
     const GrlAdamWArgs& p = *args;
     if (p.num_chunks <= 0) return 0;
     if (!p.params || !p.grads || !p.exp_avg || !p.exp_avg_sq || !p.numel || !p.chunk_tensor || !p.chunk_offset) return GRL_ERR_BAD_ARG;
-    hipLaunchKernelGGL(adamw_kernel, dim3(p.num_chunks), dim3(256), 0, (hipStream_t)stream, p);
+    const dim3 grid(p.num_chunks), block(256);
+    hipStream_t s = (hipStream_t)stream;
+    if (p.grad_clip_dev != nullptr && p.ema != nullptr) hipLaunchKernelGGL((adamw_kernel<true, true>), grid, block, 0, s, p);
+    else if (p.grad_clip_dev != nullptr) hipLaunchKernelGGL((adamw_kernel<true, false>), grid, block, 0, s, p);
+    else if (p.ema != nullptr) hipLaunchKernelGGL((adamw_kernel<false, true>), grid, block, 0, s, p);
+    else hipLaunchKernelGGL((adamw_kernel<false, false>), grid, block, 0, s, p);
+    GRL_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int grl_grad_sqnorm(void* stream, const GrlGradNormArgs* args) {
+    const GrlGradNormArgs& p = *args;
+    if (p.num_chunks <= 0) return 0;
+    if (!p.grads || !p.numel || !p.chunk_tensor || !p.chunk_offset || !p.partials || p.base < 0) return GRL_ERR_BAD_ARG;
+    hipLaunchKernelGGL(grad_sqnorm_kernel, dim3(p.num_chunks), dim3(256), 0, (hipStream_t)stream, p);
+    GRL_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int grl_grad_clip_finish(void* stream, const GrlGradClipArgs* args) {
+    const GrlGradClipArgs& p = *args;
+    if (!p.partials || !p.out || p.n_partials < 0 || !(p.max_norm > 0.f)) return GRL_ERR_BAD_ARG;
+    hipLaunchKernelGGL(grad_clip_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, p);
     GRL_CHECK_LAUNCH();
     return 0;
 }

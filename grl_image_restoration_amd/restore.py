@@ -78,6 +78,8 @@ def _parser():
                          "the model is built with 6 input and 3 output channels")
     ap.add_argument("--out", required=True, help="folder the restored images are written to (created)")
     ap.add_argument("--ckpt", default=None, help="reference checkpoint (.ckpt / .pth); random init without it")
+    ap.add_argument("--ema", action="store_true",
+                    help="load the averaged weights of --ckpt (state_dict_ema of train --ema-decay, or BasicSR's params_ema)")
     ap.add_argument("--model", default="base", choices=["tiny", "small", "base"])
     ap.add_argument("--geometry", required=True, help="a key of presets.GEOMETRIES")
     ap.add_argument("--scale", type=int, default=1, help="the model's upscaling factor; SR checkpoints need theirs (2, 3, 4)")
@@ -116,8 +118,13 @@ def main(argv: Optional[List[str]] = None):
         over.update(depths=depths, num_heads_window=[heads] * len(depths), num_heads_stripe=[heads] * len(depths))
     channels = dict(in_channels=6, out_channels=3) if a.lq_r is not None else dict(in_channels=a.channels)
     model = GRL(**make_config(a.model, a.geometry, upscale=a.scale, **channels, **over)).eval()
+    if a.ema and not a.ckpt:
+        ap.error("--ema belongs to --ckpt")
     if a.ckpt:
-        load_checkpoint(model, a.ckpt)
+        try:
+            load_checkpoint(model, a.ckpt, ema=a.ema)
+        except KeyError as e:
+            ap.error(f"--ema: {e.args[0]}")
     model = model.to(a.device)
     return restore_folder(model, a.lq, a.out, a.scale, a.tile, a.overlap, a.device, a.channels, a.suffix, a.workers,
                           a.compress_level, verbose=True, lq_r_dir=a.lq_r, self_ensemble=a.self_ensemble)

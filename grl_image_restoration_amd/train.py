@@ -72,11 +72,19 @@ baked in: at a stage change it is finished and dropped, and the next one is buil
 Checkpoints carry the two streams under ``remix_rng``; ``--resume`` derives the stage from the step.  The result gains ``"stages"``.
 Not with ``--gan``.
 
+Stabilisers.  ``--clip-grad-norm X`` clips by the global gradient norm and ``--ema-decay D`` keeps an exponential moving average
+of the generator's weights, both inside the fused optimizer step (``optim.FusedAdamW(max_grad_norm=, ema_decay=)``: no extra pass
+over the gradients or the weights, no host read, so the captured and data-parallel steps keep them).  With ``--gan`` both optimizers
+clip, each over its own parameters; the average is the generator's only.  With ``--ema-decay`` validation scores the averaged
+weights (``ema_applied``) and checkpoints gain ``state_dict_ema`` (``evaluate`` / ``restore --ema``); ``--resume`` restores the
+averages through the optimizer state.  The step line and the result gain ``grad_norm`` / ``"grad_norms"`` under ``--clip-grad-norm``.
+
 Data-parallel.  Under ``torchrun`` (torch.distributed initialised from the environment) the bare module goes to
 ``GraphedTrainStep``, which owns the gradient all-reduce; each rank's sampler is seeded ``seed + rank``; rank 0 validates and
 writes checkpoints.  ``--eager`` is single-process only.
 """
 import argparse
+import contextlib
 import os
 from collections import Counter
 from typing import List, Optional, Sequence
@@ -122,7 +130,9 @@ RECALIBRATE_EVERY = 200        # captured Charbonnier steps: eager re-measuremen
 def save_checkpoint(path: str, model, optimizer, step: int, sampler: D.PatchSampler, args: dict, model_d=None, optimizer_d=None,
                     remix=None):
     """``model_d`` / ``optimizer_d`` (--gan): the reference's GAN-stage layout -- ``model.model_g.<k>`` and ``model.model_d.<k>``, the
-    u / v buffers of the spectral normalisation among them -- and the second optimizer under ``optimizer_d``."""
+    u / v buffers of the spectral normalisation among them -- and the second optimizer under ``optimizer_d``.  An optimizer that
+    keeps a weight average (``FusedAdamW(ema_decay=...)``) adds ``state_dict_ema``: the generator's keys of ``state_dict``, every
+    optimized parameter replaced by its average (BasicSR's ``params_ema``); the averages themselves resume through ``optimizer``."""
     if model_d is None:
         sd = {"model." + k: v.detach().cpu() for k, v in model.state_dict().items()}
     else:
@@ -130,6 +140,9 @@ def save_checkpoint(path: str, model, optimizer, step: int, sampler: D.PatchSamp
         sd.update({"model.model_d." + k: v.detach().cpu() for k, v in model_d.state_dict().items()})
     obj = {"state_dict": sd,
            "step": int(step), "optimizer": optimizer.state_dict(), "sampler_rng": sampler.rng_state(), "args": dict(args)}
+    if any(g.get("ema_decay") is not None for g in optimizer.param_groups):
+        prefix = "model." if model_d is None else "model.model_g."
+        obj["state_dict_ema"] = {prefix + k: v.detach().cpu() for k, v in optimizer.ema_state_dict(model).items()}
     if optimizer_d is not None:
         obj["optimizer_d"] = optimizer_d.state_dict()
     if remix is not None:                               # the streams of remix.BatchRemix; the stage follows from the step
@@ -232,6 +245,12 @@ def _parser():
                          "MixUp_AUG, mixup: True of config/defaults.yaml)")
     ap.add_argument("--mixup-after", type=int, default=0, metavar="STEP",
                     help="--mixup: from this optimizer step on (the reference waits for its sixth epoch)")
+    ap.add_argument("--clip-grad-norm", type=float, default=None, metavar="X",
+                    help="clip the gradients to this global norm inside the fused optimizer step (Restormer's use_grad_clip); with --gan "
+                         "both optimizers clip, each over its own parameters.  The step line gains grad_norm")
+    ap.add_argument("--ema-decay", type=float, default=None, metavar="D",
+                    help="keep an exponential moving average of the generator's weights (0 <= D < 1; BasicSR's ema_decay is 0.999): "
+                         "validation runs on the averaged weights and checkpoints gain state_dict_ema (evaluate / restore --ema)")
     ap.add_argument("--device", default="cuda:0")
     return ap
 
@@ -277,6 +296,10 @@ def _check(ap, a):
         ap.error("--gan runs eagerly: --eager is single-process; the captured step owns the gradient all-reduce")
     if a.gan and (a.patch * a.scale) % 8:
         ap.error("--gan: the discriminator takes GT patches whose side (--patch times --scale) is a multiple of 8")
+    if a.clip_grad_norm is not None and not a.clip_grad_norm > 0:
+        ap.error("--clip-grad-norm must be positive")
+    if a.ema_decay is not None and not 0 <= a.ema_decay < 1:
+        ap.error("--ema-decay must be in [0, 1)")
     if a.patch < 1 or a.batch < 1 or a.steps < 0:
         ap.error("--patch and --batch must be positive")
     if a.save_every and a.out is None:
@@ -414,8 +437,9 @@ def main(argv: Optional[List[str]] = None):
         remix = BatchRemix(a.batch, a.patch, a.scale, *a.stage_lists, mixup=a.mixup, mixup_after=a.mixup_after, seed=a.seed + rank,
                            device=device)
 
-    opt = FusedAdamW(model.parameters(), lr=a.lr, weight_decay=0.0 if a.gan else a.weight_decay)
-    opt_d = FusedAdamW(model_d.parameters(), lr=a.lr, weight_decay=0.0) if a.gan else None
+    opt = FusedAdamW(model.parameters(), lr=a.lr, weight_decay=0.0 if a.gan else a.weight_decay, max_grad_norm=a.clip_grad_norm,
+                     ema_decay=a.ema_decay)
+    opt_d = FusedAdamW(model_d.parameters(), lr=a.lr, weight_decay=0.0, max_grad_norm=a.clip_grad_norm) if a.gan else None
     start = 0
     if resume is not None:
         opt.load_state_dict(resume["optimizer"])
@@ -437,6 +461,8 @@ def main(argv: Optional[List[str]] = None):
 
     lr_at = lambda n: multistep_warmup_lr(n, a.lr, a.milestone_list, a.gamma, a.warmup_iter, a.warmup_init_lr)
     out = {"steps": [], "losses": [], "lrs": [], "work": [], "val": [], "checkpoint": None}
+    if a.clip_grad_norm is not None:
+        out["grad_norms"] = []                          # per step the generator's global gradient norm, before clipping
     step_fn = None
     gan_step = None
     sizes = None                                        # (batch, patch) of the stage the captured step was built for
@@ -494,13 +520,18 @@ def main(argv: Optional[List[str]] = None):
             loss = step_fn(lq, gt)
         loss = float(loss.detach())
         out["steps"].append(n); out["losses"].append(loss); out["lrs"].append(lr); out["work"].append(work)
+        if a.clip_grad_norm is not None:
+            out["grad_norms"].append(opt.last_grad_norm())
         if rank == 0:
             style = f"  loss_g_style {out['gan'][-1]['loss_g_style']:.6f}" if gan_step is not None and "loss_g_style" in out["gan"][-1] else ""
+            if a.clip_grad_norm is not None:
+                style += f"  grad_norm {out['grad_norms'][-1]:.6f}"
             print(f"step {n:8d}  lr {lr:.3e}  loss {loss:.6f}{style}", flush=True)
         done = n + 1
         if a.val_every and done % a.val_every == 0 and rank == 0:
             model.eval()
-            with torch.no_grad():
+            # (--ema-decay: the averaged generator is what gets scored, as BasicSR validates params_ema)
+            with torch.no_grad(), (opt.ema_applied(model) if a.ema_decay is not None else contextlib.nullcontext()):
                 v = evaluate_folder(model, a.val_lq, a.val_gt, a.scale, device=a.device, verbose=False, metric_group=a.metric,
                                     channels=a.channels, task=a.task, sigma=a.sigma, taps=taps, quality=a.quality, usm_gt=a.val_usm,
                                     niqe_params=niqe_params, lpips_model=lpips_model, lq_r_dir=a.val_lq_r)

@@ -27,6 +27,13 @@ What a captured step FREEZES, and what it does not:
   * learning rate and weight decay are NOT frozen: the launch reads them from device memory and ``__call__`` refreshes them from
     ``optimizer.param_groups`` before every replay -- an LR scheduler stepping the optimizer works as in eager mode;
   * betas / eps are held by value: changing them after the capture raises (re-capture);
+  * gradient clipping (``FusedAdamW(max_grad_norm=...)``) is NOT frozen in its effect: the norm and the coefficient are computed
+    on every replay by captured launches (grl_grad_sqnorm, grl_grad_clip_finish) and stay in device memory, which the AdamW launch
+    reads -- no host read.  In the data-parallel form they sit in graph B, after the all-reduce: the norm is that of the averaged
+    gradient (the 1 / world factor goes into the finishing launch), bf16 on the wire included.  ``max_grad_norm`` itself is held by
+    value, like betas / eps: changing it after the capture raises;
+  * the weight average (``FusedAdamW(ema_decay=...)``) is updated by the captured AdamW launch; its buffers keep their addresses
+    (``load_state_dict`` copies into them).  ``ema_decay`` is held by value: changing it after the capture raises;
   * the power-of-two scale that brings the gradients into fp16 range for the backward contractions is frozen at its warm-up value
     (autograd.frozen_grad_scale, 2^10 of headroom).  That is right for losses whose top gradient does not move (L1: |dL/dy| = 1/N,
     what the reference trains GRL with, config/loss/l1.yaml).  For MSE / Charbonnier / perceptual losses the gradients shrink by

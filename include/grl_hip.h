@@ -23,7 +23,7 @@ extern "C" {
 
 #define GRL_ERR_BAD_ARG (-1)
 #define GRL_ERR_UNSUPPORTED (-2)
-#define GRL_ABI_VERSION 43
+#define GRL_ABI_VERSION 44
 
 /* element kinds of activation / weight buffers */
 enum { GRL_DT_F32 = 0, GRL_DT_BF16 = 1, GRL_DT_F16 = 2 };
@@ -525,9 +525,52 @@ typedef struct GrlAdamWArgs {
                                          /* `weight_decay` are then ignored -- an LR scheduler (the reference trains with MultiStepLR / */
                                          /* cosine / warm-up schedules, config/lr_scheduler) keeps working across replays of a captured  */
                                          /* launch: the caller refreshes the two floats before each replay                              */
+    const float* grad_clip_dev;          /* optional (ABI 44): the clip coefficient in DEVICE memory (grl_grad_clip_finish's out[0]).   */
+                                         /* The gradient scale becomes  s = grad_scale * grad_clip_dev[0]  (formed once, in fp32) and     */
+                                         /* every gradient is read as  g[i] * s ; null: s = grad_scale, as before.  A coefficient of      */
+                                         /* exactly 1 gives the weights of a step without clipping, bit for bit                           */
+    void* const* ema;                    /* optional (ABI 44): a pointer table like exp_avg -- per tensor an fp32 average of the weights. */
+                                         /* After the new weight w' is computed and stored:  e[i] = fmaf(1 - ema_decay, w' - e[i], e[i])  */
+                                         /* (1 - ema_decay in fp32); null: no average, and neither the arithmetic nor the memory traffic   */
+                                         /* of the launch differs from ABI 43's                                                            */
+    float ema_decay;
 } GrlAdamWArgs;
 
 int grl_adamw_step(void* stream, const GrlAdamWArgs* args);
+
+/* Gradient clipping by global norm (ABI 44; torch.nn.utils.clip_grad_norm_ with norm_type 2), without a host read and without
+ * rewriting the gradients: the coefficient stays in device memory and grl_adamw_step folds it into its gradient scale.
+ *
+ * grl_grad_sqnorm: over the work list grl_adamw_step takes (fp32 gradients; chunk c covers [chunk_offset[c], +4096) of tensor
+ *   chunk_tensor[c]), one workgroup per chunk:  partials[base + c] = sum_i (double)g[i]^2 , every element converted to double
+ *   and accumulated in double, reduced in a fixed order.  No atomics: the same gradients give the same bits.  Several launches
+ *   (one per parameter group) fill one buffer at their own `base`. */
+typedef struct GrlGradNormArgs {
+    const void* const* grads;
+    const int64_t* numel;
+    const int32_t* chunk_tensor;
+    const int64_t* chunk_offset;
+    int32_t num_chunks;
+    double* partials;
+    int64_t base;
+} GrlGradNormArgs;
+
+int grl_grad_sqnorm(void* stream, const GrlGradNormArgs* args);
+
+/* grl_grad_clip_finish: one workgroup sums partials[0 .. n_partials) in a fixed order, then, in double,
+ *   norm = sqrt(sum) * |grad_scale| ;  coef = max_norm / (norm + 1e-6), capped at 1 as torch.clamp(max=1) caps it
+ *   (an infinite norm gives 0, a NaN norm gives NaN) ;  out[0] = (float)coef, out[1] = (float)norm  -- one rounding each.
+ * `grad_scale` is the one the AdamW launch will apply (1 / world for summed data-parallel gradients): the norm is that of the
+ * scaled gradient.  max_norm <= 0 or a null pointer: GRL_ERR_BAD_ARG. */
+typedef struct GrlGradClipArgs {
+    const double* partials;
+    int64_t n_partials;
+    float grad_scale;
+    float max_norm;
+    float* out;
+} GrlGradClipArgs;
+
+int grl_grad_clip_finish(void* stream, const GrlGradClipArgs* args);
 
 /* Row LayerNorm of the training path (ABI 21): forward with the row statistics kept, and backward.
  *   replaces nn.LayerNorm on token matrices and autograd through it: norm1 / norm2  models/common/mixed_attn_block_efficient.py:543-556,

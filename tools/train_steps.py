@@ -15,11 +15,13 @@ ap.add_argument("--steps", type=int, default=3)
 ap.add_argument("--batch", type=int, default=8)
 ap.add_argument("--patch", type=int, default=64, help="LQ patch side (a stage of a progressive run: train --patch-sizes)")
 ap.add_argument("--graph", action="store_true", help="replay the captured step instead of eager steps (and print its time)")
+ap.add_argument("--clip-grad-norm", type=float, default=None, help="FusedAdamW(max_grad_norm=...): clipping inside the optimizer step")
+ap.add_argument("--ema-decay", type=float, default=None, help="FusedAdamW(ema_decay=...): the weight average inside the optimizer step")
 a = ap.parse_args()
 torch.manual_seed(0)
 cfg = baseline_config(5)
 m = GRL(**cfg).cuda().train()
-opt = FusedAdamW(m.parameters(), lr=2e-4, weight_decay=1e-4)
+opt = FusedAdamW(m.parameters(), lr=2e-4, weight_decay=1e-4, max_grad_norm=a.clip_grad_norm, ema_decay=a.ema_decay)
 g = torch.Generator().manual_seed(100)
 lq = torch.rand(a.batch, 3, a.patch, a.patch, generator=g).cuda()
 gt = torch.rand(a.batch, 3, a.patch * cfg["upscale"], a.patch * cfg["upscale"], generator=g).cuda()
