@@ -430,6 +430,12 @@ __global__ __launch_bounds__(256) void attn_dq_kernel(GrlAttnBwdLaunch a, int sp
     }
 
     const float inv = 1.0f / a.g_scale;
+    // slot 31 of k holds 1.0 for the forward kernel's offset (see attn_dkv_kernel): against it dQ's column 31 collects sum_j dS_ij,
+    // zero only up to the fp16 rounding of dS.  It is a pad column: it carries no gradient (register 15 of the upper half-wave)
+    if (half && p.head_dim <= 30) {
+#pragma unroll
+        for (int t = 0; t < QT; ++t) dQ[t][15] = 0.f;
+    }
 #pragma unroll
     for (int t = 0; t < QT; ++t)
         if (splits == 1 && qvalid[t]) store_cols(a.d_q, p.q, qrow[t], head, half, dQ[t], inv);

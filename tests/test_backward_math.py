@@ -65,3 +65,34 @@ def test_normalize_backward_matches_autograd():
     d = torch.randn(5, 7, 12, dtype=torch.float64)
     torch.nn.functional.normalize(x, dim=-1).backward(d)
     assert torch.allclose(BM.normalize_backward(x.detach(), d), x.grad, atol=1e-12)
+
+
+@pytest.mark.parametrize("win,anchor_df,shift,w2a", [((8, 8), 1, 4, True), ((8, 16), 2, 0, False), ((6, 10), 1, 0, True)],
+                         ids=["masked", "anchored_df2", "ragged"])
+def test_attention_backward_operands_matches_autograd(win, anchor_df, shift, w2a):
+    """The closed form in the kernel's operands (log2-domain logits, dS = ln2 P (dP - D)) against float64 autograd of
+    softmax(S ln2) @ v -- with a shift mask, with /2 anchors as the queries, and on a window that is no multiple of anything."""
+    torch.manual_seed(2)
+    nh, d = 2, 10
+    H, W = 2 * win[0], 2 * win[1]
+    index = O.rel_index(win, anchor_df, w2a)
+    Nq, Nk = index.shape
+    nW = (H // win[0]) * (W // win[1])
+    B_ = 2 * nW
+    mask = O.shift_mask((H, W), win, [shift, shift], df=anchor_df, mode="w" if anchor_df == 1 else "a2w").double() if shift else None
+    scale = torch.tensor([100.0, 7.0], dtype=torch.float64).view(1, nh, 1, 1)
+    qt = (torch.nn.functional.normalize(torch.randn(B_, nh, Nq, d, dtype=torch.float64), dim=-1) * scale * BM.LOG2E).requires_grad_(True)
+    kh = torch.nn.functional.normalize(torch.randn(B_, nh, Nk, d, dtype=torch.float64), dim=-1).requires_grad_(True)
+    v = torch.randn(B_, nh, Nk, d, dtype=torch.float64, requires_grad=True)
+    bias = (torch.rand(int(index.max()) + 1, nh, dtype=torch.float64) * 16).requires_grad_(True)
+    dO = torch.randn(B_, nh, Nq, d, dtype=torch.float64)
+    S = qt @ kh.transpose(-1, -2) + BM.LOG2E * bias[index.reshape(-1)].view(Nq, Nk, nh).permute(2, 0, 1).unsqueeze(0)
+    if mask is not None:
+        S = (S.view(2, nW, nh, Nq, Nk) + BM.LOG2E * mask.unsqueeze(1).unsqueeze(0)).view(B_, nh, Nq, Nk)
+    out = torch.softmax(S * math.log(2.0), dim=-1) @ v
+    out.backward(dO)
+    dqt, dkh, dv, dbias, o, lse = BM.attention_backward_operands(qt.detach(), kh.detach(), v.detach(), dO, bias.detach(), index, mask)
+    rel = lambda a, b: ((a - b).norm() / b.norm().clamp_min(1e-30)).item()
+    errs = dict(dqt=rel(dqt, qt.grad), dkh=rel(dkh, kh.grad), dv=rel(dv, v.grad), dbias=rel(dbias, bias.grad), o=rel(o, out.detach()),
+                lse=rel(lse, torch.logsumexp(S.detach() * math.log(2.0), dim=-1) / math.log(2.0)))
+    assert max(errs.values()) < 1e-10, errs

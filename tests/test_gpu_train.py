@@ -70,6 +70,8 @@ ATT_CASES = [
     # name, mode, (H, W), window/stripe, shift, df, nh, d
     ("win8_shift", "w", (16, 16), (8, 8), (4, 4), 1, 3, 30),
     ("win32_shift", "w", (64, 64), (32, 32), (16, 16), 1, 3, 30),
+    # 32-aligned windows whose column shift is no multiple of 16: the border windows take tile<0> WITH the diagonal-ring histogram
+    ("win32_shift8", "w", (64, 64), (32, 32), (8, 8), 1, 1, 30, 1),
     ("win12_ragged", "w", (24, 36), (12, 12), (6, 6), 1, 3, 30),
     ("win16_d32", "w", (32, 32), (16, 16), (0, 0), 1, 2, 32),
     ("a2w_64_df2", "a2w", (64, 64), (64, 64), (32, 32), 2, 3, 30),
