@@ -950,6 +950,13 @@ def check(code: int, what: str):
 _DIRTY_LDS = SW.on("GRL_DIRTY_LDS")
 
 
+def set_dirty_lds(flag: bool) -> bool:
+    """Switch the dirty-LDS mode at run time (tests); returns the previous setting.  Read per call in stream_ptr()."""
+    global _DIRTY_LDS
+    prev, _DIRTY_LDS = _DIRTY_LDS, bool(flag)
+    return prev
+
+
 def stream_ptr():
     """The current torch HIP stream as the `stream` argument of a C-ABI launch (every wrapper evaluates this right before its
     call).  GRL_DIRTY_LDS=1 (debug): first fills the LDS of every CU with NaN bytes on that stream, so that the kernel about to be

@@ -41,7 +41,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from . import item_lists
+from . import item_lists, ops
 
 INTER_LINEAR, INTER_CUBIC, INTER_AREA = 1, 2, 3
 STAGES = tuple(range(9))
@@ -441,7 +441,7 @@ class _Arenas:
     def __init__(self, x: torch.Tensor):
         self.N, self.C, self.S = x.shape[0], x.shape[1], x.shape[2]
         self.slot = self.C * self.S * self.S
-        self.buf = torch.empty(2, self.N, self.slot, dtype=torch.float32, device=x.device)
+        self.buf = ops.empty(2, self.N, self.slot, dtype=torch.float32, device=x.device)
         self.buf[0].copy_(x.reshape(self.N, -1))
         self.flat = self.buf.view(-1)
         self.side = [0] * self.N

@@ -29,6 +29,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 import torch
 
+from . import ops
 from .task_rules import TRAIN_TASKS as TASKS, resolve
 
 FLIP_ROWS, FLIP_COLS, SWAP_AXES = 1, 2, 4
@@ -101,7 +102,7 @@ class PatchStore:
             raise ValueError(f"patch and scale must be positive, got {patch}, {scale}")
         B, S = work.shape[0], patch * scale
         if out is None:
-            out = torch.empty(B, self.channels, S, S, dtype=torch.float32, device=self.data.device)
+            out = ops.empty(B, self.channels, S, S, dtype=torch.float32, device=self.data.device)
         elif out.shape != (B, self.channels, S, S) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != work.device:
             raise ValueError("out: a contiguous fp32 (B, C, patch * scale, patch * scale) tensor on the store's device")
         if self.data.is_cuda:
@@ -369,8 +370,8 @@ class PatchSampler:
             if not wt.is_cuda:
                 lq = torch.cat([self.lq_store.sample(wt, P, 1), self.lq_r_store.sample(wt, P, 1)], dim=1)
                 return lq, self.gt_store.sample(wt, P, 1)
-            lq = torch.empty(B, 6, P, P, dtype=torch.float32, device=self.device)
-            gt = torch.empty(B, 3, P, P, dtype=torch.float32, device=self.device)
+            lq = ops.empty(B, 6, P, P, dtype=torch.float32, device=self.device)
+            gt = ops.empty(B, 3, P, P, dtype=torch.float32, device=self.device)
             sample_views([(self.lq_store, 1, lq, 0), (self.lq_r_store, 1, lq, 3), (self.gt_store, 1, gt, 0)], wt, P)
             return lq, gt
         if self.lq_store is not None:                # paired stores, given or made at construction

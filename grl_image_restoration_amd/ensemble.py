@@ -34,6 +34,8 @@ from typing import Callable, List, Optional, Sequence, Tuple
 
 import torch
 
+from . import ops
+
 GROUP_A: Tuple[int, ...] = (0, 2, 4, 6)
 GROUP_B: Tuple[int, ...] = (1, 3, 5, 7)
 INVERSE: Tuple[int, ...] = (0, 3, 2, 1, 4, 5, 6, 7)
@@ -73,14 +75,12 @@ def _pack(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.T
         raise TypeError(f"dihedral_pack takes fp32 tensors on the GPU, got {x.dtype}")
     whole = None
     if H == W:
-        whole = torch.empty((8 * B, C, H, W), dtype=x.dtype, device=x.device)
+        whole = ops.empty((8 * B, C, H, W), dtype=x.dtype, device=x.device)
         a, b = whole[: 4 * B], whole[4 * B:]
     else:
-        a = torch.empty((4 * B, C, H, W), dtype=x.dtype, device=x.device)
-        b = torch.empty((4 * B, C, W, H), dtype=x.dtype, device=x.device)
+        a = ops.empty((4 * B, C, H, W), dtype=x.dtype, device=x.device)
+        b = ops.empty((4 * B, C, W, H), dtype=x.dtype, device=x.device)
     if x.is_cuda:
-        from . import ops
-
         ops.dihedral_pack(x, a, b)
     else:
         for group, dst in ((GROUP_A, a), (GROUP_B, b)):
@@ -119,9 +119,7 @@ def dihedral_merge(members: Sequence[torch.Tensor]) -> torch.Tensor:
     if members[0].is_cuda:
         if dt not in (torch.float32, torch.float16):
             raise TypeError(f"dihedral_merge takes fp32 or fp16 members on the GPU, got {dt}")
-        from . import ops
-
-        out = torch.empty((B, C, Ho, Wo), dtype=torch.float32, device=dev)
+        out = ops.empty((B, C, Ho, Wo), dtype=torch.float32, device=dev)
         ops.dihedral_merge(members, out)
         return out
     acc = torch.float32 if dt in (torch.float16, torch.bfloat16) else dt

@@ -47,9 +47,9 @@ def pack8(x: torch.Tensor, rep: int = 1) -> torch.Tensor:
         raise ValueError(f"pack8: {tuple(x.shape)} at rep {rep} is 2^31 bytes or more")
     if not x.is_cuda:
         return _torch_pack8(x, rep)
-    from . import _lib
+    from . import _lib, ops
 
-    out = torch.empty((N, H * rep, W * rep, Cn), dtype=torch.uint8, device=x.device)
+    out = ops.empty((N, H * rep, W * rep, Cn), dtype=torch.uint8, device=x.device)
     args = _lib.GrlPack8Args(x=x.data_ptr(), stride=(C.c_int64 * 4)(*x.stride()), N=N, C=Cn, H=H, W=W, rep=rep, out=out.data_ptr())
     _lib.launch("grl_image_pack8", args)
     return out

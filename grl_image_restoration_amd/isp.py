@@ -19,7 +19,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from . import item_lists
+from . import item_lists, ops
 
 CAMERAS = ("canon_eos_1d_mark_ii", "canon_eos_5d_mark_iii", "canon", "canon_eos_6d_v1", "huawei_p20", "huawei_p30", "huawei_v8",
            "nikon_d500", "nikon_d810", "nikon_d5600", "olympus_em1")                      # ISPModel.CameraType, utils_isp.py:465-477
@@ -170,7 +170,7 @@ def process(x: torch.Tensor, p: CameraParams) -> torch.Tensor:
 
 def mosaic(x: torch.Tensor) -> torch.Tensor:
     """(3, h, w) -> the RGGB plane (h, w) (``Demosaic.reverse``)."""
-    raw = torch.empty_like(x[0])
+    raw = ops.empty_like(x[0])
     raw[0::2, 0::2], raw[0::2, 1::2], raw[1::2, 0::2], raw[1::2, 1::2] = x[0, 0::2, 0::2], x[1, 0::2, 1::2], x[1, 1::2, 0::2], x[2, 1::2, 1::2]
     return raw.clamp(0, 1)
 

@@ -14,7 +14,7 @@ from typing import List, Sequence, Tuple
 
 import torch
 
-from . import _lib
+from . import _lib, ops
 
 ROW = 8
 
@@ -60,7 +60,7 @@ def pack(tensors: Sequence[torch.Tensor], align: int = 1) -> Tuple[torch.Tensor,
 def empty(shapes: Sequence[Sequence[int]], device, align: int = 1) -> Tuple[torch.Tensor, List[int]]:
     """An uninitialised fp32 arena for tensors of ``shapes``, laid out as ``pack`` would: ``(arena, offsets)``."""
     offs, total = _layout([math.prod(s) for s in shapes], align)
-    return torch.empty(total, dtype=torch.float32, device=device), offs
+    return ops.empty(total, dtype=torch.float32, device=device), offs
 
 
 def views(arena: torch.Tensor, offsets: Sequence[int], shapes: Sequence[Sequence[int]]) -> List[torch.Tensor]:

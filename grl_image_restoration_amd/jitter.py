@@ -19,7 +19,7 @@ from typing import List, Sequence, Tuple
 
 import torch
 
-from . import item_lists
+from . import item_lists, ops
 
 BRIGHTNESS, CONTRAST, SATURATION, HUE = 0, 1, 2, 3
 RANGES = ((0.8, 1.2), (0.8, 1.2), (0.8, 1.2), (-0.05, 0.05))          # b, c, s, h of the reference's ColorJitter
@@ -151,11 +151,11 @@ def color_jitter(imgs: Sequence[torch.Tensor], params: Sequence[JitterParams], w
         return (out, torch.stack([r[1].double() for r in res])) if with_means else out
     dev = imgs[0].device
     src, offs = item_lists.pack(imgs, align=4)                           # every image starts on 16 bytes: the float4 path
-    dst = torch.empty_like(src)
+    dst = ops.empty_like(src)
     rows, factors = item_rows([(o, o, im.shape[1], im.shape[2]) for o, im in zip(offs, imgs)], params)
     max_h, max_w = max(im.shape[1] for im in imgs), max(im.shape[2] for im in imgs)
-    partial = torch.empty(len(imgs) * num_workgroups(max_h, max_w), dtype=torch.float64, device=dev)
-    means = torch.empty(len(imgs), dtype=torch.float64, device=dev)
+    partial = ops.empty(len(imgs) * num_workgroups(max_h, max_w), dtype=torch.float64, device=dev)
+    means = ops.empty(len(imgs), dtype=torch.float64, device=dev)
     hip_color_jitter(src, dst, rows.to(dev), factors.to(dev), partial, means, max_h, max_w)
     out = item_lists.views(dst, offs, [im.shape for im in imgs])
     return (out, means) if with_means else out

@@ -31,6 +31,7 @@ from typing import Dict, Optional, Tuple
 import torch
 import torch.nn.functional as F
 
+from . import ops
 from . import switches as SW
 from .evaluate import rgb_to_y, shave, tensor_round
 
@@ -127,8 +128,8 @@ def hip_image_metrics(restored: torch.Tensor, target: torch.Tensor, border: int,
     t = target if target.dtype == torch.float32 else target.float()
     B, _, H, W = r.shape
     ws_bytes = int(L.grl_image_metrics_workspace_bytes(B, H, W, border))
-    ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=r.device)
-    out = torch.empty(B, _lib.METRIC_COUNT, dtype=torch.float64, device=r.device)
+    ws = ops.empty(max(ws_bytes, 8), dtype=torch.uint8, device=r.device)
+    out = ops.empty(B, _lib.METRIC_COUNT, dtype=torch.float64, device=r.device)
     taps = ssim_window()[1]
     ycoef = torch.tensor(Y_COEF, dtype=torch.float32) / 255.0     # evaluate.rgb_to_y's fp32 coefficients
     args = _lib.GrlMetricArgs(
@@ -342,8 +343,8 @@ def hip_niqe_features(restored: torch.Tensor) -> torch.Tensor:
     nbh, nbw = H // NIQE_BLOCK, W // NIQE_BLOCK
     grid, (wh, ih), (ww, iw) = _niqe_tables(nbh * NIQE_BLOCK, nbw * NIQE_BLOCK, r.device)
     ws_bytes = int(L.grl_image_niqe_workspace_bytes(B, H, W))
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=r.device)
-    out = torch.empty(B, nbh * nbw, NIQE_FEATURES, dtype=torch.float64, device=r.device)
+    ws = ops.empty(max(ws_bytes, 16), dtype=torch.uint8, device=r.device)
+    out = ops.empty(B, nbh * nbw, NIQE_FEATURES, dtype=torch.float64, device=r.device)
     args = _lib.GrlNiqeArgs(
         img=r.data_ptr(), stride=(C.c_int64 * 4)(*r.stride()), shape=(C.c_int32 * 4)(*r.shape),
         window=(C.c_double * 49)(*niqe_window().flatten().tolist()), grid=grid.data_ptr(), ngrid=grid.shape[1],

@@ -20,7 +20,8 @@ _KIND = {torch.float32: L.DT_F32, torch.float16: L.DT_F16}
 
 
 # ---- uninitialised workspace ------------------------------------------------------------------------------------------
-# Every output / workspace tensor of the C-ABI wrappers (and of autograd.py / forward_infer.py) comes from here.  GRL_POISON=1 fills it with
+# Every output / workspace tensor of the C-ABI wrappers (here, in autograd.py / forward_infer.py and in the task, data, metric and loss
+# modules) comes from here; integer tables a kernel indexes with do not (a poisoned index is a wild address).  GRL_POISON=1 fills it with
 # NaN (floating types) or 0x7f bytes first: a kernel that reads an element neither it nor a predecessor wrote turns up as a NaN
 # in the parity tests instead of depending on what the allocator handed out (zeros in a fresh process, another process's leftovers
 # in memory the driver recycled -- round 5's order-dependent failure of the captured training step).  The fill is an ordinary
@@ -28,11 +29,61 @@ _KIND = {torch.float32: L.DT_F32, torch.float16: L.DT_F16}
 _POISON = SW.on("GRL_POISON")
 
 
-def set_poison(flag: bool) -> bool:
-    """Switch the poison mode at run time (tests); returns the previous setting."""
-    global _POISON
+#
+# Guard bands (set_poison(True, guards=True), tests only): the other half -- a kernel that WRITES past either end of a tensor lands
+# in the allocator's rounding slack and nobody notices.  With guards on, empty() allocates GUARD_BYTES more on each side (the red-zone
+# size of tools/poison_alloc; a multiple of every alignment the kernels ask for, so the view keeps the alignment of a plain
+# allocation), fills both bands with GUARD_BYTE and returns the contiguous middle view; the base tensor stays alive in a registry
+# until check_guards() has compared every band bytewise with the pattern.  GRL_POISON=1 by environment never turns guards on: nobody
+# would call check_guards, and the registry would keep every tensor alive.
+GUARD_BYTES = 4096
+GUARD_BYTE = 0xA5
+_GUARDS = False
+_GUARDED: list = []          # (base uint8 tensor [G + nbytes + pad + G], payload bytes, shape, dtype)
+
+
+def set_poison(flag: bool, guards: bool = False) -> bool:
+    """Switch the poison mode at run time (tests); returns the previous setting.  ``guards=True`` also surrounds every tensor of
+    empty() / empty_like() with guard bands that check_guards() verifies."""
+    global _POISON, _GUARDS
     prev, _POISON = _POISON, bool(flag)
+    _GUARDS = bool(flag) and bool(guards)
     return prev
+
+
+def _guarded(shape, dtype, device) -> torch.Tensor:
+    shape = tuple(torch.Size(shape))
+    item = torch.empty((), dtype=dtype).element_size()
+    n = 1
+    for s in shape:
+        n *= s
+    nbytes = n * item
+    hi0 = GUARD_BYTES + (nbytes + 15) // 16 * 16          # the upper band starts at the next 16-byte boundary past the payload
+    base = torch.empty(hi0 + GUARD_BYTES, dtype=torch.uint8, device=device)
+    base[:GUARD_BYTES].fill_(GUARD_BYTE)
+    base[GUARD_BYTES + nbytes :].fill_(GUARD_BYTE)
+    _GUARDED.append((base, nbytes, shape, dtype))
+    return base[GUARD_BYTES : GUARD_BYTES + nbytes].view(dtype).view(shape)
+
+
+def check_guards() -> None:
+    """Synchronises, compares every guard band of the tensors handed out since the last call with its pattern and clears the
+    registry; raises naming shape, dtype and side of every tensor a kernel wrote outside of."""
+    global _GUARDED
+    held, _GUARDED = _GUARDED, []
+    if any(b.is_cuda for b, *_ in held):
+        torch.cuda.synchronize()
+    bad = []
+    for base, nbytes, shape, dtype in held:
+        for side, band in (("below", base[:GUARD_BYTES]), ("above", base[GUARD_BYTES + nbytes :])):
+            hit = (band != GUARD_BYTE).nonzero()
+            if hit.numel():
+                first, last = int(hit[0]), int(hit[-1])
+                where = (first - GUARD_BYTES, last - GUARD_BYTES) if side == "below" else (first, last)
+                bad.append(f"{tuple(shape)} {dtype}: {hit.numel()} guard bytes changed {side} the tensor "
+                           f"(byte offsets {where[0]}..{where[1]} from its {'start' if side == 'below' else 'end'})")
+    if bad:
+        raise AssertionError("writes outside of ops.empty tensors:\n  " + "\n  ".join(bad))
 
 
 def _poison(t: torch.Tensor) -> torch.Tensor:
@@ -101,10 +152,16 @@ def zeros_f32(n: int, device) -> torch.Tensor:
 
 
 def empty(*shape, dtype, device) -> torch.Tensor:
+    if _GUARDS:
+        if len(shape) == 1 and isinstance(shape[0], (tuple, list)):       # (torch.Size is a tuple)
+            shape = tuple(shape[0])
+        return _poison(_guarded(shape, dtype, device))
     return _poison(torch.empty(*shape, dtype=dtype, device=device))
 
 
 def empty_like(t: torch.Tensor) -> torch.Tensor:
+    if _GUARDS and t.is_contiguous():
+        return _poison(_guarded(t.shape, t.dtype, t.device))
     return _poison(torch.empty_like(t))
 
 

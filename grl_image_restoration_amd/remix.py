@@ -31,6 +31,8 @@ from typing import NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
+from . import ops
+
 
 class RemixPlan(NamedTuple):
     """The draws of one step.  ``idx``: the input samples of the output batch, in order, or None (all of them); ``x0`` / ``y0``:
@@ -128,14 +130,12 @@ def batch_remix(lq: torch.Tensor, gt: torch.Tensor, plan, scale: int, out=None, 
     b, mix = table.shape[0], plan[3] is not None
     shapes = ((b, Cl, p, p), (b, Cg, scale * p, scale * p))
     if out is None:
-        out = tuple(torch.empty(s, dtype=torch.float32, device=lq.device) for s in shapes)
+        out = tuple(ops.empty(s, dtype=torch.float32, device=lq.device) for s in shapes)
     for o, s in zip(out, shapes):
         if tuple(o.shape) != s or o.dtype != torch.float32 or o.device != lq.device or not o.is_contiguous():
             raise ValueError(f"batch_remix: out must be contiguous fp32 {s} on {lq.device}, got {tuple(o.shape)} {o.dtype} on {o.device}")
     if lq.is_cuda:
-        from . import ops
-
-        if _table is None:
+        if _table is None:                                     # an index table: never poisoned (ops.empty), every row is copied below
             _table = torch.empty((b, 5), dtype=torch.int32, device=lq.device)
         _table[:b].copy_(table)
         ops.batch_remix(lq, gt, _table, b, p, scale, mix, out[0], out[1])

@@ -60,6 +60,13 @@ import torch
 import torch.nn.functional as F
 
 
+def _ops():
+    """ops.empty / ops.empty_like: every output and workspace of a launch is poisonable (GRL_POISON); imported late, as _lib is."""
+    from . import ops
+
+    return ops
+
+
 # ---- demosaicking --------------------------------------------------------------------------------------------------------------
 def mosaic_bayer(rgb: torch.Tensor) -> torch.Tensor:
     """(N, 3, H, W) RGB -> (N, 4, H/2, W/2) packed RGGB mosaic: R at (even, even), G at (even, odd), G at (odd, even), B at
@@ -121,7 +128,7 @@ def hip_demosaic(planes) -> torch.Tensor:
     if any(p.shape != p0.shape or p.stride() != p0.stride() or p.device != p0.device for p in planes):
         raise ValueError("the four mosaic planes need one shape, one stride triple and one device")
     N, h, w = p0.shape
-    out = torch.empty(N, 3, 2 * h, 2 * w, dtype=torch.float32, device=p0.device)
+    out = _ops().empty(N, 3, 2 * h, 2 * w, dtype=torch.float32, device=p0.device)
     args = _lib.GrlDemosaicArgs(plane=(C.c_void_p * 4)(*[p.data_ptr() for p in planes]), stride=(C.c_int64 * 3)(*p0.stride()),
                                 N=N, h=h, w=w, out=out.data_ptr())
     _lib.launch("grl_demosaic_matlab", args)
@@ -325,7 +332,7 @@ def hip_resize(img: torch.Tensor, rows, cols, quantize: bool = False) -> torch.T
             raise ValueError("resize tables: float64 weights and int32 indices of one (out_len, taps) shape on the image's device")
     wh, ih, ww, iw = wh.contiguous(), ih.contiguous(), ww.contiguous(), iw.contiguous()
     N, Cn, H, W = img.shape
-    out = torch.empty(N, Cn, wh.shape[0], ww.shape[0], dtype=torch.float32, device=img.device)
+    out = _ops().empty(N, Cn, wh.shape[0], ww.shape[0], dtype=torch.float32, device=img.device)
     args = _lib.GrlResizeArgs(src=img.data_ptr(), stride=(C.c_int64 * 4)(*img.stride()), N=N, C=Cn, H=H, W=W,
                               out_h=wh.shape[0], out_w=ww.shape[0], taps_h=wh.shape[1], taps_w=ww.shape[1],
                               wh=wh.data_ptr(), ih=ih.data_ptr(), ww=ww.data_ptr(), iw=iw.data_ptr(), out=out.data_ptr(),
@@ -450,8 +457,8 @@ def hip_blur(x: torch.Tensor, taps: torch.Tensor, pad: int, add: Optional[torch.
     N, Cn, H, W = x.shape
     Ho, Wo = H + 2 * pad - K + 1, W + 2 * pad - K + 1
     shape = (N, Cn, max(Ho, 0), max(Wo, 0))
-    out = torch.empty(shape, dtype=torch.float32, device=x.device)
-    center = torch.empty(shape, dtype=torch.float32, device=x.device) if want_center else None
+    out = _ops().empty(shape, dtype=torch.float32, device=x.device)
+    center = _ops().empty(shape, dtype=torch.float32, device=x.device) if want_center else None
     add_ptr, add_stride = None, (0, 0, 0)
     if add is not None:
         if tuple(add.shape) != shape or add.device != x.device:
@@ -543,10 +550,10 @@ def hip_jpeg(x: torch.Tensor, quality: torch.Tensor, out: Optional[torch.Tensor]
     x, quality = x.contiguous(), quality.contiguous()
     N, Cn, H, W = x.shape
     if out is None:
-        out = torch.empty_like(x)
+        out = _ops().empty_like(x)
     elif out.shape != x.shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != x.device:
         raise ValueError("out: a contiguous fp32 tensor of the input's shape on its device")
-    ws = torch.empty(max(int(L.grl_jpeg_workspace_bytes(N, Cn, H, W)), 1), dtype=torch.uint8, device=x.device)
+    ws = _ops().empty(max(int(L.grl_jpeg_workspace_bytes(N, Cn, H, W)), 1), dtype=torch.uint8, device=x.device)
     args = _lib.GrlJpegArgs(x=x.data_ptr(), quality=quality.data_ptr(), N=N, C=Cn, H=H, W=W, workspace=ws.data_ptr(),
                             out=out.data_ptr())
     _lib.launch("grl_jpeg_roundtrip", args)
@@ -734,10 +741,10 @@ def hip_usm(x: torch.Tensor, taps: torch.Tensor, weight: float = 0.5, threshold:
     x, taps = x.contiguous(), taps.contiguous()
     N, Cn, H, W = x.shape
     if out is None:
-        out = torch.empty_like(x)
+        out = _ops().empty_like(x)
     elif out.shape != x.shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != x.device:
         raise ValueError("out: a contiguous fp32 tensor of the input's shape on its device")
-    ws = torch.empty((2,) + tuple(x.shape), dtype=torch.float32, device=x.device)
+    ws = _ops().empty((2,) + tuple(x.shape), dtype=torch.float32, device=x.device)
     if int(L.grl_usm_workspace_bytes(N, Cn, H, W)) != ws.numel() * 4:
         raise ValueError(f"grl_usm_sharp does not take a batch of shape {tuple(x.shape)}")
     args = _lib.GrlUsmArgs(x=x.data_ptr(), taps=taps.data_ptr(), N=N, C=Cn, H=H, W=W, K=taps.shape[0], quantise=int(bool(quantise)),

@@ -256,6 +256,10 @@ def _fixture_state():
 
 @pytest.fixture(scope="module")
 def nets():
+    return build_nets()
+
+
+def build_nets():
     """num_feat -> float64 state dict (64: seeded init with warmed u / v; 8: the reference fixture's)."""
     from grl_image_restoration_amd.discriminator import UNetDiscriminatorSN
 

@@ -28,6 +28,10 @@ SIZES = [(3, 3), (7, 9), (16, 16), (33, 20), (65, 35), (64, 64)]
 
 @pytest.fixture(scope="module")
 def banks():
+    return build_banks()
+
+
+def build_banks():
     return {"smooth": analytic_bank(), "jump": analytic_bank(jump_curve=4)}
 
 
@@ -47,6 +51,10 @@ def _cases(bank, kind):
 
 @pytest.fixture(scope="module")
 def cases(banks):
+    return build_cases(banks)
+
+
+def build_cases(banks):
     return {kind: _cases(bank, kind) for kind, bank in banks.items()}
 
 

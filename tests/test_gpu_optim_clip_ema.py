@@ -24,6 +24,10 @@ def _ulp32(x):
 
 @pytest.fixture(scope="module")
 def data():
+    return build_data()
+
+
+def build_data():
     """Start weights and four steps' gradients (shrinking by 10 ** -step, as tests/test_gpu_train.py's AdamW test does), on the host;
     the float64 norm of the first step's gradients.  Computed once, never modified."""
     g = torch.Generator().manual_seed(47)
