@@ -11,7 +11,7 @@ from . import switches as SW
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgrl_hip.so")
-ABI_VERSION = 44
+ABI_VERSION = 45
 DT_F32, DT_BF16, DT_F16 = 0, 1, 2
 
 EPI_PLAIN, EPI_GELU, EPI_GROUPNORM, EPI_LN_RES, EPI_GELU_GRAD = 0, 1, 2, 3, 4
@@ -817,6 +817,27 @@ class GrlBatchRemixArgs(_Strict):
     ]
 
 
+class GrlSpectralNormArgs(_Strict):
+    _fields_ = [
+        ("w", C.c_void_p * 16),
+        ("u", C.c_void_p * 16),
+        ("v", C.c_void_p * 16),
+        ("out", C.c_void_p * 16),
+        ("u_keep", C.c_void_p * 16),
+        ("v_keep", C.c_void_p * 16),
+        ("sigma", C.c_void_p * 16),
+        ("g", C.c_void_p * 16),
+        ("cout", C.c_int32 * 16),
+        ("k", C.c_int32 * 16),
+        ("n_layers", C.c_int32), ("advance", C.c_int32),
+        ("ws", C.c_void_p),
+        ("ws_bytes", C.c_int64),
+    ]
+
+
+SN_MAX_LAYERS = 16
+
+
 _I32, _I64, _PTR = C.c_int32, C.c_int64, C.c_void_p
 
 
@@ -911,6 +932,8 @@ SIGNATURES = {
     "grl_dihedral_pack": _launch(GrlDihedralPackArgs),
     "grl_dihedral_merge": _launch(GrlDihedralMergeArgs),
     "grl_batch_remix": _launch(GrlBatchRemixArgs),
+    "grl_spectral_norm_fwd": _launch(GrlSpectralNormArgs),
+    "grl_spectral_norm_bwd": _launch(GrlSpectralNormArgs),
     "grl_debug_dirty_lds": (C.c_int, [_PTR]),
     "grl_abi_version": (C.c_int, []),
     "grl_build_info": (C.c_char_p, []),

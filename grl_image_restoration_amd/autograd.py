@@ -9,6 +9,7 @@ the forward AND the backward pass runs in libgrl_hip.so:
   torch.ops.grl.conv3x3_lrelu   conv3x3 + LeakyReLU in the epilogue (the U-Net discriminator, discriminator.py) | as conv3x3 on the masked dy
   torch.ops.grl.conv4x4s2  4x4 conv, stride 2 (pad 1, + LeakyReLU)   fwd grl_conv4x4s2_fwd | dx = grl_conv4x4s2_bwd_data | dW = grl_gemm_tn (16 taps)
   torch.ops.grl.upsample2x bilinear x2        fwd grl_upsample2x_bilinear_fwd | grl_upsample2x_bilinear_bwd (a gather)
+  SpectralNormFn           W / sigma(W) of a LIST of layers (the discriminator's conv1 .. conv8)   fwd grl_spectral_norm_fwd | grl_spectral_norm_bwd
 
 (torch.library custom ops with registered autograd and fake kernels)
 
@@ -921,3 +922,37 @@ def conv3x3(x, w, b, B, H, W):
     if not x.is_cuda:
         return composite.conv3x3(x, w, b, B, H, W)
     return conv3x3_op(x, w, b, B, H, W)
+
+
+class SpectralNormFn(torch.autograd.Function):
+    """The spectrally normalised weights of a list of layers in one call (ops.spectral_norm: grl_spectral_norm_fwd / _bwd;
+    discriminator.UNetDiscriminatorSN._weights).  ``apply(advance, us, vs, *weight_origs)`` -> one normalised weight per layer;
+    ``us`` / ``vs`` are the modules' buffers (lists; advanced IN PLACE when ``advance``).  The backward treats the vectors as
+    constants, as torch.nn.utils.spectral_norm does, and reads THIS forward's own copies of them: a later forward may have
+    advanced the buffers by then.  It runs for the layers whose weight_orig requires a gradient; when none does (GanStep's generator
+    step) nothing is kept and no backward launch exists."""
+
+    @staticmethod
+    def forward(ctx, advance, us, vs, *ws):
+        need = [l for l in range(len(ws)) if ctx.needs_input_grad[3 + l]]
+        outs, kept = ops.spectral_norm([w.detach() for w in ws], us, vs, advance, keep=bool(need))
+        ctx.layers, ctx.n = need, len(ws)
+        if need:
+            ctx.kept_uv = (kept[0], kept[1])
+            ctx.save_for_backward(kept[2], *[ws[l] for l in need])
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, *gs):
+        grads = [None] * ctx.n
+        live = [(i, l) for i, l in enumerate(ctx.layers) if gs[l] is not None]
+        if live:
+            sigma, *ws = ctx.saved_tensors
+            dws = ops.spectral_norm_bwd([gs[l] for _, l in live], [ws[i] for i, _ in live], (*ctx.kept_uv, sigma), [l for _, l in live])
+            for (_, l), dw in zip(live, dws):
+                grads[l] = dw
+        return (None, None, None, *grads)
+
+
+def spectral_norm(ws, us, vs, advance: bool):
+    return list(SpectralNormFn.apply(bool(advance), list(us), list(vs), *ws))

@@ -43,3 +43,17 @@ def wrap(model: torch.nn.Module, device: Optional[torch.device] = None, bucket_m
     if compress_bf16:
         ddp.register_comm_hook(process_group, bf16_compress_hook)
     return ddp
+
+
+def broadcast_module_state(module: torch.nn.Module, group) -> None:
+    """Parameters and floating-point buffers of ``module`` <- the group's rank 0 (what DistributedDataParallel does when it wraps a
+    module).  Used by the steps that own their gradient all-reduce: train_graph.GraphedTrainStep and gan.GanStep."""
+    src = dist.get_global_rank(group, 0) if hasattr(dist, "get_global_rank") else 0
+    with torch.no_grad():
+        ts = [p for p in module.parameters()] + [b for b in module.buffers() if b.is_floating_point()]
+        for dt in {t.dtype for t in ts}:
+            same = [t for t in ts if t.dtype == dt]
+            flat = torch.cat([t.detach().reshape(-1) for t in same])
+            dist.broadcast(flat, src=src, group=group)
+            torch._foreach_copy_([t.detach() for t in same], [v.view_as(t) for v, t in zip(flat.split([t.numel() for t in same]), same)])
+    torch.autograd.graph.increment_version(list(module.parameters()))

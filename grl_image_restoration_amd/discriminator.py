@@ -9,8 +9,11 @@ Parameter and buffer names are the reference's -- ``conv0.weight``, ``conv0.bias
 
 CUDA tensors: every contraction is a launch of libgrl_hip.so -- torch.ops.grl.conv3x3_lrelu (3x3), torch.ops.grl.conv4x4s2 (the
 encoder's 4x4 stride-2 convolutions) and torch.ops.grl.upsample2x (the decoder's bilinear x2), forward and backward (autograd.py).
-LeakyReLU(0.2) rides in the convolutions' epilogues; the skip additions and the spectral normalisation (eight small mat-vecs) are
-torch glue.  CPU tensors take ``composite_forward``: plain differentiable torch in the parameters' dtype (float64-capable), the
+LeakyReLU(0.2) rides in the convolutions' epilogues.  The spectral normalisation of the eight layers is ONE call of
+autograd.SpectralNormFn per forward (grl_spectral_norm_fwd: three launches for the power iteration, sigma and W / sigma of all
+layers; grl_spectral_norm_bwd: two), without atomics: replicas that hold the same weights keep bit-identical ``weight_u`` /
+``weight_v`` with no broadcast (gan.GanStep(process_group=...)).  The skip additions are torch glue.  CPU tensors take
+``composite_forward`` and ``_SNConv.weight()``: plain differentiable torch in the parameters' dtype (float64-capable), the
 yardstick of the GPU tests; it is not a fallback for the GPU path.
 """
 import math
@@ -62,6 +65,14 @@ class _SNConv(nn.Module):
         return w / sigma
 
 
+def spectral_norm_grad(g: torch.Tensor, w: torch.Tensor, u: torch.Tensor, v: torch.Tensor, sigma: torch.Tensor) -> torch.Tensor:
+    """The derivative of ``w / sigma(w)``, sigma = u . (W v) with u and v held constant as in ``_SNConv.weight()``, for the output
+    gradient ``g``, in closed form: dW = g / sigma - (<g, w> / sigma^2) u v^T.  What grl_spectral_norm_bwd evaluates
+    (include/grl_hip.h), stated in torch in the arguments' dtype: the float64 yardstick of that kernel
+    (tests/test_spectral_norm.py holds it against autograd through ``_SNConv.weight()``)."""
+    return g / sigma - ((g * w).sum() / sigma ** 2) * torch.outer(u, v).view_as(w)
+
+
 def _contract(t: torch.Tensor, operand_dtype: Optional[torch.dtype]) -> torch.Tensor:
     """``operand_dtype``: the value the kernels' loaders contract -- rounded to that type -- carried on in float64."""
     return t if operand_dtype is None else t.to(operand_dtype).to(torch.float64)
@@ -97,9 +108,16 @@ class UNetDiscriminatorSN(nn.Module):
         self.conv8 = _SNConv(nf, nf, 3)
         self.conv9 = _Conv(nf, 1, 3, bias=True)
 
-    def _weights(self):
-        """The eight normalised weights of this forward, in layer order (advances u / v in training mode)."""
-        return [getattr(self, f"conv{i}").weight() for i in range(1, 9)]
+    def _weights(self, chain: bool = False):
+        """The eight normalised weights of this forward, in layer order (advances u / v in training mode).  CUDA parameters: one
+        call of the HIP kernels for the eight layers; ``chain=True`` takes the torch chain of ``_SNConv.weight()`` there as well, the
+        form the kernels replaced (tools/bench_disc.py --sn measures the two against each other by rebinding this method).  CPU parameters always take the chain."""
+        convs = [getattr(self, f"conv{i}") for i in range(1, 9)]
+        if chain or not convs[0].weight_orig.is_cuda:
+            return [c.weight() for c in convs]
+        from . import autograd as AG
+
+        return AG.spectral_norm([c.weight_orig for c in convs], [c.weight_u for c in convs], [c.weight_v for c in convs], self.training)
 
     def forward(self, x: torch.Tensor, operand_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
         """x [B, C, H, W] (H, W multiples of 8) -> logits [B, 1, H, W].  ``operand_dtype`` (CPU only): emulate the kernels' operand

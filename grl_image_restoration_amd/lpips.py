@@ -33,7 +33,7 @@ LPIPS as a training loss is ``LPIPSLoss`` below: one ``autograd.Function`` on th
 image alone, under a power-of-two scale S measured per pass (``loss_scale``).  ``GanStep(lpips=...)`` / ``train --gan --lpips-weight``.
 
 Not built: ``net="alex"`` / ``"squeeze"``, ``spatial=True`` maps, gradients for the target or the weights, the LPIPS term in a
-captured or data-parallel GAN step, a tap backward fused into a convolution.
+captured GAN step (the data-parallel ``GanStep`` carries it as it is: no trained parameters, a per-pass scale that cancels), a tap backward fused into a convolution.
 """
 import math
 from typing import Dict, List, Optional, Sequence, Tuple

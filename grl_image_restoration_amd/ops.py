@@ -1532,3 +1532,70 @@ def batch_remix(lq: torch.Tensor, gt: torch.Tensor, items: torch.Tensor, b: int,
                                lq_out=_ptr(lq_out), gt_out=_ptr(gt_out))
     with _timed("batch_remix"):
         L.launch("grl_batch_remix", args)
+
+
+# ---- spectral normalisation of the discriminator's convolutions (csrc/spectral_norm.hip): every layer in one call ---------------------
+def _sn_table(args, ws, us, vs):
+    """Fills the shared part of the layer table; returns the layers' (Cout, K).  More than L.SN_MAX_LAYERS layers: the first ones
+    are filled and n_layers says how many were asked for -- the library refuses the call."""
+    _dev_check(*ws, *us, *vs)
+    shapes = []
+    for l, (w, u, v) in enumerate(zip(ws, us, vs)):
+        cout, k = w.shape[0], w[0].numel() if w.shape[0] else 0
+        assert w.dtype == u.dtype == v.dtype == torch.float32 and w.is_contiguous() and u.is_contiguous() and v.is_contiguous()
+        assert u.numel() == cout and v.numel() == k, (tuple(w.shape), tuple(u.shape), tuple(v.shape))
+        shapes.append((cout, k))
+        if l < L.SN_MAX_LAYERS:
+            args.w[l], args.u[l], args.v[l], args.cout[l], args.k[l] = w.data_ptr(), u.data_ptr(), v.data_ptr(), cout, k
+    args.n_layers = len(shapes)
+    return shapes
+
+
+def spectral_norm(ws, us, vs, advance: bool, keep: bool = True):
+    """grl_spectral_norm_fwd on lists of layers: ``ws[l]`` fp32 contiguous (Cout, ...) -- weight_orig, seen as (Cout, K) -- with its
+    power-iteration vectors ``us[l]`` (Cout) and ``vs[l]`` (K).  ``advance``: one power iteration first, written to us / vs IN PLACE
+    (a training forward); else they are only read.  Returns (outs, kept): ``outs[l]`` = ws[l] / sigma_l in ws[l]'s shape, and
+    ``kept`` = (u list, v list, sigma [n]) -- this forward's own copies of the vectors sigma was formed with, and sigma -- for
+    spectral_norm_bwd, or None without ``keep``."""
+    ws, us, vs = list(ws), list(us), list(vs)
+    args = L.GrlSpectralNormArgs(advance=int(bool(advance)))
+    shapes = _sn_table(args, ws, us, vs)
+    dev = ws[0].device
+    outs = [empty_like(w) for w in ws]
+    kept = None
+    if keep:
+        uk = empty(sum(c for c, _ in shapes), dtype=torch.float32, device=dev).split([c for c, _ in shapes])
+        vk = empty(sum(k for _, k in shapes), dtype=torch.float32, device=dev).split([k for _, k in shapes])
+        kept = (list(uk), list(vk), empty(len(shapes), dtype=torch.float32, device=dev))
+    for l, o in enumerate(outs[:L.SN_MAX_LAYERS]):
+        args.out[l] = o.data_ptr()
+        if keep:
+            args.u_keep[l], args.v_keep[l], args.sigma[l] = kept[0][l].data_ptr(), kept[1][l].data_ptr(), kept[2].data_ptr() + 4 * l
+    n = sum((cout + 63) // 64 * k + cout for cout, k in shapes)          # include/grl_hip.h: the forward's workspace
+    wsp = empty(max(n, 1), dtype=torch.float32, device=dev)
+    args.ws, args.ws_bytes = wsp.data_ptr(), 4 * n
+    with _timed("spectral_norm"):
+        L.launch("grl_spectral_norm_fwd", args)
+    return outs, kept
+
+
+def spectral_norm_bwd(gs, ws, kept, layers=None):
+    """grl_spectral_norm_bwd: ``gs[i]`` = d/d out of layer ``layers[i]`` (default: all, in order) of the forward that returned
+    ``kept``; ``ws[i]`` that layer's weight_orig.  Returns the dW list, each in its weight's shape."""
+    gs, ws = [g.contiguous() for g in gs], list(ws)
+    layers = list(range(len(ws))) if layers is None else list(layers)
+    u, v, sigma = kept
+    _dev_check(sigma, *gs)
+    args = L.GrlSpectralNormArgs()
+    shapes = _sn_table(args, ws, [u[l] for l in layers], [v[l] for l in layers])
+    outs = [empty_like(w) for w in ws]
+    for i, (l, g, o, w) in enumerate(zip(layers, gs, outs, ws)):
+        assert g.dtype == torch.float32 and g.numel() == w.numel()
+        if i < L.SN_MAX_LAYERS:
+            args.g[i], args.out[i], args.sigma[i] = g.data_ptr(), o.data_ptr(), sigma.data_ptr() + 4 * l
+    n = sum((cout * k + 4095) // 4096 for cout, k in shapes)             # include/grl_hip.h: the backward's workspace
+    wsp = empty(max(n, 1), dtype=torch.float64, device=ws[0].device)
+    args.ws, args.ws_bytes = wsp.data_ptr(), 8 * n
+    with _timed("spectral_norm_bwd"):
+        L.launch("grl_spectral_norm_bwd", args)
+    return outs

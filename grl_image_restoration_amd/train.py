@@ -47,7 +47,8 @@ replay bumps the parameters' version counters, the inference plan keys on them, 
 eval forward -- so it is neither finished nor re-captured.  ``step.finish()`` runs before the optimizer state is read for a checkpoint.
 
 GAN stage.  ``--gan`` (``--task sr``) runs ``gan.GanStep`` per step: the generator's step on pixel loss + GAN loss, then the
-discriminator's (``discriminator.UNetDiscriminatorSN``), eagerly and single-process.  The printed loss is the generator's total.
+discriminator's (``discriminator.UNetDiscriminatorSN``), eagerly; single-process, or with ``--data-parallel`` under ``torchrun`` one
+replica per process (below).  The printed loss is the generator's total.
 Checkpoints carry both networks (``model.model_g.`` / ``model.model_d.``, u / v included) and both optimizers; ``evaluate`` reads
 the generator out of them.  ``--vgg vgg19-dcbb9e9d.pth`` adds the third term of config/loss/gan_training_loss.yaml, the VGG19
 perceptual loss (``perceptual.PerceptualLoss``); the frozen VGG is not written into checkpoints, so ``--resume`` takes ``--vgg`` again.
@@ -81,7 +82,15 @@ averages through the optimizer state.  The step line and the result gain ``grad_
 
 Data-parallel.  Under ``torchrun`` (torch.distributed initialised from the environment) the bare module goes to
 ``GraphedTrainStep``, which owns the gradient all-reduce; each rank's sampler is seeded ``seed + rank``; rank 0 validates and
-writes checkpoints.  ``--eager`` is single-process only.
+writes checkpoints.  ``--eager`` is single-process only.  ``--gan --data-parallel`` (the reference's bsr/grl.yaml: ``gpus: 8``,
+``batch_size: 1`` per GPU, ``strategy: ddp``) hands the default group to ``gan.GanStep``: both networks are broadcast from rank 0, and
+every iteration all-reduces the generator's and then the discriminator's gradients, one flat buffer each.  ``--batch`` is per replica.
+Its checkpoints gain ``sampler_rng_ranks``, the sampler states of all ranks (gathered inside ``checkpoint()``, which every rank
+calls); ``--resume`` at the same world size gives every rank its own entry, so the replicas keep drawing different patches; at
+another world size, or from a checkpoint without the key, every rank takes ``sampler_rng`` as before.
+
+    torchrun --nproc-per-node 8 -m grl_image_restoration_amd.train --task sr --scale 4 --model base --geometry bsr \\
+        --upsampler nearest+conv --gan --data-parallel --batch 1 --patch 128 --degrade --usm --ckpt runs/psnr/step_N.ckpt ...
 """
 import argparse
 import contextlib
@@ -128,11 +137,12 @@ RECALIBRATE_EVERY = 200        # captured Charbonnier steps: eager re-measuremen
 
 
 def save_checkpoint(path: str, model, optimizer, step: int, sampler: D.PatchSampler, args: dict, model_d=None, optimizer_d=None,
-                    remix=None):
+                    remix=None, sampler_rng_ranks=None):
     """``model_d`` / ``optimizer_d`` (--gan): the reference's GAN-stage layout -- ``model.model_g.<k>`` and ``model.model_d.<k>``, the
     u / v buffers of the spectral normalisation among them -- and the second optimizer under ``optimizer_d``.  An optimizer that
     keeps a weight average (``FusedAdamW(ema_decay=...)``) adds ``state_dict_ema``: the generator's keys of ``state_dict``, every
-    optimized parameter replaced by its average (BasicSR's ``params_ema``); the averages themselves resume through ``optimizer``."""
+    optimized parameter replaced by its average (BasicSR's ``params_ema``); the averages themselves resume through ``optimizer``.
+    ``sampler_rng_ranks`` (--gan --data-parallel): the sampler states of all ranks, rank 0's first, under the key of that name."""
     if model_d is None:
         sd = {"model." + k: v.detach().cpu() for k, v in model.state_dict().items()}
     else:
@@ -147,6 +157,8 @@ def save_checkpoint(path: str, model, optimizer, step: int, sampler: D.PatchSamp
         obj["optimizer_d"] = optimizer_d.state_dict()
     if remix is not None:                               # the streams of remix.BatchRemix; the stage follows from the step
         obj["remix_rng"] = remix.rng_state()
+    if sampler_rng_ranks is not None:
+        obj["sampler_rng_ranks"] = list(sampler_rng_ranks)
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     torch.save(obj, path + ".tmp")
     os.replace(path + ".tmp", path)
@@ -212,8 +224,12 @@ def _parser():
     ap.add_argument("--gan", action="store_true",
                     help="--task sr: the GAN stage of real-world SR (config/experiment/bsr/grl.yaml, engines/base_gan.py): --ckpt is the "
                          "PSNR-stage checkpoint; every step is one generator step (pixel loss + GAN loss) and one step of the "
-                         "spectrally normalised U-Net discriminator.  Runs eagerly, single-process; both optimizers are Adam "
-                         "(FusedAdamW with weight decay 0, whatever --weight-decay says) on the same schedule")
+                         "spectrally normalised U-Net discriminator.  Runs eagerly; single-process unless --data-parallel; both "
+                         "optimizers are Adam (FusedAdamW with weight decay 0, whatever --weight-decay says) on the same schedule")
+    ap.add_argument("--data-parallel", action="store_true",
+                    help="--gan under torchrun (WORLD_SIZE > 1, or an initialised process group): one replica per process, the "
+                         "reference's strategy: ddp of bsr/grl.yaml.  GanStep owns the two gradient all-reduces of an iteration; --batch "
+                         "is per replica; rank 0 prints, validates and writes checkpoints, which carry every rank's sampler state")
     ap.add_argument("--disc-ckpt", default=None, help="--gan: start weights of the discriminator (the model_d keys of a GAN checkpoint)")
     ap.add_argument("--disc-feat", type=int, default=64, help="--gan: the discriminator's num_feat")
     ap.add_argument("--gan-weight", type=float, default=1.0, help="--gan: gan_loss_weight of the engine (base_gan.py:122)")
@@ -292,7 +308,14 @@ def _check(ap, a):
             ap.error("--lpips-weight needs --lpips-vgg and --lpips-lin (torchvision's vgg16-397923af.pth / the lpips package's vgg.pth)")
         if a.patch * a.scale < 16:
             ap.error("--lpips-weight: the GT patch side (--patch times --scale) must be at least 16 (VGG16 pools four times)")
-    if a.gan and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+    import torch.distributed as dist
+
+    many = int(os.environ.get("WORLD_SIZE", "1")) > 1
+    if a.data_parallel and not a.gan:
+        ap.error("--data-parallel belongs to --gan (the other modes run data-parallel through the captured step, by themselves)")
+    if a.data_parallel and not many and not (dist.is_available() and dist.is_initialized()):
+        ap.error("--data-parallel needs WORLD_SIZE > 1 (torchrun) or an initialised process group")
+    if a.gan and many and not a.data_parallel:
         ap.error("--gan runs eagerly: --eager is single-process; the captured step owns the gradient all-reduce")
     if a.gan and (a.patch * a.scale) % 8:
         ap.error("--gan: the discriminator takes GT patches whose side (--patch times --scale) is a multiple of 8")
@@ -445,7 +468,10 @@ def main(argv: Optional[List[str]] = None):
         opt.load_state_dict(resume["optimizer"])
         if opt_d is not None:
             opt_d.load_state_dict(resume["optimizer_d"])
-        sampler.set_rng_state(resume["sampler_rng"])
+        ranks = resume.get("sampler_rng_ranks")
+        # (a --gan --data-parallel checkpoint read at the world size that wrote it: every replica goes on with ITS OWN stream;
+        # otherwise rank 0's state, as ever)
+        sampler.set_rng_state(ranks[rank] if ranks is not None and len(ranks) == world else resume["sampler_rng"])
         if remix is not None and resume.get("remix_rng") is not None:
             remix.set_rng_state(resume["remix_rng"])
         start = int(resume["step"])
@@ -473,14 +499,20 @@ def main(argv: Optional[List[str]] = None):
         gan_step = GanStep(model, model_d, opt, opt_d, loss_fn, pixel_weight=a.pixel_weight, gan_weight=a.gan_weight,
                            gan_loss_weight=a.gan_loss_weight, usm_pixel=a.usm, usm_gan=a.usm_gan, perceptual=percep,
                            perceptual_weight=a.perceptual_weight, usm_percep=a.usm_percep, lpips=lpips_loss,
-                           lpips_weight=a.lpips_weight if a.lpips_weight is not None else 1.0, usm_lpips=a.usm_lpips)
+                           lpips_weight=a.lpips_weight if a.lpips_weight is not None else 1.0, usm_lpips=a.usm_lpips,
+                           process_group=dist.group.WORLD if a.data_parallel else None)
 
     def checkpoint(n):
         if step_fn is not None:
             step_fn.finish()
+        extra = {}
+        if a.data_parallel:                             # every rank is here: the replicas' samplers run on streams of their own
+            states = [None] * world
+            dist.all_gather_object(states, sampler.rng_state())
+            extra = dict(sampler_rng_ranks=states)
         if rank == 0 and a.out is not None:
             out["checkpoint"] = save_checkpoint(os.path.join(a.out, f"step_{n}.ckpt"), model, opt, n, sampler, vars(a), model_d, opt_d,
-                                                remix)
+                                                remix, **extra)
 
     for n in range(start, a.steps):
         lr = lr_at(n)

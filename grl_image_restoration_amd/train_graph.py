@@ -81,15 +81,9 @@ class GraphedTrainStep:
     # ------------------------------------------------------------------ data-parallel plumbing
     def _broadcast_replica_state(self):
         """Parameters and floating-point buffers <- the group's rank 0 (what DistributedDataParallel does when it wraps a module)."""
-        src = dist.get_global_rank(self._group, 0) if hasattr(dist, "get_global_rank") else 0
-        with torch.no_grad():
-            ts = [p for p in self.model.parameters()] + [b for b in self.model.buffers() if b.is_floating_point()]
-            for dt in {t.dtype for t in ts}:
-                same = [t for t in ts if t.dtype == dt]
-                flat = torch.cat([t.detach().reshape(-1) for t in same])
-                dist.broadcast(flat, src=src, group=self._group)
-                torch._foreach_copy_([t.detach() for t in same], [v.view_as(t) for v, t in zip(flat.split([t.numel() for t in same]), same)])
-        torch.autograd.graph.increment_version(list(self.model.parameters()))
+        from .ddp import broadcast_module_state
+
+        broadcast_module_state(self.model, self._group)
 
     def _all_reduce(self, flat):
         dist.all_reduce(flat, group=self._group)        # SUM; the 1 / world factor rides in FusedAdamW's grad_scale

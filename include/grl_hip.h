@@ -23,7 +23,7 @@ extern "C" {
 
 #define GRL_ERR_BAD_ARG (-1)
 #define GRL_ERR_UNSUPPORTED (-2)
-#define GRL_ABI_VERSION 44
+#define GRL_ABI_VERSION 45
 
 /* element kinds of activation / weight buffers */
 enum { GRL_DT_F32 = 0, GRL_DT_BF16 = 1, GRL_DT_F16 = 2 };
@@ -1558,6 +1558,52 @@ typedef struct GrlBatchRemixArgs {
 } GrlBatchRemixArgs;
 
 int grl_batch_remix(void* stream, const GrlBatchRemixArgs* args);
+
+/* ---------------------------------------------------------------------------------------------
+ * Spectral normalisation of the discriminator's convolutions (ABI 45, csrc/spectral_norm.hip, discriminator.py): every normalised
+ * layer of a network in one call.
+ *   restates  spectral_norm(nn.Conv2d(...)) on conv1 .. conv8                        models/aux_archs/discriminator.py:92-144
+ *             SpectralNorm.compute_weight, one power iteration                       torch/nn/utils/spectral_norm.py
+ * Per layer l < n_layers: W = w[l], fp32 row-major (cout[l], k[l]) -- the contiguous weight_orig (Cout, Cin, kh, kw) seen as a matrix,
+ * k = Cin kh kw; u[l] (cout[l]) and v[l] (k[l]) the power-iteration vectors; out[l] of W's shape.  Any cout >= 1 and k >= 1.
+ *
+ * grl_spectral_norm_fwd, advance = 1 (a training forward):
+ *   t = W^T u,  v' = t / max(|t|, 1e-12),  s = W v',  u' = s / max(|s|, 1e-12),  sigma = u' . s,  out = W / sigma
+ * u[l] and v[l] are overwritten with u' and v'.  advance = 0 (eval): s = W v, sigma = u . s, out = W / sigma; u and v are only read.
+ * In both modes u_keep[l] / v_keep[l] (each optional) receive the vectors sigma was formed with and *sigma[l] (optional) sigma itself:
+ * the backward of THIS forward needs them after a later forward has advanced u and v.
+ * Three launches (two with advance = 0), whatever n_layers.
+ *
+ * grl_spectral_norm_bwd: g[l] = d/d out[l]; u[l], v[l], *sigma[l] = what the forward left in u_keep, v_keep, sigma (read only);
+ *   out[l] = dW = g / sigma - (<g, W> / sigma^2) u v^T        (u, v constants, as autograd treats them)
+ * <g, W> is summed in double.  u_keep, v_keep and advance are not read.  Two launches.
+ *
+ * No atomics: every sum runs in an order fixed by the shapes, so equal inputs give equal bits, in any process.
+ * ws: device scratch, 8-byte aligned, written before it is read.  ws_bytes at least
+ *   fwd  4 * sum_l (ceil(cout[l] / 64) * k[l] + cout[l])        bwd  8 * sum_l ceil(cout[l] * k[l] / 4096)
+ * Errors, nothing is launched.  GRL_ERR_BAD_ARG: a null args / ws / w / u / v / out (bwd: g / sigma too), n_layers outside
+ * 1 .. GRL_SN_MAX_LAYERS, a non-positive cout or k, advance not 0 / 1, a pointer not 4-byte aligned, ws_bytes too small.
+ * GRL_ERR_UNSUPPORTED: cout * k of 2^31 or more. */
+#define GRL_SN_MAX_LAYERS 16
+typedef struct GrlSpectralNormArgs {
+    const float* w[GRL_SN_MAX_LAYERS];
+    float* u[GRL_SN_MAX_LAYERS];
+    float* v[GRL_SN_MAX_LAYERS];
+    float* out[GRL_SN_MAX_LAYERS];      /* fwd: W / sigma; bwd: dW                                 */
+    float* u_keep[GRL_SN_MAX_LAYERS];   /* fwd, optional                                            */
+    float* v_keep[GRL_SN_MAX_LAYERS];   /* fwd, optional                                            */
+    float* sigma[GRL_SN_MAX_LAYERS];    /* one float each; fwd: written (optional), bwd: read       */
+    const float* g[GRL_SN_MAX_LAYERS];  /* bwd                                                      */
+    int32_t cout[GRL_SN_MAX_LAYERS];
+    int32_t k[GRL_SN_MAX_LAYERS];
+    int32_t n_layers;
+    int32_t advance;
+    void* ws;
+    int64_t ws_bytes;
+} GrlSpectralNormArgs;
+
+int grl_spectral_norm_fwd(void* stream, const GrlSpectralNormArgs* args);
+int grl_spectral_norm_bwd(void* stream, const GrlSpectralNormArgs* args);
 
 /* Debug aid (ABI 21; no reference counterpart): fills the LDS of every CU with 0xFF bytes (fp32 / fp16 NaN) by a launch on
  * `stream`.  LDS keeps what the previous workgroup left in it; a kernel that reads LDS it has not written is otherwise right or

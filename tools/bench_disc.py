@@ -14,11 +14,22 @@ calls, divided by --inner.  ``tflops`` = 2 * pixels * 16 * Cin * Cout over the m
 ones).  One JSON line per measurement, printed and written to --out.
 
     python tools/bench_disc.py [--reps 20] [--warmup 3] [--inner 10] [--out profiles/disc_bench_line.json]
+
+``--sn`` measures the spectral normalisation instead (csrc/spectral_norm.hip): the discriminator at 1 x 3 x 512 x 512 (the
+reference's per-GPU GAN batch, bsr/grl.yaml) and at 8 x 3 x 256 x 256, forward and forward + backward, once on the kernels and once
+on the torch chain they replaced -- ``UNetDiscriminatorSN._weights(chain=True)``, bound over the instance's method; the two forms
+alternate in one process, each is timed twice and reports the run with the lower median, both medians beside it -- then the two
+entry points alone on the eight layers of num_feat 64, and (unless --no-step) one ``GanStep`` on a single GPU in both forms.
+Device-event medians as above, and beside them ``host_us``: the wall-clock time of the same calls up to a final synchronize,
+which is where launch-bound glue shows.  ONE JSON line, printed and written to profiles/sn_bench_line.json.
+
+    python tools/bench_disc.py --sn [--no-step]
 """
 import argparse
 import json
 import os
 import sys
+import time
 
 import torch
 import torch.nn.functional as F
@@ -52,14 +63,99 @@ def s2d_operands(x, w, B, H, W):
     return copy, ops.pack_conv_weight(w3, 4 * Cin, Cout), torch.zeros(Cout, device=w.device)
 
 
+def sn_bench(a, timed, dev):
+    """--sn (module docstring): returns the one result line."""
+    import functools
+
+    from grl_image_restoration_amd import ops
+    from grl_image_restoration_amd.discriminator import UNetDiscriminatorSN
+    from grl_image_restoration_amd.gan import GanStep, gan_loss
+
+    def both(fn, **kw):
+        """Device-event statistics of ``fn`` and the host's wall-clock median for the same call (synchronised)."""
+        t = timed(fn, **kw)
+        walls = []
+        for _ in range(max(5, a.reps // 2)):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            walls.append((time.perf_counter() - t0) * 1e6)
+        return dict(t, host_us=round(sorted(walls)[len(walls) // 2], 2))
+
+    def ab(d, fn, **kw):
+        """kernels / chain / kernels / chain; per form the run with the lower median, both medians beside it."""
+        chain = functools.partial(UNetDiscriminatorSN._weights, d, chain=True)
+        runs = {"kernels": [], "chain": []}
+        for form in ("kernels", "chain", "kernels", "chain"):
+            if form == "chain":
+                d._weights = chain                   # (an instance attribute over the class's method)
+            else:
+                d.__dict__.pop("_weights", None)
+            runs[form].append(both(fn, **kw))
+        d.__dict__.pop("_weights", None)
+        out = {}
+        for form, (r1, r2) in runs.items():
+            best = r1 if r1["us_median"] <= r2["us_median"] else r2
+            out[form] = dict(best, us_median_first=r1["us_median"], us_median_second=r2["us_median"])
+        out["chain_over_kernels"] = round(out["chain"]["us_median"] / out["kernels"]["us_median"], 3)
+        out["host_us_saved"] = round(out["chain"]["host_us"] - out["kernels"]["host_us"], 1)
+        return out
+
+    res = dict(workload="spectral normalisation of UNetDiscriminatorSN(3, 64): HIP kernels vs the torch chain", device=dev,
+               date=time.strftime("%Y-%m-%d"), reps=a.reps, inner=2)
+    g = torch.Generator(device="cuda").manual_seed(0)
+    torch.manual_seed(0)
+    d = UNetDiscriminatorSN(3, 64, True).cuda().train()
+    for B, H in ((1, 512), (8, 256)):
+        img = torch.rand(B, 3, H, H, device="cuda", generator=g)
+        with torch.no_grad():
+            for _ in range(5):
+                d(img)
+
+        def fwd():
+            with torch.no_grad():
+                d(img)
+
+        def fwd_bwd():
+            for p in d.parameters():
+                p.grad = None
+            gan_loss(d(img), True, is_disc=True).backward()
+
+        res[f"forward {B}x3x{H}x{H}"] = ab(d, fwd, inner=2)
+        res[f"forward+backward {B}x3x{H}x{H}"] = ab(d, fwd_bwd, inner=2)
+    convs = [getattr(d, f"conv{i}") for i in range(1, 9)]
+    ws, us, vs = [c.weight_orig.detach() for c in convs], [c.weight_u.clone() for c in convs], [c.weight_v.clone() for c in convs]
+    _, kept = ops.spectral_norm(ws, us, vs, True)
+    gs = [torch.randn_like(w) for w in ws]
+    res["grl_spectral_norm_fwd, 8 layers (3 launches)"] = both(lambda: ops.spectral_norm(ws, us, vs, True))
+    res["grl_spectral_norm_fwd eval, 8 layers (2 launches)"] = both(lambda: ops.spectral_norm(ws, us, vs, False))
+    res["grl_spectral_norm_bwd, 8 layers (2 launches)"] = both(lambda: ops.spectral_norm_bwd(gs, ws, kept))
+    res["weight_megabytes"] = round(sum(w.numel() for w in ws) * 4 / 1e6, 2)
+    if not a.no_step:
+        from grl_image_restoration_amd import GRL, FusedAdamW, make_config
+
+        torch.manual_seed(0)
+        net = GRL(**make_config("base", "bsr_psnr", upscale=4, img_size=128, upsampler="nearest+conv")).cuda().train()
+        opt_g, opt_d = FusedAdamW(net.parameters(), lr=1e-4, weight_decay=0), FusedAdamW(d.parameters(), lr=1e-4, weight_decay=0)
+        lq, gt = torch.rand(1, 3, 128, 128, device="cuda", generator=g), torch.rand(1, 3, 512, 512, device="cuda", generator=g)
+        step = GanStep(net, d, opt_g, opt_d, lambda y, t_: (y - t_).abs().mean(), usm_pixel=True, usm_gan=False)
+        res["GanStep (eager), GRL-Base bsr_psnr x4, LQ 128, batch 1, one GPU"] = ab(d, lambda: step(lq, gt, gt), inner=1,
+                                                                                     reps=max(3, a.reps // 4), warmup=2)
+    return res
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--inner", type=int, default=10)
     ap.add_argument("--no-step", action="store_true")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "disc_bench_line.json"))
+    ap.add_argument("--sn", action="store_true", help="measure the spectral normalisation: kernels against the torch chain")
+    ap.add_argument("--out", default=None, help="default: profiles/disc_bench_line.json (--sn: profiles/sn_bench_line.json)")
     a = ap.parse_args(argv)
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "sn_bench_line.json" if a.sn else "disc_bench_line.json")
     if not torch.cuda.is_available():
         raise SystemExit("bench_disc needs the GPU")
     from grl_image_restoration_amd import autograd as AG
@@ -79,6 +175,14 @@ def main(argv=None):
         inner = inner or a.inner
         med, lo, hi = _median_ms(lambda: [fn() for _ in range(inner)], reps or a.reps, warmup or a.warmup)
         return dict(us_median=round(med / inner * 1e3, 2), us_min=round(lo / inner * 1e3, 2), us_max=round(hi / inner * 1e3, 2))
+
+    if a.sn:
+        line = json.dumps(sn_bench(a, timed, dev))
+        print(line, flush=True)
+        os.makedirs(os.path.dirname(a.out), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+        return
 
     g = torch.Generator(device="cuda").manual_seed(0)
     B = 1
