@@ -11,7 +11,7 @@ from . import switches as SW
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgrl_hip.so")
-ABI_VERSION = 45
+ABI_VERSION = 46
 DT_F32, DT_BF16, DT_F16 = 0, 1, 2
 
 EPI_PLAIN, EPI_GELU, EPI_GROUPNORM, EPI_LN_RES, EPI_GELU_GRAD = 0, 1, 2, 3, 4
@@ -838,6 +838,23 @@ class GrlSpectralNormArgs(_Strict):
 SN_MAX_LAYERS = 16
 
 
+class GrlTileStitchArgs(_Strict):
+    _fields_ = [
+        ("canvas", C.c_void_p),
+        ("tiles", C.c_void_p),
+        ("win", C.c_void_p),
+        ("b", C.c_int32), ("c", C.c_int32), ("h", C.c_int32), ("w", C.c_int32),
+        ("tile", C.c_int32), ("scale", C.c_int32),
+        ("ny", C.c_int32), ("nx", C.c_int32),
+        ("lo", C.c_int32), ("hi", C.c_int32),
+        ("oy", C.c_int32 * 256),
+        ("ox", C.c_int32 * 256),
+    ]
+
+
+STITCH_MAX_ORIGINS = 256
+
+
 _I32, _I64, _PTR = C.c_int32, C.c_int64, C.c_void_p
 
 
@@ -934,6 +951,7 @@ SIGNATURES = {
     "grl_batch_remix": _launch(GrlBatchRemixArgs),
     "grl_spectral_norm_fwd": _launch(GrlSpectralNormArgs),
     "grl_spectral_norm_bwd": _launch(GrlSpectralNormArgs),
+    "grl_tile_stitch": _launch(GrlTileStitchArgs),
     "grl_debug_dirty_lds": (C.c_int, [_PTR]),
     "grl_abi_version": (C.c_int, []),
     "grl_build_info": (C.c_char_p, []),

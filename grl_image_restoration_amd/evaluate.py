@@ -187,7 +187,7 @@ def _side_by_side(left: torch.Tensor, right: torch.Tensor) -> torch.Tensor:
 @torch.no_grad()
 def evaluate_pairs(model, pairs: Iterable[Tuple[torch.Tensor, torch.Tensor]], scale: int, tile: int = 0, overlap: int = 32,
                    device: str = "cuda:0", metric_group: Optional[str] = None, niqe_params=None, on_result=None, lpips_model=None,
-                   self_ensemble: bool = False):
+                   self_ensemble: bool = False, blend: str = "uniform"):
     """PSNR-Y of ``model`` on (lq, gt) tensors in [0, 1], (1,3,h,w) / (1,3,h*scale,w*scale): a list, one value per pair.
     ``tile > 0`` uses the reference's tiled inference (engines/base.py:90-116) through ``tiling.forward_tiled``.
     With ``metric_group`` (a key of ``metrics.ALL_GROUPS`` or ``metrics.PERCEPTUAL_GROUPS``): {metric name: mean over the pairs} of
@@ -195,7 +195,8 @@ def evaluate_pairs(model, pairs: Iterable[Tuple[torch.Tensor, torch.Tensor]], sc
     "restorer_perceptual" takes ``lpips_model`` (an ``lpips.LPIPS`` on ``device``) alongside ``niqe_params``.  ``on_result(index, lq, sr, gt)`` is
     called for every pair with the tensors on ``device``, after ``sr`` and ``gt`` were cropped to each other and before the metrics:
     the images the reference saves (engines/base.py:259-264, before ``shave``).  ``self_ensemble``: every forward is the x8
-    geometric self-ensemble of ``ensemble.SelfEnsemble`` -- of the whole image, or with ``tile`` of every tile on its own."""
+    geometric self-ensemble of ``ensemble.SelfEnsemble`` -- of the whole image, or with ``tile`` of every tile on its own.
+    ``blend``: how tiled inference mixes overlapping tiles (``tiling.BLENDS``; "uniform" is the reference's average)."""
     from . import tiling
     from .metrics import image_metrics
 
@@ -208,7 +209,7 @@ def evaluate_pairs(model, pairs: Iterable[Tuple[torch.Tensor, torch.Tensor]], sc
     for index, (lq, gt) in enumerate(pairs):
         lq = lq.to(device)
         if tile and tile < min(lq.shape[-2:]):
-            sr = tiling.forward_tiled(model, lq, tile, overlap, scale, out_channels=getattr(model, "out_channels", None))
+            sr = tiling.forward_tiled(model, lq, tile, overlap, scale, out_channels=getattr(model, "out_channels", None), blend=blend)
         else:
             sr = model(lq)
         if gt is None:
@@ -265,7 +266,7 @@ def evaluate_folder(model, lq_dir: Optional[str], gt_dir: Optional[str], scale: 
                     task: str = "sr", sigma: Optional[float] = None, noise_prefix: Optional[str] = None, niqe_params=None,
                     taps: Optional[torch.Tensor] = None, quality: Optional[int] = None, save_dir: Optional[str] = None,
                     save_gt: bool = False, save_workers: int = 4, usm_gt: bool = False, lpips_model=None,
-                    lq_r_dir: Optional[str] = None, self_ensemble: bool = False):
+                    lq_r_dir: Optional[str] = None, self_ensemble: bool = False, blend: str = "uniform"):
     """Mean PSNR-Y over the image pairs of two folders; with ``metric_group``, {metric name: mean} of that group.  ``channels`` 1
     reads the images as grayscale.  A ``task`` that synthesises its input ignores ``lq_dir`` and builds the LQ from the GT
     (``task_inputs``, with ``sigma``, ``taps``, ``quality`` and ``scale`` as the task's rule takes them).  A task without a ground
@@ -282,7 +283,14 @@ def evaluate_folder(model, lq_dir: Optional[str], gt_dir: Optional[str], scale: 
     the model (``GRL(in_channels=6, out_channels=3)``) gets the two side by side, ``<stem>_LQ.png`` is the LEFT view
     (engines/base.py:536-537) and the saved images go straight under the data set's name (engines/base.py:521-524).
     ``self_ensemble``: the model runs as ``ensemble.SelfEnsemble(model)``, the x8 geometric self-ensemble (per tile with ``tile``); it
-    sits at the model boundary, after the task's front end, so every task, metric and saved image goes with it."""
+    sits at the model boundary, after the task's front end, so every task, metric and saved image goes with it.  ``blend`` (with
+    ``tile``; ValueError without): "linear" or "cosine" feathers the overlaps of tiled inference instead of averaging them uniformly."""
+    from . import tiling
+
+    if blend not in tiling.BLENDS:
+        raise ValueError(f"blend is one of {', '.join(tiling.BLENDS)}, got {blend!r}")
+    if blend != "uniform" and not tile:
+        raise ValueError("blend belongs to tiled inference: give a tile size")
     if self_ensemble:
         from .ensemble import SelfEnsemble
 
@@ -328,7 +336,8 @@ def evaluate_folder(model, lq_dir: Optional[str], gt_dir: Optional[str], scale: 
     with writer:                                          # closed, every file in place, before the mean is returned
         for name, lq, gt in items:
             on_result = None if save is None else (lambda i, lq_, sr_, gt_, name=name: save(name, lq_, sr_, gt_))
-            v = evaluate_pairs(model, [(lq, gt)], scale, tile, overlap, device, metric_group, niqe_params, on_result, lpips_model)
+            v = evaluate_pairs(model, [(lq, gt)], scale, tile, overlap, device, metric_group, niqe_params, on_result, lpips_model,
+                               blend=blend)
             v = v[0] if metric_group is None else v
             vals.append(v)
             if verbose:
@@ -370,6 +379,9 @@ def _parser():
                     help="restorer_perceptual: the lpips package's weights/v0.1/vgg.pth (the five 1x1 layers)")
     ap.add_argument("--tile", type=int, default=0)
     ap.add_argument("--overlap", type=int, default=32)
+    ap.add_argument("--blend", default=None, choices=["uniform", "linear", "cosine"],
+                    help="with --tile: how overlapping tiles are mixed.  uniform (default): the reference's plain average; linear, "
+                         "cosine: a ramp over the overlap that feathers the seams")
     ap.add_argument("--self-ensemble", action="store_true",
                     help="x8 geometric self-ensemble: restore the image under the eight flips and rotations and average the results "
                          "mapped back (with --tile: every tile on its own)")
@@ -390,6 +402,13 @@ def _parser():
     return ap
 
 
+def check_blend(ap, a):
+    """--blend (evaluate and restore) belongs to --tile; fills the default."""
+    if a.blend is not None and not a.tile:
+        ap.error("--blend belongs to tiled inference: give --tile")
+    a.blend = a.blend or "uniform"
+
+
 def _check(ap, a):
     """Checks the parsed arguments against the task's rule and fills ``a.scale``, ``a.sigma`` and, without a ground truth,
     ``a.metric``."""
@@ -402,6 +421,7 @@ def _check(ap, a):
         if a.metric not in (None, "restorer_niqe"):
             ap.error(f"--task {a.task} is scored by --metric restorer_niqe")
         a.metric = "restorer_niqe"
+    check_blend(ap, a)
     o = resolve_arguments(ap, a, "evaluate", usm=a.usm_gt, dual_pixel=a.lq_r is not None)
     a.scale, a.sigma = o.scale, o.sigma
 
@@ -457,7 +477,7 @@ def main(argv: Optional[List[str]] = None):
     return evaluate_folder(model, a.lq, a.gt, a.scale, a.tile, a.overlap, a.device, metric_group=a.metric, channels=a.channels,
                            task=a.task, sigma=a.sigma, noise_prefix=a.noise_prefix, niqe_params=niqe_params, taps=taps,
                            quality=a.quality, save_dir=a.save_dir, save_gt=a.save_gt, usm_gt=a.usm_gt, lpips_model=lpips_model,
-                           lq_r_dir=a.lq_r, self_ensemble=a.self_ensemble)
+                           lq_r_dir=a.lq_r, self_ensemble=a.self_ensemble, blend=a.blend)
 
 
 if __name__ == "__main__":

@@ -1534,6 +1534,34 @@ def batch_remix(lq: torch.Tensor, gt: torch.Tensor, items: torch.Tensor, b: int,
         L.launch("grl_batch_remix", args)
 
 
+# ---- tiled inference, the stitch (csrc/stitch.hip): a chunk of tile outputs into the canvas in one launch -------------------------------
+def tile_stitch(canvas: torch.Tensor, outs, oy, ox, tile: int, scale: int, lo: int, window: Optional[torch.Tensor] = None) -> None:
+    """grl_tile_stitch: ``outs`` are the fp32 outputs (b, c, tile * scale, tile * scale) of the tiles lo .. lo + len(outs) - 1 of the
+    row-major grid ``oy`` x ``ox`` (tile origins in input pixels), read in place through their strides (views of a batch, of a wider
+    tensor, of a receive buffer; a column stride other than 1 is copied first); ``canvas`` (b, c, h * scale, w * scale) fp32
+    contiguous is written where those tiles cover it -- see include/grl_hip.h for the rule -- and ``window`` is the device fp32
+    window of tile * scale elements, None for the uniform average.  The table of addresses and strides is built here, per call."""
+    outs = [o if o.stride(-1) == 1 else o.contiguous() for o in outs]
+    _dev_check(canvas, *outs, *([] if window is None else [window]))
+    ts = tile * scale
+    assert canvas.dim() == 4 and canvas.dtype == torch.float32 and canvas.is_contiguous()
+    b, c, H, W = canvas.shape
+    assert H % scale == 0 and W % scale == 0, (tuple(canvas.shape), scale)
+    for o in outs:
+        assert o.dtype == torch.float32 and tuple(o.shape) == (b, c, ts, ts), (tuple(o.shape), (b, c, ts, ts))
+    if window is not None:
+        assert window.dtype == torch.float32 and tuple(window.shape) == (ts,) and window.is_contiguous(), tuple(window.shape)
+    rows = [[o.data_ptr(), o.stride(0), o.stride(1), o.stride(2), 0, 0, 0, 0] for o in outs]
+    table = torch.tensor(rows, dtype=torch.int64).reshape(-1, 8).pin_memory().to(canvas.device, non_blocking=True)
+    args = L.GrlTileStitchArgs(canvas=_ptr(canvas), tiles=_ptr(table), win=_ptr(window), b=b, c=c, h=H // scale, w=W // scale,
+                               tile=int(tile), scale=int(scale), ny=len(oy), nx=len(ox), lo=int(lo), hi=int(lo) + len(outs))
+    for dst, src in ((args.oy, oy), (args.ox, ox)):
+        for i, v in enumerate(src[:L.STITCH_MAX_ORIGINS]):                   # longer lists: ny / nx say so and the library refuses
+            dst[i] = int(v)
+    with _timed("tile_stitch"):
+        L.launch("grl_tile_stitch", args)
+
+
 # ---- spectral normalisation of the discriminator's convolutions (csrc/spectral_norm.hip): every layer in one call ---------------------
 def _sn_table(args, ws, us, vs):
     """Fills the shared part of the layer table; returns the layers' (Cout, K).  More than L.SN_MAX_LAYERS layers: the first ones

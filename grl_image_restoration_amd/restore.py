@@ -3,7 +3,7 @@ is written as ``<out>/<stem><suffix>.png``.  Nothing is synthesised and nothing 
 and the PNG writer are ``image8.pack8`` / ``image8.ImageWriter``, the rounding is the reference's (engines/base.py:259-264,545-550).
 
     python -m grl_image_restoration_amd.restore --model base --geometry sr_ckpt_df2 --scale 4 --ckpt sr_grl_base_c3x4.ckpt \\
-        --lq photos --out restored [--tile 256 --overlap 32] [--self-ensemble]
+        --lq photos --out restored [--tile 256 --overlap 32 [--blend linear]] [--self-ensemble]
     python -m grl_image_restoration_amd.restore --model small --geometry dn_df4 --ckpt dn_grl_small_c3s25.ckpt --lq noisy --out clean
     python -m grl_image_restoration_amd.restore --model base --geometry defocus --ckpt db_defocus_dual_pixel_grl_base.ckpt \\
         --lq shots/left --lq-r shots/right --out sharp --tile 480 --overlap 48      (dual-pixel: the two views side by side, 6 in / 3 out)
@@ -15,22 +15,29 @@ from typing import List, Optional
 
 import torch
 
-from .evaluate import _read_image, _side_by_side, gt_images, load_checkpoint
+from .evaluate import _read_image, _side_by_side, check_blend, gt_images, load_checkpoint
 from .image8 import ImageWriter
 
 
 @torch.no_grad()
 def restore_folder(model, lq_dir: str, out_dir: str, scale: int = 1, tile: int = 0, overlap: int = 32, device: str = "cuda:0",
                    channels: int = 3, suffix: str = "_HQ", workers: int = 4, compress_level: int = 6, verbose: bool = False,
-                   lq_r_dir: Optional[str] = None, self_ensemble: bool = False) -> List[str]:
+                   lq_r_dir: Optional[str] = None, self_ensemble: bool = False, blend: str = "uniform") -> List[str]:
     """Writes ``<out_dir>/<stem><suffix>.png`` for every image of ``lq_dir`` in sorted order and returns the paths; every file is
     complete when the call returns.  ``tile > 0`` restores images larger than the tile through ``tiling.forward_tiled``.  One reader
     thread decodes the next image while the device works on the current one; ``workers`` threads compress the PNGs.  ``lq_r_dir``
     (scale 1, RGB): dual-pixel inputs -- ``lq_dir`` holds the left views, ``lq_r_dir`` the right ones, matched by sorted order; the
     model (``GRL(in_channels=6, out_channels=3)``) gets the two side by side (engines/base.py:119-120) and the written file takes
     the LEFT view's stem.  ``self_ensemble``: the model runs as ``ensemble.SelfEnsemble(model)``, the x8 geometric self-ensemble (with
-    ``tile``: every tile on its own)."""
+    ``tile``: every tile on its own).  ``blend`` (with ``tile``; ValueError without): "linear" or "cosine" feathers the overlaps of
+    tiled inference (``tiling.blend_window``) instead of the reference's uniform average, which leaves a visible step where
+    neighbouring tiles disagree."""
     from . import tiling
+
+    if blend not in tiling.BLENDS:
+        raise ValueError(f"blend is one of {', '.join(tiling.BLENDS)}, got {blend!r}")
+    if blend != "uniform" and not tile:
+        raise ValueError("blend belongs to tiled inference: give a tile size")
 
     if self_ensemble:
         from .ensemble import SelfEnsemble
@@ -59,7 +66,7 @@ def restore_folder(model, lq_dir: str, out_dir: str, scale: int = 1, tile: int =
                 ahead = reader.submit(read, files[i + 1], mode)
             lq = lq.to(device)
             if tile and tile < min(lq.shape[-2:]):
-                sr = tiling.forward_tiled(model, lq, tile, overlap, scale, out_channels=getattr(model, "out_channels", None))
+                sr = tiling.forward_tiled(model, lq, tile, overlap, scale, out_channels=getattr(model, "out_channels", None), blend=blend)
             else:
                 sr = model(lq)
             path = os.path.join(out_dir, os.path.splitext(os.path.basename(f))[0] + suffix + ".png")
@@ -89,6 +96,9 @@ def _parser():
     ap.add_argument("--depths", default=None, help="blocks per stage as a+b+c instead of the model size's (short experiments)")
     ap.add_argument("--tile", type=int, default=0)
     ap.add_argument("--overlap", type=int, default=32)
+    ap.add_argument("--blend", default=None, choices=["uniform", "linear", "cosine"],
+                    help="with --tile: how overlapping tiles are mixed.  uniform (default): the reference's plain average; linear, "
+                         "cosine: a ramp over the overlap that feathers the seams")
     ap.add_argument("--self-ensemble", action="store_true",
                     help="x8 geometric self-ensemble: restore the image under the eight flips and rotations and average the results "
                          "mapped back (with --tile: every tile on its own)")
@@ -106,6 +116,7 @@ def main(argv: Optional[List[str]] = None):
     a = ap.parse_args(argv)
     if a.scale < 1:
         ap.error("--scale is at least 1")
+    check_blend(ap, a)
     if a.lq_r is not None and (a.scale != 1 or a.channels != 3):
         ap.error("--lq-r (dual-pixel inputs) goes with --scale 1 and --channels 3")
     try:
@@ -127,7 +138,7 @@ def main(argv: Optional[List[str]] = None):
             ap.error(f"--ema: {e.args[0]}")
     model = model.to(a.device)
     return restore_folder(model, a.lq, a.out, a.scale, a.tile, a.overlap, a.device, a.channels, a.suffix, a.workers,
-                          a.compress_level, verbose=True, lq_r_dir=a.lq_r, self_ensemble=a.self_ensemble)
+                          a.compress_level, verbose=True, lq_r_dir=a.lq_r, self_ensemble=a.self_ensemble, blend=a.blend)
 
 
 if __name__ == "__main__":

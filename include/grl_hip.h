@@ -23,7 +23,7 @@ extern "C" {
 
 #define GRL_ERR_BAD_ARG (-1)
 #define GRL_ERR_UNSUPPORTED (-2)
-#define GRL_ABI_VERSION 45
+#define GRL_ABI_VERSION 46
 
 /* element kinds of activation / weight buffers */
 enum { GRL_DT_F32 = 0, GRL_DT_BF16 = 1, GRL_DT_F16 = 2 };
@@ -1604,6 +1604,51 @@ typedef struct GrlSpectralNormArgs {
 
 int grl_spectral_norm_fwd(void* stream, const GrlSpectralNormArgs* args);
 int grl_spectral_norm_bwd(void* stream, const GrlSpectralNormArgs* args);
+
+/* ---------------------------------------------------------------------------------------------
+ * Tiled inference, the stitch (ABI 46, csrc/stitch.hip, tiling.py): the canvas accumulation of tiled whole-image inference for a
+ * contiguous range of the tile list in one launch, with an optional blending window.
+ *   restates  forward_tile: E += out, W += 1, E / W                                   engines/base.py:100-116
+ * Inputs.  The reference's tile grid oy = tile_origins(h, tile, overlap), ox = tile_origins(w, tile, overlap) (input pixels,
+ * strictly ascending); tile t = iy * nx + ix in row-major order, the reference's loop order; ts = tile * scale; a 1-D fp32 window
+ * win[0 .. ts), strictly positive, a null pointer meaning all ones; a contiguous range [lo, hi) of the tile list; the fp32 outputs
+ * of those tiles, each (b, c, ts, ts), read in place through their batch / channel / row ELEMENT strides (column stride 1).
+ * tiles: DEVICE table of hi - lo rows of eight int64, row k for tile lo + k: the address of its element (0, 0, 0, 0), the batch,
+ * channel and row stride, four reserved.  canvas: (b, c, h * scale, w * scale) fp32, contiguous.
+ *
+ * For a canvas pixel (y, x) the covering tiles C are those with oy[iy] * scale <= y < oy[iy] * scale + ts and likewise in x: a
+ * contiguous range of iy times a contiguous range of ix -- of any length: with overlap > tile / 2, or a last tile that lands close to
+ * its neighbour, three or more tiles per axis cover a pixel -- visited in row-major order.  For each channel and batch item:
+ *   - if no tile of C lies in [lo, hi) the pixel is not touched: neither read nor written;
+ *   - the running value starts at +0.0f if the first tile of C has index >= lo, else at the canvas value;
+ *   - for each tile of C in [lo, hi), in order: acc = acc + o * wgt, wgt = win[y - oy * scale] * win[x - ox * scale]: three
+ *     separately rounded fp32 operations, no FMA (the file is compiled with -ffp-contract=off);
+ *   - if the last tile of C has index < hi the pixel is complete: acc = acc / wsum, an IEEE division, where wsum starts at +0.0f
+ *     and adds wgt over ALL tiles of C in the same order;
+ *   - the pixel is written once.
+ * So the canvas may be uninitialised memory; a pixel is read only when an earlier chunk started it; there are no atomics and no
+ * workspace; calling the entry chunk after chunk in list order gives the bits of one call with [0, n); with a null window that is
+ * tiling.stitch (0 + o1 + o2 ... in the same order, divided by the exact count), and -0.0 inputs come out as +0.0, as in torch.
+ * The grid covers the bounding box of the chunk's tiles only: its band of tile rows, and all columns unless it lies in one tile row.
+ *
+ * Errors, nothing is launched.  GRL_ERR_BAD_ARG: a null args / canvas / tiles, a non-positive b, c, h, w, tile, scale, ny or nx,
+ * tile > h or tile > w, lo < 0, lo >= hi, hi > ny * nx, an origin list that does not ascend strictly or holds a tile outside the
+ * canvas.  GRL_ERR_UNSUPPORTED: more than GRL_STITCH_MAX_ORIGINS origins on an axis, canvas or win not 4-byte or tiles not 8-byte
+ * aligned, b * c above 65535, more than 4 * 65535 canvas rows in the chunk's band. */
+#define GRL_STITCH_MAX_ORIGINS 256
+typedef struct GrlTileStitchArgs {
+    float* canvas;              /* (b, c, h * scale, w * scale), device                            */
+    const int64_t* tiles;       /* [hi - lo][8], device                                            */
+    const float* win;           /* [tile * scale], device, or null                                 */
+    int32_t b, c, h, w;         /* the INPUT's shape                                               */
+    int32_t tile, scale;
+    int32_t ny, nx;
+    int32_t lo, hi;
+    int32_t oy[GRL_STITCH_MAX_ORIGINS];
+    int32_t ox[GRL_STITCH_MAX_ORIGINS];
+} GrlTileStitchArgs;
+
+int grl_tile_stitch(void* stream, const GrlTileStitchArgs* args);
 
 /* Debug aid (ABI 21; no reference counterpart): fills the LDS of every CU with 0xFF bytes (fp32 / fp16 NaN) by a launch on
  * `stream`.  LDS keeps what the previous workgroup left in it; a kernel that reads LDS it has not written is otherwise right or

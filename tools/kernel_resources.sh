@@ -6,9 +6,9 @@
 set -u
 cd "$(dirname "$0")/../grl_image_restoration_amd/csrc"
 echo "# hipcc --offload-arch=gfx950 -O3 -Rpass-analysis=kernel-resource-usage  (tools/kernel_resources.sh)"
-for f in spectral_norm remix ensemble gram jitter isp cvresize blur_items lpips vgg disc usm image8 jpeg blur patches niqe imresize attention attention_rows attention_bwd mlp tail_regs qkv qkv_anchor conv conv192 cab_conv2 linear_split grad misc planes ln_train cpb linear linear_k576; do
+for f in stitch spectral_norm remix ensemble gram jitter isp cvresize blur_items lpips vgg disc usm image8 jpeg blur patches niqe imresize attention attention_rows attention_bwd mlp tail_regs qkv qkv_anchor conv conv192 cab_conv2 linear_split grad misc planes ln_train cpb linear linear_k576; do
   extra=""
-  case $f in attention|attention_bwd) extra="-mllvm -amdgpu-mfma-vgpr-form";; remix) extra="-ffp-contract=off";; esac   # as in csrc/Makefile
+  case $f in attention|attention_bwd) extra="-mllvm -amdgpu-mfma-vgpr-form";; remix|stitch) extra="-ffp-contract=off";; esac   # as in csrc/Makefile
   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=fast -I../../include --cuda-device-only $extra -c $f.hip -o /dev/null \
         -Rpass-analysis=kernel-resource-usage 2>&1 |
     awk '/remark: Function Name:/{name=$(NF-1)} /remark: +TotalSGPRs:/{s=$(NF-1)} /remark: +VGPRs:/{v=$(NF-1)} /remark: +AGPRs:/{a=$(NF-1)}
